@@ -22,7 +22,14 @@ HBM too (device pointers come back; `--outputs host` / `DFX_BENCH_FUSED=0` resto
 to pinned host memory inside it).  The PCIe legs either side are measured and reported next to `value`, never inside it:
 `host_prepare_ms` (design -> packed parameters -> H2D) and `outputs.value_with_outputs_on_host`.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--members M] [--size 128]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--members M] [--size 128] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds the legs that take runs of their own: the
+1-stream per-launch roofline leg, the 1-member `single_system`, the second region with the gradients copied to host memory,
+`launch_bound` (C2 x 1, C3 x 1, C4 x 8 designs), `c3_as_written` (the whole 50 000-step horizon) and `cpu_baseline`; the
+`--no-*` switches leave single legs out of a full run.  `--dump-outputs DIR` writes what the timed call returned (objectives and
+gradients, float64) to DIR/<name>.npy after the timed region; an array of more than DUMP_MAX_VALUES values is written as a fixed,
+seeded sample of that many of its entries (the same positions in every run), so that the files stay below 64 MB in all.
 
 N > 1: one rank per GPU, every rank integrates its own designs (weak scaling, no data-path collective), objectives are
 gathered with ONE RCCL all-gather inside libdfx.  Launched either by the driver (`python -m torch.distributed.run ...
@@ -754,6 +761,29 @@ def cpu_baseline(size, seed, n_steps=100, repeats=5, budget_s=40.0, make=None, a
                       + ("; " + "; ".join(notes) if notes else "")}
 
 
+DUMP_MAX_VALUES = 1 << 21        # per array of --dump-outputs (16 MiB of float64); the c3 call returns 3 gradients + the objectives
+DUMP_SEED = 20240611
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as `out_dir/<name>.npy` in float64; one of more than DUMP_MAX_VALUES values as the entries at a fixed,
+    seeded set of flat positions (sorted), which depends on the array's size only.  Returns the bytes written."""
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.size > DUMP_MAX_VALUES:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_MAX_VALUES, replace=False))
+            a = a.reshape(-1)[idx]
+        out[name] = a
+    total = sum(a.nbytes for a in out.values())
+    if total > 64e6:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, more than 64 MB")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return total
+
+
 def launch_ranks(n, argv):
     """`--gpus N` without a launcher: start the N rank processes (fresh interpreters, before this process has made any GPU
     call), relay rank 0's output, return the worst exit code."""
@@ -844,7 +874,15 @@ def main():
                          "engages every narrow void of the 25-degree design: contact branches and their gradient traffic everywhere)")
     ap.add_argument("--contact-min-deg", type=float, default=-15.0, help="void angle at which the penalty diverges (C3: -15)")
     ap.add_argument("--target-shift", type=int, nargs=2, default=None, help="target placement (C3 text: 21 25); default: next to the drive")
+    ap.add_argument("--full", action="store_true",
+                    help="c3: also run the legs beside the headline (roofline leg, single_system, gradients-on-host region, launch_bound, "
+                         "c3_as_written, cpu_baseline); a plain run times the K steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="c3: write the objectives and gradients of the last timed call to DIR/<name>.npy (float64; arrays of more than "
+                         f"{DUMP_MAX_VALUES} values as a fixed seeded sample)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.workload != "c3" or args.forward_only):
+        ap.error("--dump-outputs: the c3 workload with its adjoint (objectives + gradients) only")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -925,7 +963,7 @@ def main():
     #     rocprofv3 --kernel-trace --stats reports the same average durations (profiles/).  Rank 0, before the timed job, on its
     #     own engine (closed again before the big checkpoint of the timed job is allocated).
     rr = None
-    if rank == 0 and not args.no_roofline_leg:
+    if rank == 0 and args.full and not args.no_roofline_leg:
         os.environ["DFX_STREAMS"] = "1"
         timed_level = os.environ.get("DFX_CHECKPOINT")
         if timed_level == "segments":          # the segments level runs the records kernels inside every output interval
@@ -943,7 +981,7 @@ def main():
         if timed_level is not None:
             os.environ["DFX_CHECKPOINT"] = timed_level
     single = None
-    if rank == 0 and world == 1 and args.members > 1 and adjoint and not args.no_single:
+    if rank == 0 and world == 1 and args.members > 1 and adjoint and args.full and not args.no_single:
         # the same config with ONE design per GPU (launch-bound: one wave per SIMD), for reference.  The engine chooses its checkpoint
         # level itself here (the level pinned above is the 16-member job's: a 5 000-step default run pins "stages", at which one member's
         # reverse sweep would keep the stage launches although its records fit)
@@ -1006,8 +1044,13 @@ def main():
     out_bytes = sum(getattr(a, "nbytes", 0) for a in (res.get("grads") or {}).values())
     fetch_s = fetch(res)                       # outputs over PCIe to the host: after the timed region, reported
     gnorm = grad_norm(res)
+    if args.dump_outputs:                      # before any further call on the engine (host-output views are only valid until then)
+        objective_all = comm.all_gather(res["objective"]).ravel()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, dict({"objective": objective_all},
+                                                 **{f"grad_{k}": v for k, v in sorted(res["grads"].items())}))
     wall_host_outputs = None
-    if device_outputs and K <= 2500:
+    if args.full and device_outputs and K <= 2500:
         # the PCIe-inclusive rate of the same job: one more region through the host-output call (gradients arrive as pinned views)
         run_once(fw, obj, designs, K, adjoint=adjoint)
         prepare(fw, designs, K)
@@ -1130,12 +1173,12 @@ def main():
         line["end_to_end_frac_of_hbm_peak"] = per_step_bytes * total_units_steps / wall / 1e9 / HBM_PEAK_GBS
         if single is not None:
             line["single_system"] = single
-        if world == 1 and adjoint and not args.no_launch_bound:
+        if args.full and world == 1 and adjoint and not args.no_launch_bound:
             line["launch_bound"] = launch_bound_block(local_rank, sync, single)
         line["csrc"] = source_ids()
-        if world == 1 and adjoint and not args.no_as_written and args.size == 128 and args.as_written_steps > 0:
+        if args.full and world == 1 and adjoint and not args.no_as_written and args.size == 128 and args.as_written_steps > 0:
             line["c3_as_written"] = c3_as_written_leg(args, local_rank, sync, steps=args.as_written_steps)
-        if not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only
             line["cpu_baseline"] = cpu_baseline(args.size, 3)
         print(json.dumps(line), flush=True)
     comm.barrier()

@@ -426,6 +426,23 @@ def test_bench_times_exactly_k_steps():
         assert total == k and abs(ts[-1] - k * bench.DT) < 1e-18 and np.all(np.diff(ts) > 0)
 
 
+def test_bench_dump_outputs_is_repeatable_and_bounded(tmp_path):
+    """`bench.py --dump-outputs DIR`: one float64 .npy per array; an array of more than DUMP_MAX_VALUES values comes out as the same
+    seeded sample of its entries in every run, so that two builds can be compared file by file."""
+    import bench
+    rng = np.random.default_rng(0)
+    small, big = rng.standard_normal((4, 3)), rng.standard_normal(bench.DUMP_MAX_VALUES + 1000)
+    for d in ("a", "b"):
+        n = bench.dump_outputs(str(tmp_path / d), {"objective": small.astype(np.float32), "grad_x": big})
+        assert n <= 64e6
+    for name in ("objective", "grad_x"):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+    assert np.array_equal(np.load(tmp_path / "a" / "objective.npy"), small.astype(np.float32).astype(np.float64))
+    s = np.load(tmp_path / "a" / "grad_x.npy")
+    assert s.shape == (bench.DUMP_MAX_VALUES,) and np.isin(s, big).all() and len(np.unique(s)) == s.size
+
+
 def test_geometry_cache_tells_kagome_lattices_with_different_bases_apart():
     """the per-design geometry cache keyed kagome lattices by their scalar attributes only; two lattices that
     differ in direct_basis (cell_size / cell_angle) must not share centroids and node vectors for one design object."""

@@ -16,6 +16,6 @@ timeout 600 python bench.py --workload c5 --c5-members 32 --c5-iterations 4 --no
 for a in "quads 128 1 2000 1 1 DFX_PERSIST=1,DFX_CHECKPOINT=segments DFX_PERSIST=1,DFX_CHECKPOINT=segments,DFX_SEG_OVERLAP=0" "quads 128 1 400" "quads 128 2 400" "quads 128 4 400" "kagome 64 8 400" "quads 64 8 400" "quads 32 1 2000 0 0" "quads 32 64 1000 0 0"; do timeout 300 python tools/persist_probe.py $a; done > $OUT/persist_probe.txt 2>/dev/null
 timeout 600 python tools/c4_problem_timing.py 8 4000 > $OUT/c4_8_designs.txt 2>&1
 timeout 900 python examples/multi_input_ensemble.py --members 256 --iterations 4 2>&1 | grep -E "designs x|evaluations of|device time" > $OUT/c5_256_designs_4_iterations.txt
-timeout 600 python bench.py --gpus 2 --backend socket --all-ranks-device 0 --steps 250 --warmup 250 --members 8 --no-cpu-baseline > $OUT/bench_two_rank_rehearsal_socket.json 2> $OUT/bench_two_rank.err
+timeout 600 python bench.py --full --gpus 2 --backend socket --all-ranks-device 0 --steps 250 --warmup 250 --members 8 --no-cpu-baseline > $OUT/bench_two_rank_rehearsal_socket.json 2> $OUT/bench_two_rank.err
 timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1
 tail -3 $OUT/gpu_pytest.txt; cat $OUT/c5_256_designs_4_iterations.txt; tail -2 $OUT/smoke.txt; tail -c 600 $OUT/bench_c5_256_designs.json

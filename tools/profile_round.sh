@@ -1,14 +1,14 @@
 #!/bin/bash
 # usage (on the GPU box): tools/profile_round.sh TAG [MEMBERS]
 # Collects what DESIGN.md section 4 cites, into gpurun_out/prof_TAG/:
-#   bench.json            default bench line
+#   bench.json            full bench line (--full)
 #   stats/                rocprofv3 --kernel-trace --stats of `bench.py --streams 1` (one stream: the regime the profiler can observe)
 #   pmc_fetch|pmc_write|pmc_sq*/   PMC passes (separate runs, --kernel-trace only), DFX_DUAL_CHAIN=0
 TAG=${1:-rXX}; M=${2:-16}
 OUT=gpurun_out/prof_$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
-timeout 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err
-timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/bench_steps20.json 2> $OUT/bench_steps20.err
+timeout 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_steps20.json 2> $OUT/bench_steps20.err
 ARGS="bench.py --streams 1 --members $M --steps 250 --warmup 0 --no-cpu-baseline --no-single --no-roofline-leg --no-as-written --no-launch-bound"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o trace -- python3 $ARGS > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
 PARGS="bench.py --streams 1 --members $M --steps 250 --warmup 0 --no-cpu-baseline --no-single --no-roofline-leg --no-as-written --no-launch-bound"
