@@ -24,7 +24,7 @@ from . import _binding as _b
 from .energy import _EnergyFn
 from .geometry import (DOFsInfo, compute_inertia, compute_inertia_vjp, void_angles0, void_angles0_vjp)
 from .loading import as_time_function, zero
-from .utils import (ContactParams, ControlParams, GeometricalParams, MechanicalParams)
+from .utils import (ContactParams, ControlParams, GeometricalParams, MechanicalParams, _frozen)
 
 
 _FLAT_CACHE = {}      # id(centroid_node_vectors) -> (weakref, bonds, density, inertia, void_angle0)
@@ -40,15 +40,42 @@ def remember_flat(cnv, bonds, density, inertia, void_angle0):
     _FLAT_CACHE[key] = (weakref.ref(cnv, lambda _r, k=key: _FLAT_CACHE.pop(k, None)), bonds, np.array(density, copy=True), inertia, void_angle0)
 
 
-def _same_scalars(a, b):
+def _leaf_key(x):
+    """What ``DynamicSolver._memo`` keeps of a ControlParams leaf to recognise it: a frozen array by identity, a Python / NumPy scalar by
+    value, a tuple element by element, anything else (writeable arrays, 0-d arrays, lists) by a private copy of its content."""
+    if isinstance(x, tuple):
+        return ("t", tuple(_leaf_key(v) for v in x))
+    if x is None:
+        return ("n",)
+    if isinstance(x, np.ndarray):
+        return ("f", x) if _frozen(x) else ("c", np.array(x, copy=True))
+    if isinstance(x, (int, float, np.generic)):
+        return ("s", x)
     try:
-        if isinstance(a, tuple) or isinstance(b, tuple):
-            return isinstance(a, tuple) and isinstance(b, tuple) and len(a) == len(b) and all(_same_scalars(x, y) for x, y in zip(a, b))
-        if a is None or b is None:
-            return a is b
-        return np.ndim(a) == 0 and np.ndim(b) == 0 and float(a) == float(b)
+        return ("c", np.array(x, copy=True))
     except (TypeError, ValueError):
-        return False
+        return ("x",)
+
+
+def _leaf_unchanged(key, x):
+    kind = key[0]
+    if kind == "t":
+        return isinstance(x, tuple) and len(x) == len(key[1]) and all(_leaf_unchanged(k, v) for k, v in zip(key[1], x))
+    if kind == "n":
+        return x is None
+    if kind == "f":
+        return key[1] is x
+    if kind == "s":
+        return isinstance(x, (int, float, np.generic)) and type(x) is type(key[1]) and x == key[1]
+    if kind == "c":
+        if x is None or isinstance(x, tuple):
+            return False
+        try:
+            a = np.asarray(x)
+        except (TypeError, ValueError):
+            return False
+        return a.shape == key[1].shape and a.dtype == key[1].dtype and np.array_equal(a, key[1])
+    return False
 
 
 def _bcast(x, n):
@@ -113,20 +140,25 @@ class DynamicSolver:
                                 batch=self.batch, tableau=integrator, device=device, lib=lib,
                                 fn_tables=[getattr(f, "table", None) for f in self.con_terms + self.load_terms], streams=streams)
         self._last = None
+        self._memo_pass = None
         self.solve_count = 0          # forward solves run so far (what the engine's resident history belongs to)
 
     # -- ControlParams -> engine arrays -------------------------------------------------------------
     def _memo(self, name, source, build):
         """The flattened form of a ControlParams leaf that rarely changes between members and evaluations (stiffnesses, reference vectors,
-        damping): rebuilt only when the leaf is another object (arrays) or another value (scalars / tuples of scalars)."""
+        damping): rebuilt unless the leaf cannot have changed since (the same frozen array, the same scalar values) or still holds the
+        content it had (an array that may have been written in place in between is compared against a private copy -- once per
+        ``prepare`` for the members that share it)."""
         cache = self.__dict__.setdefault("_memo_cache", {})
         hit = cache.get(name)
-        same = hit is not None and (hit[0] is source or (not isinstance(source, np.ndarray) and not isinstance(hit[0], np.ndarray) and _same_scalars(hit[0], source)))
-        if same:
-            return hit[1]
+        if hit is not None:
+            key, arr, seen_in, seen = hit
+            if (seen_in is not None and seen_in is self._memo_pass and seen is source) or _leaf_unchanged(key, source):
+                cache[name] = (key, arr, self._memo_pass, source)
+                return arr
         arr = build()
         arr.flags.writeable = False
-        cache[name] = (source, arr)
+        cache[name] = (_leaf_key(source), arr, self._memo_pass, source)
         return arr
 
     def _stack(self, flats):
@@ -141,9 +173,9 @@ class DynamicSolver:
             if buf is None or buf[0].shape != shape:
                 buf = bufs[k] = [np.empty(shape), [None] * len(rows)]
             for m, r in enumerate(rows):
-                if buf[1][m] is not r or not isinstance(r, np.ndarray) or r.flags.writeable:
+                if buf[1][m] is not r or not _frozen(r):
                     buf[0][m] = r
-                    buf[1][m] = r if isinstance(r, np.ndarray) and not r.flags.writeable else None     # (only read-only arrays are trusted to be unchanged)
+                    buf[1][m] = r if _frozen(r) else None     # (only frozen arrays are trusted to be unchanged)
             out[k] = buf[0]
         return out
 
@@ -165,7 +197,7 @@ class DynamicSolver:
                  _bcast(bp.k_rot, nbd) if self.spec.bond_model != _b.BOND_SIMPLE_SPRING else zero], 1)),
         }
         cached = _FLAT_CACHE.get(id(cnv)) if mp.inertia is None else None
-        if cached is not None and cached[0]() is cnv and (cached[1] is self.bonds or np.array_equal(cached[1], self.bonds)) and np.array_equal(cached[2], mp.density):
+        if cached is not None and cached[0]() is cnv and _frozen(cnv) and (cached[1] is self.bonds or np.array_equal(cached[1], self.bonds)) and np.array_equal(cached[2], mp.density):
             out["inertia"] = cached[3]        # same design seen through another solver (multi-input problems): reuse
             if self.spec.contact == _b.CONTACT_ANGLE and cached[4] is not None:
                 out["void_angle0"] = cached[4]
@@ -187,8 +219,8 @@ class DynamicSolver:
             elif "void_angle0" not in out:
                 out["void_angle0"] = void_angles0(cnv, self.bonds)
             out["contact"] = np.array([c.min_angle, c.cutoff_angle, c.k_contact], dtype=float)
-        if mp.inertia is None and cached is None and not cnv.flags.writeable:
-            # geometry arrays that come out of the design cache are read-only and shared: remember what was derived from them
+        if mp.inertia is None and cached is None and _frozen(cnv):
+            # geometry arrays that come out of the design cache are frozen and shared: remember what was derived from them
             import weakref
             key = id(cnv)
             if len(_FLAT_CACHE) > 1024:
@@ -263,7 +295,11 @@ class DynamicSolver:
         """Host side of a solve: ``ControlParams`` -> flattened arrays -> device (``dfx_set_params``).  After it the inputs of
         :meth:`solve_resident` are resident in HBM."""
         cps = self._members(control_params)
-        flats = [self._flatten(cp) for cp in cps]
+        self._memo_pass = object()          # (the members of one prepare share their leaves' content checks)
+        try:
+            flats = [self._flatten(cp) for cp in cps]
+        finally:
+            self._memo_pass = None
         self.engine.set_params(**self._stack(flats))
         self._prepared = (cps, flats)
         return cps, flats

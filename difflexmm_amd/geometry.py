@@ -11,6 +11,8 @@ import math
 
 import numpy as np
 
+from .utils import freeze
+
 _CSTEP = 1e-40
 
 
@@ -46,7 +48,7 @@ _PROPS_CACHE = {}
 
 def _remember_props(cnv, area, ip):
     import weakref
-    cnv.flags.writeable = False
+    freeze(cnv)
     key = id(cnv)
     _PROPS_CACHE[key] = (weakref.ref(cnv, lambda _r, k=key: _PROPS_CACHE.pop(k, None)), area, ip)
 

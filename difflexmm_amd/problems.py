@@ -16,7 +16,7 @@ from . import energy as E
 from . import loading as L
 from .dynamics import setup_dynamic_solver
 from .geometry import KagomeGeometry, QuadGeometry, compute_inertia
-from .utils import (ContactParams, ControlParams, GeometricalParams, LigamentParams, MechanicalParams, SolutionData)
+from .utils import (ContactParams, ControlParams, GeometricalParams, LigamentParams, MechanicalParams, SolutionData, freeze)
 
 
 _GEOMETRY_CACHE = {}   # (lattice signature, ids of the design arrays) -> (design arrays, block_centroids, centroid_node_vectors)
@@ -34,8 +34,8 @@ def _signature(geometry):
 
 
 def _remember_geometry(geometry, design, centroids, cnv):
-    centroids.flags.writeable = False
-    cnv.flags.writeable = False
+    freeze(centroids)
+    freeze(cnv)
     if len(_GEOMETRY_CACHE) > 1024:
         _GEOMETRY_CACHE.clear()
     _GEOMETRY_CACHE[(_signature(geometry),) + tuple(id(a) for a in design)] = (tuple(design), centroids, cnv)   # (holds the design arrays: ids stay unique)
@@ -96,9 +96,9 @@ def prefetch_designs(fw, designs):
     cen, cnv, inertia, va = ndm.forward(lib, todo, float(fw.density), void_angles=contact == _b.CONTACT_ANGLE)
     for i, d in enumerate(todo):
         ci, vi, ii, ai = cen[i], cnv[i], inertia[i], (None if va is None else va[i])
-        ii.flags.writeable = False
+        freeze(ii)
         if ai is not None:
-            ai.flags.writeable = False
+            freeze(ai)
         _remember_geometry(fw.geometry, d, ci, vi)
         remember_flat(vi, fw.solve_dynamics.bonds, fw.density, ii, ai)
 

@@ -7,6 +7,27 @@ from typing import Any, Dict, NamedTuple, Optional, Union
 import numpy as np
 
 
+def _frozen(a):
+    """True for an ndarray nobody can write through: it is read-only, and so is every array it is a view of (a read-only view of a
+    writeable array changes when its base does)."""
+    while isinstance(a, np.ndarray):
+        if a.flags.writeable:
+            return False
+        if a.base is None:
+            return True
+        a = a.base
+    return False
+
+
+def freeze(a):
+    """Make ``a`` and every array it is a view of read-only (what ``_frozen`` trusts); returns ``a``."""
+    b = a
+    while isinstance(b, np.ndarray):
+        b.flags.writeable = False
+        b = b.base
+    return a
+
+
 class SolutionData(NamedTuple):
     """utils.py:9-25."""
     block_centroids: Any

@@ -42,7 +42,7 @@ class Case:
 
     def __init__(self, lattice="quads", n=4, nonlinear=True, contact=False, damping=True, seed=0, lib=None,
                  cutoff_deg=-10.0, min_deg=-15.0, batch=1, integrator="dopri5", per_bond_k=False, perturb=0.02, extra_bonds=None,
-                 scramble=None):
+                 scramble=None, damped_blocks=None):
         rng = np.random.default_rng(seed)
         self.rng = rng
         if lattice == "quads":
@@ -103,8 +103,8 @@ class Case:
         ksh = K_SHEAR * (1 + 0.1 * rng.uniform(-1, 1, nbd)) if per_bond_k else K_SHEAR
         kr = K_ROT * (1 + 0.1 * rng.uniform(-1, 1, nbd)) if per_bond_k else K_ROT
         self.contact = contact
-        self.damped = np.arange(self.geo.n_blocks) if damping else None
-        dval = paper_damping() * np.ones((self.geo.n_blocks, 1)) if damping else 0.0
+        self.damped = (np.arange(self.geo.n_blocks) if damped_blocks is None else np.asarray(damped_blocks)) if damping else None
+        dval = paper_damping() * np.ones((len(self.damped), 1)) if damping else 0.0
         self.contact_params = (min_deg * math.pi / 180, cutoff_deg * math.pi / 180, 1.5)
         efn = en_mod.ligament_energy if nonlinear else en_mod.ligament_energy_linearized
         energy = en_mod.build_strain_energy(self.bonds, efn)

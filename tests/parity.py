@@ -263,3 +263,154 @@ def check_several_dofs_of_one_block_share_a_time_function(lib, spi=6, n_out=5):
     for name, g in zip(("amplitude", "loading_rate", "input_delay"), gr):
         e = abs(tree.constraint_params[name] - g.item()) / abs(g.item())
         assert e < RTOL_GRAD, (name, e)
+
+
+# -- every parameter leaf, per member (tests/param_shapes.py builds the parameter images) ---------------------------------------------
+
+RAW_WHICH = ("centroid_node_vectors", "void_angle0", "inertia", "damping", "fn_params")
+
+
+def member_leaf_errors(mine, ref, prefix=""):
+    """relerr of every leaf of every member on its own (``mine`` / ``ref``: one dict of arrays per member): a global maximum over a batch
+    would hide a member whose entries are smaller than its neighbours'.  Returns {(member, leaf): error}."""
+    assert len(mine) == len(ref)
+    errs = {}
+    for m, (a, b) in enumerate(zip(mine, ref)):
+        assert set(a) == set(b), (sorted(a), sorted(b))
+        for k in b:
+            assert np.shape(a[k]) == np.shape(b[k]), (m, k, np.shape(a[k]), np.shape(b[k]))
+            errs[(m, prefix + k)] = relerr(a[k], b[k])
+    return errs
+
+
+def _fields_bar(sc, n_t, seed=77):
+    s, rng = sc.c.solver, np.random.default_rng(seed)
+    fb = rng.normal(size=(len(sc.members), n_t, 2, sc.c.geo.n_blocks, 3))
+    fb.reshape(len(sc.members), n_t, 2, -1)[:, :, :, s.constrained_DOF_ids] = 0.0
+    return fb
+
+
+def _y0(sc, seed=78):
+    rng = np.random.default_rng(seed)
+    y = rng.normal(size=(2, sc.c.geo.n_blocks, 3)) * np.array([0.05, 0.05, 0.02])
+    y[1] *= 5.0
+    return y
+
+
+def run_engine_param_leaves(sc, ts, spi=None, adaptive=False, rtol=1e-5, atol=1e-5):
+    """The engine on every leaf of ``sc`` (a ShapeCase): forward fields, then the reverse sweep twice -- ``vjp_raw`` (no ligament gradients:
+    the persistent reverse loop where it applies) and ``vjp`` (the whole tree: the build that accumulates ligament / damping gradients),
+    each after a forward solve of its own.  Returns per-member dicts of NumPy arrays in the oracle's layout plus the run's stats."""
+    c, s = sc.c, sc.c.solver
+    B, y0 = len(sc.members), _y0(sc)
+    fb = _fields_bar(sc, len(ts))
+    free = s.free_DOF_ids
+    if adaptive:
+        s.rtol, s.atol = rtol, atol
+
+    def solve():
+        out = s(y0, ts, sc.engine_params(), keep_trajectory=True, steps_per_interval=None if adaptive else spi)
+        return np.array(out).reshape(B, len(ts), 2, c.geo.n_blocks, 3), dict(s.stats)
+
+    fields, st_fwd = solve()
+    step_times = [np.concatenate([ts[:1], s.engine.adaptive_step_times(m)]) for m in range(B)] if adaptive else None
+    raw = {k: np.array(v) for k, v in s.vjp_raw(fb if B > 1 else fb[0], which=RAW_WHICH).items()}
+    st_raw = dict(s.adjoint_stats)
+    fields2, st_fwd2 = solve()
+    trees, s0 = s.vjp(fb if B > 1 else fb[0])
+    st_tree = dict(s.adjoint_stats)
+    trees, s0 = (trees, s0) if B > 1 else ([trees], s0[None])
+    out = []
+    zc = np.zeros_like(c.cen)
+    for m, (p, tree) in enumerate(zip(sc.members, trees)):
+        d = {"fields": fields[m].reshape(len(ts), 2, -1)[:, :, free]}
+        gp, mp = tree.geometrical_params, tree.mechanical_params
+        for i, g in enumerate(c.geo.vjp(c.design, gp.centroid_node_vectors, gp.block_centroids)):
+            d[f"design{i}"] = g
+        bp = mp.bond_params
+        d.update(ks=bp.k_stretch, ksh=bp.k_shear, kr=bp.k_rot, refv=bp.reference_vector, inertia=mp.inertia, damping=mp.damping)
+        if c.contact:
+            d.update(min_angle=mp.contact_params.min_angle, cutoff_angle=mp.contact_params.cutoff_angle, k_contact=mp.contact_params.k_contact)
+        for k in ("amplitude", "loading_rate", "input_delay"):
+            d[k] = tree.constraint_params[k]
+        d["state0"] = s0[m].reshape(2, -1)[:, free]
+        # the raw sweep, mapped onto the same leaves
+        r = {}
+        cnv_bar = raw["centroid_node_vectors"][m]
+        if c.contact:
+            cnv_bar = cnv_bar + geo.void_angles0_vjp(c.cnv, c.bonds, raw["void_angle0"][m])
+        for i, g in enumerate(c.geo.vjp(c.design, cnv_bar, zc)):
+            r[f"design{i}"] = g
+        r["inertia"] = raw["inertia"][m].reshape(np.shape(p["inertia"]))
+        rows = raw["damping"][m][c.damped]
+        r["damping"] = rows.reshape(np.shape(p["damping"])) if np.shape(p["damping"]) == rows.shape else rows.sum(0)
+        r["amplitude"], r["loading_rate"], r["input_delay"] = raw["fn_params"][m][0][:3]
+        d["raw"] = r
+        d["fields_again"] = fields2[m].reshape(len(ts), 2, -1)[:, :, free]
+        out.append(d)
+    return dict(members=out, fwd_stats=st_fwd, fwd_stats_again=st_fwd2, raw_stats=st_raw, tree_stats=st_tree, step_times=step_times)
+
+
+def oracle_param_leaves(sc, ts, spi=None, step_times=None, integrator="dopri5"):
+    """torch.autograd through the oracle's unrolled fixed-grid solve (or its replay of the engine's accepted adaptive steps, one list of
+    step boundaries per member) with every parameter leaf on the tape, member by member."""
+    c = sc.c
+    B, y0 = len(sc.members), _y0(sc)
+    fb = _fields_bar(sc, len(ts))
+    out = []
+    for m, p in enumerate(sc.members):
+        design = [T64(d, True) for d in c.design]
+        cnv, cen = c.ogeo.centroid_node_vectors(*design), c.ogeo.block_centroids(*design)
+        names = ["ks", "ksh", "kr", "refv", "inertia", "damping", "amplitude", "loading_rate", "input_delay"]
+        src = dict(ks=p["ks"], ksh=p["ksh"], kr=p["kr"], refv=p["refv"], inertia=p["inertia"], damping=p["damping"], amplitude=7.5,
+                   loading_rate=3000.0, input_delay=1e-5, min_angle=c.contact_params[0], cutoff_angle=c.contact_params[1],
+                   k_contact=c.contact_params[2])
+        if c.contact:
+            names += ["min_angle", "cutoff_angle", "k_contact"]
+        leaves = {k: T64(src[k], True) for k in names}
+        y0t = T64(y0, True)
+        cp = c.oracle_cp(dict(cnv=cnv, cen=cen, **leaves))
+        if step_times is None:
+            osol = c.oracle_solver(integrator="fixed", steps_per_interval=spi, tableau=integrator)
+            hist, _ = OD.solve_fixed_differentiable(osol, c.ogeo, y0t, ts, cp, spi, integrator)
+        else:
+            osol = c.oracle_solver(integrator="adaptive")
+            hist, _ = OD.solve_adaptive_replay_differentiable(osol, c.ogeo, y0t, ts, cp, step_times[m])
+        free = osol.free_DOF_ids
+        L = (hist * T64(fb[m].reshape(len(ts), 2, -1)[:, :, free])).sum()
+        gr = torch.autograd.grad(L, design + [leaves[k] for k in names] + [y0t])
+        d = {"fields": hist.detach().numpy()}
+        for i, g in enumerate(gr[:len(design)]):
+            d[f"design{i}"] = g.numpy()
+        for k, g in zip(names, gr[len(design):-1]):
+            d[k] = g.numpy()
+        d["state0"] = gr[-1].numpy().reshape(2, -1)[:, free]
+        if c.contact:
+            assert np.abs([d[k] for k in ("min_angle", "cutoff_angle", "k_contact")]).max() > 0, "contact inactive: the test would be vacuous"
+        out.append(d)
+    return out
+
+
+def raw_part(ref_members):
+    """The leaves the raw sweep (``vjp_raw(which=RAW_WHICH)``) reaches, out of the oracle's per-member dicts."""
+    keys = [k for k in ref_members[0] if k.startswith("design")] + ["inertia", "damping", "amplitude", "loading_rate", "input_delay"]
+    return [{k: d[k] for k in keys} for d in ref_members]
+
+
+def compare_param_leaves(eng, ref, rtol_fwd=RTOL_TRAJ, rtol_grad=RTOL_GRAD):
+    """Every member, every leaf: the whole-tree sweep, the raw sweep and both forward solves against the oracle."""
+    mine = [{k: v for k, v in d.items() if k not in ("raw", "fields_again")} for d in eng["members"]]
+    errs = member_leaf_errors(mine, ref)
+    errs.update(member_leaf_errors([d["raw"] for d in eng["members"]], raw_part(ref), prefix="raw:"))
+    errs.update(member_leaf_errors([{"fields": d["fields_again"]} for d in eng["members"]], [{"fields": d["fields"]} for d in ref],
+                                   prefix="again:"))
+    bad = {k: v for k, v in errs.items() if not v < (rtol_fwd if k[1].endswith("fields") else rtol_grad)}
+    assert not bad, bad
+    return errs
+
+
+def check_param_leaves(sc, ts, spi=None, adaptive=False, integrator="dopri5", rtol=1e-5, atol=1e-5):
+    """Engine against the oracle on every parameter leaf of ``sc``; returns (engine result, errors)."""
+    eng = run_engine_param_leaves(sc, ts, spi=spi, adaptive=adaptive, rtol=rtol, atol=atol)
+    ref = oracle_param_leaves(sc, ts, spi=spi, step_times=eng["step_times"], integrator=integrator)
+    return eng, compare_param_leaves(eng, ref)

@@ -1,0 +1,79 @@
+"""A ControlParams leaf changed in place between two solves must reach the second solve: the solver caches flattened leaves
+(DynamicSolver._memo, _stack), and an optimiser that updates its stiffness / damping / reference-vector arrays in place would otherwise
+integrate the old values.  Shared by the CPU-port suite and the -m gpu twin; the bar is bit-for-bit equality with a fresh solver
+given a copy (same library, same arithmetic)."""
+import numpy as np
+
+import difflexmm_amd as dm
+
+from .common import DENSITY, K_ROT, K_SHEAR, K_STRETCH, Case
+
+TS = np.linspace(0.0, 3e-4, 3)
+FAST = dict(amplitude=7.5, loading_rate=3000.0, input_delay=1e-5)
+
+
+def _params(c, leaves):
+    return dm.ControlParams(
+        dm.GeometricalParams(leaves.get("cen", c.cen), leaves.get("cnv", c.cnv)),
+        dm.MechanicalParams(dm.LigamentParams(leaves["ks"], K_SHEAR, K_ROT, leaves["refv"]), DENSITY, None, leaves["damping"],
+                            dm.ContactParams(*c.contact_params)),
+        constraint_params=dict(FAST))
+
+
+def _solve_and_vjp(c, cp):
+    fields = np.array(c.solver(np.zeros((2, c.geo.n_blocks, 3)), TS, cp, keep_trajectory=True, steps_per_interval=6))
+    fb = np.random.default_rng(5).normal(size=fields.shape)
+    fb.reshape(len(TS), 2, -1)[:, :, c.solver.constrained_DOF_ids] = 0.0
+    tree, s0 = c.solver.vjp(fb)
+    mp = tree.mechanical_params
+    return dict(fields=fields, cnv=np.array(tree.geometrical_params.centroid_node_vectors), ks=np.array(mp.bond_params.k_stretch),
+                refv=np.array(mp.bond_params.reference_vector), damping=np.array(mp.damping), s0=np.array(s0))
+
+
+def _case(lib):
+    return Case("quads", 5, True, True, seed=21, lib=lib, cutoff_deg=42.0)
+
+
+def _leaves(c):
+    nbd = len(c.bonds)
+    rng = np.random.default_rng(9)
+    return dict(ks=K_STRETCH * (1 + 0.1 * rng.uniform(-1, 1, nbd)), refv=np.broadcast_to(c.refv, (nbd, 2)).copy(),
+                damping=np.array(c.dval, dtype=float))
+
+
+def _assert_same(a, b):
+    for k in b:
+        assert np.array_equal(a[k], b[k]), (k, np.abs(a[k] - b[k]).max())
+
+
+def check_in_place_change(lib, leaf):
+    """solve; change ``leaf`` in place; solve again and vjp: equal to a fresh solver given a copy, and different from the first solve."""
+    c = _case(lib)
+    lv = _leaves(c)
+    cp = _params(c, lv)
+    first = _solve_and_vjp(c, cp)
+    key = {"damping": "damping", "reference_vector": "refv", "k_stretch": "ks"}[leaf]
+    lv[key] *= {"damping": 50.0, "refv": 1.05, "ks": 1.2}[key]       # in place: the ControlParams still holds the same array
+    again = _solve_and_vjp(c, cp)
+    fresh_case = _case(lib)
+    fresh = _solve_and_vjp(fresh_case, _params(fresh_case, {k: v.copy() for k, v in lv.items()}))
+    assert not np.array_equal(first["fields"], fresh["fields"]), "the change does not change the fields: the test would be vacuous"
+    _assert_same(again, fresh)
+
+
+def check_read_only_view_of_writeable_base(lib):
+    """Node vectors passed as a read-only VIEW of an array that stays writeable: the base changes in place between two solves."""
+    c = _case(lib)
+    lv = _leaves(c)
+    base = np.array(c.cnv, dtype=float)
+    view = base.view()
+    view.flags.writeable = False
+    lv["cnv"] = view
+    cp = _params(c, lv)
+    first = _solve_and_vjp(c, cp)
+    base *= 1.01
+    again = _solve_and_vjp(c, cp)
+    fresh_case = _case(lib)
+    fresh = _solve_and_vjp(fresh_case, _params(fresh_case, dict(lv, cnv=base.copy())))
+    assert not np.array_equal(first["fields"], fresh["fields"])
+    _assert_same(again, fresh)
