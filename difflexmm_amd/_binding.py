@@ -61,10 +61,11 @@ EXPORTS = ["dfx_create", "dfx_destroy", "dfx_last_error", "dfx_set_params", "dfx
            "dfx_objective_kinetic", "dfx_adjoint_kinetic", "dfx_kinetic_value_and_grad", "dfx_response_data", "dfx_rhs", "dfx_rhs_vjp", "dfx_energy",
            "dfx_device_count", "dfx_version", "dfx_share_checkpoint", "dfx_abi_layout", "dfx_member_status", "dfx_set_failure_policy",
            "dfx_test_set_spin_limit", "dfx_design_forward", "dfx_design_vjp"]
-# multi-GPU collective (RCCL inside libdfx) and device helpers: HIP library only
+# multi-GPU collective (RCCL inside libdfx), device helpers and forward mode: HIP library only
 COMM_EXPORTS = ["dfx_comm_unique_id", "dfx_comm_init", "dfx_comm_destroy", "dfx_comm_rccl_version", "dfx_comm_rank", "dfx_comm_size",
                 "dfx_gather_objectives", "dfx_reduce_grads", "dfx_comm_allreduce", "dfx_comm_barrier", "dfx_comm_last_error",
-                "dfx_mem_info", "dfx_device_synchronize", "dfx_kinetic_value_and_grad_device", "dfx_download", "dfx_forward_kinetic_value_and_grad"]
+                "dfx_mem_info", "dfx_device_synchronize", "dfx_kinetic_value_and_grad_device", "dfx_download", "dfx_forward_kinetic_value_and_grad",
+                "dfx_forward_tangent"]
 EXPORTS = EXPORTS + COMM_EXPORTS
 
 
@@ -126,6 +127,9 @@ def declare(lib):
     for name in EXPORTS:
         if name not in ("dfx_last_error", "dfx_version", "dfx_comm_last_error") and (name not in COMM_EXPORTS or hasattr(lib, name)):
             getattr(lib, name).restype = C.c_int
+    if hasattr(lib, "dfx_forward_tangent"):      # (the CPU port of the oracle has no forward mode)
+        lib.dfx_forward_tangent.argtypes = [H, _dp, _dp, C.POINTER(dfx_params), _dp, C.c_int32, _ip, _dp, C.c_int32, _dp, _dp,
+                                            C.POINTER(dfx_stats)]
     if hasattr(lib, "dfx_comm_init"):
         lib.dfx_comm_unique_id.argtypes = [C.c_char_p]
         lib.dfx_comm_init.argtypes = [C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(H)]
@@ -334,6 +338,51 @@ class Engine:
                                                   int(bool(keep_trajectory)), _ptr(fields), C.byref(st)), "dfx_forward_grid")
         self.n_timepoints = T
         return fields, _stats(st)
+
+    @property
+    def has_forward_tangent(self):
+        return hasattr(self.lib, "dfx_forward_tangent")
+
+    def forward_tangent(self, state0, state0_dot, params_dot, timepoints, steps_per_interval, step_times=None):
+        """Primal fields and their directional derivative along (state0_dot, params_dot) of the fixed-grid solve (``dfx_forward_tangent``)
+        on the parameters of the last :meth:`set_params`.  ``params_dot``: arrays by ``dfx_params`` field name (a missing one: zero
+        tangent); ``timepoints`` (T,) or (batch, T) (then every member its own grid, as :meth:`forward`).  Returns (fields, fields_dot, stats)."""
+        if not self.has_forward_tangent:
+            raise NotImplementedError(f"forward mode: the library {getattr(self.lib, '_name', self.lib)!r} has no dfx_forward_tangent "
+                                      "(the CPU port of the oracle is reverse mode only; build the HIP engine)")
+        B, nb = self.batch, self.n_blocks
+        state0 = _f64(state0, (B, 2, nb, 3)) if state0 is not None else None
+        state0_dot = _f64(state0_dot, (B, 2, nb, 3)) if state0_dot is not None else None
+        ts = _f64(timepoints)
+        T = ts.shape[-1]
+        spis = np.ascontiguousarray(np.broadcast_to(steps_per_interval, (max(T - 1, 0),)), dtype=np.int32)
+        n = int(spis.sum())
+        per_member = ts.ndim == 2
+        if per_member:
+            if ts.shape[0] != B:
+                raise ValueError(f"per-member timepoints must be (batch={B}, T)")
+            if step_times is None:      # equal steps inside every member's own intervals (as forward)
+                step_times = np.stack([np.concatenate([a + (b - a) * np.arange(k) / k for a, b, k in zip(row[:-1], row[1:], spis)] + [row[-1:]])
+                                       for row in ts])
+            step_times = _f64(step_times, (B, n + 1))
+        elif step_times is not None:
+            step_times = _f64(step_times, (n + 1,))
+        sh = self.shapes()
+        p = dfx_params()
+        keep = []
+        for name in _PARAM_FIELDS + ["block_centroids"]:
+            a = params_dot.get(name) if params_dot else None
+            if a is None:
+                continue
+            a = _f64(a, sh[name])
+            keep.append(a)
+            setattr(p, name, _ptr(a))
+        fields, fields_dot = np.empty((B, T, 2, nb, 3)), np.empty((B, T, 2, nb, 3))
+        st = dfx_stats()
+        self._check(self.lib.dfx_forward_tangent(self._h, _ptr(state0), _ptr(state0_dot), C.byref(p), _ptr(ts), T, spis.ctypes.data_as(_ip),
+                                                 _ptr(step_times), int(per_member), _ptr(fields), _ptr(fields_dot), C.byref(st)),
+                    "dfx_forward_tangent")
+        return fields, fields_dot, _stats(st)
 
     def adaptive_step_counts(self):
         """(batch, T-1) accepted steps of the last forward_adaptive per member and output interval."""

@@ -222,11 +222,14 @@ struct BondPartner {
 // (ro) / (rp) are the centroid->node vectors of the two bonded nodes, (lx,ly) the
 // reference vector oriented node1 -> node2.
 // T: type of the kinematic state (double, or Dual in the reverse sweep); P: type of the parameters -- double in every
-// kernel: a parameter carries no epsilon part, and typing it as a Dual with a zero epsilon would cost an extra multiply-add
-// per product (x * 0.0 cannot be folded away under IEEE semantics).
-template <int MODEL, class T, class P>
-DFX_HD void bond_grad(const BlockRec<T>& o, const BlockRec<T>& p, P rox, P roy, P rpx, P rpy,
-                      P lx, P ly, double l0v, double il0v, P ks, P ksh, P kr, double sgn, BondGrad<T>& g, BondPartner<T>* pg = nullptr) {
+// kernel but the tangent stage (dfx_tangent.h, where parameters carry their tangents): a parameter carries no epsilon part,
+// and typing it as a Dual with a zero epsilon would cost an extra multiply-add per product (x * 0.0 cannot be folded away
+// under IEEE semantics).
+// L: type of |l0| and 1/|l0| -- double in bond_grad (per-solve constants), P in bond_grad_p (the tangent solve, dfx_tangent.h, seeds the
+// reference vector with its tangent, so |l0| carries one too).
+template <int MODEL, class T, class P, class L>
+DFX_HD void bond_grad_l(const BlockRec<T>& o, const BlockRec<T>& p, P rox, P roy, P rpx, P rpy,
+                        P lx, P ly, L l0v, L il0v, P ks, P ksh, P kr, double sgn, BondGrad<T>& g, BondPartner<T>* pg) {
   // rotation of own / partner block from the half angles
   T co = o.ch * o.ch - o.sh * o.sh, so = 2.0 * (o.sh * o.ch);
   T cp = p.ch * p.ch - p.sh * p.sh, sp = 2.0 * (p.sh * p.ch);
@@ -236,10 +239,10 @@ DFX_HD void bond_grad(const BlockRec<T>& o, const BlockRec<T>& p, P rox, P roy, 
   T dUx = sgn * ((o.x + qox - rox) - (p.x + qpx - rpx));
   T dUy = sgn * ((o.y + qoy - roy) - (p.y + qpy - rpy));
   T kap = sgn * (o.th - p.th);  // theta_2 - theta_1
-  // l0 = |(lx, ly)| and 1/l0 are per-solve constants (the reference vector is a parameter: it carries no
-  // epsilon part, and every derivative w.r.t. it below is written in closed form)
+  // l0 = |(lx, ly)| and 1/l0 are per-solve constants (bond_grad: the reference vector is a parameter that carries no
+  // epsilon part, and every derivative w.r.t. it below is written in closed form; bond_grad_p: of type P, tangent included)
   P l02 = lx * lx + ly * ly;
-  const double l0 = l0v, il0 = il0v;
+  const L l0 = l0v, il0 = il0v;
   T gbx, gby, gtb;  // dE/d(dU), dE/d(mean rotation)
   if (MODEL == kNonlinear) {
     // energy.py:139-155,172-176
@@ -300,7 +303,7 @@ DFX_HD void bond_grad(const BlockRec<T>& o, const BlockRec<T>& p, P rox, P roy, 
     gbx = (kse * lx - kshe * ly) * il0;
     gby = (kse * ly + kshe * lx) * il0;
     gtb = -(kshe * l0);
-    const double il02 = il0 * il0;
+    const L il02 = il0 * il0;
     T c3 = crs * (il0 * il02);
     g.lx = kse * (dUx * il0 - es * (lx * il02)) + kshe * (dUy * il0 - c3 * lx - tb * (lx * il0));
     g.ly = kse * (dUy * il0 - es * (ly * il02)) + kshe * (-(dUx * il0) - c3 * ly - tb * (ly * il0));
@@ -320,6 +323,18 @@ DFX_HD void bond_grad(const BlockRec<T>& o, const BlockRec<T>& p, P rox, P roy, 
     pg->rx = -(sgn * (cp * gbx + sp * gby - gbx));
     pg->ry = -(sgn * (cp * gby - sp * gbx - gby));
   }
+}
+
+template <int MODEL, class T, class P>
+DFX_HD void bond_grad(const BlockRec<T>& o, const BlockRec<T>& p, P rox, P roy, P rpx, P rpy,
+                      P lx, P ly, double l0v, double il0v, P ks, P ksh, P kr, double sgn, BondGrad<T>& g, BondPartner<T>* pg = nullptr) {
+  bond_grad_l<MODEL, T, P, double>(o, p, rox, roy, rpx, rpy, lx, ly, l0v, il0v, ks, ksh, kr, sgn, g, pg);
+}
+// The same with |l0| and 1/|l0| of the parameter type: P = Dual carries their tangents (d|l0| = l0 . dl0 / |l0|).
+template <int MODEL, class T, class P>
+DFX_HD void bond_grad_p(const BlockRec<T>& o, const BlockRec<T>& p, P rox, P roy, P rpx, P rpy,
+                        P lx, P ly, P l0v, P il0v, P ks, P ksh, P kr, double sgn, BondGrad<T>& g) {
+  bond_grad_l<MODEL, T, P, P>(o, p, rox, roy, rpx, rpy, lx, ly, l0v, il0v, ks, ksh, kr, sgn, g, nullptr);
 }
 
 // Angle-based contact of one bond (energy.py:333-361 on the two void angles of energy.py:204-219).

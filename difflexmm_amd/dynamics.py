@@ -22,7 +22,8 @@ import numpy as np
 
 from . import _binding as _b
 from .energy import _EnergyFn
-from .geometry import (DOFsInfo, compute_inertia, compute_inertia_vjp, void_angles0, void_angles0_vjp)
+from .geometry import (DOFsInfo, compute_inertia, compute_inertia_jvp, compute_inertia_vjp, void_angles0, void_angles0_jvp,
+                       void_angles0_vjp)
 from .loading import as_time_function, zero
 from .utils import (ContactParams, ControlParams, GeometricalParams, MechanicalParams, _frozen)
 
@@ -232,6 +233,58 @@ class DynamicSolver:
             out["fn_params"] = np.stack(fnp)
         return out
 
+    def _flatten_tangent(self, cp: ControlParams, cp_dot):
+        """The tangent of :meth:`_flatten` at ``cp`` along ``cp_dot`` (a ``ControlParams``-shaped tree of tangents; a leaf of None, a
+        missing sub-tree or a missing dict key is a zero tangent): the same arrays, the same broadcasts (scalar stiffnesses, damping on
+        ``damped_blocks`` only), the same zeroing of what a spring model does not read, and the exact host derivatives of the derived
+        leaves -- inertia through compute_inertia (when ``mechanical_params.inertia`` is None), void angles through void_angles0,
+        time-function parameters through each term's ``resolve``.  Linear in ``cp_dot``."""
+        gp, mp = cp.geometrical_params, cp.mechanical_params
+        gd = getattr(cp_dot, "geometrical_params", None)
+        md = getattr(cp_dot, "mechanical_params", None)
+
+        def leaf(tree, name):
+            v = getattr(tree, name, None) if tree is not None else None
+            return 0.0 if v is None else v
+        cnv = np.asarray(gp.centroid_node_vectors, dtype=float)
+        cnv_dot = np.broadcast_to(np.asarray(leaf(gd, "centroid_node_vectors"), dtype=float), cnv.shape).copy()
+        nbd = len(self.bonds)
+        bp = mp.bond_params
+        bd = getattr(md, "bond_params", None)
+        zero = np.zeros(nbd)
+        refv_dot = leaf(bd, "reference_vector") if hasattr(bp, "reference_vector") else 0.0
+        out = {
+            "centroid_node_vectors": cnv_dot,
+            "reference_vector": np.broadcast_to(np.asarray(refv_dot, dtype=float), (nbd, 2)).copy(),
+            "k_bond": np.stack([_bcast(leaf(bd, "k_stretch"), nbd),
+                                _bcast(leaf(bd, "k_shear"), nbd) if self.spec.bond_model in (_b.BOND_LINEARIZED, _b.BOND_NONLINEAR) else zero,
+                                _bcast(leaf(bd, "k_rot"), nbd) if self.spec.bond_model != _b.BOND_SIMPLE_SPRING else zero], 1),
+        }
+        if mp.inertia is None:
+            out["inertia"] = compute_inertia_jvp(cnv, mp.density, cnv_dot, leaf(md, "density"))
+        else:
+            out["inertia"] = np.broadcast_to(np.asarray(leaf(md, "inertia"), dtype=float).reshape(-1), (self.n_blocks * 3,)).reshape(
+                self.n_blocks, 3).copy()
+        damping = np.zeros((self.n_blocks, 3))
+        if self.damped_blocks is not None:
+            damping[self.damped_blocks] = np.broadcast_to(np.asarray(leaf(md, "damping"), dtype=float), (len(self.damped_blocks), 3))
+        out["damping"] = damping
+        if self.spec.contact:
+            cd = getattr(md, "contact_params", None)
+            if self.spec.contact == _b.CONTACT_DISTANCE:
+                out["block_centroids"] = np.broadcast_to(np.asarray(leaf(gd, "block_centroids"), dtype=float).reshape(-1),
+                                                         (self.n_blocks * 2,)).reshape(self.n_blocks, 2).copy()
+            else:
+                out["void_angle0"] = void_angles0_jvp(cnv, self.bonds, cnv_dot)
+            out["contact"] = np.array([leaf(cd, "min_angle"), leaf(cd, "cutoff_angle"), leaf(cd, "k_contact")], dtype=float)
+        con_dot = getattr(cp_dot, "constraint_params", None)
+        load_dot = getattr(cp_dot, "loading_params", None)
+        fnp = [f.resolve_jvp(cp.constraint_params, con_dot) for f in self.con_terms] + \
+              [f.resolve_jvp(cp.loading_params, load_dot) for f in self.load_terms]
+        if fnp:
+            out["fn_params"] = np.stack(fnp)
+        return out
+
     def _members(self, control_params):
         cps = list(control_params) if isinstance(control_params, (list, tuple)) and not isinstance(control_params, ControlParams) \
             else [control_params]
@@ -368,6 +421,81 @@ class DynamicSolver:
         self._last_fields = fields
         self.stats = dict(stats, steps_per_interval=spi, step_times=step_times, step_control=control)
         return fields
+
+    # -- forward mode ------------------------------------------------------------------------------------
+    def jvp(self, state0, timepoints, control_params, state0_dot, control_params_dot, steps_per_interval=None, step_times=None):
+        """Forward-mode derivative of the FIXED-GRID solve:  ``fields, fields_dot = jvp(state0, timepoints, control_params, state0_dot,
+        control_params_dot)``, ``fields_dot = d fields / d(state0, control_params) . (state0_dot, control_params_dot)`` with the steps frozen
+        (``dfx_forward_tangent``: one stage launch per Runge-Kutta stage computes the primal and the tangent together).  This is the map
+        :meth:`vjp` transposes: on the same grid  ``sum(fields_bar * fields_dot) == <vjp(fields_bar), tangent>``.
+
+        * ``control_params_dot``: a ``ControlParams``-shaped tree of tangents (the shape :meth:`vjp` returns), or a list of them, one per
+          member; a leaf of None, a missing sub-tree or a missing key of ``constraint_params`` / ``loading_params`` is a zero tangent.
+          ``state0_dot`` (None: zero) has the shape of ``state0``.  Several directions for one design are members that share the design,
+          each with its own tangent (a ``jacfwd`` over k leaves = k members).  Tangents of derived leaves are exact host derivatives:
+          inertia (through compute_inertia when ``mechanical_params.inertia`` is None), void angles, time-function parameters.
+        * ``fields`` is the primal history of the same call; on the same grid it equals ``solve_dynamics(..., steps_per_interval=...,
+          step_times=...)`` to rounding.
+        * ``steps_per_interval=None`` (and no default grid set at setup): the grid the adaptive controller chooses is frozen first
+          (:meth:`adaptive_grid`, as the ``"adaptive-grid"`` path of a differentiable solve) and the tangent pass runs on it.  These
+          ``fields`` are then the frozen-grid RE-INTEGRATION, not the adaptive solve's dense output: they differ from what
+          ``solve_dynamics(state0, timepoints, control_params)`` returns by O(tolerance).  ``self.stats`` reports the grid.
+        * rows of PRESCRIBED DOFs in ``fields_dot`` are  sum_f coef (dg_f/dp . dp, dg_f'/dp . dp)  from each term's ``param_partials``,
+          as :meth:`vjp` computes their cotangents -- a central difference, accurate to ~1e-9 relative, not to rounding.
+        * not supported (``RuntimeError`` from the engine): lattices whose nodes carry more than one ligament.  The CPU port of the
+          oracle has no forward mode (``NotImplementedError``).
+
+        The solver's trajectory checkpoint is not kept by this call: a ``vjp`` must follow a solve with ``keep_trajectory=True``."""
+        if not self.engine.has_forward_tangent:
+            lib = self.engine.lib
+            raise NotImplementedError(f"DynamicSolver.jvp: the library {getattr(lib, '_name', lib)!r} has no dfx_forward_tangent "
+                                      "(forward mode runs on the HIP engine only; the CPU port of the oracle is reverse mode only)")
+        cps, flats = self.prepare(control_params)
+        self._last = None                   # (dfx_set_params dropped the handle's checkpoint)
+        dots = list(control_params_dot) if isinstance(control_params_dot, (list, tuple)) and not isinstance(control_params_dot, ControlParams) \
+            else [control_params_dot]
+        if len(dots) == 1 and self.batch > 1:
+            dots = dots * self.batch
+        if len(dots) != self.batch:
+            raise ValueError(f"expected {self.batch} tangents, got {len(dots)}")
+        tflats = [self._flatten_tangent(cp, cd) for cp, cd in zip(cps, dots)]
+        params_dot = {k: np.stack([f[k] for f in tflats]) for k in tflats[0]}
+        ts = np.asarray(timepoints, dtype=float)
+        B, nb = self.batch, self.n_blocks
+
+        def members(x):
+            if x is None:
+                return None
+            x = np.asarray(x, dtype=float)
+            return np.broadcast_to(x, (B,) + x.shape) if x.ndim == 3 else x
+        s0, s0d = members(state0), members(state0_dot)
+        spi = steps_per_interval if steps_per_interval is not None else self.steps_per_interval
+        control = "fixed"
+        if spi is None:
+            if ts.ndim == 2:
+                raise ValueError("per-member timepoints need steps_per_interval (the adaptive controller chooses one grid per call)")
+            spi, step_times = self.adaptive_grid(np.zeros((B, 2, nb, 3)) if s0 is None else s0, ts, flats)
+            control = "adaptive-grid"
+        fields, fields_dot, stats = self.engine.forward_tangent(s0, s0d, params_dot, ts, spi, step_times=step_times)
+        self.stats = dict(stats, steps_per_interval=spi, step_times=step_times, step_control=control)
+        if len(self.constrained_pairs) and self.con_terms:
+            n_con = len(self.constrained_pairs)
+            dofs = self.constrained_pairs[:, 0] * 3 + self.constrained_pairs[:, 1]
+            for m, (cp, cd) in enumerate(zip(cps, dots)):
+                fdm = fields_dot[m].reshape(ts.shape[-1], 2, -1)
+                fdm[:, :, dofs] = 0.0
+                for term in self.con_terms:
+                    dp = term.resolve_jvp(cp.constraint_params, getattr(cd, "constraint_params", None))
+                    if not np.any(dp):
+                        continue
+                    p = term.resolve(cp.constraint_params)
+                    vec = _bcast(term.vector, n_con)
+                    for k, t in enumerate(ts[m] if ts.ndim == 2 else ts):
+                        fdm[k, 0, dofs] += vec * float(term.param_partials(float(t), p, "value") @ dp)
+                        fdm[k, 1, dofs] += vec * float(term.param_partials(float(t), p, "rate") @ dp)
+        if self.batch == 1 and not isinstance(control_params, list):
+            return fields[0], fields_dot[0]
+        return fields, fields_dot
 
     # -- reverse mode ------------------------------------------------------------------------------------
     def vjp(self, fields_bar):

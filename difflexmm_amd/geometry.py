@@ -177,6 +177,23 @@ def polygon_props_vjp(v, area_bar=None, cen_bar=None, ip_bar=None):
     return out
 
 
+def polygon_props_jvp(v, v_dot):
+    """Tangents of polygon_props' (area, centroid, polar moment) along a tangent v_dot (..., n, 2) of the vertices: the closed-form
+    gradients of polygon_props_vjp contracted with v_dot (exact, no differences)."""
+    v = np.asarray(v, dtype=float)
+    vd = np.asarray(v_dot, dtype=float)
+    one = np.ones(v.shape[:-2])
+    zero = np.zeros(v.shape[:-2])
+
+    def along(g):
+        return (g * vd).sum((-2, -1))
+    area_dot = along(polygon_props_vjp(v, area_bar=one))
+    cen_dot = np.stack([along(polygon_props_vjp(v, cen_bar=np.stack([one, zero], -1))),
+                        along(polygon_props_vjp(v, cen_bar=np.stack([zero, one], -1)))], -1)
+    ip_dot = along(polygon_props_vjp(v, ip_bar=one))
+    return area_dot, cen_dot, ip_dot
+
+
 def compute_inertia(vertices, density):
     """geometry.py:144-160 -> (n_blocks, 3) = [rho A, rho A, rho I_p]."""
     hit = _recall_props(vertices)
@@ -198,6 +215,18 @@ def compute_inertia_vjp(vertices, density, inertia_bar):
     v_bar = polygon_props_vjp(vertices, area_bar=rho * gm, ip_bar=rho * inertia_bar[:, 2])
     rho_bar = gm * area + inertia_bar[:, 2] * ip
     return v_bar, (rho_bar.sum() if np.ndim(density) == 0 else rho_bar)
+
+
+def compute_inertia_jvp(vertices, density, vertices_dot, density_dot=None):
+    """Tangent of compute_inertia's result, (n_blocks, 3), along (vertices_dot, density_dot) (density_dot None: 0)."""
+    vertices = np.asarray(vertices, dtype=float)
+    hit = _recall_props(vertices)
+    area, ip = hit if hit is not None else polygon_props(vertices)[::2]
+    area_dot, _, ip_dot = polygon_props_jvp(vertices, vertices_dot)
+    rho = np.broadcast_to(np.asarray(density, dtype=float), area.shape)
+    rho_dot = np.broadcast_to(np.asarray(0.0 if density_dot is None else density_dot, dtype=float), area.shape)
+    m_dot = rho_dot * area + rho * area_dot
+    return np.column_stack((m_dot, m_dot, rho_dot * ip + rho * ip_dot))
 
 
 def DOFsInfo(n_blocks, constrained_block_DOF_pairs):
@@ -276,6 +305,19 @@ def void_angles0(cnv, bonds):
     cnv = np.asarray(cnv, dtype=float)
     _, e1p, e1m, e2p, e2m = _edge_pairs(cnv, bonds)
     return np.stack([_angle(e2m, e1p), _angle(e1m, e2p)], 1)   # geometry.py:248-249
+
+
+def void_angles0_jvp(cnv, bonds, cnv_dot):
+    """Tangent (n_bonds, 2) of void_angles0 along cnv_dot:  phi = atan2(u x w, u . w)  =>  dphi = -perp(u) . du / |u|^2 + perp(w) . dw / |w|^2,
+    perp(a) = (-a_y, a_x) (the gradients of void_angles0_vjp)."""
+    cnv = np.asarray(cnv, dtype=float)
+    _, e1p, e1m, e2p, e2m = _edge_pairs(cnv, bonds)
+    _, d1p, d1m, d2p, d2m = _edge_pairs(np.asarray(cnv_dot, dtype=float), bonds)      # (the edge vectors are linear in cnv)
+
+    def dangle(u, w, du, dw):
+        return (-(-u[:, 1] * du[:, 0] + u[:, 0] * du[:, 1]) / (u ** 2).sum(1)
+                + (-w[:, 1] * dw[:, 0] + w[:, 0] * dw[:, 1]) / (w ** 2).sum(1))
+    return np.stack([dangle(e2m, e1p, d2m, d1p), dangle(e1m, e2p, d1m, d2p)], 1)
 
 
 def void_angles0_vjp(cnv, bonds, phi_bar):

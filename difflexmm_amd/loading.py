@@ -15,6 +15,12 @@ from ._binding import (DFX_FN_PARAMS, FN_CONSTANT, FN_HARMONIC, FN_PULSE, FN_RAM
                        FN_SECH2TANH, FN_TABLE, FN_ZERO)
 
 
+def _tangent(params_dot, name):
+    """Entry ``name`` of a tangent dict; a missing dict, key or value is a zero tangent."""
+    v = None if params_dot is None else params_dot.get(name)
+    return 0.0 if v is None else float(v)
+
+
 class TimeFunction:
     """vector * g(t; params).  ``vector`` is a scalar or one coefficient per constrained / loaded DOF."""
     type_id = FN_ZERO
@@ -38,6 +44,15 @@ class TimeFunction:
                     raise KeyError(f"{type(self).__name__}: parameter '{v}' missing from the params dict")
                 v = params_dict[v]
             out[i] = float(v)
+        return out
+
+    def resolve_jvp(self, params_dict, params_dot):
+        """Tangent of :meth:`resolve` (5 numbers) along ``params_dot``, a dict keyed like ``params_dict`` (a missing key or None: 0)."""
+        out = np.zeros(DFX_FN_PARAMS)
+        for i, n in enumerate(self.param_names):
+            v = self.params[n]
+            if isinstance(v, str):
+                out[i] = _tangent(params_dot, v)
         return out
 
     def scatter_grad(self, grad5, out_dict, params_dict=None):
@@ -180,6 +195,16 @@ class DelayedPulse(Pulse):
     def resolve(self, params_dict):
         out = super().resolve(params_dict)
         out[2] += self._lookup(self.strain, params_dict) / self._lookup(self.strain_rate, params_dict)
+        return out
+
+    def resolve_jvp(self, params_dict, params_dot):
+        out = super().resolve_jvp(params_dict, params_dot)
+        # delay = strain / rate + input_delay:  d delay = d strain / rate - strain d rate / rate^2
+        eps, rate = self._lookup(self.strain, params_dict), self._lookup(self.strain_rate, params_dict)
+        if isinstance(self.strain, str):
+            out[2] += _tangent(params_dot, self.strain) / rate
+        if isinstance(self.strain_rate, str):
+            out[2] -= _tangent(params_dot, self.strain_rate) * eps / rate ** 2
         return out
 
     def scatter_grad(self, grad5, out_dict, params_dict=None):

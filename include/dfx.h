@@ -226,6 +226,23 @@ int dfx_adaptive_step_times(dfx_handle* h, int32_t member, double* times, int64_
  * fields_bar: (batch, T, 2, n_blocks, 3) cotangent of `fields`. */
 int dfx_adjoint(dfx_handle* h, const double* fields_bar, dfx_grads* grads, dfx_stats* stats);
 
+/* Forward mode: the directional derivative of the fixed-grid solve (dfx_forward_grid, or dfx_forward_grid_members when
+ * per_member_times != 0: timepoints (batch, n_timepoints), step_times (batch, sum(steps_per_interval) + 1) required) along
+ * (state0_dot, params_dot), with its steps frozen.  fields (batch, T, 2, n_blocks, 3) is the primal history of the same call (equal to
+ * dfx_forward_grid's to rounding); fields_dot = d fields / d(state0, params) . (state0_dot, params_dot).  On the same grid this is the
+ * exact transpose of dfx_adjoint:  sum(fields_bar * fields_dot) == <dfx_adjoint(fields_bar), (state0_dot, params_dot)>.
+ * params_dot has the shapes of dfx_params; a NULL array (or params_dot == NULL, state0_dot == NULL) is a zero tangent.  The primal
+ * parameters are the ones dfx_set_params left on the handle; state0 == NULL: at rest.  The rows of PRESCRIBED DOFs in fields_dot hold the
+ * tangent of c(t) in the position rows and 0 in the velocity rows (the caller assembles dc'/dp . dp if it needs them).
+ * One stage launch per Runge-Kutta stage, primal and tangent in one pass (Dual numbers); supported: every bond model, no / angle-based /
+ * distance-based contact, 3 and 4 nodes per block; nodes with more than one ligament return 1.  The call keeps its buffers to itself: the
+ * trajectory checkpoint and the resident history of the last dfx_forward are left untouched, so a later dfx_adjoint still reverses THAT
+ * solve.  Non-finite values in fields or fields_dot: return 3. */
+int dfx_forward_tangent(dfx_handle* h, const double* state0, const double* state0_dot, const dfx_params* params_dot,
+                        const double* timepoints, int32_t n_timepoints, const int32_t* steps_per_interval,
+                        const double* step_times, int32_t per_member_times,
+                        double* fields, double* fields_dot, dfx_stats* stats);
+
 /* Device-resident variants for benchmarking: the forward keeps the (T, ...) fields on the device and
  * the cotangent is the target-kinetic-energy objective  sum_t sum_{b in target} m_bd v_bd^2 / 2
  * (energy.py:494-499, problems/quads_focusing.py:447-467), evaluated on the device. */

@@ -1,0 +1,262 @@
+"""-m gpu: forward mode (DynamicSolver.jvp -> dfx_forward_tangent) against torch.autograd through the oracle's fixed-grid solve, as the
+transpose of the discrete adjoint at size, against central differences at size, and its grid semantics."""
+import numpy as np
+import pytest
+import torch
+
+import difflexmm_amd as dm
+from difflexmm_amd import geometry as geo
+from oracle import ref_dynamics as OD
+
+from .common import DENSITY, Case, relerr
+from .parity import RTOL_GRAD, T64
+
+pytestmark = pytest.mark.gpu
+
+FAST = dict(amplitude=7.5, loading_rate=3000.0, input_delay=1e-5)     # a full pulse inside the short windows below
+
+
+def _case(lattice, n, nonlinear, contact, integrator="dopri5", seed=5, batch=1, **kw):
+    c = Case(lattice, n, nonlinear, contact, seed=seed, cutoff_deg=125.0 if lattice == "kagome" else 42.0, integrator=integrator,
+             batch=batch, **kw)
+    c.cp = c.cp._replace(constraint_params=dict(FAST))
+    return c
+
+
+def _explicit_inertia(c):
+    """The Case's tree with inertia given as a leaf (so the tangent can seed it directly)."""
+    inertia = geo.compute_inertia(c.cnv, DENSITY)
+    return c.cp._replace(mechanical_params=c.cp.mechanical_params._replace(inertia=inertia)), inertia
+
+
+def _tangent_tree(c, rng, inertia=None, scale=1.0):
+    """A tangent of every leaf of the Case's tree (relative size ~ scale)."""
+    mp = c.cp.mechanical_params
+    bp = mp.bond_params
+
+    def d(x):
+        return scale * rng.normal(size=np.shape(x)) * (np.abs(np.asarray(x, dtype=float)) + 1e-12)
+    contact = dm.ContactParams(*[scale * 0.05 * rng.normal() for _ in range(3)]) if c.contact else None
+    bd = dm.LigamentParams(d(np.broadcast_to(bp.k_stretch, (len(c.bonds),))), d(np.broadcast_to(bp.k_shear, (len(c.bonds),))),
+                           d(np.broadcast_to(bp.k_rot, (len(c.bonds),))), d(np.broadcast_to(bp.reference_vector, (len(c.bonds), 2))))
+    return dm.ControlParams(dm.GeometricalParams(None, scale * 0.02 * rng.normal(size=np.shape(c.cnv))),
+                            dm.MechanicalParams(bd, None if inertia is not None else scale * 0.1 * DENSITY, None if inertia is None else d(inertia),
+                                                d(mp.damping), contact),
+                            constraint_params={k: scale * 0.1 * rng.normal() * v for k, v in FAST.items()})
+
+
+def _per_bond(c):
+    """The Case's tree with per-bond stiffness arrays (the tangent tree has them per bond)."""
+    bp = c.cp.mechanical_params.bond_params
+    nbd = len(c.bonds)
+    bp = bp._replace(k_stretch=np.broadcast_to(bp.k_stretch, (nbd,)).copy(), k_shear=np.broadcast_to(bp.k_shear, (nbd,)).copy(),
+                     k_rot=np.broadcast_to(bp.k_rot, (nbd,)).copy())
+    return c.cp._replace(mechanical_params=c.cp.mechanical_params._replace(bond_params=bp))
+
+
+def _grid(ts, spi, unequal):
+    if not unequal:
+        return None
+    return np.concatenate([a + (b - a) * np.linspace(0, 1, spi + 1)[:-1] ** 1.7 for a, b in zip(ts[:-1], ts[1:])] + [ts[-1:]])
+
+
+# (the nonlinear kagome lattice with contact on the unequal grid is ill-conditioned at these states: a 1e-16 change of the inertia moves the
+# oracle's own trajectory by 4e-8, so that combination is checked on equal steps)
+CASES = [("quads", True, True, "dopri5", False), ("quads", True, False, "rk4", True), ("quads", False, True, "rk4", False),
+         ("quads", False, False, "dopri5", True), ("kagome", True, True, "dopri5", False), ("kagome", False, True, "dopri5", True),
+         ("kagome", False, False, "rk4", True)]
+
+
+@pytest.mark.parametrize("lattice,nonlinear,contact,integrator,unequal", CASES)
+def test_tangent_matches_autograd_through_the_oracle(lattice, nonlinear, contact, integrator, unequal):
+    c = _case(lattice, 4, nonlinear, contact, integrator)
+    rng = np.random.default_rng(3)
+    c.cp = _per_bond(c)
+    cp, inertia = _explicit_inertia(c)
+    ts = np.linspace(0, 3e-4, 4)
+    spi = 4
+    st = _grid(ts, spi, unequal)
+    y0 = c.random_state(0.05, 0.02, 5.0)
+    y0d = c.random_state(0.05, 0.02, 5.0)
+    cd = _tangent_tree(c, rng, inertia)
+    fields, fdot = c.solver.jvp(y0, ts, cp, y0d, cd, steps_per_interval=spi, step_times=st)
+    # the oracle: every leaf seeded at once
+    osol = c.oracle_solver(integrator="fixed", steps_per_interval=spi, tableau=integrator, step_times=st)
+    free = osol.free_DOF_ids
+    mp, md = cp.mechanical_params, cd.mechanical_params
+    names = ["cnv", "refv", "ks", "ksh", "kr", "inertia", "damping", "amplitude", "loading_rate", "input_delay", "state0"]
+    prim = dict(cnv=c.cnv, refv=np.broadcast_to(c.refv, (len(c.bonds), 2)), ks=mp.bond_params.k_stretch, ksh=mp.bond_params.k_shear,
+                kr=mp.bond_params.k_rot, inertia=inertia, damping=mp.damping, state0=y0, **FAST)
+    tan = dict(cnv=cd.geometrical_params.centroid_node_vectors, refv=md.bond_params.reference_vector, ks=md.bond_params.k_stretch,
+               ksh=md.bond_params.k_shear, kr=md.bond_params.k_rot, inertia=md.inertia, damping=md.damping, state0=y0d,
+               **cd.constraint_params)
+    if contact:
+        names += ["min_angle", "cutoff_angle", "k_contact"]
+        prim.update(min_angle=mp.contact_params.min_angle, cutoff_angle=mp.contact_params.cutoff_angle, k_contact=mp.contact_params.k_contact)
+        tan.update(min_angle=md.contact_params.min_angle, cutoff_angle=md.contact_params.cutoff_angle, k_contact=md.contact_params.k_contact)
+
+    def f(*xs):
+        lv = dict(zip(names, xs))
+        y0t = lv.pop("state0")
+        hist, _ = OD.solve_fixed_differentiable(osol, c.ogeo, y0t, ts, c.oracle_cp(lv), spi, integrator, step_times=st)
+        return hist
+    of, ojv = torch.autograd.functional.jvp(f, tuple(T64(prim[k]) for k in names), tuple(T64(tan[k]) for k in names))
+    n = len(ts)
+    assert relerr(fields.reshape(n, 2, -1)[:, :, free], of.detach().numpy()) < 1e-10
+    e = relerr(fdot.reshape(n, 2, -1)[:, :, free], ojv.numpy())
+    assert e < RTOL_GRAD, (lattice, nonlinear, contact, integrator, unequal, e)
+    if contact:
+        # the contact constants must matter, or the check above says nothing about them
+        cd0 = cd._replace(mechanical_params=md._replace(contact_params=dm.ContactParams(0.0, 0.0, 0.0)))
+        _, fdot0 = c.solver.jvp(y0, ts, cp, y0d, cd0, steps_per_interval=spi, step_times=st)
+        assert np.abs(fdot0 - fdot).max() > 1e-6 * np.abs(fdot).max()
+
+
+def _tree_dot(a, b):
+    """Sum over the leaves of two ControlParams-shaped trees of <a leaf, b leaf> (None: zero; dict entries by key)."""
+    if a is None or b is None:
+        return 0.0
+    if isinstance(a, dict):
+        return sum(_tree_dot(v, b.get(k)) for k, v in a.items())
+    if isinstance(a, tuple) and hasattr(a, "_fields"):
+        return sum(_tree_dot(getattr(a, f), getattr(b, f, None)) for f in a._fields)
+    return float(np.sum(np.asarray(a, dtype=float) * np.asarray(b, dtype=float)))
+
+
+def _transpose_check(c, ts, spi, y0, trees, cps, step_times=None):
+    s = c.solver
+    rng = np.random.default_rng(11)
+    B = s.batch
+    y0d = rng.normal(size=(B, 2, c.geo.n_blocks, 3)) * np.abs(y0).max()
+    y0d.reshape(B, 2, -1)[:, :, s.constrained_DOF_ids] = 0.0          # (state0 of prescribed DOFs is not read)
+    _, fdot = s.jvp(y0, ts, cps, y0d, trees, steps_per_interval=spi, step_times=step_times)
+    fields = s(y0, ts, cps, keep_trajectory=True, steps_per_interval=spi, step_times=step_times)
+    fb = rng.normal(size=fields.shape)
+    fb.reshape(B, len(ts) if np.ndim(ts) == 1 else ts.shape[1], 2, -1)[:, :, :, s.constrained_DOF_ids] = 0.0
+    bars, s0b = s.vjp(fb)
+    if B == 1:
+        bars, s0b = [bars], np.asarray(s0b)[None]
+    lhs = float(np.sum(fb * fdot))
+    rhs = sum(_tree_dot(bars[m], trees[m]) for m in range(B)) + float(np.sum(np.asarray(s0b) * y0d))
+    assert abs(lhs - rhs) <= 1e-11 * max(abs(lhs), abs(rhs)), (lhs, rhs, abs(lhs - rhs) / abs(rhs))
+    return fields
+
+
+def test_tangent_is_the_transpose_of_the_adjoint_128x128_contact():
+    c = _case("quads", 128, True, True, batch=1, seed=2)
+    c.cp = _per_bond(c)
+    rng = np.random.default_rng(4)
+    ts = np.linspace(0, 3e-4, 3)
+    y0 = c.random_state(0.05, 0.02, 5.0)[None]
+    _transpose_check(c, ts, 250, y0, [_tangent_tree(c, rng)], [c.cp])        # 500 steps, density-derived inertia and void angles
+
+
+def test_tangent_is_the_transpose_of_the_adjoint_kagome_64x64():
+    c = _case("kagome", 64, True, True, seed=3)
+    c.cp = _per_bond(c)
+    rng = np.random.default_rng(5)
+    ts = np.linspace(0, 3e-4, 4)
+    y0 = c.random_state(0.05, 0.02, 5.0)[None]
+    _transpose_check(c, ts, 40, y0, [_tangent_tree(c, rng)], [c.cp])
+
+
+def test_tangent_is_the_transpose_of_the_adjoint_per_member_grids():
+    c = _case("quads", 16, True, True, batch=4, seed=6)
+    c.cp = _per_bond(c)
+    rng = np.random.default_rng(7)
+    ts = np.stack([np.linspace(0, 3e-4, 4) + 1e-5 * m for m in range(4)])          # every member its own output times
+    spi = 12
+    st = np.stack([_grid(row, spi, True) for row in ts])
+    y0 = np.stack([c.random_state(0.05, 0.02, 5.0) for _ in range(4)])
+    _transpose_check(c, ts, spi, y0, [_tangent_tree(c, rng, scale=1.0 + m) for m in range(4)], [c.cp] * 4, step_times=st)
+
+
+def test_tangent_matches_central_differences_128x128_contact():
+    c = _case("quads", 128, True, True, seed=8)
+    s = c.solver
+    rng = np.random.default_rng(9)
+    ts = np.linspace(0, 2e-4, 3)
+    spi = 125
+    y0 = c.random_state(0.05, 0.02, 5.0)
+    y0d = c.random_state(0.05, 0.02, 5.0)
+    mp = c.cp.mechanical_params
+    cd = dm.ControlParams(dm.GeometricalParams(None, 0.02 * rng.normal(size=np.shape(c.cnv))),
+                          dm.MechanicalParams(dm.LigamentParams(0.3 * mp.bond_params.k_stretch, None, 0.2 * mp.bond_params.k_rot, None), None, None,
+                                              0.5 * np.asarray(mp.damping)),
+                          constraint_params=dict(amplitude=0.4))
+    fields, fdot = s.jvp(y0, ts, c.cp, y0d, cd, steps_per_interval=spi)
+    eps = 1e-6
+
+    def moved(sign):
+        e = sign * eps
+        bp = mp.bond_params._replace(k_stretch=mp.bond_params.k_stretch * (1 + 0.3 * e), k_rot=mp.bond_params.k_rot * (1 + 0.2 * e))
+        cp = c.cp._replace(geometrical_params=c.cp.geometrical_params._replace(
+                               centroid_node_vectors=c.cnv + e * cd.geometrical_params.centroid_node_vectors),
+                           mechanical_params=mp._replace(bond_params=bp, damping=np.asarray(mp.damping) * (1 + 0.5 * e)),
+                           constraint_params=dict(FAST, amplitude=FAST["amplitude"] + 0.4 * e))
+        return s(y0 + e * y0d, ts, cp, steps_per_interval=spi)
+    fd = (moved(1) - moved(-1)) / (2 * eps)
+    free = s.free_DOF_ids
+    e = relerr(fdot.reshape(len(ts), 2, -1)[:, :, free], fd.reshape(len(ts), 2, -1)[:, :, free])
+    assert e < 1e-6, e
+
+
+def test_primal_fields_zero_tangent_and_the_adaptive_grid():
+    c = _case("quads", 8, True, True, seed=10)
+    s = c.solver
+    ts = np.linspace(0, 3e-4, 5)
+    y0 = c.random_state(0.05, 0.02, 5.0)
+    st = _grid(ts, 30, True)
+    ref = s(y0, ts, c.cp, steps_per_interval=30, step_times=st)
+    zero = dm.ControlParams(dm.GeometricalParams(None, None), dm.MechanicalParams(None, None))
+    fields, fdot = s.jvp(y0, ts, c.cp, None, zero, steps_per_interval=30, step_times=st)
+    assert relerr(fields, ref) < 1e-13
+    assert np.all(fdot == 0.0)
+    assert s.stats["step_control"] == "fixed" and s.stats["steps"] == 120
+    # no grid: the adaptive controller's grid is frozen first
+    s.rtol, s.atol = 1e-6, 1e-6
+    cd = dm.ControlParams(dm.GeometricalParams(None, None), dm.MechanicalParams(None, None), constraint_params=dict(amplitude=1.0))
+    fields, fdot = s.jvp(y0, ts, c.cp, None, cd)
+    assert s.stats["step_control"] == "adaptive-grid"
+    spi_used, st_used = s.stats["steps_per_interval"], s.stats["step_times"]
+    _, flats = s.prepare(c.cp)
+    spi, grid = s.adaptive_grid(y0[None], ts, flats)
+    assert np.array_equal(spi, spi_used) and np.array_equal(grid, st_used)
+    ref = s(y0, ts, c.cp, steps_per_interval=spi, step_times=grid)
+    assert relerr(fields, ref) < 1e-13
+    assert np.abs(fdot).max() > 0.0
+
+
+def test_extra_ligaments_are_refused_and_the_handle_still_works():
+    c = _case("quads", 4, True, False, seed=12, extra_bonds=[[1, 6], [9, 14]])
+    ts = np.linspace(0, 1e-4, 3)
+    y0 = c.random_state(0.05, 0.02, 5.0)
+    cd = dm.ControlParams(dm.GeometricalParams(None, None), dm.MechanicalParams(None, None), constraint_params=dict(amplitude=1.0))
+    with pytest.raises(RuntimeError, match="more than one ligament"):
+        c.solver.jvp(y0, ts, c.cp, None, cd, steps_per_interval=4)
+    fields = c.solver(y0, ts, c.cp, steps_per_interval=4)
+    assert np.all(np.isfinite(fields)) and np.abs(fields).max() > 0
+    # and a lattice without them on the same process still runs forward mode
+    c2 = _case("quads", 4, True, False, seed=12)
+    _, fdot = c2.solver.jvp(y0, ts, c2.cp, None, cd, steps_per_interval=4)
+    assert np.abs(fdot).max() > 0
+
+
+@pytest.mark.parametrize("lattice", ["quads", "kagome"])
+def test_distance_contact_tangent_is_the_transpose_of_the_adjoint(lattice):
+    from .test_distance_contact import DistCase
+    c = DistCase(lattice, None, n=8, seed=5)
+    rng = np.random.default_rng(13)
+    ts = np.linspace(0, 3e-4, 4)
+    y0 = (rng.normal(size=(2, c.geo.n_blocks, 3)) * np.array([0.05, 0.05, 0.02]) * np.array([[1.0], [5.0]])[:, :, None])[None]
+    refv = np.broadcast_to(c.refv, (len(c.bonds), 2))
+    cd = dm.ControlParams(dm.GeometricalParams(0.05 * rng.normal(size=np.shape(c.cen)), 0.02 * rng.normal(size=np.shape(c.cnv))),
+                          dm.MechanicalParams(dm.LigamentParams(3.0, 0.05, 0.04, 0.01 * rng.normal(size=refv.shape)), 0.1 * DENSITY, None, None,
+                                              dm.ContactParams(0.02, -0.03, 0.05)),
+                          constraint_params=dict(amplitude=0.2, loading_rate=-40.0, input_delay=2e-7))
+    _transpose_check(c, ts, 6, y0, [cd], [c.cp])
+    # the centroids and contact constants reach the tangent (this contact model reads absolute node positions)
+    _, f1 = c.solver.jvp(y0[0], ts, c.cp, None, cd, steps_per_interval=6)
+    _, f0 = c.solver.jvp(y0[0], ts, c.cp, None, cd._replace(geometrical_params=cd.geometrical_params._replace(block_centroids=None)),
+                         steps_per_interval=6)
+    assert np.abs(f1 - f0).max() > 1e-8 * np.abs(f1).max()
