@@ -2,6 +2,7 @@
 // launches, member groups
 // (one of five translation units; shared declarations in dfx_engine.h, the design in DESIGN.md section 3)
 #include "dfx_engine.h"
+#include <climits>
 
 using namespace dfx_persist;
 
@@ -364,8 +365,21 @@ static int persist_max_chunks() {
   const char* e = getenv("DFX_PERSIST_CHUNKS");
   return e ? std::max(1, atoi(e)) : 2;
 }
-static bool persist_common_ok(dfx_handle* h, const DevCtx& c) {
-  if (!persist_shape_ok(h) || h->adaptive || h->groups.size() != 1) return false;
+// The reverse sweep of the RECORDS level has a rule of its own: there the stage launch pays the launch boundary in bytes (parameters,
+// lambda, the later stages' Ybar and the accumulators: ~600 B per unit and launch at 0.97 of the HBM stream) that the persistent loop
+// keeps in registers and LDS.  Measured (profiles/r07_persist_wide.txt, 128x128 quads + contact, 3 members fit one reverse launch):
+// 1.27 us per member-stage for 32 members in 11 launches in a row and for 64 members in 22 -- the same as one launch of 3 (1.28),
+// against 1.64-1.69 on stage launches; one launch of 2 members 1.56, of 1 member 2.54.  Launches of one stream follow each other, so the
+// cost per member does not grow with their number: the wide ensemble is cut into as many launches as it takes, as long as the narrowest
+// of them still fills half the room of the chip.  DFX_PERSIST_ADJ_CHUNKS=<n> caps the launches per segment (A/B runs; 2: as the forward).
+static int persist_adj_max_chunks() {
+  const char* e = getenv("DFX_PERSIST_ADJ_CHUNKS");
+  return e ? std::max(1, atoi(e)) : INT_MAX;
+}
+// balanced launches: `n_chunks` launches of nm / n_chunks members, the first nm % n_chunks of them one member more
+static int chunk_members(int nm, int n_chunks, int k) { return nm / n_chunks + (k < nm % n_chunks ? 1 : 0); }
+static bool persist_common_ok(dfx_handle* h, const DevCtx& c, bool any_groups = false) {
+  if (!persist_shape_ok(h) || h->adaptive || (h->groups.size() != 1 && !any_groups)) return false;
   if (h->pl.n_fns > 0 && !c.fn_tab) return false;
   h->persist_npb = (h->pl.n_npb == 3 && pack3(h)) ? 3 : 4;
   h->persist_wpm = persist_waves_per_member(h, h->persist_npb);
@@ -373,6 +387,15 @@ static bool persist_common_ok(dfx_handle* h, const DevCtx& c) {
 }
 bool persist_members_ok(const dfx_handle* h, int per_launch) {
   return per_launch > 0 && (h->pl.batch + per_launch - 1) / per_launch <= persist_max_chunks();
+}
+// the reverse sweep: the forward's rule, or up to persist_adj_max_chunks() launches whose narrowest still fills half the room the
+// kernel has on the chip (waves; one 128x128 design is a third of it: alone 2.54 us per member-stage)
+static bool persist_adj_members_ok(const dfx_handle* h, const void* fn, int per_launch) {
+  if (persist_members_ok(h, per_launch)) return true;
+  const int nm = h->pl.batch, n_chunks = per_launch > 0 ? (nm + per_launch - 1) / per_launch : 0;
+  if (n_chunks <= 0 || n_chunks > persist_adj_max_chunks()) return false;
+  const long long room = (long long)persist_cap(fn) * h->n_cu * 4;
+  return 2LL * chunk_members(nm, n_chunks, n_chunks - 1) * h->persist_wpm >= room;
 }
 // would both sweeps of a fixed-grid solve of this handle run the persistent loop?  (asked before the context exists: the checkpoint choice)
 bool persist_would_serve(dfx_handle* h) {
@@ -392,14 +415,18 @@ void persist_plan(dfx_handle* h, const DevCtx& c) {
   if (h->d_ring.ensure((size_t)kPRing * h->pl.batch * h->pl.n_blocks * kPos) != hipSuccess) { (void)hipGetLastError(); return; }
   h->persist_fwd = true;
 }
+// At the records level the reverse sweep also serves a handle of several member groups (its launches take the whole batch on group 0's
+// stream, after every group's work so far: enqueue_interleaved) and a batch in more than persist_max_chunks() launches.  The segments
+// level (rps > 1 as well) keeps the forward's rule: one member group, at most persist_max_chunks() launches.
 void persist_plan_adj(dfx_handle* h, const DevCtx& c) {
   h->persist_adj = false;
-  if (h->pair_adj || h->lig_adj_used || !persist_common_ok(h, c)) return;
+  const bool wide = h->records;
+  if (h->pair_adj || h->lig_adj_used || !persist_common_ok(h, c, wide)) return;
   if (c.rps <= 1 || c.g_b || c.AD || !c.lam_pairs) return;          // the records build of the reverse stage, nothing else
   const void* fn = dfx_persist::adj_kernel(h->pl.model, h->pl.contact, h->persist_npb);
   if (!fn) return;
   h->persist_adj_members = persist_members_that_fit(h, fn, h->persist_npb);
-  if (!persist_members_ok(h, h->persist_adj_members)) return;
+  if (!(wide ? persist_adj_members_ok(h, fn, h->persist_adj_members) : persist_members_ok(h, h->persist_adj_members))) return;
   if (h->d_ring.ensure((size_t)kPRing * h->pl.batch * h->pl.n_blocks * kPos) != hipSuccess) { (void)hipGetLastError(); return; }
   h->persist_adj = true;
 }
@@ -482,9 +509,9 @@ static void launch_segment_persist(dfx_handle* h, const DevCtx& c, hipStream_t s
     for (int jj = 0; jj <= kPersistStages; ++jj) { pca.col[i][jj] = ac.col[jj]; pca.cur[i][jj] = ac.cur[jj]; }
     pca.c[i] = ac.c_i;
   }
-  const int n_chunks = (nm + per - 1) / per, even = (nm + n_chunks - 1) / n_chunks;      // members that do not fit at once: equal launches
-  for (int off = 0; off < nm; off += even) {
-    const int cnt = std::min(even, nm - off);
+  const int n_chunks = (nm + per - 1) / per;      // members that do not fit at once: launches of balanced widths
+  for (int k = 0, off = 0; k < n_chunks; off += chunk_members(nm, n_chunks, k++)) {
+    const int cnt = chunk_members(nm, n_chunks, k);
     DevCtx cc = c;
     cc.m0 = c.m0 + off;
     int grid = 0, per_cu = 0;
@@ -735,7 +762,20 @@ void enqueue_interleaved(dfx_handle* h, const DevCtx& cbase, int n_steps, int ki
         for (int gi = 0; gi < ng; ++gi)
           launch_fwd_unit(h, cg[gi], h->groups[gi].stream, slot_grid(h, h->groups[gi]), u, j);
   } else if (h->persist_adj) {
-    for (int gi = 0; gi < ng; ++gi) launch_adj_persist(h, cg[gi], h->groups[gi].stream, h->groups[gi].nm, n_steps);
+    // the whole batch in launches on group 0's stream (persist_plan_adj): it first waits for every group (their stage launches, cursor
+    // ticks and time-function tables -- no persistent launch may find the compute units taken by another group's stage launch), and every
+    // group waits for its last launch (the next segment's table of a group must not overwrite what the launches still read).  The cursor
+    // of group 0 serves all members: every group's cursor walks the same segments.
+    Group& g0 = h->groups[0];
+    for (int gi = 1; gi < ng; ++gi) {
+      (void)hipEventRecord(h->groups[gi].done, h->groups[gi].stream);
+      (void)hipStreamWaitEvent(g0.stream, h->groups[gi].done, 0);
+    }
+    launch_adj_persist(h, cg[0], g0.stream, ng > 1 ? h->pl.batch : g0.nm, n_steps);
+    if (ng > 1) {
+      (void)hipEventRecord(g0.done, g0.stream);
+      for (int gi = 1; gi < ng; ++gi) (void)hipStreamWaitEvent(h->groups[gi].stream, g0.done, 0);
+    }
   } else {
     for (int j = n_steps - 1; j >= 0; --j)
       for (int u = 0; u < step_units(h, 1); ++u)
