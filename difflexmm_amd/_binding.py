@@ -65,7 +65,7 @@ EXPORTS = ["dfx_create", "dfx_destroy", "dfx_last_error", "dfx_set_params", "dfx
 COMM_EXPORTS = ["dfx_comm_unique_id", "dfx_comm_init", "dfx_comm_destroy", "dfx_comm_rccl_version", "dfx_comm_rank", "dfx_comm_size",
                 "dfx_gather_objectives", "dfx_reduce_grads", "dfx_comm_allreduce", "dfx_comm_barrier", "dfx_comm_last_error",
                 "dfx_mem_info", "dfx_device_synchronize", "dfx_kinetic_value_and_grad_device", "dfx_download", "dfx_forward_kinetic_value_and_grad",
-                "dfx_forward_tangent"]
+                "dfx_forward_tangent", "dfx_forward_tangent_dense", "dfx_dense_output_map"]
 EXPORTS = EXPORTS + COMM_EXPORTS
 
 
@@ -130,6 +130,11 @@ def declare(lib):
     if hasattr(lib, "dfx_forward_tangent"):      # (the CPU port of the oracle has no forward mode)
         lib.dfx_forward_tangent.argtypes = [H, _dp, _dp, C.POINTER(dfx_params), _dp, C.c_int32, _ip, _dp, C.c_int32, _dp, _dp,
                                             C.POINTER(dfx_stats)]
+    if hasattr(lib, "dfx_forward_tangent_dense"):
+        _lp = C.POINTER(C.c_int64)
+        lib.dfx_forward_tangent_dense.argtypes = [H, _dp, _dp, C.POINTER(dfx_params), _dp, C.c_int32, _dp, _lp, C.c_int64, _dp, _dp,
+                                                  C.POINTER(dfx_stats)]
+        lib.dfx_dense_output_map.argtypes = [_dp, _lp, C.c_int64, C.c_int32, _dp, C.c_int32, _ip, _dp]
     if hasattr(lib, "dfx_comm_init"):
         lib.dfx_comm_unique_id.argtypes = [C.c_char_p]
         lib.dfx_comm_init.argtypes = [C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(H)]
@@ -163,6 +168,43 @@ def device_synchronize(device=0, lib=None):
     lib = lib if lib is not None else load_library()
     if lib.dfx_device_synchronize(int(device)) != 0:
         raise RuntimeError("dfx_device_synchronize failed: " + lib.dfx_comm_last_error().decode())
+
+
+def padded_step_times(step_times, t0):
+    """Per-member accepted step END times (a list of 1-D arrays, as :meth:`Engine.adaptive_step_times` returns them) -> the padded
+    ``(batch, stride)`` array ``t_0 .. t_{N_m}`` (the rest of a row repeats its last entry) and ``n_steps`` (batch,) int64 that
+    ``dfx_forward_tangent_dense`` / ``dfx_dense_output_map`` take."""
+    n_steps = np.array([len(a) for a in step_times], dtype=np.int64)
+    out = np.empty((len(step_times), int(n_steps.max(initial=0)) + 1))
+    for m, a in enumerate(step_times):
+        out[m, 0] = t0
+        out[m, 1:len(a) + 1] = a
+        out[m, len(a) + 1:] = out[m, len(a)]
+    return out, n_steps
+
+
+_MAP_ERRORS = {1: "step times must be strictly increasing", 2: "every member's t_0 must be timepoints[0]",
+               3: "every member's last step must end at or beyond the last timepoint", 4: "n_steps[m] must lie in [0, stride - 1]"}
+
+
+def dense_output_map(step_times, n_steps, timepoints, lib=None):
+    """``dfx_dense_output_map``: which outputs of an adaptive solve lie in which of its frozen accepted steps, and where.
+    ``step_times`` (batch, stride) rows ``t_0 .. t_{N_m}``, ``n_steps`` (batch,), ``timepoints`` (T,).  Returns ``out_ptr`` (batch, stride)
+    int32 -- outputs ``out_ptr[m, n] .. out_ptr[m, n + 1] - 1`` lie in step n -- and ``theta`` (batch, T).  Pure host code of the HIP
+    library (no device needed)."""
+    lib = lib if lib is not None else load_library()
+    st = _f64(step_times)
+    ns = np.ascontiguousarray(n_steps, dtype=np.int64)
+    ts = _f64(timepoints)
+    if st.ndim != 2 or ns.shape != (st.shape[0],) or ts.ndim != 1:
+        raise ValueError("dense_output_map: step_times (batch, stride), n_steps (batch,), timepoints (T,)")
+    out_ptr = np.zeros(st.shape, dtype=np.int32)
+    theta = np.zeros((st.shape[0], len(ts)))
+    rc = lib.dfx_dense_output_map(_ptr(st), ns.ctypes.data_as(C.POINTER(C.c_int64)), st.shape[1], st.shape[0], _ptr(ts), len(ts),
+                                  out_ptr.ctypes.data_as(_ip), _ptr(theta))
+    if rc != 0:
+        raise ValueError("dense_output_map: " + _MAP_ERRORS.get(rc, f"error {rc}"))
+    return out_ptr, theta
 
 
 _LIB = None
@@ -382,6 +424,45 @@ class Engine:
         self._check(self.lib.dfx_forward_tangent(self._h, _ptr(state0), _ptr(state0_dot), C.byref(p), _ptr(ts), T, spis.ctypes.data_as(_ip),
                                                  _ptr(step_times), int(per_member), _ptr(fields), _ptr(fields_dot), C.byref(st)),
                     "dfx_forward_tangent")
+        return fields, fields_dot, _stats(st)
+
+    @property
+    def has_forward_tangent_dense(self):
+        return hasattr(self.lib, "dfx_forward_tangent_dense")
+
+    def forward_tangent_dense(self, state0, state0_dot, params_dot, timepoints, step_times, n_steps):
+        """Primal fields and their directional derivative of the ADAPTIVE solve's dense output on every member's own frozen accepted steps
+        (``dfx_forward_tangent_dense``): ``step_times`` (batch, stride) rows ``t_0 .. t_{N_m}``, ``n_steps`` (batch,)
+        (:func:`padded_step_times`), ``timepoints`` (T,).  Otherwise as :meth:`forward_tangent`.  Returns (fields, fields_dot, stats)."""
+        if not self.has_forward_tangent_dense:
+            raise NotImplementedError(f"forward mode: the library {getattr(self.lib, '_name', self.lib)!r} has no dfx_forward_tangent_dense "
+                                      "(the CPU port of the oracle is reverse mode only; build the HIP engine)")
+        B, nb = self.batch, self.n_blocks
+        state0 = _f64(state0, (B, 2, nb, 3)) if state0 is not None else None
+        state0_dot = _f64(state0_dot, (B, 2, nb, 3)) if state0_dot is not None else None
+        ts = _f64(timepoints)
+        if ts.ndim != 1:
+            raise ValueError("forward_tangent_dense: one row of timepoints for all members")
+        T = len(ts)
+        st_times = _f64(step_times)
+        ns = np.ascontiguousarray(n_steps, dtype=np.int64)
+        if st_times.ndim != 2 or st_times.shape[0] != B or ns.shape != (B,):
+            raise ValueError(f"forward_tangent_dense: step_times (batch={B}, stride) and n_steps (batch,)")
+        sh = self.shapes()
+        p = dfx_params()
+        keep = []
+        for name in _PARAM_FIELDS + ["block_centroids"]:
+            a = params_dot.get(name) if params_dot else None
+            if a is None:
+                continue
+            a = _f64(a, sh[name])
+            keep.append(a)
+            setattr(p, name, _ptr(a))
+        fields, fields_dot = np.empty((B, T, 2, nb, 3)), np.empty((B, T, 2, nb, 3))
+        st = dfx_stats()
+        self._check(self.lib.dfx_forward_tangent_dense(self._h, _ptr(state0), _ptr(state0_dot), C.byref(p), _ptr(ts), T, _ptr(st_times),
+                                                       ns.ctypes.data_as(C.POINTER(C.c_int64)), st_times.shape[1], _ptr(fields),
+                                                       _ptr(fields_dot), C.byref(st)), "dfx_forward_tangent_dense")
         return fields, fields_dot, _stats(st)
 
     def adaptive_step_counts(self):

@@ -13,6 +13,11 @@
 // The velocities of driven DOFs enter no force; their tangents are left at 0 here and the rows of prescribed DOFs in fields_dot are
 // assembled on the host (difflexmm_amd/dynamics.py, DynamicSolver.jvp).
 //
+// dfx_forward_tangent_dense differentiates the ADAPTIVE solve instead -- the map dfx_adjoint transposes after dfx_forward_adaptive_keep: the
+// same stage kernel on every member's own frozen accepted steps (TanCtx::n_steps: a member that is done leaves; one more stage 0 at its
+// final state gives A_6 of its last step), and k_tan_dense forms the outputs inside the steps and their tangents by the quartic dense
+// output of the adaptive pass, which is linear in (q_n, v_n, A_0 .. A_6) with coefficients that hold primal step data only.
+//
 // The parameter image is a plain per-slot layout of its own (value, then tangent), NOT the packed image of dfx_plan.h:pack_params, which
 // is not linear in the parameters (it stores 1/m, a dictionary of reference vectors, uniform stiffnesses once per member).
 #pragma once
@@ -42,15 +47,32 @@ struct TanCtx {
   const double* t0;              // n_grids: the first output time
   long long grid_stride;         // elements between the grids of two members in tgrid (0: one grid)
   int t0_stride;                 // 1: one t0 per member, 0: shared
+  int a_rows;                    // places per member in A / DA: n_stages, or 7 in the dense pass (A_6 = the FSAL acceleration)
+  const long long* n_steps;      // B: the step count N_m of every member (dense pass), or null: every member takes every step
 };
 
 struct TanStage {
   const double *S_in, *D_in;     // primal / tangent records of this stage, B * nb * kRec (tangent: q at 0..2, v at 5..7)
   const double *Y, *DY;          // step base
   double *S_out, *D_out;         // next stage records (stage s-1: the next step base)
-  double *A, *DA;                // stage accelerations and their tangents, B * n_stages * nb * 3
+  double *A, *DA;                // stage accelerations and their tangents, B * a_rows * nb * 3
   long long n;                   // step ordinal
   int i;                         // stage index
+  int a0;                        // place of A_0 of this step: 0, or in the dense pass 0 / 6 by the step's parity (A_0 of step n + 1 is A_6 of step n)
+};
+
+// the dense output of step n (dfx_forward_tangent_dense): launched after stage 0 of step n + 1 has left A_6
+struct TanDense {
+  const double *Y0, *DY0;        // step base of step n (records)
+  const double *Y1, *DY1;        // step base of step n + 1
+  const double *A, *DA;          // stage accelerations, 7 places per member
+  const int32_t* out_ptr;        // B * op_stride: outputs [out_ptr[n], out_ptr[n + 1]) lie in step n
+  const double* theta;           // B * Tn: relative position of every output in its step
+  const double* ts;              // Tn output times
+  double *fields, *fields_dot;   // B * Tn * 2 * nb * 3
+  long long op_stride, n;
+  int Tn, a0, a6;                // places of A_0 and A_6 of step n
+  double cm[7], cma[7];          // mid-point weights (velocity / position form, Dopri of dfx_physics.h)
 };
 
 DFX_HD BlockRec<Dual> tan_rec(const double* S, const double* D, int b) {
@@ -120,6 +142,12 @@ __global__ void __launch_bounds__(256) k_tan_stage(TanCtx c, Tableau T, TanStage
   const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= (long long)c.B * c.nb) return;
   const int m = (int)(gid / c.nb), b = (int)(gid % c.nb);
+  if (c.n_steps) {
+    // dense pass: a member that has taken its N_m steps leaves (its step base stays put); at n == N_m only the evaluation at its final
+    // state runs, as stage 0 of a step of size zero
+    const long long N = c.n_steps[m];
+    if (st.n > N || (st.n == N && st.i > 0)) return;
+  }
   const size_t moff = (size_t)m * c.nb;                 // first block of this member in the record buffers
   const double* S_in = st.S_in + moff * kRec;
   const double* D_in = st.D_in + moff * kRec;
@@ -170,8 +198,8 @@ __global__ void __launch_bounds__(256) k_tan_stage(TanCtx c, Tableau T, TanStage
   const int sidx = c.block_special[b];
   const double* bk = c.blk + (moff + b) * kTanBlk;
   const size_t nd = (size_t)c.nb * 3;
-  double* A = st.A + (size_t)m * c.n_stages * nd;
-  double* DA = st.DA + (size_t)m * c.n_stages * nd;
+  double* A = st.A + (size_t)m * c.a_rows * nd;
+  double* DA = st.DA + (size_t)m * c.a_rows * nd;
   const double* rin = S_in + (size_t)b * kRec;
   const double* din = D_in + (size_t)b * kRec;
   const double* yb = st.Y + (moff + b) * kRec;
@@ -194,11 +222,12 @@ __global__ void __launch_bounds__(256) k_tan_stage(TanCtx c, Tableau T, TanStage
     const double a = constrained ? 0.0 : (fload - f[d].v - damp * v_i) * inv_m;
     // a = F / m: da = dF / m + F d(1/m)
     const double da = constrained ? 0.0 : (dfload - f[d].e - ddamp * v_i - damp * dv_i) * inv_m + (fload - f[d].v - damp * v_i) * dinv_m;
-    A[(size_t)i * nd + dof] = a;
-    DA[(size_t)i * nd + dof] = da;
+    A[(size_t)(i ? i : st.a0) * nd + dof] = a;
+    DA[(size_t)(i ? i : st.a0) * nd + dof] = da;
     double sv = T.a[r][i] * a, sq = T.aa[r][i] * a, dsv = T.a[r][i] * da, dsq = T.aa[r][i] * da;
     for (int l = 0; l < i; ++l) {
-      const double al = A[(size_t)l * nd + dof], dal = DA[(size_t)l * nd + dof];
+      const size_t row = l ? l : st.a0;
+      const double al = A[row * nd + dof], dal = DA[row * nd + dof];
       sv += T.a[r][l] * al; sq += T.aa[r][l] * al;
       dsv += T.a[r][l] * dal; dsq += T.aa[r][l] * dal;
     }
@@ -232,6 +261,56 @@ __global__ void k_tan_snapshot(int B, int nb, int Tn, int k, const double* S, co
     fields[row + nd + b * 3 + j] = r[5 + j];
     fields_dot[row + b * 3 + j] = d[j];
     fields_dot[row + nd + b * 3 + j] = d[5 + j];
+  }
+}
+
+// rows [out_ptr[n], out_ptr[n + 1]) of fields and fields_dot from the dense output of step n: the quartic of the adaptive pass (k_prepare
+// of dfx_kernels.h, the same expressions in the same order) on (q_n, q_n+1, q_mid, v_n, v_n+1) and on (v_n, v_n+1, v_mid, A_0, A_6), and
+// the same linear formula on their tangents -- its coefficients hold primal step data only (h, theta).  One lane per (member, block).
+__global__ void __launch_bounds__(256) k_tan_dense(TanCtx c, TanDense dn) {
+  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= (long long)c.B * c.nb) return;
+  const int m = (int)(gid / c.nb), b = (int)(gid % c.nb);
+  if (dn.n >= c.n_steps[m]) return;
+  const int32_t* op = dn.out_ptr + (size_t)m * dn.op_stride;
+  const int lo = op[dn.n], hi = op[dn.n + 1];
+  if (hi <= lo) return;
+  const double h = c.tgrid[(size_t)m * c.grid_stride + 2 * (size_t)dn.n + 1];
+  const size_t nd = (size_t)c.nb * 3;
+  const double* A = dn.A + (size_t)m * c.a_rows * nd;
+  const double* DA = dn.DA + (size_t)m * c.a_rows * nd;
+  const double* y0 = dn.Y0 + (size_t)gid * kRec;
+  const double* dy0 = dn.DY0 + (size_t)gid * kRec;
+  const double* y1 = dn.Y1 + (size_t)gid * kRec;
+  const double* dy1 = dn.DY1 + (size_t)gid * kRec;
+  const int sidx = c.block_special[b];
+  for (int d = 0; d < 3; ++d) {
+    const size_t dof = (size_t)b * 3 + d;
+    const bool constrained = sidx >= 0 && ((c.special[sidx].con_mask >> d) & 1);
+    const double qn = y0[d], vn = y0[5 + d], q1 = y1[d], v1 = y1[5 + d];
+    const double dqn = dy0[d], dvn = dy0[5 + d], dq1 = dy1[d], dv1 = dy1[5 + d];
+    const double a0 = A[(size_t)dn.a0 * nd + dof], a6 = A[(size_t)dn.a6 * nd + dof];
+    const double da0 = DA[(size_t)dn.a0 * nd + dof], da6 = DA[(size_t)dn.a6 * nd + dof];
+    double sm = dn.cm[0] * a0 + dn.cm[6] * a6, sma = dn.cma[0] * a0 + dn.cma[6] * a6;
+    double dsm = dn.cm[0] * da0 + dn.cm[6] * da6, dsma = dn.cma[0] * da0 + dn.cma[6] * da6;
+    for (int l = 1; l < 6; ++l) {
+      const double al = A[(size_t)l * nd + dof], dal = DA[(size_t)l * nd + dof];
+      sm += dn.cm[l] * al; sma += dn.cma[l] * al;
+      dsm += dn.cm[l] * dal; dsma += dn.cma[l] * dal;
+    }
+    const double qmid = qn + h * (0.5 * vn + h * sma), vmid = vn + h * sm;
+    const double dqmid = dqn + h * (0.5 * dvn + h * dsma), dvmid = dvn + h * dsm;
+    for (int kk = lo; kk < hi; ++kk) {
+      const double r = dn.theta[(size_t)m * dn.Tn + kk];
+      double oq = dopri_dense(qn, q1, qmid, vn, v1, h, r), ov = dopri_dense(vn, v1, vmid, a0, a6, h, r);
+      double doq = dopri_dense(dqn, dq1, dqmid, dvn, dv1, h, r), dov = dopri_dense(dvn, dv1, dvmid, da0, da6, h, r);
+      if (constrained) { tan_drive(c, m, c.special[sidx].con_coef[d], dn.ts[kk], oq, ov, doq); dov = 0.0; }
+      const size_t row = ((size_t)m * dn.Tn + kk) * 2 * nd;
+      dn.fields[row + dof] = oq;
+      dn.fields[row + nd + dof] = ov;
+      dn.fields_dot[row + dof] = doq;
+      dn.fields_dot[row + nd + dof] = dov;
+    }
   }
 }
 

@@ -423,9 +423,11 @@ class DynamicSolver:
         return fields
 
     # -- forward mode ------------------------------------------------------------------------------------
-    def jvp(self, state0, timepoints, control_params, state0_dot, control_params_dot, steps_per_interval=None, step_times=None):
-        """Forward-mode derivative of the FIXED-GRID solve:  ``fields, fields_dot = jvp(state0, timepoints, control_params, state0_dot,
-        control_params_dot)``, ``fields_dot = d fields / d(state0, control_params) . (state0_dot, control_params_dot)`` with the steps frozen
+    def jvp(self, state0, timepoints, control_params, state0_dot, control_params_dot, steps_per_interval=None, step_times=None,
+            adaptive=False):
+        """Forward-mode derivative of the FIXED-GRID solve (``adaptive=True``: of the adaptive solve itself, see below):
+        ``fields, fields_dot = jvp(state0, timepoints, control_params, state0_dot, control_params_dot)``,
+        ``fields_dot = d fields / d(state0, control_params) . (state0_dot, control_params_dot)`` with the steps frozen
         (``dfx_forward_tangent``: one stage launch per Runge-Kutta stage computes the primal and the tangent together).  This is the map
         :meth:`vjp` transposes: on the same grid  ``sum(fields_bar * fields_dot) == <vjp(fields_bar), tangent>``.
 
@@ -440,13 +442,30 @@ class DynamicSolver:
           (:meth:`adaptive_grid`, as the ``"adaptive-grid"`` path of a differentiable solve) and the tangent pass runs on it.  These
           ``fields`` are then the frozen-grid RE-INTEGRATION, not the adaptive solve's dense output: they differ from what
           ``solve_dynamics(state0, timepoints, control_params)`` returns by O(tolerance).  ``self.stats`` reports the grid.
+        * ``adaptive=True`` (no grid of any kind: not with ``steps_per_interval``, ``step_times``, a default grid set at setup,
+          ``grid_refine > 1`` or per-member ``timepoints`` -- ``ValueError``): the map differentiated is the reference's call,
+          ``solve_dynamics(state0, timepoints, control_params)``.  The adaptive pass runs first (keeping its accepted steps where the
+          library and the physics allow it), then the tangent pass takes every member over ITS OWN accepted steps, frozen, and forms the
+          outputs and their tangents inside the steps by the controller's quartic dense output (``dfx_forward_tangent_dense``).  ``fields``
+          are the fields of that call to rounding, and ``fields_dot`` is the transpose of what :meth:`vjp` computes on the
+          ``"adaptive-records"`` path: when the steps were kept (``self.stats["kept_trajectory"]``), ``vjp`` may follow this call directly
+          and differentiates the same solve.  Step sizes and accept / reject decisions are not differentiated.  ``self.stats`` reports
+          ``step_control="adaptive-dense"`` and ``steps_per_member``.
         * rows of PRESCRIBED DOFs in ``fields_dot`` are  sum_f coef (dg_f/dp . dp, dg_f'/dp . dp)  from each term's ``param_partials``,
           as :meth:`vjp` computes their cotangents -- a central difference, accurate to ~1e-9 relative, not to rounding.
         * not supported (``RuntimeError`` from the engine): lattices whose nodes carry more than one ligament.  The CPU port of the
           oracle has no forward mode (``NotImplementedError``).
 
-        The solver's trajectory checkpoint is not kept by this call: a ``vjp`` must follow a solve with ``keep_trajectory=True``."""
-        if not self.engine.has_forward_tangent:
+        The solver's trajectory checkpoint is not kept by this call (``adaptive=True`` apart): a ``vjp`` must follow a solve with
+        ``keep_trajectory=True``."""
+        if adaptive:
+            grids = [name for name, on in (("steps_per_interval", steps_per_interval is not None), ("step_times", step_times is not None),
+                                           ("a default grid of the solver", self.steps_per_interval is not None),
+                                           ("grid_refine > 1", self.grid_refine > 1), ("per-member timepoints", np.ndim(timepoints) == 2)) if on]
+            if grids:
+                raise ValueError("DynamicSolver.jvp: adaptive=True differentiates the adaptive solve on its own accepted steps and takes no grid "
+                                 f"(got {', '.join(grids)})")
+        if not self.engine.has_forward_tangent or (adaptive and not self.engine.has_forward_tangent_dense):
             lib = self.engine.lib
             raise NotImplementedError(f"DynamicSolver.jvp: the library {getattr(lib, '_name', lib)!r} has no dfx_forward_tangent "
                                       "(forward mode runs on the HIP engine only; the CPU port of the oracle is reverse mode only)")
@@ -471,13 +490,38 @@ class DynamicSolver:
         s0, s0d = members(state0), members(state0_dot)
         spi = steps_per_interval if steps_per_interval is not None else self.steps_per_interval
         control = "fixed"
-        if spi is None:
-            if ts.ndim == 2:
-                raise ValueError("per-member timepoints need steps_per_interval (the adaptive controller chooses one grid per call)")
-            spi, step_times = self.adaptive_grid(np.zeros((B, 2, nb, 3)) if s0 is None else s0, ts, flats)
-            control = "adaptive-grid"
-        fields, fields_dot, stats = self.engine.forward_tangent(s0, s0d, params_dot, ts, spi, step_times=step_times)
-        self.stats = dict(stats, steps_per_interval=spi, step_times=step_times, step_control=control)
+        if adaptive:
+            # What the tangent pass refuses (extra ligaments, a tableau without dense output) is refused before the adaptive pass is paid
+            # for: the same entry point on the initial state alone, one timepoint and no step.  Then the adaptive pass, its accepted steps
+            # kept for a vjp of the same solve where the kept-steps path serves the physics, and the tangent pass over every member's own
+            # step boundaries.
+            self.engine.forward_tangent_dense(s0, None, None, ts[:1], np.full((B, 1), ts[0]), np.zeros(B, dtype=np.int64))
+            kept, primal, astats = False, None, None
+            if self.engine.can_keep_adaptive and os.environ.get("DFX_ADAPTIVE_RECORDS", "1") != "0":
+                try:
+                    primal, astats = self.engine.forward_adaptive(s0, ts, self.rtol, self.atol, max_attempts=self.max_attempts, keep_trajectory=True)
+                    kept = True
+                except RuntimeError as e:
+                    if "forward_adaptive_keep:" not in str(e):
+                        raise
+            if not kept:
+                primal, astats = self.engine.forward_adaptive(s0, ts, self.rtol, self.atol, max_attempts=self.max_attempts)
+            self.adaptive_stats = astats
+            grid, n_steps = _b.padded_step_times([self.engine.adaptive_step_times(m) for m in range(B)], ts[0])
+            fields, fields_dot, stats = self.engine.forward_tangent_dense(s0, s0d, params_dot, ts, grid, n_steps)
+            if kept:        # as a differentiable solve leaves it: vjp reverses the adaptive pass above
+                self._last = (cps, flats, ts)
+                self._last_fields = primal
+            self.stats = dict(stats, steps_per_interval=None, step_times=grid, step_control="adaptive-dense",
+                              steps_per_member=[int(n) for n in n_steps], kept_trajectory=kept)
+        else:
+            if spi is None:
+                if ts.ndim == 2:
+                    raise ValueError("per-member timepoints need steps_per_interval (the adaptive controller chooses one grid per call)")
+                spi, step_times = self.adaptive_grid(np.zeros((B, 2, nb, 3)) if s0 is None else s0, ts, flats)
+                control = "adaptive-grid"
+            fields, fields_dot, stats = self.engine.forward_tangent(s0, s0d, params_dot, ts, spi, step_times=step_times)
+            self.stats = dict(stats, steps_per_interval=spi, step_times=step_times, step_control=control)
         if len(self.constrained_pairs) and self.con_terms:
             n_con = len(self.constrained_pairs)
             dofs = self.constrained_pairs[:, 0] * 3 + self.constrained_pairs[:, 1]

@@ -243,6 +243,29 @@ int dfx_forward_tangent(dfx_handle* h, const double* state0, const double* state
                         const double* step_times, int32_t per_member_times,
                         double* fields, double* fields_dot, dfx_stats* stats);
 
+/* Forward mode through the ADAPTIVE solve's dense output: the directional derivative of the map dfx_adjoint transposes after
+ * dfx_forward_adaptive_keep.  Every member runs on its own accepted step boundaries, frozen: step_times (batch, stride), row m holds
+ * t_0 .. t_{N_m} with N_m = n_steps[m] (dfx_adaptive_step_times gives t_1 .. t_{N_m}; t_0 = timepoints[0]); six Dopri5 stages per step,
+ * output k taken from the step with t_n < timepoints[k] <= t_{n+1} by the quartic dense output the adaptive pass uses, which needs the
+ * FSAL acceleration at y_{n+1} (after the last step: one extra evaluation at the final state, a step of size zero).  Output 0 is state0.
+ * Neither the accept / reject decisions nor the step sizes are differentiated.  timepoints (n_timepoints), shared by the members.
+ * Otherwise the contract of dfx_forward_tangent: fields / fields_dot (batch, T, 2, n_blocks, 3), buffers of its own (the checkpoint and
+ * the resident history of the handle stay untouched: a dfx_adjoint after it still reverses the solve that was kept), every bond model
+ * and contact model, one ligament per node; non-finite values, or a member the last forward pass flagged (dfx_member_status != 0):
+ * return 3.  Return 1 (dfx_last_error says why) for a tableau other than dopri5, step times that do not increase,
+ * t_0 != timepoints[0] or t_{N_m} < timepoints[n_timepoints - 1]. */
+int dfx_forward_tangent_dense(dfx_handle* h, const double* state0, const double* state0_dot, const dfx_params* params_dot,
+                              const double* timepoints, int32_t n_timepoints, const double* step_times, const int64_t* n_steps,
+                              int64_t stride, double* fields, double* fields_dot, dfx_stats* stats);
+
+/* The host half of dfx_forward_tangent_dense, on its own (no handle, no device): which outputs every frozen step holds and where.
+ * out_ptr (batch, stride): outputs [out_ptr[m][n], out_ptr[m][n + 1]) lie in step n of member m (entries 0 .. N_m; out_ptr[m][0] = 1,
+ * output 0 is the initial state); theta (batch, n_timepoints): (timepoints[k] - t_n) / (t_{n+1} - t_n), theta[m][0] = 0.  The rule and
+ * the two IEEE operations are the adaptive controller's: timepoints[k] <= t_{n+1} puts an output on a step boundary into the step that
+ * ends there.  Returns 0, or 1 step times not increasing, 2 t_0 != timepoints[0], 3 t_{N_m} < the last timepoint, 4 bad sizes. */
+int dfx_dense_output_map(const double* step_times, const int64_t* n_steps, int64_t stride, int32_t batch,
+                         const double* timepoints, int32_t n_timepoints, int32_t* out_ptr, double* theta);
+
 /* Device-resident variants for benchmarking: the forward keeps the (T, ...) fields on the device and
  * the cotangent is the target-kinetic-energy objective  sum_t sum_{b in target} m_bd v_bd^2 / 2
  * (energy.py:494-499, problems/quads_focusing.py:447-467), evaluated on the device. */

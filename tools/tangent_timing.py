@@ -3,7 +3,11 @@ fixed-grid forward solve solve_dynamics(..., steps_per_interval=...) on the same
   * 128 x 128 quads with angle contact, 16 members, 250 dopri5 steps;
   * the paper's lattice (24 x 16 quads, spacing 15 mm, contact -15 / -10 deg, damping), 1 member, 250 steps.
 Prints device ms per step of both (HIP events around the stage launches), the wall time per call, and the ratio.
-    python tools/tangent_timing.py"""
+    python tools/tangent_timing.py
+--adaptive: the paper's lattice at the paper's tolerances (rtol 1e-8 / atol 1e-4, 200 outputs over 2 / 30 s), forward mode of the default
+call both ways: jvp(adaptive=True) (adaptive pass + tangent pass on every member's own accepted steps with the dense output) beside the
+no-grid jvp (adaptive pass + tangent pass on the frozen grid of the slowest member).  Wall ms per call and device ms of the tangent pass.
+    python tools/tangent_timing.py --adaptive"""
 import math
 import os
 import sys
@@ -76,6 +80,30 @@ def time_case(label, n1, n2, batch, steps, reps=3):
     return t_ms / f_ms
 
 
+def time_adaptive(reps=3):
+    n1, n2 = 24, 16
+    s, cps, dots = quads_problem(n1, n2, 1)
+    s.rtol, s.atol = 1e-8, 1e-4
+    ts = np.linspace(0.0, 2.0 / 30.0, 200)
+    y0 = np.zeros((1, 2, n1 * n2, 3))
+    rows = {"adaptive=True": [], "no grid": []}
+    for rep in range(reps + 1):                              # (the first round warms up)
+        for label, kw in (("adaptive=True", dict(adaptive=True)), ("no grid", {})):
+            t0 = time.perf_counter()
+            fields, fdot = s.jvp(y0, ts, cps, None, dots, **kw)
+            wall = time.perf_counter() - t0
+            assert np.all(np.isfinite(fdot)) and np.abs(fdot[:, -1]).max() > 0
+            if rep:
+                rows[label].append((wall, s.stats["kernel_ms"], s.stats["steps"], s.stats["launches"], s.stats["step_control"]))
+    for label, r in rows.items():
+        wall, ms, steps, launches, control = min(r)
+        print(f"paper 24x16 quads + contact, rtol 1e-8 / atol 1e-4, 200 outputs | jvp {label} ({control}): wall {1e3 * wall:.1f} ms per call, "
+              f"tangent pass {ms:.1f} ms on the device, {steps} steps, {launches} launches")
+
+
 if __name__ == "__main__":
+    if "--adaptive" in sys.argv[1:]:
+        time_adaptive()
+        sys.exit(0)
     time_case("128x128 quads + contact", 128, 128, 16, 250)
     time_case("paper 24x16 quads + contact", 24, 16, 1, 250)
