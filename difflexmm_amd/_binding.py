@@ -65,7 +65,8 @@ EXPORTS = ["dfx_create", "dfx_destroy", "dfx_last_error", "dfx_set_params", "dfx
 COMM_EXPORTS = ["dfx_comm_unique_id", "dfx_comm_init", "dfx_comm_destroy", "dfx_comm_rccl_version", "dfx_comm_rank", "dfx_comm_size",
                 "dfx_gather_objectives", "dfx_reduce_grads", "dfx_comm_allreduce", "dfx_comm_barrier", "dfx_comm_last_error",
                 "dfx_mem_info", "dfx_device_synchronize", "dfx_kinetic_value_and_grad_device", "dfx_download", "dfx_forward_kinetic_value_and_grad",
-                "dfx_forward_tangent", "dfx_forward_tangent_dense", "dfx_dense_output_map"]
+                "dfx_forward_tangent", "dfx_forward_tangent_dense", "dfx_dense_output_map", "dfx_forward_tangent_multi",
+                "dfx_forward_tangent_dense_multi"]
 EXPORTS = EXPORTS + COMM_EXPORTS
 
 
@@ -135,6 +136,12 @@ def declare(lib):
         lib.dfx_forward_tangent_dense.argtypes = [H, _dp, _dp, C.POINTER(dfx_params), _dp, C.c_int32, _dp, _lp, C.c_int64, _dp, _dp,
                                                   C.POINTER(dfx_stats)]
         lib.dfx_dense_output_map.argtypes = [_dp, _lp, C.c_int64, C.c_int32, _dp, C.c_int32, _ip, _dp]
+    if hasattr(lib, "dfx_forward_tangent_multi"):
+        lib.dfx_forward_tangent_multi.argtypes = [H, _dp, _dp, C.POINTER(dfx_params), C.c_int32, _dp, C.c_int32, _ip, _dp, C.c_int32, _dp, _dp,
+                                                  C.POINTER(dfx_stats)]
+    if hasattr(lib, "dfx_forward_tangent_dense_multi"):
+        lib.dfx_forward_tangent_dense_multi.argtypes = [H, _dp, _dp, C.POINTER(dfx_params), C.c_int32, _dp, C.c_int32, _dp, C.POINTER(C.c_int64),
+                                                        C.c_int64, _dp, _dp, C.POINTER(dfx_stats)]
     if hasattr(lib, "dfx_comm_init"):
         lib.dfx_comm_unique_id.argtypes = [C.c_char_p]
         lib.dfx_comm_init.argtypes = [C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(H)]
@@ -464,6 +471,103 @@ class Engine:
                                                        ns.ctypes.data_as(C.POINTER(C.c_int64)), st_times.shape[1], _ptr(fields),
                                                        _ptr(fields_dot), C.byref(st)), "dfx_forward_tangent_dense")
         return fields, fields_dot, _stats(st)
+
+    # -- forward mode, several directions per member ------------------------------------------------
+    def _params_dots(self, params_dots, K):
+        """K ``dfx_params`` (one per direction) from a list of dicts of arrays by field name (None / a missing name: zero tangent)."""
+        sh = self.shapes()
+        arr = (dfx_params * K)()
+        keep = []
+        for k in range(K):
+            pd = params_dots[k] if params_dots is not None else None
+            for name in _PARAM_FIELDS + ["block_centroids"]:
+                a = pd.get(name) if pd else None
+                if a is None:
+                    continue
+                a = _f64(a, sh[name])
+                keep.append(a)
+                setattr(arr[k], name, _ptr(a))
+        return arr, keep
+
+    def _state0_dots(self, state0_dots, K):
+        if state0_dots is None:
+            return None
+        B, nb = self.batch, self.n_blocks
+        a = np.ascontiguousarray(state0_dots, dtype=np.float64)
+        if a.shape != (B, K, 2, nb, 3):
+            raise ValueError(f"state0_dots must be (batch={B}, n_dirs={K}, 2, {nb}, 3), got {a.shape}")
+        return a
+
+    @property
+    def has_forward_tangent_multi(self):
+        return hasattr(self.lib, "dfx_forward_tangent_multi")
+
+    def forward_tangent_multi(self, state0, state0_dots, params_dots, n_dirs, timepoints, steps_per_interval, step_times=None):
+        """:meth:`forward_tangent` for ``n_dirs`` directions per member with the primal evaluated once per stage
+        (``dfx_forward_tangent_multi``): ``state0_dots`` (batch, n_dirs, 2, nb, 3) or None, ``params_dots`` a list of ``n_dirs`` dicts of
+        arrays by ``dfx_params`` field name (or None).  Returns (fields (batch, T, ...), fields_dots (batch, n_dirs, T, ...), stats)."""
+        if not self.has_forward_tangent_multi:
+            raise NotImplementedError(f"forward mode: the library {getattr(self.lib, '_name', self.lib)!r} has no dfx_forward_tangent_multi "
+                                      "(the CPU port of the oracle is reverse mode only; build the HIP engine)")
+        K = int(n_dirs)
+        if K < 1 or (params_dots is not None and len(params_dots) != K):
+            raise ValueError(f"forward_tangent_multi: need n_dirs >= 1 and one params_dot per direction (n_dirs={K})")
+        B, nb = self.batch, self.n_blocks
+        state0 = _f64(state0, (B, 2, nb, 3)) if state0 is not None else None
+        state0_dots = self._state0_dots(state0_dots, K)
+        ts = _f64(timepoints)
+        T = ts.shape[-1]
+        spis = np.ascontiguousarray(np.broadcast_to(steps_per_interval, (max(T - 1, 0),)), dtype=np.int32)
+        n = int(spis.sum())
+        per_member = ts.ndim == 2
+        if per_member:
+            if ts.shape[0] != B:
+                raise ValueError(f"per-member timepoints must be (batch={B}, T)")
+            if step_times is None:      # equal steps inside every member's own intervals (as forward)
+                step_times = np.stack([np.concatenate([a + (b - a) * np.arange(k) / k for a, b, k in zip(row[:-1], row[1:], spis)] + [row[-1:]])
+                                       for row in ts])
+            step_times = _f64(step_times, (B, n + 1))
+        elif step_times is not None:
+            step_times = _f64(step_times, (n + 1,))
+        p, keep = self._params_dots(params_dots, K)
+        fields, fields_dots = np.empty((B, T, 2, nb, 3)), np.empty((B, K, T, 2, nb, 3))
+        st = dfx_stats()
+        self._check(self.lib.dfx_forward_tangent_multi(self._h, _ptr(state0), _ptr(state0_dots), p, K, _ptr(ts), T, spis.ctypes.data_as(_ip),
+                                                       _ptr(step_times), int(per_member), _ptr(fields), _ptr(fields_dots), C.byref(st)),
+                    "dfx_forward_tangent_multi")
+        return fields, fields_dots, _stats(st)
+
+    @property
+    def has_forward_tangent_dense_multi(self):
+        return hasattr(self.lib, "dfx_forward_tangent_dense_multi")
+
+    def forward_tangent_dense_multi(self, state0, state0_dots, params_dots, n_dirs, timepoints, step_times, n_steps):
+        """:meth:`forward_tangent_dense` for ``n_dirs`` directions per member (``dfx_forward_tangent_dense_multi``); arguments as
+        :meth:`forward_tangent_multi` and :meth:`forward_tangent_dense`.  Returns (fields, fields_dots (batch, n_dirs, T, ...), stats)."""
+        if not self.has_forward_tangent_dense_multi:
+            raise NotImplementedError(f"forward mode: the library {getattr(self.lib, '_name', self.lib)!r} has no dfx_forward_tangent_dense_multi "
+                                      "(the CPU port of the oracle is reverse mode only; build the HIP engine)")
+        K = int(n_dirs)
+        if K < 1 or (params_dots is not None and len(params_dots) != K):
+            raise ValueError(f"forward_tangent_dense_multi: need n_dirs >= 1 and one params_dot per direction (n_dirs={K})")
+        B, nb = self.batch, self.n_blocks
+        state0 = _f64(state0, (B, 2, nb, 3)) if state0 is not None else None
+        state0_dots = self._state0_dots(state0_dots, K)
+        ts = _f64(timepoints)
+        if ts.ndim != 1:
+            raise ValueError("forward_tangent_dense_multi: one row of timepoints for all members")
+        T = len(ts)
+        st_times = _f64(step_times)
+        ns = np.ascontiguousarray(n_steps, dtype=np.int64)
+        if st_times.ndim != 2 or st_times.shape[0] != B or ns.shape != (B,):
+            raise ValueError(f"forward_tangent_dense_multi: step_times (batch={B}, stride) and n_steps (batch,)")
+        p, keep = self._params_dots(params_dots, K)
+        fields, fields_dots = np.empty((B, T, 2, nb, 3)), np.empty((B, K, T, 2, nb, 3))
+        st = dfx_stats()
+        self._check(self.lib.dfx_forward_tangent_dense_multi(self._h, _ptr(state0), _ptr(state0_dots), p, K, _ptr(ts), T, _ptr(st_times),
+                                                             ns.ctypes.data_as(C.POINTER(C.c_int64)), st_times.shape[1], _ptr(fields),
+                                                             _ptr(fields_dots), C.byref(st)), "dfx_forward_tangent_dense_multi")
+        return fields, fields_dots, _stats(st)
 
     def adaptive_step_counts(self):
         """(batch, T-1) accepted steps of the last forward_adaptive per member and output interval."""

@@ -75,6 +75,7 @@ struct TanDense {
   double cm[7], cma[7];          // mid-point weights (velocity / position form, Dopri of dfx_physics.h)
 };
 
+// (the kernels that are no templates are static: dfx_tangent_multi.h's translation unit reads this header too)
 DFX_HD BlockRec<Dual> tan_rec(const double* S, const double* D, int b) {
   const BlockRec<double> r = load_rec(S, b);
   const double* d = D + (size_t)b * kRec;
@@ -99,7 +100,7 @@ DFX_HD void tan_drive(const TanCtx& c, int m, const double* coef /* DFX_MAX_FNS 
   }
 }
 
-__global__ void k_tan_init(TanCtx c, const double* state0, const double* state0_dot, double* S, double* D) {
+static __global__ void k_tan_init(TanCtx c, const double* state0, const double* state0_dot, double* S, double* D) {
   const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= (long long)c.B * c.nb) return;
   const int m = (int)(gid / c.nb), b = (int)(gid % c.nb);
@@ -248,7 +249,7 @@ __global__ void __launch_bounds__(256) k_tan_stage(TanCtx c, Tableau T, TanStage
 }
 
 // row k of fields and fields_dot (B, T, 2, nb, 3) from the step-base records
-__global__ void k_tan_snapshot(int B, int nb, int Tn, int k, const double* S, const double* D, double* fields, double* fields_dot) {
+static __global__ void k_tan_snapshot(int B, int nb, int Tn, int k, const double* S, const double* D, double* fields, double* fields_dot) {
   const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= (long long)B * nb) return;
   const int m = (int)(gid / nb), b = (int)(gid % nb);
@@ -267,7 +268,7 @@ __global__ void k_tan_snapshot(int B, int nb, int Tn, int k, const double* S, co
 // rows [out_ptr[n], out_ptr[n + 1]) of fields and fields_dot from the dense output of step n: the quartic of the adaptive pass (k_prepare
 // of dfx_kernels.h, the same expressions in the same order) on (q_n, q_n+1, q_mid, v_n, v_n+1) and on (v_n, v_n+1, v_mid, A_0, A_6), and
 // the same linear formula on their tangents -- its coefficients hold primal step data only (h, theta).  One lane per (member, block).
-__global__ void __launch_bounds__(256) k_tan_dense(TanCtx c, TanDense dn) {
+static __global__ void __launch_bounds__(256) k_tan_dense(TanCtx c, TanDense dn) {
   const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= (long long)c.B * c.nb) return;
   const int m = (int)(gid / c.nb), b = (int)(gid % c.nb);

@@ -1,0 +1,473 @@
+// dfx_tangent_multi.h -- the forward-mode (tangent) solve of dfx_tangent.h for SEVERAL directions per member in one pass.
+//
+// k_tan_stage (dfx_tangent.h) evaluates the primal and one tangent together as Dual numbers, so K directions cost K times the primal chain:
+// the half-angle records, atan2 / sqrt / rsqrt, the branch decisions, every parameter and record load.  Here the scalar is DualN<K>: one
+// value and K epsilon parts.  Every primal operation (the transcendental expansions included) happens once; every epsilon operation happens
+// K times, in the order Dual performs it, so a column differs from the single-direction kernel by floating-point contraction only.  The
+// physics is not restated: bond_grad_p / contact_grad / distance_contact_grad (dfx_physics.h) are instantiated with T = P = DualN<K>.
+//
+// Semantics per direction are those of k_tan_stage: branches follow the primal, nothing is culled, the DOF part is da = (dF - a dm) / m with
+// damping, driven DOFs and loads through eval_time_fn's gp, the linear RK combine takes every tangent alike, and the dense pass keeps the
+// per-member step counts, the a0 parity rule and the zero-size final step.  One lane per (member, block); no atomics, nothing depends on the
+// launch geometry.
+//
+// Layouts (KC = the chunk width, a template parameter; the host runs ceil(K / KC) passes, dfx_forward_tangent_multi):
+//   * parameter images, plain per-slot, value then tangents -- the primal half once, then KC tangent halves:
+//       slot    9 * (1 + KC):  r(2) l(2) k(3) phi(2), then the same nine per direction
+//       block   6 * (1 + KC):  1/m(3) c(3), then d(1/m)(3) dc(3) per direction
+//       member  3 + kTanMemDir * KC:  contact(3), then dcontact(3) dfn_params per direction
+//       centre  2 * (1 + KC):  centroid(2), then its tangent per direction                        (distance-based contact)
+//   * tangent records and DA: one plane per direction (d_plane / da_plane elements apart), each laid out as the single-direction buffers;
+//   * fields_dot of a pass: (B, KT, T, 2, nb, 3), KT = the directions of the pass.
+// A pass may hold several SLICES of KC directions each, one per blockIdx.y (TanSlices): every slice has an image of its own and its own
+// planes, and runs the same arithmetic; slice 0 alone stores the primal results (all slices compute the same ones).  Lattices too small to
+// fill the chip take all their directions as slices of width 1 in one pass -- the replicated-members form, which is cheaper there
+// (profiles/r09_tangent_multi.txt); everything else takes one slice of the widest width per pass.
+#pragma once
+#include "dfx_tangent.h"
+
+namespace dfx {
+
+// ---------------------------------------------------------------------------------------
+// first-order forward-mode number with K epsilon parts
+// ---------------------------------------------------------------------------------------
+template <int K>
+struct DualN {
+  double v, e[K];
+  DFX_HD DualN() : v(0.0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) e[k] = 0.0;
+  }
+  DFX_HD DualN(double a) : v(a) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) e[k] = 0.0;
+  }
+};
+#define DFX_DN_EACH _Pragma("unroll") for (int k = 0; k < K; ++k)
+template <int K> DFX_HD DualN<K> operator+(DualN<K> a, DualN<K> b) { DualN<K> r; r.v = a.v + b.v; DFX_DN_EACH r.e[k] = a.e[k] + b.e[k]; return r; }
+template <int K> DFX_HD DualN<K> operator-(DualN<K> a, DualN<K> b) { DualN<K> r; r.v = a.v - b.v; DFX_DN_EACH r.e[k] = a.e[k] - b.e[k]; return r; }
+template <int K> DFX_HD DualN<K> operator-(DualN<K> a) { DualN<K> r; r.v = -a.v; DFX_DN_EACH r.e[k] = -a.e[k]; return r; }
+template <int K> DFX_HD DualN<K> operator*(DualN<K> a, DualN<K> b) {
+  DualN<K> r; r.v = a.v * b.v; DFX_DN_EACH r.e[k] = a.v * b.e[k] + a.e[k] * b.v; return r;
+}
+template <int K> DFX_HD DualN<K> operator*(double a, DualN<K> b) { DualN<K> r; r.v = a * b.v; DFX_DN_EACH r.e[k] = a * b.e[k]; return r; }
+template <int K> DFX_HD DualN<K> operator*(DualN<K> a, double b) { DualN<K> r; r.v = a.v * b; DFX_DN_EACH r.e[k] = a.e[k] * b; return r; }
+template <int K> DFX_HD DualN<K> operator+(DualN<K> a, double b) { a.v = a.v + b; return a; }
+template <int K> DFX_HD DualN<K> operator+(double a, DualN<K> b) { b.v = a + b.v; return b; }
+template <int K> DFX_HD DualN<K> operator-(DualN<K> a, double b) { a.v = a.v - b; return a; }
+template <int K> DFX_HD DualN<K> operator-(double a, DualN<K> b) { DualN<K> r; r.v = a - b.v; DFX_DN_EACH r.e[k] = -b.e[k]; return r; }
+template <int K> DFX_HD DualN<K> operator/(DualN<K> a, DualN<K> b) {
+  const double r = 1.0 / b.v, q = a.v * r;
+  DualN<K> o; o.v = q; DFX_DN_EACH o.e[k] = (a.e[k] - q * b.e[k]) * r; return o;
+}
+template <int K> DFX_HD DualN<K> operator/(double a, DualN<K> b) {
+  const double r = 1.0 / b.v, q = a * r;
+  DualN<K> o; o.v = q; DFX_DN_EACH o.e[k] = -q * b.e[k] * r; return o;
+}
+
+// what the physics templates look up by argument type
+template <int K> DFX_HD double val(DualN<K> a) { return a.v; }
+template <int K> DFX_HD double eps(DualN<K> a, int k) { return a.e[k]; }
+template <int K> DFX_HD DualN<K> trcp(DualN<K> a) {
+  const double r = trcp(a.v);
+  DualN<K> o; o.v = r; DFX_DN_EACH o.e[k] = -a.e[k] * r * r; return o;
+}
+template <int K> DFX_HD DualN<K> tsqrt(DualN<K> a) {
+  const double s = sqrt(a.v);
+  DualN<K> o; o.v = s; DFX_DN_EACH o.e[k] = 0.5 * a.e[k] / s; return o;
+}
+template <int K> DFX_HD DualN<K> trsqrt(DualN<K> a) {
+  const double r = trsqrt(a.v);
+  DualN<K> o; o.v = r; DFX_DN_EACH o.e[k] = -0.5 * a.e[k] * r * r * r; return o;
+}
+template <int K> DFX_HD DualN<K> tatan2(DualN<K> y, DualN<K> x) {
+  const double w = trcp(x.v * x.v + y.v * y.v);
+  DualN<K> o; o.v = fast_atan2(y.v, x.v); DFX_DN_EACH o.e[k] = (x.v * y.e[k] - y.v * x.e[k]) * w; return o;
+}
+template <int K> DFX_HD DualN<K> twrap(DualN<K> a) { a.v = twrap(a.v); return a; }
+
+// seed_rec for K directions: the half-angle pair follows theta in every one
+template <int K>
+DFX_HD BlockRec<DualN<K>> seed_rec(const BlockRec<double>& r, const double (&wx)[K], const double (&wy)[K], const double (&wth)[K]) {
+  BlockRec<DualN<K>> d;
+  d.x.v = r.x; d.y.v = r.y; d.th.v = r.th; d.ch.v = r.ch; d.sh.v = r.sh;
+  DFX_DN_EACH {
+    d.x.e[k] = wx[k]; d.y.e[k] = wy[k]; d.th.e[k] = wth[k];
+    d.ch.e[k] = -0.5 * r.sh * wth[k];
+    d.sh.e[k] = 0.5 * r.ch * wth[k];
+  }
+  return d;
+}
+
+constexpr int kTanSlotVals = kTanSlot / 2;                         // 9: the primal half of a slot (and of every tangent half)
+constexpr int kTanBlkVals = kTanBlk / 2;                           // 6
+constexpr int kTanMemDir = 3 + DFX_MAX_FNS * DFX_FN_PARAMS;        // dcontact(3), dfn_params
+constexpr int kTanMaxWidth = 4;                                    // the widest chunk the library ships (profiles/r09_tangent_multi.txt)
+DFX_HD constexpr int tan_slot_n(int kc) { return kTanSlotVals * (1 + kc); }
+DFX_HD constexpr int tan_blk_n(int kc) { return kTanBlkVals * (1 + kc); }
+DFX_HD constexpr int tan_mem_n(int kc) { return 3 + kTanMemDir * kc; }
+DFX_HD constexpr int tan_cen_n(int kc) { return 2 * (1 + kc); }
+
+// where the directions of a pass lie: planes of the tangent buffers, and the images of the slices
+struct TanSlices {
+  long long d_plane, da_plane;                         // elements between the planes of two directions in D_in / DY / D_out, and in DA
+  long long tp_plane, blk_plane, mem_plane, cen_plane; // elements between the images of two slices
+  int kt;                                              // directions of the pass: slices * KC
+};
+
+// a stage of a pass: TanStage, with the tangent buffers holding one plane per direction
+struct TanStageM {
+  TanStage s;
+  TanSlices sl;
+};
+
+struct TanDenseM {
+  TanDense d;
+  TanSlices sl;
+};
+
+template <int K>
+DFX_HD BlockRec<DualN<K>> tan_rec_n(const double* S, const double* D, long long plane, int b) {
+  const BlockRec<double> r = load_rec(S, b);
+  double wx[K], wy[K], wth[K];
+  DFX_DN_EACH {
+    const double* d = D + (size_t)k * plane + (size_t)b * kRec;
+    wx[k] = d[0]; wy[k] = d[1]; wth[k] = d[2];
+  }
+  return seed_rec(r, wx, wy, wth);
+}
+
+template <int K>
+DFX_HD DualN<K> tan_par_n(const double* s, int j) {
+  DualN<K> o; o.v = s[j];
+  DFX_DN_EACH o.e[k] = s[kTanSlotVals * (1 + k) + j];
+  return o;
+}
+
+// value (vi) and K tangents (ti + stride * k) of one scalar of an image
+template <int K>
+DFX_HD DualN<K> tan_scalar_n(const double* p, int vi, int ti, int stride) {
+  DualN<K> o; o.v = p[vi];
+  DFX_DN_EACH o.e[k] = p[ti + stride * k];
+  return o;
+}
+
+// tan_drive for K directions: the time functions are evaluated once
+template <int K>
+DFX_HD void tan_drive_n(const TanCtx& c, int m, const double* mem /* the member's image of this slice */, const double* coef /* DFX_MAX_FNS */,
+                        double t, double& g_sum, double& gt_sum, double (&dg_sum)[K]) {
+  g_sum = 0.0; gt_sum = 0.0;
+  DFX_DN_EACH dg_sum[k] = 0.0;
+  const double* dfn = mem + 3 + 3;
+  for (int f = 0; f < c.n_fns; ++f) {
+    if (coef[f] == 0.0) continue;
+    double g, gt, gp[kMaxFnParams];
+    eval_time_fn(c.fns[(size_t)m * DFX_MAX_FNS + f], t, g, gt, gp);
+    g_sum += coef[f] * g;
+    gt_sum += coef[f] * gt;
+    DFX_DN_EACH {
+      double dg = 0.0;
+      for (int j = 0; j < kMaxFnParams; ++j) dg += gp[j] * dfn[kTanMemDir * k + f * DFX_FN_PARAMS + j];
+      dg_sum[k] += coef[f] * dg;
+    }
+  }
+}
+
+// state0_dot: (KT, B, 2, nb, 3) -- the directions of this pass (a padded direction is all zero), or null
+template <int K>
+__global__ void k_tan_init_multi(TanCtx c, const double* state0, const double* state0_dot, double* S, double* D, TanSlices sl) {
+  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= (long long)c.B * c.nb) return;
+  const int m = (int)(gid / c.nb), b = (int)(gid % c.nb);
+  const int slice = blockIdx.y;
+  const long long d_plane = sl.d_plane;
+  const double* mem = c.mem + (size_t)slice * sl.mem_plane + (size_t)m * tan_mem_n(K);
+  D += (size_t)slice * K * d_plane;
+  if (state0_dot) state0_dot += (size_t)slice * K * c.B * 2 * c.nb * 3;
+  const double t0 = c.t0[m * c.t0_stride];
+  const int sidx = c.block_special[b];
+  double rr[kRec];
+  double* r = rr;
+  const size_t nd = (size_t)c.nb * 3;
+  const size_t s0_plane = (size_t)c.B * 2 * nd;
+  for (int j = 0; j < 3; ++j) {
+    double q = state0 ? state0[(size_t)m * 2 * nd + b * 3 + j] : 0.0;
+    double v = state0 ? state0[(size_t)m * 2 * nd + nd + b * 3 + j] : 0.0;
+    double dq[K], dv[K];
+    DFX_DN_EACH {
+      dq[k] = state0_dot ? state0_dot[k * s0_plane + (size_t)m * 2 * nd + b * 3 + j] : 0.0;
+      dv[k] = state0_dot ? state0_dot[k * s0_plane + (size_t)m * 2 * nd + nd + b * 3 + j] : 0.0;
+    }
+    if (sidx >= 0 && ((c.special[sidx].con_mask >> j) & 1)) {
+      tan_drive_n<K>(c, m, mem, c.special[sidx].con_coef[j], t0, q, v, dq);
+      DFX_DN_EACH dv[k] = 0.0;
+    }
+    r[j] = q; r[5 + j] = v;
+    DFX_DN_EACH {
+      double* d = D + (size_t)k * d_plane + (size_t)gid * kRec;
+      d[j] = dq[k]; d[5 + j] = dv[k];
+    }
+  }
+  double s, co;
+  fast_sincos(0.5 * r[2], &s, &co);
+  r[3] = co; r[4] = s;
+  if (slice == 0) {
+    double* out = S + (size_t)gid * kRec;
+    for (int j = 0; j < kRec; ++j) out[j] = r[j];
+  }
+  DFX_DN_EACH {
+    double* d = D + (size_t)k * d_plane + (size_t)gid * kRec;
+    d[3] = 0.0; d[4] = 0.0;
+  }
+}
+
+// node vectors of the bonded node, its next and its previous node on the block (distance-based contact)
+template <int NPB, int K>
+DFX_HD void tan_node_triple_n(const double* tp, int slot, DualN<K> (&r)[3][2]) {
+  const int b = slot >> 2, k = slot & 3;
+  const int ks[3] = {k, (k + 1) % NPB, (k + NPB - 1) % NPB};
+  for (int i = 0; i < 3; ++i) {
+    const double* s = tp + (size_t)(b * kSlots + ks[i]) * tan_slot_n(K);
+    r[i][0] = tan_par_n<K>(s, 0); r[i][1] = tan_par_n<K>(s, 1);
+  }
+}
+
+template <int MODEL, int CONTACT, int NPB, int KC>
+__global__ void __launch_bounds__(256) k_tan_stage_multi(TanCtx c, Tableau T, TanStageM sm) {
+  using D = DualN<KC>;
+  constexpr int K = KC;
+  const TanStage& st = sm.s;
+  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= (long long)c.B * c.nb) return;
+  const int m = (int)(gid / c.nb), b = (int)(gid % c.nb);
+  if (c.n_steps) {
+    // dense pass: a member that has taken its N_m steps leaves; at n == N_m only the evaluation at its final state runs (k_tan_stage)
+    const long long N = c.n_steps[m];
+    if (st.n > N || (st.n == N && st.i > 0)) return;
+  }
+  const size_t moff = (size_t)m * c.nb;                 // first block of this member in the record buffers
+  const TanSlices& sl = sm.sl;
+  const int slice = blockIdx.y;                         // this lane's KC directions: planes [slice * KC, (slice + 1) * KC), image `slice`
+  const bool first = slice == 0;                        // the slice that stores the primal results
+  const size_t doff = (size_t)slice * K * sl.d_plane, daoff = (size_t)slice * K * sl.da_plane;
+  const double* S_in = st.S_in + moff * kRec;
+  const double* D_in = st.D_in + doff + moff * kRec;
+  const double* tp = c.tp + (size_t)slice * sl.tp_plane + moff * kSlots * tan_slot_n(K);
+  const double* mem = c.mem + (size_t)slice * sl.mem_plane + (size_t)m * tan_mem_n(K);
+  const BlockRec<D> o = tan_rec_n<K>(S_in, D_in, sl.d_plane, b);
+  D f[3];
+#pragma unroll
+  for (int kk = 0; kk < NPB; ++kk) {
+    const int slot = b * kSlots + kk;
+    const int info = c.slot_info[slot];
+    if (info < 0) continue;
+    const int ps = info >> 1;
+    const double sgn = (info & 1) ? 1.0 : -1.0;
+    const double* sp = tp + (size_t)slot * tan_slot_n(K);
+    const double* pp = tp + (size_t)ps * tan_slot_n(K);
+    const BlockRec<D> p = tan_rec_n<K>(S_in, D_in, sl.d_plane, ps >> 2);
+    const D lx = tan_par_n<K>(sp, 2), ly = tan_par_n<K>(sp, 3);
+    const D l0 = tsqrt(lx * lx + ly * ly);
+    const D il0 = 1.0 / l0;
+    BondGrad<D> g;
+    bond_grad_p<MODEL, D, D>(o, p, tan_par_n<K>(sp, 0), tan_par_n<K>(sp, 1), tan_par_n<K>(pp, 0), tan_par_n<K>(pp, 1), lx, ly, l0, il0,
+                             tan_par_n<K>(sp, 4), tan_par_n<K>(sp, 5), tan_par_n<K>(sp, 6), sgn, g);
+    f[0] = f[0] + g.fx; f[1] = f[1] + g.fy; f[2] = f[2] + g.fth;
+    if (CONTACT == DFX_CONTACT_DISTANCE) {
+      const D am = tan_scalar_n<K>(mem, 0, 3, kTanMemDir), ac = tan_scalar_n<K>(mem, 1, 4, kTanMemDir), kc = tan_scalar_n<K>(mem, 2, 5, kTanMemDir);
+      D ro[3][2], rp[3][2];
+      tan_node_triple_n<NPB, K>(tp, slot, ro);
+      tan_node_triple_n<NPB, K>(tp, ps, rp);
+      const double* cen = c.cen + (size_t)slice * sl.cen_plane;
+      const double* co = cen + (moff + b) * tan_cen_n(K);
+      const double* cp = cen + (moff + (ps >> 2)) * tan_cen_n(K);
+      DistContactGrad<D> dc;
+      distance_contact_grad<D, D>(o, p, tan_scalar_n<K>(co, 0, 2, 2), tan_scalar_n<K>(co, 1, 3, 2), tan_scalar_n<K>(cp, 0, 2, 2),
+                                  tan_scalar_n<K>(cp, 1, 3, 2), ro, rp, info & 1, am, ac, kc, dc);
+      f[0] = f[0] + dc.fx; f[1] = f[1] + dc.fy; f[2] = f[2] + dc.fth;
+    } else if (CONTACT == DFX_CONTACT_ANGLE) {
+      const D am = tan_scalar_n<K>(mem, 0, 3, kTanMemDir), ac = tan_scalar_n<K>(mem, 1, 4, kTanMemDir), kc = tan_scalar_n<K>(mem, 2, 5, kTanMemDir);
+      ContactGrad<D> cg;
+      const D kap = sgn * (o.th - p.th);
+      contact_grad<D, D>(kap, tan_par_n<K>(sp, 7), tan_par_n<K>(sp, 8), am, ac, kc, cg);
+      f[2] = f[2] + sgn * cg.dkap;
+    }
+  }
+  // DOF part (k_tan_stage's, the tangent lines once per direction)
+  const double* tg = c.tgrid + (size_t)m * c.grid_stride + 2 * (size_t)st.n;
+  const double t = tg[0], h = tg[1];
+  const int i = st.i, r = i + 1;
+  const double t_i = t + T.c[i] * h, t_next = t + T.c[r] * h;
+  const int sidx = c.block_special[b];
+  const double* bk = c.blk + (size_t)slice * sl.blk_plane + (moff + b) * tan_blk_n(K);
+  const size_t nd = (size_t)c.nb * 3;
+  double* A = st.A + (size_t)m * c.a_rows * nd;
+  double* DA = st.DA + daoff + (size_t)m * c.a_rows * nd;
+  const double* rin = S_in + (size_t)b * kRec;
+  const double* din = D_in + (size_t)b * kRec;
+  const double* yb = st.Y + (moff + b) * kRec;
+  const double* dyb = st.DY + doff + (moff + b) * kRec;
+  double* ro = st.S_out + (moff + b) * kRec;
+  double* dro = st.D_out + doff + (moff + b) * kRec;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    const size_t dof = (size_t)b * 3 + d;
+    bool constrained = false;
+    double fload = 0.0, cnext = 0.0, cdnext = 0.0;
+    double dfload[K], dcnext[K];
+    DFX_DN_EACH { dfload[k] = 0.0; dcnext[k] = 0.0; }
+    if (sidx >= 0) {
+      const dfx_special& sp = c.special[sidx];
+      constrained = (sp.con_mask >> d) & 1;
+      double unused;
+      if (constrained) tan_drive_n<K>(c, m, mem, sp.con_coef[d], t_next, cnext, cdnext, dcnext);
+      else tan_drive_n<K>(c, m, mem, sp.load_coef[d], t_i, fload, unused, dfload);
+    }
+    const double v_i = rin[5 + d];
+    const double inv_m = bk[d], damp = bk[3 + d];
+    const double F = fload - f[d].v - damp * v_i;
+    const double a = constrained ? 0.0 : F * inv_m;
+    const size_t arow = (size_t)(i ? i : st.a0) * nd + dof;
+    if (first) A[arow] = a;
+    double sv = T.a[r][i] * a, sq = T.aa[r][i] * a;
+    double dsv[K], dsq[K];
+    DFX_DN_EACH {
+      const double dv_i = din[(size_t)k * sl.d_plane + 5 + d];
+      const double dinv_m = bk[kTanBlkVals * (1 + k) + d], ddamp = bk[kTanBlkVals * (1 + k) + 3 + d];
+      // a = F / m: da = dF / m + F d(1/m)
+      const double da = constrained ? 0.0 : (dfload[k] - f[d].e[k] - ddamp * v_i - damp * dv_i) * inv_m + F * dinv_m;
+      DA[(size_t)k * sl.da_plane + arow] = da;
+      dsv[k] = T.a[r][i] * da; dsq[k] = T.aa[r][i] * da;
+    }
+    for (int l = 0; l < i; ++l) {
+      const size_t row = (size_t)(l ? l : st.a0) * nd + dof;
+      const double al = A[row];
+      sv += T.a[r][l] * al; sq += T.aa[r][l] * al;
+      DFX_DN_EACH {
+        const double dal = DA[(size_t)k * sl.da_plane + row];
+        dsv[k] += T.a[r][l] * dal; dsq[k] += T.aa[r][l] * dal;
+      }
+    }
+    double qnext = yb[d] + h * (T.c[r] * yb[5 + d] + h * sq);
+    double vnext = yb[5 + d] + h * sv;
+    if (constrained) { qnext = cnext; vnext = cdnext; }
+    if (first) { ro[d] = qnext; ro[5 + d] = vnext; }
+    DFX_DN_EACH {
+      const double* dy = dyb + (size_t)k * sl.d_plane;
+      double dqnext = dy[d] + h * (T.c[r] * dy[5 + d] + h * dsq[k]);
+      double dvnext = dy[5 + d] + h * dsv[k];
+      if (constrained) { dqnext = dcnext[k]; dvnext = 0.0; }
+      double* dr = dro + (size_t)k * sl.d_plane;
+      dr[d] = dqnext; dr[5 + d] = dvnext;
+      if (d == 2) { dr[3] = 0.0; dr[4] = 0.0; }
+    }
+    if (d == 2) {
+      double s, co;
+      fast_sincos(0.5 * qnext, &s, &co);
+      if (first) { ro[3] = co; ro[4] = s; }
+    }
+  }
+}
+
+// row j of fields (B, T, 2, nb, 3) and of this pass's fields_dot (B, KT, T, 2, nb, 3) from the step-base records
+template <int K>
+__global__ void k_tan_snapshot_multi(int B, int nb, int Tn, int j, const double* S, const double* D, TanSlices sl, double* fields,
+                                     double* fields_dot) {
+  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= (long long)B * nb) return;
+  const int m = (int)(gid / nb), b = (int)(gid % nb);
+  const int slice = blockIdx.y;
+  const size_t nd = (size_t)nb * 3;
+  const size_t row = ((size_t)m * Tn + j) * 2 * nd;
+  const double* r = S + (size_t)gid * kRec;
+  if (slice == 0)
+    for (int q = 0; q < 3; ++q) {
+      fields[row + b * 3 + q] = r[q];
+      fields[row + nd + b * 3 + q] = r[5 + q];
+    }
+  DFX_DN_EACH {
+    const double* d = D + (size_t)(slice * K + k) * sl.d_plane + (size_t)gid * kRec;
+    const size_t drow = (((size_t)m * sl.kt + slice * K + k) * Tn + j) * 2 * nd;
+    for (int q = 0; q < 3; ++q) {
+      fields_dot[drow + b * 3 + q] = d[q];
+      fields_dot[drow + nd + b * 3 + q] = d[5 + q];
+    }
+  }
+}
+
+// k_tan_dense for K directions: the quartic's primal evaluation once, the same linear formula on every tangent
+template <int K>
+__global__ void __launch_bounds__(256) k_tan_dense_multi(TanCtx c, TanDenseM dm) {
+  const TanDense& dn = dm.d;
+  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= (long long)c.B * c.nb) return;
+  const int m = (int)(gid / c.nb), b = (int)(gid % c.nb);
+  if (dn.n >= c.n_steps[m]) return;
+  const int32_t* op = dn.out_ptr + (size_t)m * dn.op_stride;
+  const int lo = op[dn.n], hi = op[dn.n + 1];
+  if (hi <= lo) return;
+  const TanSlices& sl = dm.sl;
+  const int slice = blockIdx.y;
+  const double* mem = c.mem + (size_t)slice * sl.mem_plane + (size_t)m * tan_mem_n(K);
+  const double h = c.tgrid[(size_t)m * c.grid_stride + 2 * (size_t)dn.n + 1];
+  const size_t nd = (size_t)c.nb * 3;
+  const double* A = dn.A + (size_t)m * c.a_rows * nd;
+  const double* DA = dn.DA + (size_t)slice * K * sl.da_plane + (size_t)m * c.a_rows * nd;
+  const double* y0 = dn.Y0 + (size_t)gid * kRec;
+  const double* y1 = dn.Y1 + (size_t)gid * kRec;
+  const int sidx = c.block_special[b];
+  for (int d = 0; d < 3; ++d) {
+    const size_t dof = (size_t)b * 3 + d;
+    const bool constrained = sidx >= 0 && ((c.special[sidx].con_mask >> d) & 1);
+    const double qn = y0[d], vn = y0[5 + d], q1 = y1[d], v1 = y1[5 + d];
+    const double a0 = A[(size_t)dn.a0 * nd + dof], a6 = A[(size_t)dn.a6 * nd + dof];
+    double sm = dn.cm[0] * a0 + dn.cm[6] * a6, sma = dn.cma[0] * a0 + dn.cma[6] * a6;
+    for (int l = 1; l < 6; ++l) {
+      const double al = A[(size_t)l * nd + dof];
+      sm += dn.cm[l] * al; sma += dn.cma[l] * al;
+    }
+    const double qmid = qn + h * (0.5 * vn + h * sma), vmid = vn + h * sm;
+    double dqn[K], dvn[K], dq1[K], dv1[K], da0[K], da6[K], dqmid[K], dvmid[K];
+    DFX_DN_EACH {
+      const double* dy0 = dn.DY0 + (size_t)(slice * K + k) * sl.d_plane + (size_t)gid * kRec;
+      const double* dy1 = dn.DY1 + (size_t)(slice * K + k) * sl.d_plane + (size_t)gid * kRec;
+      const double* DAk = DA + (size_t)k * sl.da_plane;
+      dqn[k] = dy0[d]; dvn[k] = dy0[5 + d]; dq1[k] = dy1[d]; dv1[k] = dy1[5 + d];
+      da0[k] = DAk[(size_t)dn.a0 * nd + dof]; da6[k] = DAk[(size_t)dn.a6 * nd + dof];
+      double dsm = dn.cm[0] * da0[k] + dn.cm[6] * da6[k], dsma = dn.cma[0] * da0[k] + dn.cma[6] * da6[k];
+      for (int l = 1; l < 6; ++l) {
+        const double dal = DAk[(size_t)l * nd + dof];
+        dsm += dn.cm[l] * dal; dsma += dn.cma[l] * dal;
+      }
+      dqmid[k] = dqn[k] + h * (0.5 * dvn[k] + h * dsma);
+      dvmid[k] = dvn[k] + h * dsm;
+    }
+    for (int kk = lo; kk < hi; ++kk) {
+      const double r = dn.theta[(size_t)m * dn.Tn + kk];
+      double oq = dopri_dense(qn, q1, qmid, vn, v1, h, r), ov = dopri_dense(vn, v1, vmid, a0, a6, h, r);
+      double doq[K], dov[K];
+      DFX_DN_EACH {
+        doq[k] = dopri_dense(dqn[k], dq1[k], dqmid[k], dvn[k], dv1[k], h, r);
+        dov[k] = dopri_dense(dvn[k], dv1[k], dvmid[k], da0[k], da6[k], h, r);
+      }
+      if (constrained) {
+        tan_drive_n<K>(c, m, mem, c.special[sidx].con_coef[d], dn.ts[kk], oq, ov, doq);
+        DFX_DN_EACH dov[k] = 0.0;
+      }
+      const size_t row = ((size_t)m * dn.Tn + kk) * 2 * nd;
+      if (slice == 0) {
+        dn.fields[row + dof] = oq;
+        dn.fields[row + nd + dof] = ov;
+      }
+      DFX_DN_EACH {
+        const size_t drow = (((size_t)m * sl.kt + slice * K + k) * dn.Tn + kk) * 2 * nd;
+        dn.fields_dot[drow + dof] = doq[k];
+        dn.fields_dot[drow + nd + dof] = dov[k];
+      }
+    }
+  }
+}
+
+#undef DFX_DN_EACH
+
+}  // namespace dfx

@@ -83,6 +83,51 @@ def _bcast(x, n):
     return np.broadcast_to(np.asarray(x, dtype=float), (n,)).copy()
 
 
+JACFWD_LEAVES = ("k_stretch", "k_shear", "k_rot", "density", "damping", "min_angle", "cutoff_angle", "k_contact")
+
+
+def unit_tangent(control_params: ControlParams, name):
+    """The ``ControlParams``-shaped tangent tree that is 1 on the scalar leaf ``name`` and zero (None) elsewhere -- one column of
+    :meth:`DynamicSolver.jacfwd`.  ``name``: one of ``JACFWD_LEAVES`` (stiffnesses of ``bond_params``, ``density`` / ``damping`` of
+    ``mechanical_params``, the contact constants) or a key of ``constraint_params`` / ``loading_params``.  The leaf must be ONE number: a
+    Python / 0-d scalar, or an array that holds one value broadcast over bonds or blocks -- that one gets an all-ones tangent of its
+    shape.  ``ValueError``: an unknown name, a name both dicts hold, a leaf that is missing or holds different values."""
+    mp = control_params.mechanical_params
+
+    def ones(leaf, where):
+        if leaf is None:
+            raise ValueError(f"unit_tangent: {where} is not set in these ControlParams")
+        a = np.asarray(leaf, dtype=float)
+        if a.ndim and (a.size == 0 or np.any(a != a.reshape(-1)[0])):
+            raise ValueError(f"unit_tangent: {where} is not a scalar leaf (shape {a.shape}, different values): seed it with jvp_multi")
+        return np.ones(a.shape) if a.ndim else 1.0
+    geo0 = GeometricalParams(None, None)
+    if name in ("k_stretch", "k_shear", "k_rot"):
+        bp = mp.bond_params
+        if not hasattr(bp, name):
+            raise ValueError(f"unit_tangent: these bond parameters have no {name}")
+        bd = type(bp)(**{f: (ones(getattr(bp, f), f"bond_params.{name}") if f == name else None) for f in bp._fields})
+        return ControlParams(geo0, MechanicalParams(bd, None))
+    if name in ("density", "damping"):
+        return ControlParams(geo0, MechanicalParams(None, None)._replace(**{name: ones(getattr(mp, name), f"mechanical_params.{name}")}))
+    if name in ("min_angle", "cutoff_angle", "k_contact"):
+        c = mp.contact_params
+        if c is None:
+            raise ValueError(f"unit_tangent: {name}: these ControlParams have no contact_params")
+        cd = ContactParams(**{f: (ones(getattr(c, f), f"contact_params.{name}") if f == name else None) for f in c._fields})
+        return ControlParams(geo0, MechanicalParams(None, None, contact_params=cd))
+    in_con = name in (control_params.constraint_params or {})
+    in_load = name in (control_params.loading_params or {})
+    if in_con and in_load:
+        raise ValueError(f"unit_tangent: {name!r} is a key of both constraint_params and loading_params: seed it with jvp_multi")
+    if in_con or in_load:
+        src = control_params.constraint_params if in_con else control_params.loading_params
+        if np.ndim(src[name]) != 0:
+            raise ValueError(f"unit_tangent: {name!r} is not a scalar leaf (shape {np.shape(src[name])})")
+        return ControlParams(geo0, MechanicalParams(None, None), **{"constraint_params" if in_con else "loading_params": {name: 1.0}})
+    raise ValueError(f"unit_tangent: unknown leaf {name!r} (one of {', '.join(JACFWD_LEAVES)}, or a key of constraint_params / loading_params)")
+
+
 class DynamicSolver:
     """Callable returned by :func:`setup_dynamic_solver`."""
 
@@ -433,8 +478,8 @@ class DynamicSolver:
 
         * ``control_params_dot``: a ``ControlParams``-shaped tree of tangents (the shape :meth:`vjp` returns), or a list of them, one per
           member; a leaf of None, a missing sub-tree or a missing key of ``constraint_params`` / ``loading_params`` is a zero tangent.
-          ``state0_dot`` (None: zero) has the shape of ``state0``.  Several directions for one design are members that share the design,
-          each with its own tangent (a ``jacfwd`` over k leaves = k members).  Tangents of derived leaves are exact host derivatives:
+          ``state0_dot`` (None: zero) has the shape of ``state0``.  One direction per member here; several directions per member (a
+          ``jacfwd`` over k leaves, on a solver of any batch) are :meth:`jvp_multi`.  Tangents of derived leaves are exact host derivatives:
           inertia (through compute_inertia when ``mechanical_params.inertia`` is None), void angles, time-function parameters.
         * ``fields`` is the primal history of the same call; on the same grid it equals ``solve_dynamics(..., steps_per_interval=...,
           step_times=...)`` to rounding.
@@ -471,12 +516,7 @@ class DynamicSolver:
                                       "(forward mode runs on the HIP engine only; the CPU port of the oracle is reverse mode only)")
         cps, flats = self.prepare(control_params)
         self._last = None                   # (dfx_set_params dropped the handle's checkpoint)
-        dots = list(control_params_dot) if isinstance(control_params_dot, (list, tuple)) and not isinstance(control_params_dot, ControlParams) \
-            else [control_params_dot]
-        if len(dots) == 1 and self.batch > 1:
-            dots = dots * self.batch
-        if len(dots) != self.batch:
-            raise ValueError(f"expected {self.batch} tangents, got {len(dots)}")
+        dots = self._member_tangents(control_params_dot)
         tflats = [self._flatten_tangent(cp, cd) for cp, cd in zip(cps, dots)]
         params_dot = {k: np.stack([f[k] for f in tflats]) for k in tflats[0]}
         ts = np.asarray(timepoints, dtype=float)
@@ -522,24 +562,146 @@ class DynamicSolver:
                 control = "adaptive-grid"
             fields, fields_dot, stats = self.engine.forward_tangent(s0, s0d, params_dot, ts, spi, step_times=step_times)
             self.stats = dict(stats, steps_per_interval=spi, step_times=step_times, step_control=control)
-        if len(self.constrained_pairs) and self.con_terms:
-            n_con = len(self.constrained_pairs)
-            dofs = self.constrained_pairs[:, 0] * 3 + self.constrained_pairs[:, 1]
-            for m, (cp, cd) in enumerate(zip(cps, dots)):
-                fdm = fields_dot[m].reshape(ts.shape[-1], 2, -1)
-                fdm[:, :, dofs] = 0.0
-                for term in self.con_terms:
-                    dp = term.resolve_jvp(cp.constraint_params, getattr(cd, "constraint_params", None))
-                    if not np.any(dp):
-                        continue
-                    p = term.resolve(cp.constraint_params)
-                    vec = _bcast(term.vector, n_con)
-                    for k, t in enumerate(ts[m] if ts.ndim == 2 else ts):
-                        fdm[k, 0, dofs] += vec * float(term.param_partials(float(t), p, "value") @ dp)
-                        fdm[k, 1, dofs] += vec * float(term.param_partials(float(t), p, "rate") @ dp)
+        for m, (cp, cd) in enumerate(zip(cps, dots)):
+            self._prescribed_tangent_rows(fields_dot[m], cp, cd, ts[m] if ts.ndim == 2 else ts)
         if self.batch == 1 and not isinstance(control_params, list):
             return fields[0], fields_dot[0]
         return fields, fields_dot
+
+    def _prescribed_tangent_rows(self, fields_dot_m, cp, cd, ts_m):
+        """The rows of PRESCRIBED DOFs of one member's ``fields_dot`` (T, 2, nb, 3) along one direction ``cd``, in place:
+        sum_f coef (dg_f/dp . dp, dg_f'/dp . dp) at the member's output times (:meth:`jvp`, :meth:`jvp_multi`)."""
+        if not (len(self.constrained_pairs) and self.con_terms):
+            return
+        n_con = len(self.constrained_pairs)
+        dofs = self.constrained_pairs[:, 0] * 3 + self.constrained_pairs[:, 1]
+        fdm = fields_dot_m.reshape(len(ts_m), 2, -1)
+        fdm[:, :, dofs] = 0.0
+        for term in self.con_terms:
+            dp = term.resolve_jvp(cp.constraint_params, getattr(cd, "constraint_params", None))
+            if not np.any(dp):
+                continue
+            p = term.resolve(cp.constraint_params)
+            vec = _bcast(term.vector, n_con)
+            for k, t in enumerate(ts_m):
+                fdm[k, 0, dofs] += vec * float(term.param_partials(float(t), p, "value") @ dp)
+                fdm[k, 1, dofs] += vec * float(term.param_partials(float(t), p, "rate") @ dp)
+
+    def _member_tangents(self, control_params_dot):
+        """``control_params_dot`` of one direction as a list of one tangent tree per member (:meth:`jvp`'s rules)."""
+        dots = list(control_params_dot) if isinstance(control_params_dot, (list, tuple)) and not isinstance(control_params_dot, ControlParams) \
+            else [control_params_dot]
+        if len(dots) == 1 and self.batch > 1:
+            dots = dots * self.batch
+        if len(dots) != self.batch:
+            raise ValueError(f"expected {self.batch} tangents, got {len(dots)}")
+        return dots
+
+    def jvp_multi(self, state0, timepoints, control_params, tangents, steps_per_interval=None, step_times=None, adaptive=False):
+        """:meth:`jvp` along K directions in one pass: ``fields, fields_dot = jvp_multi(state0, timepoints, control_params, tangents)``
+        with ``tangents`` a list of K pairs ``(state0_dot, control_params_dot)`` (either element may be None: zero; ``control_params_dot``
+        follows :meth:`jvp`'s rules -- None leaves, missing keys, a list of one tree per member when batch > 1).  The stage kernel carries
+        one value and several epsilon parts (``dfx_forward_tangent_multi`` / ``dfx_forward_tangent_dense_multi``), so the primal chain --
+        records, transcendentals, branch decisions, parameter loads -- is paid once per chunk of directions instead of once per
+        direction, and a solver of batch 1 returns a whole Jacobian over a few leaves.  ``fields`` is what :meth:`jvp` returns;
+        ``fields_dot`` has a direction axis in front of T: (K, T, 2, nb, 3) for a single design, (batch, K, T, 2, nb, 3) otherwise, and
+        ``fields_dot[..., k, :, :, :, :]`` is :meth:`jvp` along ``tangents[k]`` to rounding.  Grid semantics, ``adaptive=True`` (a
+        ``ValueError`` with a grid of any kind), ``self.stats`` and "``vjp`` may follow on the kept solve" are :meth:`jvp`'s."""
+        if adaptive:
+            grids = [name for name, on in (("steps_per_interval", steps_per_interval is not None), ("step_times", step_times is not None),
+                                           ("a default grid of the solver", self.steps_per_interval is not None),
+                                           ("grid_refine > 1", self.grid_refine > 1), ("per-member timepoints", np.ndim(timepoints) == 2)) if on]
+            if grids:
+                raise ValueError("DynamicSolver.jvp_multi: adaptive=True differentiates the adaptive solve on its own accepted steps and takes "
+                                 f"no grid (got {', '.join(grids)})")
+        tangents = list(tangents) if tangents is not None else []
+        if not tangents:
+            raise ValueError("DynamicSolver.jvp_multi: need at least one (state0_dot, control_params_dot) pair")
+        for tg in tangents:
+            if not (isinstance(tg, (tuple, list)) and not isinstance(tg, ControlParams) and len(tg) == 2):
+                raise ValueError("DynamicSolver.jvp_multi: every tangent is a pair (state0_dot, control_params_dot)")
+        K = len(tangents)
+        dots = [self._member_tangents(cd) for _, cd in tangents]            # [direction][member]
+        engine = self.engine
+        if not engine.has_forward_tangent_multi or (adaptive and not engine.has_forward_tangent_dense_multi):
+            lib = engine.lib
+            raise NotImplementedError(f"DynamicSolver.jvp_multi: the library {getattr(lib, '_name', lib)!r} has no dfx_forward_tangent_multi "
+                                      "(forward mode runs on the HIP engine only; the CPU port of the oracle is reverse mode only)")
+        cps, flats = self.prepare(control_params)
+        self._last = None                   # (dfx_set_params dropped the handle's checkpoint)
+        params_dots = []
+        for k in range(K):
+            tflats = [self._flatten_tangent(cp, cd) for cp, cd in zip(cps, dots[k])]
+            params_dots.append({name: np.stack([f[name] for f in tflats]) for name in tflats[0]})
+        ts = np.asarray(timepoints, dtype=float)
+        B, nb = self.batch, self.n_blocks
+
+        def members(x):
+            if x is None:
+                return None
+            x = np.asarray(x, dtype=float)
+            return np.broadcast_to(x, (B,) + x.shape) if x.ndim == 3 else x
+        s0 = members(state0)
+        s0ds = None
+        if any(sd is not None for sd, _ in tangents):
+            s0ds = np.zeros((B, K, 2, nb, 3))
+            for k, (sd, _) in enumerate(tangents):
+                if sd is not None:
+                    s0ds[:, k] = members(sd)
+        spi = steps_per_interval if steps_per_interval is not None else self.steps_per_interval
+        control = "fixed"
+        if adaptive:
+            # as jvp(adaptive=True): the refusals first (the same entry on the initial state alone), the adaptive pass with its steps kept
+            # where the physics allows it, then the tangent pass over every member's own accepted steps
+            engine.forward_tangent_dense_multi(s0, None, None, 1, ts[:1], np.full((B, 1), ts[0]), np.zeros(B, dtype=np.int64))
+            kept, primal, astats = False, None, None
+            if engine.can_keep_adaptive and os.environ.get("DFX_ADAPTIVE_RECORDS", "1") != "0":
+                try:
+                    primal, astats = engine.forward_adaptive(s0, ts, self.rtol, self.atol, max_attempts=self.max_attempts, keep_trajectory=True)
+                    kept = True
+                except RuntimeError as e:
+                    if "forward_adaptive_keep:" not in str(e):
+                        raise
+            if not kept:
+                primal, astats = engine.forward_adaptive(s0, ts, self.rtol, self.atol, max_attempts=self.max_attempts)
+            self.adaptive_stats = astats
+            grid, n_steps = _b.padded_step_times([engine.adaptive_step_times(m) for m in range(B)], ts[0])
+            fields, fields_dot, stats = engine.forward_tangent_dense_multi(s0, s0ds, params_dots, K, ts, grid, n_steps)
+            if kept:        # as a differentiable solve leaves it: vjp reverses the adaptive pass above
+                self._last = (cps, flats, ts)
+                self._last_fields = primal
+            self.stats = dict(stats, steps_per_interval=None, step_times=grid, step_control="adaptive-dense",
+                              steps_per_member=[int(n) for n in n_steps], kept_trajectory=kept)
+        else:
+            if spi is None:
+                if ts.ndim == 2:
+                    raise ValueError("per-member timepoints need steps_per_interval (the adaptive controller chooses one grid per call)")
+                # (the refusals before the adaptive pass that chooses the grid is paid for)
+                engine.forward_tangent_multi(s0, None, None, 1, ts[:1], 1)
+                spi, step_times = self.adaptive_grid(np.zeros((B, 2, nb, 3)) if s0 is None else s0, ts, flats)
+                control = "adaptive-grid"
+            fields, fields_dot, stats = engine.forward_tangent_multi(s0, s0ds, params_dots, K, ts, spi, step_times=step_times)
+            self.stats = dict(stats, steps_per_interval=spi, step_times=step_times, step_control=control)
+        for m, cp in enumerate(cps):
+            for k in range(K):
+                self._prescribed_tangent_rows(fields_dot[m, k], cp, dots[k][m], ts[m] if ts.ndim == 2 else ts)
+        if self.batch == 1 and not isinstance(control_params, list):
+            return fields[0], fields_dot[0]
+        return fields, fields_dot
+
+    def jacfwd(self, state0, timepoints, control_params, wrt, **grid_kwargs):
+        """Columns of the Jacobian of the fields with respect to scalar leaves, by :meth:`jvp_multi` on one unit tangent per name
+        (:func:`unit_tangent`): ``fields, {name: fields_dot} = jacfwd(state0, timepoints, control_params, wrt)``.  ``wrt``: names from
+        ``JACFWD_LEAVES`` and keys of ``constraint_params`` / ``loading_params``; ``grid_kwargs``: ``steps_per_interval``, ``step_times``,
+        ``adaptive``.  With batch > 1 every member's leaf of that name is seeded (a list of ``ControlParams``: one tree per member)."""
+        wrt = list(wrt)
+        if isinstance(control_params, (list, tuple)) and not isinstance(control_params, ControlParams):
+            trees = [[unit_tangent(cp, name) for cp in control_params] for name in wrt]
+        else:
+            trees = [unit_tangent(control_params, name) for name in wrt]
+        fields, fields_dot = self.jvp_multi(state0, timepoints, control_params, [(None, t) for t in trees], **grid_kwargs)
+        single = fields_dot.ndim == 5
+        return fields, {name: (fields_dot[k] if single else fields_dot[:, k]) for k, name in enumerate(wrt)}
 
     # -- reverse mode ------------------------------------------------------------------------------------
     def vjp(self, fields_bar):

@@ -266,6 +266,25 @@ int dfx_forward_tangent_dense(dfx_handle* h, const double* state0, const double*
 int dfx_dense_output_map(const double* step_times, const int64_t* n_steps, int64_t stride, int32_t batch,
                          const double* timepoints, int32_t n_timepoints, int32_t* out_ptr, double* theta);
 
+/* Forward mode for SEVERAL directions per member: n_dirs directional derivatives of the same solve with the primal evaluated once per
+ * stage (the stage kernel carries one value and KC epsilon parts; the library serves the n_dirs directions in ceil(n_dirs / KC) passes of
+ * its compiled chunk widths, the spare directions of the last pass zero).  state0_dots (batch, n_dirs, 2, n_blocks, 3) or NULL;
+ * params_dots: n_dirs entries, each with the shapes and the NULL rules of dfx_forward_tangent's params_dot (params_dots == NULL: every
+ * parameter tangent zero).  fields (batch, T, 2, n_blocks, 3) comes from the first pass; fields_dots (batch, n_dirs, T, 2, n_blocks, 3),
+ * column k = what dfx_forward_tangent / dfx_forward_tangent_dense return for direction k, to the rounding of a differently contracted
+ * epsilon arithmetic.  Contracts, return codes and refusals are those of the single-direction entries; n_dirs < 1 returns 1.  The device
+ * buffers of the call hold one pass (they do not grow with n_dirs) and are all allocated before the first pass: a failed allocation is
+ * return 2 with nothing left behind.  stats->launches and kernel_ms cover all passes.  Where batch * n_blocks * n_dirs <= 65536 (too few
+ * lanes to give every SIMD a wave) all directions run in ONE pass instead, spread over lanes at width 1, which is the cheaper form there;
+ * the environment variable DFX_TANGENT_MULTI_FORM=chunked|spread forces either form. */
+int dfx_forward_tangent_multi(dfx_handle* h, const double* state0, const double* state0_dots, const dfx_params* params_dots,
+                              int32_t n_dirs, const double* timepoints, int32_t n_timepoints, const int32_t* steps_per_interval,
+                              const double* step_times, int32_t per_member_times,
+                              double* fields, double* fields_dots, dfx_stats* stats);
+int dfx_forward_tangent_dense_multi(dfx_handle* h, const double* state0, const double* state0_dots, const dfx_params* params_dots,
+                                    int32_t n_dirs, const double* timepoints, int32_t n_timepoints, const double* step_times,
+                                    const int64_t* n_steps, int64_t stride, double* fields, double* fields_dots, dfx_stats* stats);
+
 /* Device-resident variants for benchmarking: the forward keeps the (T, ...) fields on the device and
  * the cotangent is the target-kinetic-energy objective  sum_t sum_{b in target} m_bd v_bd^2 / 2
  * (energy.py:494-499, problems/quads_focusing.py:447-467), evaluated on the device. */
