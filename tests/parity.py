@@ -351,9 +351,11 @@ def run_engine_param_leaves(sc, ts, spi=None, adaptive=False, rtol=1e-5, atol=1e
     return dict(members=out, fwd_stats=st_fwd, fwd_stats_again=st_fwd2, raw_stats=st_raw, tree_stats=st_tree, step_times=step_times)
 
 
-def oracle_param_leaves(sc, ts, spi=None, step_times=None, integrator="dopri5"):
+def oracle_param_leaves(sc, ts, spi=None, step_times=None, integrator="dopri5", expanded=False):
     """torch.autograd through the oracle's unrolled fixed-grid solve (or its replay of the engine's accepted adaptive steps, one list of
-    step boundaries per member) with every parameter leaf on the tape, member by member."""
+    step boundaries per member) with every parameter leaf on the tape, member by member.  ``expanded``: the leaves a forward-mode
+    tangent is given on -- the stiffnesses per ligament even where the member's are scalars, and also the gradient with respect to the node
+    vectors themselves (key ``cnv``; inertia is a leaf of its own here, so this is their path through the energy and the void angles)."""
     c = sc.c
     B, y0 = len(sc.members), _y0(sc)
     fb = _fields_bar(sc, len(ts))
@@ -367,6 +369,8 @@ def oracle_param_leaves(sc, ts, spi=None, step_times=None, integrator="dopri5"):
                    k_contact=c.contact_params[2])
         if c.contact:
             names += ["min_angle", "cutoff_angle", "k_contact"]
+        if expanded:
+            src.update({k: np.broadcast_to(p[k], (len(c.bonds),)) for k in ("ks", "ksh", "kr")})
         leaves = {k: T64(src[k], True) for k in names}
         y0t = T64(y0, True)
         cp = c.oracle_cp(dict(cnv=cnv, cen=cen, **leaves))
@@ -378,8 +382,10 @@ def oracle_param_leaves(sc, ts, spi=None, step_times=None, integrator="dopri5"):
             hist, _ = OD.solve_adaptive_replay_differentiable(osol, c.ogeo, y0t, ts, cp, step_times[m])
         free = osol.free_DOF_ids
         L = (hist * T64(fb[m].reshape(len(ts), 2, -1)[:, :, free])).sum()
-        gr = torch.autograd.grad(L, design + [leaves[k] for k in names] + [y0t])
+        gr = torch.autograd.grad(L, design + [leaves[k] for k in names] + [y0t] + ([cnv] if expanded else []))
         d = {"fields": hist.detach().numpy()}
+        if expanded:
+            d["cnv"], gr = gr[-1].numpy(), gr[:-1]
         for i, g in enumerate(gr[:len(design)]):
             d[f"design{i}"] = g.numpy()
         for k, g in zip(names, gr[len(design):-1]):
@@ -414,3 +420,133 @@ def check_param_leaves(sc, ts, spi=None, adaptive=False, integrator="dopri5", rt
     eng = run_engine_param_leaves(sc, ts, spi=spi, adaptive=adaptive, rtol=rtol, atol=atol)
     ref = oracle_param_leaves(sc, ts, spi=spi, step_times=eng["step_times"], integrator=integrator)
     return eng, compare_param_leaves(eng, ref)
+
+
+# -- forward mode on the same parameter images --------------------------------------------------------------------------------------------
+
+LEAF_OF_SHAPE = {"k_per_bond": ("ks", "ksh", "kr"), "uniform": ("ks", "ksh", "kr"), "damping_per_block": ("damping",)}     # else: refv
+JVP_NAMES = ("cnv", "refv", "ks", "ksh", "kr", "inertia", "damping", "amplitude", "loading_rate", "input_delay", "state0")
+CONTACT_NAMES = ("min_angle", "cutoff_angle", "k_contact")
+
+
+def shape_leaf_names(shape):
+    """The leaves a shape of tests/param_shapes.py is named after (oracle names)."""
+    return LEAF_OF_SHAPE.get(shape, ("refv",))
+
+
+def tangent_tree_of(sc, leaves):
+    """(state0_dot, ControlParams-shaped tangent tree) out of a dict of oracle-named tangent leaves, following ``DynamicSolver.jvp``'s rules:
+    a leaf the dict does not hold is None (a zero tangent), and so is state0_dot."""
+    import difflexmm_amd as dm
+    g = leaves.get
+    contact = None
+    if sc.c.contact and any(k in leaves for k in CONTACT_NAMES):
+        contact = dm.ContactParams(*[g(k) for k in CONTACT_NAMES])
+    con = {k: leaves[k] for k in ("amplitude", "loading_rate", "input_delay") if k in leaves}
+    tree = dm.ControlParams(dm.GeometricalParams(None, g("cnv")),
+                            dm.MechanicalParams(dm.LigamentParams(g("ks"), g("ksh"), g("kr"), g("refv")), None, g("inertia"), g("damping"), contact),
+                            constraint_params=con or None)
+    return g("state0"), tree
+
+
+def shape_tangents(sc, seed):
+    """Per member of a ShapeCase, named directions over the member's OWN leaves: ``out[m][name] = (state0_dot, tree, leaves)`` with
+    ``(state0_dot, tree)`` what ``jvp`` takes for that member and ``leaves`` the same content under the oracle's names (a leaf that is
+    missing there is a zero tangent).  ``"all"``: a random tangent of every leaf at relative size ~1 (as _tangent_tree of
+    tests/test_gpu_tangent.py: node vectors, reference vectors and stiffnesses per ligament, inertia per block and DOF -- a ShapeCase gives
+    it as a leaf, so it is seeded directly --, damping in the leaf's own shape, contact constants, pulse parameters, state0).  ``"leaf"``:
+    only the leaves the shape is named after, with the values they have in ``"all"`` (so all - leaf is ``"all"`` without them): relerr
+    normalises by the global maximum, and the tangent of e.g. the damping alone sits three decades under the all-leaf column."""
+    c = sc.c
+    rng = np.random.default_rng(seed)
+    nbd = len(c.bonds)
+    assert all(p["inertia"] is not None for p in sc.members), "shape_tangents seeds the inertia leaf directly"
+    fast = dict(amplitude=7.5, loading_rate=3000.0, input_delay=1e-5)
+    out = []
+    for p in sc.members:
+        def d(x):
+            return rng.normal(size=np.shape(x)) * (np.abs(np.asarray(x, dtype=float)) + 1e-12)
+        lv = dict(cnv=0.02 * rng.normal(size=np.shape(c.cnv)), refv=d(np.broadcast_to(p["refv"], (nbd, 2))),
+                  ks=d(np.broadcast_to(p["ks"], (nbd,))), ksh=d(np.broadcast_to(p["ksh"], (nbd,))), kr=d(np.broadcast_to(p["kr"], (nbd,))),
+                  inertia=d(p["inertia"]), damping=d(p["damping"]))
+        assert np.shape(lv["damping"]) == np.shape(p["damping"])
+        if c.contact:
+            lv.update({k: 0.05 * rng.normal() for k in CONTACT_NAMES})
+        lv.update({k: 0.1 * rng.normal() * v for k, v in fast.items()})
+        y0d = rng.normal(size=(2, c.geo.n_blocks, 3)) * np.array([0.05, 0.05, 0.02])
+        y0d[1] *= 5.0
+        y0d.reshape(2, -1)[:, c.solver.constrained_DOF_ids] = 0.0          # (state0 of prescribed DOFs is not read)
+        lv["state0"] = y0d
+        only = {k: lv[k] for k in shape_leaf_names(sc.shape)}
+        out.append({"all": tangent_tree_of(sc, lv) + (lv,), "leaf": tangent_tree_of(sc, only) + (only,)})
+    return out
+
+
+def oracle_member_leaves(sc, p):
+    """The primal leaves of one member under the oracle's names (NumPy), state0 included."""
+    c = sc.c
+    nbd = len(c.bonds)
+    lv = dict(cnv=c.cnv, refv=np.broadcast_to(p["refv"], (nbd, 2)), ks=np.broadcast_to(p["ks"], (nbd,)), ksh=np.broadcast_to(p["ksh"], (nbd,)),
+              kr=np.broadcast_to(p["kr"], (nbd,)), inertia=p["inertia"], damping=p["damping"], amplitude=7.5, loading_rate=3000.0,
+              input_delay=1e-5, state0=_y0(sc))
+    if c.contact:
+        lv.update(zip(CONTACT_NAMES, c.contact_params))
+    return lv
+
+
+def oracle_param_jvp(sc, ts, directions, spi=None, step_times=None, names=("all", "leaf"), members=None):
+    """torch.autograd.functional.jvp through the oracle's unrolled fixed-grid solve (``step_times[m]``: through its replay of the accepted
+    adaptive steps of member m), member by member and direction by direction; ``directions``: what :func:`shape_tangents` returns.
+    Returns per member ``{"fields": (T, 2, n_free), name: fields_dot (T, 2, n_free), ...}`` on the free DOFs (None for a member that
+    ``members`` leaves out)."""
+    c = sc.c
+    keys = list(JVP_NAMES) + (list(CONTACT_NAMES) if c.contact else [])
+    out = []
+    for m, p in enumerate(sc.members):
+        if members is not None and m not in members:
+            out.append(None)
+            continue
+        prim = oracle_member_leaves(sc, p)
+        if step_times is None:
+            osol = c.oracle_solver(integrator="fixed", steps_per_interval=spi, tableau="dopri5")
+        else:
+            osol = c.oracle_solver(integrator="adaptive")
+
+        def f(*xs):
+            lv = dict(zip(keys, xs))
+            y0t = lv.pop("state0")
+            if step_times is None:
+                return OD.solve_fixed_differentiable(osol, c.ogeo, y0t, ts, c.oracle_cp(lv), spi, "dopri5")[0]
+            return OD.solve_adaptive_replay_differentiable(osol, c.ogeo, y0t, ts, c.oracle_cp(lv), step_times[m])[0]
+        d = {}
+        for name in names:
+            tan = directions[m][name][2]
+            assert set(tan) <= set(keys), sorted(set(tan) - set(keys))
+            of, ojv = torch.autograd.functional.jvp(f, tuple(T64(prim[k]) for k in keys),
+                                                    tuple(T64(tan[k]) if k in tan else torch.zeros_like(T64(prim[k])) for k in keys))
+            d["fields"] = of.detach().numpy()
+            d[name] = ojv.numpy()
+        out.append(d)
+    return out
+
+
+def oracle_param_fields(sc, ts, spi, m, **replaced):
+    """The oracle's own fixed-grid fields (free DOFs) of member m, with leaves of ``replaced`` instead of the member's."""
+    c = sc.c
+    lv = dict(oracle_member_leaves(sc, sc.members[m]), **replaced)
+    y0 = lv.pop("state0")
+    osol = c.oracle_solver(integrator="fixed", steps_per_interval=spi, tableau="dopri5")
+    of = osol(y0, ts, c.oracle_cp({k: T64(v) for k, v in lv.items()})).numpy()
+    return of.reshape(len(ts), 2, -1)[:, :, osol.free_DOF_ids]
+
+
+def uniform_twin(sc, m):
+    """The leaves that turn member m's image into its uniform twin: the leaf the shape is named after replaced by its mean (stiffnesses,
+    damping per DOF) or by the lattice's own reference vectors."""
+    c, p = sc.c, sc.members[m]
+    names = shape_leaf_names(sc.shape)
+    if names == ("refv",):
+        return dict(refv=np.broadcast_to(c.refv, (len(c.bonds), 2)).copy())
+    if names == ("damping",):
+        return dict(damping=np.broadcast_to(p["damping"], (len(c.damped), 3)).mean(0))
+    return {k: float(np.mean(p[k])) for k in names}

@@ -77,3 +77,48 @@ def check_read_only_view_of_writeable_base(lib):
     fresh = _solve_and_vjp(fresh_case, _params(fresh_case, dict(lv, cnv=base.copy())))
     assert not np.array_equal(first["fields"], fresh["fields"])
     _assert_same(again, fresh)
+
+
+def _jvp(c, cp, tangent):
+    s = c.solver
+    rng = np.random.default_rng(6)
+    y0d = rng.normal(size=(2, c.geo.n_blocks, 3)) * np.array([0.05, 0.05, 0.02])
+    fields, fdot = s.jvp(np.zeros((2, c.geo.n_blocks, 3)), TS, cp, y0d, tangent, steps_per_interval=6)
+    return dict(fields=np.array(fields), fields_dot=np.array(fdot))
+
+
+def check_image_shape_change_reaches_jvp(lib, leaf):
+    """Forward mode rebuilds its per-slot image from the packed one on every call: jvp on a uniform image; change ``leaf`` in place so
+    that the SHAPE of the packed image changes -- ``k_stretch`` to per-ligament values (k_uniform flips and p_k is filled for the first
+    time), ``reference_vector`` scaled by per-ligament factors on 13 x 13 quads (more than 256 distinct vectors: l_dict_ok flips and p_l
+    is filled for the first time) --; jvp again: bit-equal to a fresh solver given a copy, and different from the first call."""
+    n = {"k_stretch": 5, "reference_vector": 13}[leaf]
+
+    def case():
+        return Case("quads", n, True, True, seed=21, lib=lib, cutoff_deg=42.0)
+    c = case()
+    nbd = len(c.bonds)
+    rng = np.random.default_rng(9)
+    lv = dict(ks=np.full(nbd, K_STRETCH), refv=np.broadcast_to(c.refv, (nbd, 2)).copy(), damping=np.array(c.dval, dtype=float))
+    tangent = dm.ControlParams(
+        dm.GeometricalParams(None, 0.02 * rng.normal(size=np.shape(c.cnv))),
+        dm.MechanicalParams(dm.LigamentParams(K_STRETCH * rng.normal(size=nbd), K_SHEAR * rng.normal(size=nbd), K_ROT * rng.normal(size=nbd),
+                                              rng.normal(size=(nbd, 2))), None, None, lv["damping"] * rng.normal(size=lv["damping"].shape)),
+        constraint_params=dict(amplitude=0.7))
+    cp = _params(c, lv)
+    distinct = lambda: len(np.unique(lv["refv"], axis=0))      # noqa: E731
+    assert np.all(lv["ks"] == lv["ks"][0]) and distinct() <= 16
+    first = _jvp(c, cp, tangent)
+    if leaf == "k_stretch":
+        lv["ks"] *= 1 + 0.1 * rng.uniform(-1, 1, nbd)          # in place: the ControlParams still holds the same array
+        assert len(np.unique(lv["ks"])) == nbd
+    else:
+        lv["refv"] *= (1 + 0.04 * (np.arange(nbd) / (nbd - 1) - 0.5))[:, None]
+        assert distinct() > 256, distinct()
+    again = _jvp(c, cp, tangent)
+    fresh_case = case()
+    fresh = _jvp(fresh_case, _params(fresh_case, {k: v.copy() for k, v in lv.items()}), tangent)
+    for k in ("fields", "fields_dot"):
+        assert np.abs(fresh[k]).max() > 0
+        assert not np.array_equal(first[k], fresh[k]), "the change does not change the result: the test would be vacuous"
+    _assert_same(again, fresh)
