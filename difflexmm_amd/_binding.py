@@ -66,7 +66,7 @@ COMM_EXPORTS = ["dfx_comm_unique_id", "dfx_comm_init", "dfx_comm_destroy", "dfx_
                 "dfx_gather_objectives", "dfx_reduce_grads", "dfx_comm_allreduce", "dfx_comm_barrier", "dfx_comm_last_error",
                 "dfx_mem_info", "dfx_device_synchronize", "dfx_kinetic_value_and_grad_device", "dfx_download", "dfx_forward_kinetic_value_and_grad",
                 "dfx_forward_tangent", "dfx_forward_tangent_dense", "dfx_dense_output_map", "dfx_forward_tangent_multi",
-                "dfx_forward_tangent_dense_multi"]
+                "dfx_forward_tangent_dense_multi", "dfx_rhs_jvp"]
 EXPORTS = EXPORTS + COMM_EXPORTS
 
 
@@ -142,6 +142,8 @@ def declare(lib):
     if hasattr(lib, "dfx_forward_tangent_dense_multi"):
         lib.dfx_forward_tangent_dense_multi.argtypes = [H, _dp, _dp, C.POINTER(dfx_params), C.c_int32, _dp, C.c_int32, _dp, C.POINTER(C.c_int64),
                                                         C.c_int64, _dp, _dp, C.POINTER(dfx_stats)]
+    if hasattr(lib, "dfx_rhs_jvp"):
+        lib.dfx_rhs_jvp.argtypes = [H, _dp, C.c_double, _dp, C.POINTER(dfx_params), C.c_int32, _dp, _dp]
     if hasattr(lib, "dfx_comm_init"):
         lib.dfx_comm_unique_id.argtypes = [C.c_char_p]
         lib.dfx_comm_init.argtypes = [C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(H)]
@@ -755,6 +757,28 @@ class Engine:
         g, out = self._grads(which)
         self._check(self.lib.dfx_rhs_vjp(self._h, _ptr(y), float(t), _ptr(lam), _ptr(y_bar), C.byref(g)), "dfx_rhs_vjp")
         return y_bar, out
+
+    @property
+    def has_rhs_jvp(self):
+        return hasattr(self.lib, "dfx_rhs_jvp")
+
+    def rhs_jvp(self, y, t, y_dots, params_dots, n_dirs):
+        """Forward mode of :meth:`rhs` for ``n_dirs`` directions (``dfx_rhs_jvp``, the twin of :meth:`rhs_vjp`): ``y_dots``
+        (batch, n_dirs, 2, nb, 3) or None, ``params_dots`` a list of ``n_dirs`` dicts of arrays by ``dfx_params`` field name (or None).
+        Returns (dy (batch, 2, nb, 3), dy_dots (batch, n_dirs, 2, nb, 3)); rows of constrained DOFs are 0."""
+        if not self.has_rhs_jvp:
+            raise NotImplementedError(f"forward mode: the library {getattr(self.lib, '_name', self.lib)!r} has no dfx_rhs_jvp "
+                                      "(the CPU port of the oracle is reverse mode only; build the HIP engine)")
+        K = int(n_dirs)
+        if params_dots is not None and len(params_dots) != K:
+            raise ValueError(f"rhs_jvp: need one params_dot per direction (n_dirs={K})")
+        B, nb = self.batch, self.n_blocks
+        y = _f64(y, (B, 2, nb, 3))
+        y_dots = self._state0_dots(y_dots, K) if K >= 1 else None
+        p, keep = self._params_dots(params_dots, K) if K >= 1 else (None, [])
+        dy, dy_dots = np.empty((B, 2, nb, 3)), np.empty((B, max(K, 0), 2, nb, 3))
+        self._check(self.lib.dfx_rhs_jvp(self._h, _ptr(y), float(t), _ptr(y_dots), p, K, _ptr(dy), _ptr(dy_dots)), "dfx_rhs_jvp")
+        return dy, dy_dots
 
     def energy(self, u):
         u = _f64(u, (self.batch, self.n_blocks, 3))

@@ -395,6 +395,39 @@ __global__ void k_tan_snapshot_multi(int B, int nb, int Tn, int j, const double*
   }
 }
 
+// The output of ONE right-hand-side evaluation (dfx_rhs_jvp) from what k_tan_init_multi and stage 0 of a step of size zero left behind: the
+// step-base records Y / DY (velocities and their tangents) and row 0 of A / DA (accelerations and their tangents).  dy (B, 2, nb, 3) and this
+// pass's dy_dots (B, KT, 2, nb, 3) are laid out as k_tan_snapshot_multi lays out one row of fields / fields_dot; the rows of prescribed DOFs
+// are 0 (the stage already stores a = da = 0 there; their velocity is c'(t) in the records and is masked here).
+template <int K>
+__global__ void k_tan_rhs_out_multi(TanCtx c, const double* Y, const double* DY, const double* A, const double* DA, TanSlices sl, double* dy,
+                                    double* dy_dots) {
+  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= (long long)c.B * c.nb) return;
+  const int m = (int)(gid / c.nb), b = (int)(gid % c.nb);
+  const int slice = blockIdx.y;
+  const size_t nd = (size_t)c.nb * 3;
+  const size_t arow = (size_t)m * c.a_rows * nd + (size_t)b * 3;
+  const size_t row = (size_t)m * 2 * nd;
+  const int sidx = c.block_special[b];
+  const int con_mask = sidx >= 0 ? c.special[sidx].con_mask : 0;
+  const double* r = Y + (size_t)gid * kRec;
+  if (slice == 0)
+    for (int q = 0; q < 3; ++q) {
+      dy[row + b * 3 + q] = ((con_mask >> q) & 1) ? 0.0 : r[5 + q];
+      dy[row + nd + b * 3 + q] = A[arow + q];
+    }
+  DFX_DN_EACH {
+    const double* d = DY + (size_t)(slice * K + k) * sl.d_plane + (size_t)gid * kRec;
+    const double* da = DA + (size_t)(slice * K + k) * sl.da_plane + arow;
+    const size_t drow = ((size_t)m * sl.kt + slice * K + k) * 2 * nd;
+    for (int q = 0; q < 3; ++q) {
+      dy_dots[drow + b * 3 + q] = ((con_mask >> q) & 1) ? 0.0 : d[5 + q];
+      dy_dots[drow + nd + b * 3 + q] = da[q];
+    }
+  }
+}
+
 // k_tan_dense for K directions: the quartic's primal evaluation once, the same linear formula on every tangent
 template <int K>
 __global__ void __launch_bounds__(256) k_tan_dense_multi(TanCtx c, TanDenseM dm) {

@@ -1,5 +1,6 @@
 // engine_tangent_multi.hip -- forward mode for several directions per member (kernels in dfx_tangent_multi.h): dfx_forward_tangent_multi and
-// dfx_forward_tangent_dense_multi, the K-direction forms of dfx_forward_tangent / dfx_forward_tangent_dense (engine_tangent.hip).
+// dfx_forward_tangent_dense_multi, the K-direction forms of dfx_forward_tangent / dfx_forward_tangent_dense (engine_tangent.hip), and
+// dfx_rhs_jvp, one right-hand-side evaluation with K tangents (the forward-mode twin of dfx_rhs_vjp).
 //
 // The K directions are served in passes of a compile-time chunk width (kWidths; the tail takes the narrowest shipped width that holds it,
 // its spare directions zero).  A pass is the single-direction solve with DualN<KC> in place of Dual: one stage launch per Runge-Kutta stage,
@@ -541,6 +542,65 @@ extern "C" int dfx_forward_tangent_dense_multi(dfx_handle* h, const double* stat
       stats->streams = 1;
     }
     if (rc) return rc;
+  }
+  return 0;
+}
+
+namespace {
+
+template <int KC>
+void launch_rhs_out(dim3 grid, hipStream_t s, const TanCtx& c, const MultiBufs& d, const TanSlices& sl) {
+  hipLaunchKernelGGL(k_tan_rhs_out_multi<KC>, grid, dim3(256), 0, s, c, (const double*)d.Y[0].p, (const double*)d.DY[0].p, (const double*)d.A.p,
+                     (const double*)d.DA.p, sl, d.fields.p, d.fields_dot.p);
+}
+
+}  // namespace
+
+// One evaluation is the tangent solve's own machinery on a step of size zero at t: k_tan_init_multi builds the records (prescribed DOFs and
+// their tangents from c(t)), stage 0 of the unchanged k_tan_stage_multi leaves a and da in row 0 of A / DA (the dense pass ends every
+// member with exactly this evaluation), and k_tan_rhs_out_multi writes the two results in the layout of one output row, so the pass forms,
+// the images and the download are those of dfx_forward_tangent_multi.  The stage kernel itself is not touched: its ligament walk shares no
+// code with a second kernel, so the shipped builds keep their registers (profiles/r09_tangent_multi_resources.txt).
+extern "C" int dfx_rhs_jvp(dfx_handle* h, const double* y, double t, const double* y_dots, const dfx_params* params_dots, int32_t n_dirs,
+                           double* dy, double* dy_dots) {
+  HIP_OK(hipSetDevice(h->device));
+  if (!h->have_params) { h->err = "rhs_jvp: set_params first"; return 1; }
+  const Plan& pl = h->pl;
+  if (pl.n_ovf) {
+    h->err = "rhs_jvp: nodes that carry more than one ligament (extra ligaments of a general bond list) are not supported";
+    return 1;
+  }
+  if (n_dirs < 1) { h->err = "rhs_jvp: need >= 1 direction"; return 1; }
+  if (!y) { h->err = "rhs_jvp: need y (batch, 2, n_blocks, 3)"; return 1; }
+  const int B = pl.batch, nb = pl.n_blocks;
+  const std::vector<double> tgrid{t, 0.0}, t0{t};          // one step of size zero at t
+  const std::vector<Pass> passes = plan_passes(n_dirs, (long long)B * nb);
+  MultiBufs d;
+  TanCtx c;
+  if (int rc = multi_alloc(h, passes[0], tgrid, t0, y, y_dots != nullptr, 1, 1, d, c)) return rc;
+  hipStream_t st = h->stream;
+  for (const Pass& p : passes) {
+    if (int rc = multi_upload_pass(h, params_dots, y_dots, n_dirs, p, d)) return rc;
+    const MultiKernels kn = pick_kernels(pl.model, pl.contact, pl.n_npb, p.kc);
+    const dim3 grid((unsigned)(((size_t)B * nb + 255) / 256), (unsigned)p.slices);
+    const TanSlices sl = pass_slices(h, p, 1);
+    kn.init(grid, st, c, d.s0.p, y_dots ? d.s0d.p : nullptr, d.Y[0].p, d.DY[0].p, sl);
+    TanStageM tm;
+    TanStage& ts = tm.s;
+    ts.S_in = d.Y[0].p; ts.D_in = d.DY[0].p;
+    ts.Y = d.Y[0].p; ts.DY = d.DY[0].p;
+    ts.S_out = d.S[1].p; ts.D_out = d.DS[1].p;          // (the records of a next stage nobody runs)
+    ts.A = d.A.p; ts.DA = d.DA.p;
+    ts.n = 0; ts.i = 0; ts.a0 = 0;
+    tm.sl = sl;
+    kn.stage(grid, st, c, pl.tab, tm);
+    switch (p.kc) {
+      case 4: launch_rhs_out<4>(grid, st, c, d, sl); break;
+      case 2: launch_rhs_out<2>(grid, st, c, d, sl); break;
+      default: launch_rhs_out<1>(grid, st, c, d, sl); break;
+    }
+    HIP_OK(hipGetLastError());
+    if (int rc = multi_download_pass(h, p, n_dirs, 1, d, dy, dy_dots, "rhs_jvp")) return rc;
   }
   return 0;
 }

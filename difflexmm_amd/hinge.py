@@ -10,7 +10,11 @@ The reference differentiates all of it with ``jax.grad``.  Here the dynamics and
 reaction force: a second, unconstrained handle with one member per output time evaluates ``a = -M^-1 dE/du`` for all output
 configurations in one call (``dfx_rhs``), and its Hessian-vector hook (``dfx_rhs_vjp``) gives, again in one call, both pieces of the
 gradient that do not come from the reverse sweep -- ``K(u_t) e_R`` (the cotangent of the displacement history, which the reverse sweep
-then carries back to the stiffnesses) and the explicit derivative of the elastic force w.r.t. the stiffnesses."""
+then carries back to the stiffnesses) and the explicit derivative of the elastic force w.r.t. the stiffnesses.
+
+Not in the reference: the same two pieces in forward mode (``force_jvp`` on the engine's ``dfx_rhs_jvp``, ``force_jacobian`` on
+``solve_dynamics.jacfwd``), the residuals and their Jacobian (``HingeResponseError.residuals_and_jacobian``) and a Levenberg-Marquardt fit on
+them (``run_optimization_lm``): three unknowns and a few dozen residuals are a least-squares problem, not a descent problem."""
 from dataclasses import InitVar, dataclass
 from typing import Any, Dict, List, Optional
 
@@ -136,6 +140,38 @@ class _HingeBase:
         fields_bar = np.zeros_like(solution_data.fields)
         fields_bar[:, 0] = y_bar[:, 0]
         return fields_bar, g["k_bond"].sum((0, 1))
+
+    def force_jvp(self, solution_data, control_params, fields_dots, k_dots):
+        """Forward-mode twin of :meth:`force_vjp`: the tangent of the (multiplied) force history along K directions, (K, T).
+        ``fields_dots[k]`` (T, 2, n_blocks, 3) is the tangent of the fields and ``k_dots[k]`` that of (k_stretch, k_shear, k_rot):
+        d force_t = K(u_t)[R, :] du_t + dF_R/dk . dk, one batched ``dfx_rhs_jvp`` call with one member per output time (the inertia
+        does not depend on the stiffnesses)."""
+        inertia = self._load_force_engine(control_params)
+        T, n = self.n_timepoints, self.geometry.n_blocks
+        K = len(k_dots)
+        y = np.zeros((T, 2, n, 3))
+        y[:, 0] = solution_data.fields[:, 0]
+        y_dots = np.zeros((T, K, 2, n, 3))
+        for k in range(K):
+            y_dots[:, k, 0] = np.asarray(fields_dots[k], dtype=float)[:, 0]
+        n_bonds = len(self.bond_connectivity)
+        params_dots = [dict(k_bond=np.broadcast_to(np.asarray(kd, dtype=float), (T, n_bonds, 3)).copy()) for kd in k_dots]
+        _, dy_dots = self._force.engine.rhs_jvp(y, 0.0, y_dots, params_dots, K)
+        rb, rd = self.reaction_block_DOF_pairs[:, 0], self.reaction_block_DOF_pairs[:, 1]
+        return -(dy_dots[:, :, 1][:, :, rb, rd] * inertia[rb, rd]).sum(2).T * self.force_multiplier
+
+    def force_jacobian(self, k_values):
+        """(forces (T,), jac (T, 3)): the multiplied force history and its Jacobian w.r.t. (k_stretch, k_shear, k_rot) in forward mode --
+        one ``solve_dynamics.jacfwd`` (on the problem's ``steps_per_interval``, or through the adaptive solve when there is none; the
+        fields come from that same pass), then :meth:`force_jvp`.  Not in the reference, which has reverse mode only."""
+        names = ["k_stretch", "k_shear", "k_rot"]
+        cp = self.control_params(k_values)
+        grid = dict(steps_per_interval=self.steps_per_interval) if self.steps_per_interval is not None else dict(adaptive=True)
+        fields, cols = self.solve_dynamics.jacfwd(self.state0, self.timepoints, cp, names, **grid)
+        self.solution_data = SolutionData(self._block_centroids, self._centroid_node_vectors, self.bond_connectivity, self.timepoints, fields)
+        _, forces = self.force_displacement(self.solution_data, cp)
+        jac = self.force_jvp(self.solution_data, cp, [cols[name] for name in names], np.eye(3))
+        return forces, jac.T
 
 
 @dataclass
@@ -288,6 +324,38 @@ class HingeResponseError:
             implicit = p.solve_dynamics.vjp_raw(fields_bar, which=("k_bond",))["k_bond"]
             grad += explicit + np.asarray(implicit, dtype=float)[0].sum(0)
         return value, tuple(grad)
+
+    def residuals_and_jacobian(self, k_values):
+        """``r`` (n_tests * T,) = reaction forces - target forces and ``J`` (n_tests * T, 3) = dr / d(k_stretch, k_shear, k_rot), tests
+        in the order of ``forward_problems``; the objective is ``mean(r ** 2)`` and its gradient ``2 J^T r / r.size``.  An addition to
+        the reference (forward mode: ``_HingeBase.force_jacobian``)."""
+        if not self.is_setup:
+            self.setup_objective()
+        r, J = [], []
+        for p, target in zip(self.forward_problems, self.target_forces):
+            forces, jac = p.force_jacobian(k_values)
+            r.append(forces - target)
+            J.append(jac)
+        return np.concatenate(r), np.concatenate(J)
+
+    def run_optimization_lm(self, initial_guess, n_iterations, lower_bound=None, upper_bound=None, verbose=False):
+        """AN ADDITION TO THE REFERENCE, which has no such loop: the fit as the nonlinear least-squares problem it is, by the bounded
+        Levenberg-Marquardt of ``difflexmm_amd.optimize`` on :meth:`residuals_and_jacobian` (at most ``n_iterations`` evaluations).
+        Every evaluation is recorded in ``objective_values`` / ``design_values`` as the other two loops do; ``fitted_responses`` are
+        those of the best design evaluated."""
+        from .optimize import levenberg_marquardt
+
+        def fun(x):
+            r, J = self.residuals_and_jacobian(tuple(x))
+            v = float(np.mean(r ** 2))
+            self.objective_values.append(v)
+            self.design_values.append(tuple(float(a) for a in x))
+            if verbose:
+                print(f"Iteration: {len(self.objective_values)}\nObjective = {v}")
+            return r, J
+        history = levenberg_marquardt(fun, np.asarray(initial_guess, dtype=float), lower=lower_bound, upper=upper_bound,
+                                      max_evaluations=n_iterations)
+        self.fitted_responses = self.compute_fitted_responses(tuple(float(a) for a in history["x"][-1]))
 
     def run_optimization_GD(self, initial_guess, n_iterations, step_size, lower_bound=None, upper_bound=None, verbose=False):
         self.objective_values, self.design_values = naive_GD(self.value_and_grad, initial_guess, step_size, n_iterations, lower_bound,

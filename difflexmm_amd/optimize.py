@@ -1,4 +1,4 @@
-"""Method of moving asymptotes for the design loop.
+"""Method of moving asymptotes for the design loop, and a bounded Levenberg-Marquardt for the least-squares fits.
 
 The reference maximises its objectives with NLopt's ``LD_MMA`` (``problems/quads_focusing.py:546-652``:
 ``nlopt.opt(nlopt.LD_MMA, n)``, ``add_inequality_mconstraint``, ``set_max_objective``, bounds, ``maxeval``).  NLopt is a
@@ -20,6 +20,9 @@ NLopt uses it --
 
 Constraint Jacobians may be ``scipy.sparse`` matrices (the geometric constraints of the lattices are local).
 Host code (a few thousand variables, once per design iteration), not part of the kernel path.
+
+``levenberg_marquardt`` is not in the reference: it serves the fits whose objective is a mean of squared residuals over a handful of
+unknowns (the hinge characterisation), where forward mode delivers the residual Jacobian in one pass.
 """
 import numpy as np
 import scipy.optimize
@@ -225,6 +228,77 @@ def mma_minimize(fun, x0, **kw):
     ``(c, jac)`` pair in ``constraints`` (c(x) -> (m,), jac(x) -> (m, n) dense or sparse).
     ``maxeval`` counts objective evaluations like NLopt's ``set_maxeval``."""
     return _drive(mma_steps(x0, **kw), fun)
+
+
+def levenberg_marquardt(fun, x0, lower=None, upper=None, max_evaluations=20, lam0=1e-3, xtol=1e-10, ftol=0.0):
+    """Bounded Levenberg-Marquardt on ``mean(r ** 2)``: ``fun(x) -> (r (m,), J (m, n))``.
+
+    Marquardt scaling: ``(J^T J + lam diag(J^T J)) delta = -J^T r``; the trial point is ``clip(x + delta, lower, upper)``.  It is accepted
+    when ``mean(r ** 2)`` decreases, and then ``lam <- max(lam / 10, 1e-12)``; otherwise ``lam <- 10 lam``.  Every ``fun`` call, accepted
+    or not, counts as one evaluation (a trial needs the residuals only, but ``fun`` returns J with them).  A system that cannot be
+    solved (a column of J that is zero) costs no evaluation: lam grows.  An unknown that sits on a bound while the step pushes it
+    outwards is held there and the system is solved again for the others: clipping alone leaves them a step that counts on the move
+    that was clipped away, and the loop then stalls beside a minimum that lies on a bound.  Stops at ``max_evaluations`` (status ``"maxeval"``), at a trial
+    step with ``|dx| <= xtol |x|`` (``"xtol"``), at an accepted relative decrease of the objective ``<= ftol`` (``"ftol"``, off at 0) or
+    at ``lam > 1e8`` (``"lambda"``).  Returns the iterate history: ``x`` the accepted iterates (``x[0] = x0``, the last one the best
+    point), ``fun`` their objectives, ``evaluated`` every ``(x, objective, accepted)`` in call order, ``n_eval``, ``lam``, ``status``."""
+    x = np.array(x0, dtype=float).reshape(-1)
+    if lower is not None or upper is not None:
+        x = np.clip(x, lower, upper)
+    lo_v = np.broadcast_to(np.asarray(-np.inf if lower is None else lower, dtype=float), x.shape)
+    hi_v = np.broadcast_to(np.asarray(np.inf if upper is None else upper, dtype=float), x.shape)
+
+    def call(z):
+        r, J = fun(z.copy())
+        r, J = np.asarray(r, dtype=float).reshape(-1), np.asarray(J, dtype=float)
+        return r, J.reshape(r.size, x.size), float(np.mean(r ** 2))
+    r, J, f = call(x)
+    n_eval, lam, status = 1, float(lam0), "maxeval"
+    xs, fs, evaluated = [x.copy()], [f], [(x.copy(), f, True)]
+    while True:
+        if lam > 1e8:
+            status = "lambda"
+            break
+        JtJ, g = J.T @ J, J.T @ r
+        A = JtJ + lam * np.diag(np.diag(JtJ))
+        free = np.ones(x.size, dtype=bool)
+        try:
+            while True:
+                delta = np.zeros(x.size)
+                delta[free] = np.linalg.solve(A[np.ix_(free, free)], -g[free])
+                held = free & (((x <= lo_v) & (delta < 0)) | ((x >= hi_v) & (delta > 0)))
+                if not held.any():
+                    break
+                free &= ~held
+        except np.linalg.LinAlgError:
+            delta = None
+        if delta is None or not np.all(np.isfinite(delta)):
+            lam *= 10.0
+            continue
+        trial = x + delta
+        if lower is not None or upper is not None:
+            trial = np.clip(trial, lower, upper)
+        if np.linalg.norm(trial - x) <= xtol * np.linalg.norm(x):
+            status = "xtol"
+            break
+        if n_eval >= max_evaluations:
+            break
+        r_t, J_t, f_t = call(trial)
+        n_eval += 1
+        accepted = f_t < f
+        evaluated.append((trial.copy(), f_t, accepted))
+        if not accepted:
+            lam *= 10.0
+            continue
+        decrease = (f - f_t) / f
+        x, r, J, f = trial, r_t, J_t, f_t
+        xs.append(x.copy())
+        fs.append(f)
+        lam = max(lam / 10.0, 1e-12)
+        if decrease <= ftol:
+            status = "ftol"
+            break
+    return MMAResult(x=xs, fun=fs, evaluated=evaluated, n_eval=n_eval, lam=lam, status=status)
 
 
 def maximizing(gen):

@@ -333,6 +333,20 @@ int dfx_response_data(dfx_handle* h, double* strain_energy_stretch, double* stra
 int dfx_rhs(dfx_handle* h, const double* y, double t, double* dy);
 int dfx_rhs_vjp(dfx_handle* h, const double* y, double t, const double* lam, double* y_bar, dfx_grads* grads);
 
+/* Forward mode of one RHS evaluation, the twin of dfx_rhs_vjp: n_dirs tangents of dfx_rhs at (y, t) along (y_dots, params_dots).
+ * y (batch, 2, n_blocks, 3); y_dots (batch, n_dirs, 2, n_blocks, 3) or NULL; params_dots: n_dirs entries with the shapes and the NULL
+ * rules of dfx_forward_tangent_multi, or NULL.  dy (batch, 2, n_blocks, 3), may be NULL, equals dfx_rhs's result to rounding; dy_dots
+ * (batch, n_dirs, 2, n_blocks, 3): velocity tangents in the position rows, acceleration tangents in the velocity rows.  The primal
+ * parameters are those of the last dfx_set_params; t is not differentiated.  Constrained DOFs of y and of y_dots are ignored: they follow
+ * c(t), their position tangent is dc(t)/d fn_params . fn_params_dot, and their rows of dy / dy_dots are returned as 0.  Over the free
+ * DOFs it is the exact transpose of dfx_rhs_vjp:  sum(lam * dy_dots[:, k]) == sum(y_bar * y_dots[:, k]) + <grads, params_dots[k]>.
+ * One evaluation of the tangent stage kernel on a step of size zero (no Runge-Kutta combine is used), in the pass forms of
+ * dfx_forward_tangent_multi (DFX_TANGENT_MULTI_FORM applies); every bond model and contact model, 3 and 4 nodes per block; nodes with
+ * more than one ligament, or n_dirs < 1: return 1.  Non-finite results: return 3.  The call uses buffers of its own: the checkpoint and
+ * the resident history of the handle stay as they were (a later dfx_adjoint still reverses the solve that was kept). */
+int dfx_rhs_jvp(dfx_handle* h, const double* y, double t, const double* y_dots, const dfx_params* params_dots, int32_t n_dirs,
+                double* dy, double* dy_dots);
+
 /* Potential energy of a full-DOF configuration, (batch, n_blocks, 3) -> (batch,)  (test hook) */
 int dfx_energy(dfx_handle* h, const double* u, double* energy);
 
