@@ -647,7 +647,7 @@ DFX_HD void eval_time_fn(const TimeFn& f, double t, double& g, double& gt, doubl
       g = -pre * se2 * th;                       // tanh(3 - t/s) = -tanh(z)
       double dgdz = -pre * se2 * (1.0 - 3.0 * th * th);
       gt = dgdz / s;
-      gp[0] = g / A;
+      gp[0] = -2.0 / (s * s) * se2 * th;         // (not g / A: an amplitude of 0 is an ordinary input)
       gp[1] = -2.0 * g / s + dgdz * (-t / (s * s));
     } break;
     case kFnConstant:
