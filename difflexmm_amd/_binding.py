@@ -14,6 +14,7 @@ DFX_FN_PARAMS = 5
 BOND_LINEARIZED, BOND_NONLINEAR, BOND_SIMPLE_SPRING, BOND_STRETCH_TORSION = 0, 1, 2, 3
 CONTACT_NONE, CONTACT_ANGLE, CONTACT_DISTANCE = 0, 1, 2
 TABLEAU = {"dopri5": 0, "rk4": 1}
+OBJ_KINETIC, OBJ_ANGULAR_MOMENTUM = 0, 1
 FN_ZERO, FN_PULSE, FN_HARMONIC, FN_RAMP, FN_SECH2TANH, FN_CONSTANT, FN_RAMP_CAP, FN_TABLE = range(8)
 
 _dp = C.POINTER(C.c_double)
@@ -66,7 +67,7 @@ COMM_EXPORTS = ["dfx_comm_unique_id", "dfx_comm_init", "dfx_comm_destroy", "dfx_
                 "dfx_gather_objectives", "dfx_reduce_grads", "dfx_comm_allreduce", "dfx_comm_barrier", "dfx_comm_last_error",
                 "dfx_mem_info", "dfx_device_synchronize", "dfx_kinetic_value_and_grad_device", "dfx_download", "dfx_forward_kinetic_value_and_grad",
                 "dfx_forward_tangent", "dfx_forward_tangent_dense", "dfx_dense_output_map", "dfx_forward_tangent_multi",
-                "dfx_forward_tangent_dense_multi", "dfx_rhs_jvp"]
+                "dfx_forward_tangent_dense_multi", "dfx_rhs_jvp", "dfx_objective_value", "dfx_objective_value_and_grad"]
 EXPORTS = EXPORTS + COMM_EXPORTS
 
 
@@ -144,6 +145,10 @@ def declare(lib):
                                                         C.c_int64, _dp, _dp, C.POINTER(dfx_stats)]
     if hasattr(lib, "dfx_rhs_jvp"):
         lib.dfx_rhs_jvp.argtypes = [H, _dp, C.c_double, _dp, C.POINTER(dfx_params), C.c_int32, _dp, _dp]
+    if hasattr(lib, "dfx_objective_value_and_grad"):
+        lib.dfx_objective_value.argtypes = [H, C.c_int32, _dp, C.c_int32, _dp, _dp, C.c_int32, _dp]
+        lib.dfx_objective_value_and_grad.argtypes = [H, C.c_int32, _dp, C.c_int32, _dp, _dp, C.c_int32, _dp, C.POINTER(dfx_grads),
+                                                     C.POINTER(dfx_grads), C.c_int32, C.POINTER(dfx_stats)]
     if hasattr(lib, "dfx_comm_init"):
         lib.dfx_comm_unique_id.argtypes = [C.c_char_p]
         lib.dfx_comm_init.argtypes = [C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(H)]
@@ -727,6 +732,68 @@ class Engine:
                 a.flags.writeable = False
                 out[n] = a
         return obj, out, _stats(st_f), _stats(st_a)
+
+    # -- weighted objectives on the device-resident history ----------------------------------------------
+    @property
+    def has_objective(self):
+        return hasattr(self.lib, "dfx_objective_value_and_grad")
+
+    def _objective_args(self, kind, block_weights, time_weights, lever0):
+        """The array arguments of ``dfx_objective_value[_and_grad]``: weights (n_blocks,) or (batch, n_blocks), time weights (T,) or
+        None, lever0 (n_blocks, 2) or (batch, n_blocks, 2) or None."""
+        if not self.has_objective:
+            raise NotImplementedError(f"device objectives: the library {getattr(self.lib, '_name', self.lib)!r} has no dfx_objective_value_and_grad "
+                                      "(the CPU port of the oracle has the kinetic entries only; build the HIP engine)")
+        B, nb = self.batch, self.n_blocks
+        w = _f64(block_weights)
+        if w.shape not in ((nb,), (B, nb)):
+            raise ValueError(f"block_weights must be ({nb},) or ({B}, {nb}), got {w.shape}")
+        tau = None
+        if time_weights is not None:
+            tau = _f64(time_weights)
+            if self.n_timepoints is not None and tau.shape != (self.n_timepoints,):
+                raise ValueError(f"time_weights must be ({self.n_timepoints},), got {tau.shape}")
+        lev = None
+        if lever0 is not None:
+            lev = _f64(lever0)
+            if lev.shape not in ((nb, 2), (B, nb, 2)):
+                raise ValueError(f"lever0 must be ({nb}, 2) or ({B}, {nb}, 2), got {lev.shape}")
+        return w, int(w.ndim == 2), tau, lev, int(lev is not None and lev.ndim == 3)
+
+    def objective_value(self, kind, block_weights, time_weights=None, lever0=None):
+        """(batch,) value of a weighted objective (``OBJ_KINETIC`` / ``OBJ_ANGULAR_MOMENTUM``, ``dfx_objective_value``) on the resident
+        history of the last forward pass."""
+        w, wpm, tau, lev, lpm = self._objective_args(kind, block_weights, time_weights, lever0)
+        obj = np.zeros(self.batch)
+        self._check(self.lib.dfx_objective_value(self._h, int(kind), _ptr(w), wpm, _ptr(tau), _ptr(lev), lpm, _ptr(obj)), "dfx_objective_value")
+        return obj
+
+    def objective_value_and_grad(self, kind, block_weights, time_weights=None, lever0=None, which=ALL_GRADS, device=False):
+        """Value (batch,) and the requested gradients of a weighted objective in ONE call (``dfx_objective_value_and_grad``): the cotangent
+        is formed on the device, the objective rides along with the reverse sweep, the explicit inertia / block-centroid terms are added
+        behind it.  Results as :meth:`kinetic_value_and_grad`: read-only views of pinned memory, or ``DeviceArray`` handles with
+        ``device=True``; ``block_centroids`` is available on every lattice for the angular kind."""
+        w, wpm, tau, lev, lpm = self._objective_args(kind, block_weights, time_weights, lever0)
+        sh = self.shapes()
+        want, views = dfx_grads(), dfx_grads()
+        names = [n for n in which if not (n == "fn_params" and self.n_fns == 0) and not (n == "contact" and not self.contact)
+                 and not (n == "void_angle0" and self.contact != CONTACT_ANGLE)
+                 and not (n == "block_centroids" and self.contact != CONTACT_DISTANCE and int(kind) != OBJ_ANGULAR_MOMENTUM)]
+        flag = np.zeros(1)
+        for n in names:
+            setattr(want, n, _ptr(flag))
+        obj = np.zeros(self.batch)
+        st = dfx_stats()
+        self._check(self.lib.dfx_objective_value_and_grad(self._h, int(kind), _ptr(w), wpm, _ptr(tau), _ptr(lev), lpm, _ptr(obj), C.byref(want),
+                                                          C.byref(views), int(bool(device)), C.byref(st)), "dfx_objective_value_and_grad")
+        if device:
+            return obj, {n: DeviceArray(self, C.cast(getattr(views, n), C.c_void_p).value, sh[n]) for n in names}, _stats(st)
+        out = {}
+        for n in names:
+            a = np.ctypeslib.as_array(getattr(views, n), shape=sh[n])
+            a.flags.writeable = False
+            out[n] = a
+        return obj, out, _stats(st)
 
     def response_data(self, strains=True, kinetic=True):
         """Per-ligament strain energies (batch, T, n_bonds) x 3 and per-block kinetic energy (batch, T, n_blocks) of the last

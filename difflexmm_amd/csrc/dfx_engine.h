@@ -4,6 +4,7 @@
 //   engine_adaptive.hip  the reference's adaptive odeint semantics
 //   engine_reverse.hip   reverse sweep, gradient collection, objectives
 //   engine_dense.hip     reverse sweep of an adaptive solve that kept its accepted steps (dense-output discrete adjoint)
+//   engine_objective.hip weighted objectives on the device-resident history (kernels: dfx_objective.h)
 //   engine_abi.hip       create / destroy / set_params / reserve, test hooks, post-processing, downloads
 // The kernels live in dfx_kernels.h (stage kernels: instantiated by engine_launch.hip, the reverse per-stage builds by stage_builds_adj.hip)
 // and dfx_persist.hip.
@@ -85,6 +86,12 @@ struct CheckpointPool {
   const void* writer = nullptr;
 };
 
+// the objective call in flight (engine_objective.hip): what its explicit-term launch behind the sweep needs besides the handle's buffers
+struct ObjJob {
+  int kind, n_act, w_stride, lever_stride;
+  bool has_tau;
+};
+
 struct dfx_handle {
   CheckpointPool* ck = new CheckpointPool();
   Plan pl;
@@ -130,6 +137,13 @@ struct dfx_handle {
   hipEvent_t ev_rebuilt[2] = {nullptr, nullptr}, ev_reversed[2] = {nullptr, nullptr};
   DevBuf<double> d_YB, d_LAM, d_W, d_KQ, d_G, d_g_r, d_g_phi, d_g_b, d_blk_m, d_blk_c, d_fn_g, d_tmp, d_obj;
   DevBuf<int32_t> d_target;
+  // dfx_objective_value[_and_grad] (engine_objective.hip): the listed blocks, weights, levers and per-workgroup partials of the call; obj_job is
+  // non-null while such a call runs its reverse sweep (the sweep then ends with the objective's explicit terms), obj_centroids while
+  // that call also accumulates a block-centroid gradient (angular kind: on every lattice, not only with distance contact)
+  DevBuf<int32_t> d_obj_blocks;
+  DevBuf<double> d_obj_w, d_obj_tau, d_obj_lever, d_obj_part;
+  const ObjJob* obj_job = nullptr;
+  bool obj_centroids = false;
   std::vector<double> ts;
   std::vector<int> spis;           // RK steps in each output interval (fixed grid)
   std::vector<long long> step0;    // first step ordinal of each interval
@@ -206,6 +220,9 @@ static const char* const kPersistGaveUp =
     "a wave of the persistent stage loop gave up waiting for a neighbour's record (a workgroup of the launch was not resident: "
     "another process on the device?); DFX_PERSIST=0 keeps one launch per stage";
 
+static const char* const kStaleCheckpoint =
+    "the shared trajectory checkpoint was overwritten by a solve of another handle (dfx_share_checkpoint): run this handle's forward again";
+
 // internal functions that cross translation units: hidden, they are not part of the library's interface (include/dfx.h is)
 #pragma GCC visibility push(hidden)
 // engine_launch.hip
@@ -269,4 +286,8 @@ int zero_grad_accumulators(dfx_handle* h, double* extra = nullptr, size_t n_extr
     int n_target = 0);
 int collect_grads(dfx_handle* h, const dfx_grads* want, dfx_grads* grads, dfx_grads* views, bool with_state0);
 void set_grad_wishes(dfx_handle* h, const dfx_grads* g);
+int run_adjoint(dfx_handle* h, const dfx_grads* want, dfx_grads* grads, dfx_grads* views, dfx_stats* stats, bool kinetic, int n_target,
+    bool accumulators_cleared = false);
+// engine_objective.hip: the explicit terms of the objective call in flight (h->obj_job), queued behind the sweep
+void launch_objective_explicit(dfx_handle* h, const DevCtx& c);
 #pragma GCC visibility pop

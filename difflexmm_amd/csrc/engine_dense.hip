@@ -72,6 +72,7 @@ int run_adjoint_dense(dfx_handle* h, const dfx_grads* want, dfx_grads* grads, df
     dim3 g((unsigned)((n_target * 3 + 63) / 64), (unsigned)B);
     hipLaunchKernelGGL(k_kinetic_mass_grad, g, dim3(64), 0, h->stream, c, (const double*)h->d_fields.p, (const int32_t*)h->d_target.p, n_target);
   }
+  if (h->obj_job) launch_objective_explicit(h, c);
   HIP_OK(hipEventRecord(h->ev3, h->stream));
   if (int rc = collect_grads(h, want, grads, views, true)) return rc;
   if (*persist_give_up_word(h)) {

@@ -1,0 +1,153 @@
+// engine_objective.hip -- libdfx host side: weighted kinetic-energy and angular-momentum objectives evaluated and differentiated on the
+// device-resident history (dfx_objective_value, dfx_objective_value_and_grad).  "Fill the cotangent buffer G, reduce the value" before the
+// reverse sweep, "add the explicit d objective / d parameters" after it: the sweep itself is run_adjoint, unchanged.
+// (shared declarations in dfx_engine.h, the kernels in dfx_objective.h)
+#include "dfx_engine.h"
+#include "dfx_objective.h"
+
+#include <cmath>
+
+namespace {
+
+struct ObjHost {               // the validated arguments of a call, compacted
+  ObjJob job;
+  std::vector<int32_t> blocks; // blocks whose weight is non-zero in any member
+};
+
+// argument checks shared by the two entries (return 1 with h->err), then the uploads: listed blocks, weights, output-time weights, levers
+int prepare_objective(dfx_handle* h, const char* who, int32_t kind, const double* w, int32_t w_per_member, const double* tau, const double* lever,
+                      int32_t lever_per_member, ObjHost& out) {
+  const Plan& pl = h->pl;
+  const size_t B = pl.batch, nb = pl.n_blocks;
+  const int Tn = (int)h->ts.size();
+  if (kind != DFX_OBJ_KINETIC && kind != DFX_OBJ_ANGULAR_MOMENTUM) {
+    h->err = std::string(who) + ": unknown objective kind " + std::to_string(kind) + " (DFX_OBJ_KINETIC = 0, DFX_OBJ_ANGULAR_MOMENTUM = 1)";
+    return 1;
+  }
+  if (!w) { h->err = std::string(who) + ": block_weights is NULL"; return 1; }
+  if (kind == DFX_OBJ_ANGULAR_MOMENTUM && !lever) {
+    h->err = std::string(who) + ": the angular-momentum objective needs lever0 (block centroid - spin centre of every block)";
+    return 1;
+  }
+  const size_t nw = (w_per_member ? B : 1) * nb, nl = kind == DFX_OBJ_ANGULAR_MOMENTUM ? (lever_per_member ? B : 1) * nb * 2 : 0;
+  for (size_t i = 0; i < nw; ++i)
+    if (!std::isfinite(w[i])) { h->err = std::string(who) + ": non-finite block weight"; return 1; }
+  for (int k = 0; tau && k < Tn; ++k)
+    if (!std::isfinite(tau[k])) { h->err = std::string(who) + ": non-finite time weight"; return 1; }
+  for (size_t i = 0; i < nl; ++i)
+    if (!std::isfinite(lever[i])) { h->err = std::string(who) + ": non-finite lever0"; return 1; }
+  out.blocks.clear();
+  for (size_t b = 0; b < nb; ++b) {
+    bool any = false;
+    for (size_t m = 0; m < (w_per_member ? B : 1) && !any; ++m) any = w[m * nb + b] != 0.0;
+    if (any) out.blocks.push_back((int32_t)b);
+  }
+  out.job.kind = kind;
+  out.job.n_act = (int)out.blocks.size();
+  out.job.w_stride = w_per_member ? (int)nb : 0;
+  out.job.lever_stride = lever_per_member ? (int)nb * 2 : 0;
+  out.job.has_tau = tau != nullptr;
+  HIP_OK(h->d_obj_blocks.ensure(std::max<size_t>(1, out.blocks.size())));
+  HIP_OK(h->d_obj_w.ensure(nw));
+  HIP_OK(h->d_obj.ensure(B));
+  if (!out.blocks.empty())
+    HIP_OK(hipMemcpyAsync(h->d_obj_blocks.p, out.blocks.data(), sizeof(int32_t) * out.blocks.size(), hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipMemcpyAsync(h->d_obj_w.p, w, sizeof(double) * nw, hipMemcpyHostToDevice, h->stream));
+  if (tau) {
+    HIP_OK(h->d_obj_tau.ensure(Tn));
+    HIP_OK(hipMemcpyAsync(h->d_obj_tau.p, tau, sizeof(double) * Tn, hipMemcpyHostToDevice, h->stream));
+  }
+  if (nl) {
+    HIP_OK(h->d_obj_lever.ensure(nl));
+    HIP_OK(hipMemcpyAsync(h->d_obj_lever.p, lever, sizeof(double) * nl, hipMemcpyHostToDevice, h->stream));
+  }
+  return 0;
+}
+
+ObjArgs obj_args(const dfx_handle* h, const ObjJob& j) {
+  ObjArgs a;
+  a.fields = h->d_fields.p; a.blocks = h->d_obj_blocks.p; a.w = h->d_obj_w.p;
+  a.tau = j.has_tau ? h->d_obj_tau.p : nullptr;
+  a.lever = j.kind == DFX_OBJ_ANGULAR_MOMENTUM ? h->d_obj_lever.p : nullptr;
+  a.n_act = j.n_act; a.w_stride = j.w_stride; a.lever_stride = j.lever_stride;
+  return a;
+}
+
+// cotangents into G (may be null: value only), the value into d_obj and, when given, into pinned host memory
+int launch_objective(dfx_handle* h, const ObjJob& j, double* G, double* objective_host) {
+  const size_t B = h->pl.batch;
+  const long long items = (long long)h->ts.size() * j.n_act;
+  const unsigned chunks = (unsigned)std::max<long long>(1, (items + kObjThreads - 1) / kObjThreads);
+  HIP_OK(h->d_obj_part.ensure(B * chunks));
+  DevCtx c = make_ctx(h);
+  const ObjArgs a = obj_args(h, j);
+  const dim3 grid(chunks, (unsigned)B);
+  if (j.kind == DFX_OBJ_KINETIC) hipLaunchKernelGGL(k_objective<DFX_OBJ_KINETIC>, grid, dim3(kObjThreads), 0, h->stream, c, a, G, h->d_obj_part.p);
+  else hipLaunchKernelGGL(k_objective<DFX_OBJ_ANGULAR_MOMENTUM>, grid, dim3(kObjThreads), 0, h->stream, c, a, G, h->d_obj_part.p);
+  hipLaunchKernelGGL(k_objective_finish, dim3((unsigned)B), dim3(kObjThreads), 0, h->stream, (const double*)h->d_obj_part.p, (int)chunks, h->d_obj.p,
+                     objective_host);
+  return 0;
+}
+
+}  // namespace
+
+void launch_objective_explicit(dfx_handle* h, const DevCtx& c) {
+  const ObjJob& j = *h->obj_job;
+  if (j.n_act == 0) return;
+  const ObjArgs a = obj_args(h, j);
+  const dim3 grid((unsigned)((j.n_act + 63) / 64), (unsigned)h->pl.batch);
+  if (j.kind == DFX_OBJ_KINETIC) hipLaunchKernelGGL(k_objective_explicit<DFX_OBJ_KINETIC>, grid, dim3(64), 0, h->stream, c, a);
+  else hipLaunchKernelGGL(k_objective_explicit<DFX_OBJ_ANGULAR_MOMENTUM>, grid, dim3(64), 0, h->stream, c, a);
+}
+
+int dfx_objective_value(dfx_handle* h, int32_t kind, const double* block_weights, int32_t weights_per_member, const double* time_weights,
+                        const double* lever0, int32_t lever_per_member, double* objective) {
+  HIP_OK(hipSetDevice(h->device));
+  if (!h->have_fields) { h->err = "objective_value: run forward first"; return 1; }
+  if (!objective) { h->err = "objective_value: objective is NULL"; return 1; }
+  ObjHost oh;
+  if (int rc = prepare_objective(h, "objective_value", kind, block_weights, weights_per_member, time_weights, lever0, lever_per_member, oh)) return rc;
+  if (int rc = launch_objective(h, oh.job, nullptr, nullptr)) return rc;
+  HIP_OK(hipMemcpyAsync(objective, h->d_obj.p, sizeof(double) * h->pl.batch, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int dfx_objective_value_and_grad(dfx_handle* h, int32_t kind, const double* block_weights, int32_t weights_per_member,
+                                 const double* time_weights, const double* lever0, int32_t lever_per_member, double* objective,
+                                 const dfx_grads* want, dfx_grads* views, int32_t device_views, dfx_stats* stats) {
+  HIP_OK(hipSetDevice(h->device));
+  if (!h->have_traj || !h->have_fields) { h->err = "objective_value_and_grad: run forward with keep_trajectory=1 first"; return 1; }
+  if (h->ck->writer != h) { h->err = std::string("objective_value_and_grad: ") + kStaleCheckpoint; return 1; }
+  const Plan& pl = h->pl;
+  const size_t B = pl.batch, nb = pl.n_blocks;
+  const int Tn = (int)h->ts.size();
+  ObjHost oh;
+  if (int rc = prepare_objective(h, "objective_value_and_grad", kind, block_weights, weights_per_member, time_weights, lever0, lever_per_member, oh))
+    return rc;
+  if (ensure_adjoint_buffers(h)) return 2;
+  HIP_OK(h->d_G.ensure(B * Tn * nb * 6));
+  // the angular kind depends on the block centroids through its levers: that accumulator exists for this call on every lattice
+  const bool centroids = kind == DFX_OBJ_ANGULAR_MOMENTUM;
+  // (on a lattice without distance contact the buffer stays on the handle afterwards: the stage kernels touch g_c with distance contact only,
+  // and the other entries neither zero nor collect it)
+  if (centroids) HIP_OK(h->d_g_c.ensure(B * nb * 2));
+  if (objective) HIP_OK(h->obj_stage.ensure(sizeof(double) * B));
+  // what the sweep consults on the handle for this call (explicit terms behind it, the centroid accumulator, device views) is taken back on
+  // EVERY way out of this function, a failed launch or allocation included: the next call on the handle must not inherit it
+  struct Scope {
+    dfx_handle* h;
+    ~Scope() { h->obj_job = nullptr; h->obj_centroids = false; h->device_views = false; }
+  } scope{h};
+  h->obj_centroids = centroids;
+  h->obj_job = &oh.job;
+  h->device_views = device_views != 0;
+  set_grad_wishes(h, want);
+  // one launch: accumulators and cotangents cleared, cursors at the last segment (as the kinetic entries)
+  if (zero_grad_accumulators(h, h->d_G.p, B * Tn * nb * 6, (int)h->segs.size())) return 2;
+  if (int rc = launch_objective(h, oh.job, h->d_G.p, objective ? reinterpret_cast<double*>(h->obj_stage.p) : nullptr)) return rc;
+  if (int rc = run_adjoint(h, want, nullptr, views, stats, false, 0, true)) return rc;
+  if (objective) memcpy(objective, h->obj_stage.p, sizeof(double) * B);
+  return 0;
+}

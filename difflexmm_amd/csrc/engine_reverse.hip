@@ -45,7 +45,7 @@ int zero_grad_accumulators(dfx_handle* h, double* extra, size_t n_extra, int cur
   if (pl.n_ovf) zero(h->d_ovf_g.p, B * pl.n_ovf * kOvfG);
   if (h->want_bond_grads || pl.n_ovf) zero(h->d_g_b.p, B * pl.n_slots * 8);
   zero(h->d_blk_m.p, B * nb * 3);
-  if (pl.contact == DFX_CONTACT_DISTANCE) zero(h->d_g_c.p, B * nb * 2);
+  if (pl.contact == DFX_CONTACT_DISTANCE || h->obj_centroids) zero(h->d_g_c.p, B * nb * 2);
   if (h->want_damping_grads) zero(h->d_blk_c.p, B * nb * 3);
   zero(h->d_fn_g.p, B * nsp * DFX_MAX_FNS * DFX_FN_PARAMS);
   zero(extra, n_extra);
@@ -87,9 +87,11 @@ int collect_grads(dfx_handle* h, const dfx_grads* want, dfx_grads* grads, dfx_gr
 #endif
   if (h->device_views) {    // the gradients stay where the sweep accumulated them: re-layout on the device, no copy over PCIe
     if (want->reference_vector || want->k_bond || want->contact || want->fn_params || pl.n_ovf ||
-        (want->void_angle0 && pl.contact != DFX_CONTACT_ANGLE) || (want->block_centroids && pl.contact != DFX_CONTACT_DISTANCE)) {
+        (want->void_angle0 && pl.contact != DFX_CONTACT_ANGLE) ||
+        (want->block_centroids && pl.contact != DFX_CONTACT_DISTANCE && !h->obj_centroids)) {
       h->err = "device-resident gradients: centroid_node_vectors, void_angle0 (angle contact), inertia, damping, state0, block_centroids "
-               "(distance contact) of lattices without extra ligaments; the others are assembled on the host (dfx_kinetic_value_and_grad)";
+               "(distance contact, or the angular-momentum objective) of lattices without extra ligaments; the others are assembled on the host "
+               "(dfx_kinetic_value_and_grad, dfx_objective_value_and_grad with device_views = 0)";
       return 1;
     }
     const bool d_r = want->centroid_node_vectors, d_phi = want->void_angle0, d_lam = with_state0 && want->state0;
@@ -134,7 +136,7 @@ int collect_grads(dfx_handle* h, const dfx_grads* want, dfx_grads* grads, dfx_gr
       phi_zero = true; w_phi = false;
     }
   }
-  const bool w_cen = want->block_centroids && pl.contact == DFX_CONTACT_DISTANCE;
+  const bool w_cen = want->block_centroids && (pl.contact == DFX_CONTACT_DISTANCE || h->obj_centroids);
   const bool w_b = h->want_bond_grads && (want->reference_vector || want->k_bond || want->contact);
   const bool w_m = want->inertia, w_c = want->damping && h->want_damping_grads, w_fn = want->fn_params && h->want_fn_grads;
   const bool w_lam = with_state0 && want->state0;
@@ -262,8 +264,8 @@ void set_grad_wishes(dfx_handle* h, const dfx_grads* g) {
 // accumulators_cleared: the caller's prelude launch has already zeroed the gradient accumulators and set the cursors (adjoint_kinetic
 // does it in the launch that clears its cotangents) -- an argument, not handle state: a flag left behind by a call that failed half way
 // made the next sweep skip its zeroing (round-4 advice)
-static int run_adjoint(dfx_handle* h, const dfx_grads* want, dfx_grads* grads, dfx_grads* views, dfx_stats* stats, bool kinetic, int n_target,
-                       bool accumulators_cleared = false) {
+int run_adjoint(dfx_handle* h, const dfx_grads* want, dfx_grads* grads, dfx_grads* views, dfx_stats* stats, bool kinetic, int n_target,
+                bool accumulators_cleared) {
   if (h->adaptive_records) {       // the accepted steps of an adaptive solve: engine_dense.hip (accumulators cleared by the caller's prelude
     set_grad_wishes(h, want);      // launch, or here)
     if (!accumulators_cleared && zero_grad_accumulators(h, nullptr, 0, -1)) return 2;
@@ -386,6 +388,7 @@ static int run_adjoint(dfx_handle* h, const dfx_grads* want, dfx_grads* grads, d
     dim3 g((unsigned)((n_target * 3 + 63) / 64), (unsigned)B);
     hipLaunchKernelGGL(k_kinetic_mass_grad, g, dim3(64), 0, h->stream, c, (const double*)h->d_fields.p, (const int32_t*)h->d_target.p, n_target);
   }
+  if (h->obj_job) launch_objective_explicit(h, c);
   HIP_OK(hipEventRecord(h->ev3, h->stream));
   if (timing) fprintf(stderr, "[dfx] adjoint: sweep enqueued %.0f us after entry\n", since(ta0));
   if (int rc = collect_grads(h, want, grads, views, true)) return rc;
@@ -431,10 +434,6 @@ static int run_adjoint(dfx_handle* h, const dfx_grads* want, dfx_grads* grads, d
   }
   return 0;
 }
-
-
-static const char* kStaleCheckpoint =
-    "the shared trajectory checkpoint was overwritten by a solve of another handle (dfx_share_checkpoint): run this handle's forward again";
 
 int dfx_adjoint(dfx_handle* h, const double* fields_bar, dfx_grads* grads, dfx_stats* stats) {
   HIP_OK(hipSetDevice(h->device));

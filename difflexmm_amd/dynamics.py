@@ -829,6 +829,24 @@ class DynamicSolver:
         self.adjoint_stats = stats
         return obj, grads
 
+    def objective_value(self, spec):
+        """(batch,) value of a weighted objective (``objective.ObjectiveSpec``) on the device-resident history of the last solve."""
+        return self.engine.objective_value(spec.kind, spec.block_weights, spec.time_weights, spec.lever0)
+
+    def objective_value_and_raw(self, spec, which=("centroid_node_vectors", "void_angle0", "inertia"), device=False):
+        """A weighted kinetic-energy / angular-momentum objective (``objective.ObjectiveSpec``) of the last kept solve, evaluated and
+        differentiated on the device like :meth:`kinetic_energy_value_and_raw`: the history stays in HBM, the cotangent is formed there,
+        and the explicit inertia / block-centroid terms are already in the raw gradients returned (``block_centroids`` is added to
+        ``which`` for the angular kind: its levers contain the centroids)."""
+        from .objective import ANGULAR_MOMENTUM
+        which = tuple(w for w in which if not (w == "void_angle0" and self.spec.contact != _b.CONTACT_ANGLE))
+        if (self.spec.contact == _b.CONTACT_DISTANCE or spec.kind == ANGULAR_MOMENTUM) and "block_centroids" not in which:
+            which = which + ("block_centroids",)
+        obj, grads, stats = self.engine.objective_value_and_grad(spec.kind, spec.block_weights, spec.time_weights, spec.lever0, which=which,
+                                                                 device=device)
+        self.adjoint_stats = stats
+        return obj, grads
+
     @staticmethod
     def _bond_params_bar(bp, kb, refv_bar, like):
         """Gradient tree with the structure of the bond parameters that were passed in (LigamentParams /

@@ -1,7 +1,12 @@
 """Cross-correlation measures between recorded signals -- the names of ``difflexmm/objective.py`` (post-processing of space-time
-records in the notebooks; host code, SciPy where the reference uses ``jax.scipy.signal``)."""
+records in the notebooks; host code, SciPy where the reference uses ``jax.scipy.signal``) -- and the weighted objectives the engine
+evaluates and differentiates on the device-resident history (``ObjectiveSpec``; ``include/dfx.h``: ``dfx_objective_value_and_grad``)."""
+from typing import Any, NamedTuple
+
 import numpy as np
 import scipy.signal
+
+KINETIC, ANGULAR_MOMENTUM = 0, 1          # DFX_OBJ_*
 
 
 def compute_xcorr2d(signal0, signal1, shift=(None, None)):
@@ -36,3 +41,77 @@ def compute_max_xcorr2d_at_shift(signal0, signal1, shift, shift_axis=0):
 def compute_space_time_xcorr(space_time0, space_time1):
     """objective.py:78-89: space on axis 0, time on axis 1 -> (largest cross-correlation at zero space shift, its time delay)."""
     return compute_max_xcorr2d_at_shift(space_time0, space_time1, shift=0, shift_axis=0)
+
+
+# ---- weighted objectives on the device-resident history -----------------------------------------------------------------------------
+class ObjectiveSpec(NamedTuple):
+    """A weighted sum over blocks and output times (``include/dfx.h``, DFX_OBJ_*):
+
+        KINETIC            J_m = sum_k tau_k sum_b w_mb sum_d p_mbd v_mkbd^2 / 2
+        ANGULAR_MOMENTUM   J_m = sum_k tau_k sum_b w_mb [ (a_x + u_x) m_y v_y - (a_y + u_y) m_x v_x + J omega ]
+
+    ``block_weights`` (n_blocks,) or (batch, n_blocks); ``time_weights`` (T,) or None = all ones; ``lever0`` = block centroid - spin
+    centre, (n_blocks, 2) or (batch, n_blocks, 2), angular kind only; p = (m_x, m_y, J) the inertia, (u, v) the fields."""
+    kind: int
+    block_weights: Any
+    time_weights: Any = None
+    lever0: Any = None
+
+
+def block_weights_from_targets(n_blocks, target_blocks_list, weights):
+    """Weights of target regions -> weights of blocks.  ``target_blocks_list``: one array of block ids per target; ``weights``: one row
+    (n_targets,) -> (n_blocks,), or one row per member (batch, n_targets) -> (batch, n_blocks).  Overlapping targets add."""
+    w = np.asarray(weights, dtype=float)
+    if w.shape[-1:] != (len(target_blocks_list),) or w.ndim not in (1, 2):
+        raise ValueError(f"weights must be ({len(target_blocks_list)},) or (batch, {len(target_blocks_list)}), got {w.shape}")
+    out = np.zeros(w.shape[:-1] + (int(n_blocks),))
+    for i, tb in enumerate(target_blocks_list):
+        tb = np.asarray(tb, dtype=np.int64).reshape(-1)
+        if tb.size and (tb.min() < 0 or tb.max() >= n_blocks):
+            raise ValueError(f"target {i}: block out of range [0, {n_blocks})")
+        np.add.at(out, (Ellipsis, tb), w[..., i:i + 1])
+    return out
+
+
+def host_value_and_cotangent(spec, fields, inertia):
+    """NumPy restatement of the two formulas: ``fields`` (batch, T, 2, n_blocks, 3) or (T, 2, n_blocks, 3), ``inertia`` (batch, n_blocks, 3)
+    or (n_blocks, 3).  Returns (value, fields_bar, inertia_bar, centroid_bar): the value per member, its cotangent on the fields (what
+    ``vjp`` / ``dfx_adjoint`` take), and the explicit terms d J / d inertia (.., n_blocks, 3) and d J / d block_centroids = d J / d lever0
+    (.., n_blocks, 2; zeros for the kinetic kind) -- with the member axis of ``fields``."""
+    f = np.asarray(fields, dtype=float)
+    single = f.ndim == 4
+    if single:
+        f = f[None]
+    B, T, _, nb, _ = f.shape
+    p = np.broadcast_to(np.asarray(inertia, dtype=float), (B, nb, 3))
+    w = np.broadcast_to(np.asarray(spec.block_weights, dtype=float), (B, nb))
+    tau = np.ones(T) if spec.time_weights is None else np.asarray(spec.time_weights, dtype=float)
+    if tau.shape != (T,):
+        raise ValueError(f"time_weights must be ({T},), got {tau.shape}")
+    tw = tau[None, :, None] * w[:, None, :]                     # (B, T, nb)
+    u, v = f[:, :, 0], f[:, :, 1]
+    fb = np.zeros_like(f)
+    cen_bar = np.zeros((B, nb, 2))
+    if spec.kind == KINETIC:
+        value = np.sum(tw[..., None] * p[:, None] * v ** 2 / 2, axis=(1, 2, 3))
+        fb[:, :, 1] = tw[..., None] * p[:, None] * v
+        m_bar = np.sum(tw[..., None] * v ** 2 / 2, axis=1)
+    elif spec.kind == ANGULAR_MOMENTUM:
+        if spec.lever0 is None:
+            raise ValueError("the angular-momentum objective needs lever0")
+        a = np.broadcast_to(np.asarray(spec.lever0, dtype=float), (B, nb, 2))
+        rx, ry = a[:, None, :, 0] + u[..., 0], a[:, None, :, 1] + u[..., 1]
+        mx, my, J = p[:, None, :, 0], p[:, None, :, 1], p[:, None, :, 2]
+        value = np.sum(tw * (rx * my * v[..., 1] - ry * mx * v[..., 0] + J * v[..., 2]), axis=(1, 2))
+        fb[:, :, 0, :, 0] = tw * my * v[..., 1]
+        fb[:, :, 0, :, 1] = -tw * mx * v[..., 0]
+        fb[:, :, 1, :, 0] = -tw * ry * mx
+        fb[:, :, 1, :, 1] = tw * rx * my
+        fb[:, :, 1, :, 2] = tw * J
+        m_bar = np.stack([-(tw * ry * v[..., 0]).sum(1), (tw * rx * v[..., 1]).sum(1), (tw * v[..., 2]).sum(1)], axis=-1)
+        cen_bar = np.stack([(tw * my * v[..., 1]).sum(1), -(tw * mx * v[..., 0]).sum(1)], axis=-1)
+    else:
+        raise ValueError(f"unknown objective kind {spec.kind!r}")
+    if single:
+        return float(value[0]), fb[0], m_bar[0], cen_bar[0]
+    return value, fb, m_bar, cen_bar

@@ -752,6 +752,17 @@ class StaticTuningKineticEnergy:
         return float(self.weights @ vals), grads
 
 
+def _in_batches(fw, design, evaluate):
+    """A list of designs longer than the engine integrates side by side (``fw.batch``) is evaluated one engine call after the other:
+    ``evaluate(chunk)`` for consecutive chunks of ``fw.batch`` designs, results in order -- or None when ``design`` fits one call.  A
+    list whose length is no multiple of ``fw.batch`` is refused here."""
+    if not isinstance(design, list) or len(design) == fw.batch:
+        return None
+    if len(design) == 0 or len(design) % fw.batch:
+        raise ValueError(f"{len(design)} designs for a forward problem built with batch={fw.batch}: pass batch designs, or a multiple of it")
+    return [evaluate(design[i:i + fw.batch]) for i in range(0, len(design), fw.batch)]
+
+
 def design_gradients(fw, designs, raw):
     """The engine's raw gradients (batch-leading arrays for centroid_node_vectors, void_angle0, inertia[, block_centroids]) mapped
     back to the designs: void-angle and inertia chain rules, then the lattice map (all linear in the cotangent) -- one native pass over the
@@ -805,10 +816,10 @@ class TargetKineticEnergy:
         reverse stage to its variant that also accumulates per-ligament stiffness / reference-vector / contact-constant / damping
         gradients -- twice the time per launch on the 64x64 kagome of config 4 (profiles/r02_c4_design_gradient_subset.txt)."""
         fw = self.forward
-        if isinstance(design, list) and len(design) > fw.batch and len(design) % fw.batch == 0:
-            # more designs than the engine integrates side by side: one call after the other (an ensemble whose checkpoint does not fit
-            # the device at once -- config 4 as written, 64 designs x 75 000 steps on ONE GPU -- runs as two calls of 32)
-            parts = [self.value_and_grad(design[i:i + fw.batch]) for i in range(0, len(design), fw.batch)]
+        # more designs than the engine integrates side by side: one call after the other (an ensemble whose checkpoint does not fit
+        # the device at once -- config 4 as written, 64 designs x 75 000 steps on ONE GPU -- runs as two calls of 32)
+        parts = _in_batches(fw, design, self.value_and_grad)
+        if parts is not None:
             return np.concatenate([p[0] for p in parts]), [g for p in parts for g in p[1]]
         fw.solve(design, keep_trajectory=True, want_fields=False)
         obj, raw = fw.solve_dynamics.kinetic_energy_value_and_raw(self.target_blocks)
@@ -827,7 +838,8 @@ class SplitTargetKineticEnergy:
     """objective(design) = weights @ [kinetic energy of every target region] for ONE forward problem -- the energy of a single input
     split between several targets (problems/quads_energy_splitting.py:14-88).  One forward solve and ONE reverse sweep: the cotangent
     of the weighted sum goes through ``solve_dynamics.vjp`` (w_k m v on the velocities of target k), the explicit dependence on the
-    inertia of the target blocks (w_k sum_t v^2 / 2) is added here."""
+    inertia of the target blocks (w_k sum_t v^2 / 2) is added here.  A list of designs (an ensemble, ``run_ensemble_optimization``) or
+    ``on_device=True`` evaluates and differentiates the objective on the device instead (``objective.ObjectiveSpec``)."""
 
     def __init__(self, forward, target_sizes, target_shifts, weights):
         self.forward = forward
@@ -851,7 +863,32 @@ class SplitTargetKineticEnergy:
     def value(self, design):
         return float(self.weights @ self.individual(design))
 
-    def value_and_grad(self, design):
+    def _value_and_grad_device(self, design):
+        """The objective on the device (``dfx_objective_value_and_grad``, kinetic kind with the targets' weights on their blocks): the
+        histories stay in HBM, the cotangent is formed there, one design or a list of ``forward.batch`` designs as one ensemble."""
+        from .objective import KINETIC, ObjectiveSpec, block_weights_from_targets
+        fw = self.forward
+        many = isinstance(design, list)
+        parts = _in_batches(fw, design, lambda chunk: self._value_and_grad_device(chunk) + (self.last_individual,))
+        if parts is not None:
+            self.last_individual = np.concatenate([p[2] for p in parts])
+            return np.concatenate([p[0] for p in parts]), [g for p in parts for g in p[1]]
+        fw.solve(design, keep_trajectory=True, want_fields=False)
+        sd, nb = fw.solve_dynamics, fw.geometry.n_blocks
+        # every target's own kinetic energy: one reduction over the resident history per target
+        ind = np.stack([sd.objective_value(ObjectiveSpec(KINETIC, block_weights_from_targets(nb, [tb], [1.0])))
+                        for tb in self.target_blocks_list], axis=-1)
+        obj, raw = sd.objective_value_and_raw(ObjectiveSpec(KINETIC, block_weights_from_targets(nb, self.target_blocks_list, self.weights)))
+        grads = design_gradients(fw, design if many else [design], raw)
+        self.last_individual = ind if many else ind[0]
+        obj = np.asarray(obj, dtype=float)
+        return (obj, grads) if many else (float(obj[0]), grads[0])
+
+    def value_and_grad(self, design, on_device=False):
+        """A single design takes the host path (the history is downloaded, the cotangent built in NumPy) unless ``on_device``; a list of
+        designs is an ensemble and always runs on the device.  Return shapes as ``TargetKineticEnergy.value_and_grad``."""
+        if on_device or isinstance(design, list):
+            return self._value_and_grad_device(design)
         fw = self.forward
         sol = fw.solve(design, keep_trajectory=True)
         vals, inertia = self._individual(sol)
@@ -899,7 +936,31 @@ class TargetAngularMomentum:
     def value(self, design):
         return self._value(self.forward.solve(design))[0]
 
-    def value_and_grad(self, design):
+    def _value_and_grad_device(self, design):
+        """The objective on the device (``dfx_objective_value_and_grad``, angular kind, levers = block centroids of every design - spin
+        centre): one design or a list of ``forward.batch`` designs as one ensemble; the explicit centroid and inertia terms come back
+        inside the raw gradients."""
+        from .objective import ANGULAR_MOMENTUM, ObjectiveSpec, block_weights_from_targets
+        fw = self.forward
+        many = isinstance(design, list)
+        parts = _in_batches(fw, design, self._value_and_grad_device)
+        if parts is not None:
+            return np.concatenate([p[0] for p in parts]), [g for p in parts for g in p[1]]
+        designs = design if many else [design]
+        fw.solve(design, keep_trajectory=True, want_fields=False)
+        nb = fw.geometry.n_blocks
+        lever0 = np.stack([np.asarray(geometry_from_design_cached(fw.geometry, d)[0], dtype=float) - self.spin_center for d in designs])
+        spec = ObjectiveSpec(ANGULAR_MOMENTUM, block_weights_from_targets(nb, [self.target_blocks], [1.0]), None, lever0)
+        obj, raw = fw.solve_dynamics.objective_value_and_raw(spec)
+        grads = design_gradients(fw, designs, raw)
+        obj = np.asarray(obj, dtype=float)
+        return (obj, grads) if many else (float(obj[0]), grads[0])
+
+    def value_and_grad(self, design, on_device=False):
+        """A single design takes the host path unless ``on_device``; a list of designs always runs on the device (see
+        ``SplitTargetKineticEnergy.value_and_grad``)."""
+        if on_device or isinstance(design, list):
+            return self._value_and_grad_device(design)
         from .geometry import compute_inertia_vjp
         fw, tb = self.forward, self.target_blocks
         sol = fw.solve(design, keep_trajectory=True)

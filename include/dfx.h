@@ -113,7 +113,7 @@ typedef struct dfx_grads {
   double* contact;                        /* (batch, 3)                                          */
   double* fn_params;                      /* (batch, n_fns, DFX_FN_PARAMS)                       */
   double* state0;                         /* (batch, 2, n_blocks, 3)                             */
-  double* block_centroids;                /* (batch, n_blocks, 2): non-zero with DFX_CONTACT_DISTANCE only */
+  double* block_centroids;                /* (batch, n_blocks, 2): non-zero with DFX_CONTACT_DISTANCE, and for DFX_OBJ_ANGULAR_MOMENTUM */
 } dfx_grads;
 
 typedef struct dfx_stats {
@@ -319,6 +319,34 @@ int dfx_forward_kinetic_value_and_grad(dfx_handle* h, const double* state0, cons
                                        const int32_t* steps_per_interval, const int32_t* target_blocks, int32_t n_target,
                                        double* objective, const dfx_grads* want, dfx_grads* views, int32_t device_views,
                                        dfx_stats* forward_stats, dfx_stats* adjoint_stats);
+
+/* Weighted objectives on the device-resident history (HIP library only).  The other objectives of the reference's problems/ directory are
+ * weighted sums over blocks and output times too, and get what the kinetic entries above give: the fields never leave HBM, the
+ * objective rides along with the reverse sweep, and a list of designs runs as one ensemble.
+ *   DFX_OBJ_KINETIC            J_m = sum_k tau_k sum_b w_mb sum_d p_mbd v_mkbd^2 / 2
+ *                              (problems/quads_energy_splitting.py:66-88: w = the weights of the target regions, overlaps added)
+ *   DFX_OBJ_ANGULAR_MOMENTUM   J_m = sum_k tau_k sum_b w_mb [ (a_x + u_x) m_y v_y - (a_y + u_y) m_x v_x + J omega ]
+ *                              (problems/quads_spin.py:380-430 with energy.py:502-519)
+ * p = (m_x, m_y, J) is the inertia of dfx_set_params, (u, v) the history of the last forward pass.
+ * block_weights: (batch, n_blocks) when weights_per_member != 0, else (n_blocks,) shared by all members; blocks whose weight is zero in
+ * every member cost nothing.  time_weights: NULL = all ones, else EXACTLY T = n_timepoints of the last forward pass doubles (the library
+ * reads that many and cannot check the length of the caller's array).  lever0 (angular kind; ignored by the kinetic kind): a = block
+ * centroid - spin centre, (batch, n_blocks, 2) when lever_per_member != 0, else (n_blocks, 2) -- passed by the caller, so the library
+ * needs no centroid image on lattices without distance contact.  objective: (batch,), may be NULL in the gradient call.
+ * dfx_objective_value needs a forward pass whose history is resident.  dfx_objective_value_and_grad equals dfx_adjoint on the
+ * fields_bar of these formulas (position rows as well as velocity rows) PLUS the explicit terms d J / d inertia and, angular kind,
+ * d J / d block_centroids = d J / d a (available on every lattice for this call; with distance contact it is added to what the sweep
+ * accumulated) -- same cotangent buffer, same sweep, for every sweep form and checkpoint level, the kept steps of an adaptive solve
+ * included.  Preconditions and refusals are those of dfx_kinetic_value_and_grad[_device]; want / views as there, device_views != 0:
+ * `views` receives device pointers.  The value is a fixed-order two-level sum: two calls on the same history return the same bits.  With
+ * 0/1 weights and time_weights == NULL the kinetic kind is dfx_kinetic_value_and_grad up to the order of that sum.
+ * Return 1 (dfx_last_error says why): unknown kind, lever0 == NULL for the angular kind, non-finite weights or levers. */
+enum { DFX_OBJ_KINETIC = 0, DFX_OBJ_ANGULAR_MOMENTUM = 1 };
+int dfx_objective_value(dfx_handle* h, int32_t kind, const double* block_weights, int32_t weights_per_member,
+                        const double* time_weights, const double* lever0, int32_t lever_per_member, double* objective);
+int dfx_objective_value_and_grad(dfx_handle* h, int32_t kind, const double* block_weights, int32_t weights_per_member,
+                                 const double* time_weights, const double* lever0, int32_t lever_per_member,
+                                 double* objective, const dfx_grads* want, dfx_grads* views, int32_t device_views, dfx_stats* stats);
 
 /* Post-processing of the last forward solve on its device-resident history (problems/quads_focusing.py:319-372 with
  * energy.py:522-534): strain energies of every ligament 1/2 k (strain |l0|)^2 for the axial, shear and bending strain of
