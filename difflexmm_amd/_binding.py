@@ -395,91 +395,12 @@ class Engine:
         self.n_timepoints = T
         return fields, _stats(st)
 
-    @property
-    def has_forward_tangent(self):
-        return hasattr(self.lib, "dfx_forward_tangent")
-
-    def forward_tangent(self, state0, state0_dot, params_dot, timepoints, steps_per_interval, step_times=None):
-        """Primal fields and their directional derivative along (state0_dot, params_dot) of the fixed-grid solve (``dfx_forward_tangent``)
-        on the parameters of the last :meth:`set_params`.  ``params_dot``: arrays by ``dfx_params`` field name (a missing one: zero
-        tangent); ``timepoints`` (T,) or (batch, T) (then every member its own grid, as :meth:`forward`).  Returns (fields, fields_dot, stats)."""
-        if not self.has_forward_tangent:
-            raise NotImplementedError(f"forward mode: the library {getattr(self.lib, '_name', self.lib)!r} has no dfx_forward_tangent "
+    # -- forward mode: the single-direction entries are the K-direction ones at K = 1, and share their marshalling -------------------
+    def _need(self, entry):
+        if not hasattr(self.lib, entry):
+            raise NotImplementedError(f"forward mode: the library {getattr(self.lib, '_name', self.lib)!r} has no {entry} "
                                       "(the CPU port of the oracle is reverse mode only; build the HIP engine)")
-        B, nb = self.batch, self.n_blocks
-        state0 = _f64(state0, (B, 2, nb, 3)) if state0 is not None else None
-        state0_dot = _f64(state0_dot, (B, 2, nb, 3)) if state0_dot is not None else None
-        ts = _f64(timepoints)
-        T = ts.shape[-1]
-        spis = np.ascontiguousarray(np.broadcast_to(steps_per_interval, (max(T - 1, 0),)), dtype=np.int32)
-        n = int(spis.sum())
-        per_member = ts.ndim == 2
-        if per_member:
-            if ts.shape[0] != B:
-                raise ValueError(f"per-member timepoints must be (batch={B}, T)")
-            if step_times is None:      # equal steps inside every member's own intervals (as forward)
-                step_times = np.stack([np.concatenate([a + (b - a) * np.arange(k) / k for a, b, k in zip(row[:-1], row[1:], spis)] + [row[-1:]])
-                                       for row in ts])
-            step_times = _f64(step_times, (B, n + 1))
-        elif step_times is not None:
-            step_times = _f64(step_times, (n + 1,))
-        sh = self.shapes()
-        p = dfx_params()
-        keep = []
-        for name in _PARAM_FIELDS + ["block_centroids"]:
-            a = params_dot.get(name) if params_dot else None
-            if a is None:
-                continue
-            a = _f64(a, sh[name])
-            keep.append(a)
-            setattr(p, name, _ptr(a))
-        fields, fields_dot = np.empty((B, T, 2, nb, 3)), np.empty((B, T, 2, nb, 3))
-        st = dfx_stats()
-        self._check(self.lib.dfx_forward_tangent(self._h, _ptr(state0), _ptr(state0_dot), C.byref(p), _ptr(ts), T, spis.ctypes.data_as(_ip),
-                                                 _ptr(step_times), int(per_member), _ptr(fields), _ptr(fields_dot), C.byref(st)),
-                    "dfx_forward_tangent")
-        return fields, fields_dot, _stats(st)
 
-    @property
-    def has_forward_tangent_dense(self):
-        return hasattr(self.lib, "dfx_forward_tangent_dense")
-
-    def forward_tangent_dense(self, state0, state0_dot, params_dot, timepoints, step_times, n_steps):
-        """Primal fields and their directional derivative of the ADAPTIVE solve's dense output on every member's own frozen accepted steps
-        (``dfx_forward_tangent_dense``): ``step_times`` (batch, stride) rows ``t_0 .. t_{N_m}``, ``n_steps`` (batch,)
-        (:func:`padded_step_times`), ``timepoints`` (T,).  Otherwise as :meth:`forward_tangent`.  Returns (fields, fields_dot, stats)."""
-        if not self.has_forward_tangent_dense:
-            raise NotImplementedError(f"forward mode: the library {getattr(self.lib, '_name', self.lib)!r} has no dfx_forward_tangent_dense "
-                                      "(the CPU port of the oracle is reverse mode only; build the HIP engine)")
-        B, nb = self.batch, self.n_blocks
-        state0 = _f64(state0, (B, 2, nb, 3)) if state0 is not None else None
-        state0_dot = _f64(state0_dot, (B, 2, nb, 3)) if state0_dot is not None else None
-        ts = _f64(timepoints)
-        if ts.ndim != 1:
-            raise ValueError("forward_tangent_dense: one row of timepoints for all members")
-        T = len(ts)
-        st_times = _f64(step_times)
-        ns = np.ascontiguousarray(n_steps, dtype=np.int64)
-        if st_times.ndim != 2 or st_times.shape[0] != B or ns.shape != (B,):
-            raise ValueError(f"forward_tangent_dense: step_times (batch={B}, stride) and n_steps (batch,)")
-        sh = self.shapes()
-        p = dfx_params()
-        keep = []
-        for name in _PARAM_FIELDS + ["block_centroids"]:
-            a = params_dot.get(name) if params_dot else None
-            if a is None:
-                continue
-            a = _f64(a, sh[name])
-            keep.append(a)
-            setattr(p, name, _ptr(a))
-        fields, fields_dot = np.empty((B, T, 2, nb, 3)), np.empty((B, T, 2, nb, 3))
-        st = dfx_stats()
-        self._check(self.lib.dfx_forward_tangent_dense(self._h, _ptr(state0), _ptr(state0_dot), C.byref(p), _ptr(ts), T, _ptr(st_times),
-                                                       ns.ctypes.data_as(C.POINTER(C.c_int64)), st_times.shape[1], _ptr(fields),
-                                                       _ptr(fields_dot), C.byref(st)), "dfx_forward_tangent_dense")
-        return fields, fields_dot, _stats(st)
-
-    # -- forward mode, several directions per member ------------------------------------------------
     def _params_dots(self, params_dots, K):
         """K ``dfx_params`` (one per direction) from a list of dicts of arrays by field name (None / a missing name: zero tangent)."""
         sh = self.shapes()
@@ -505,23 +426,10 @@ class Engine:
             raise ValueError(f"state0_dots must be (batch={B}, n_dirs={K}, 2, {nb}, 3), got {a.shape}")
         return a
 
-    @property
-    def has_forward_tangent_multi(self):
-        return hasattr(self.lib, "dfx_forward_tangent_multi")
-
-    def forward_tangent_multi(self, state0, state0_dots, params_dots, n_dirs, timepoints, steps_per_interval, step_times=None):
-        """:meth:`forward_tangent` for ``n_dirs`` directions per member with the primal evaluated once per stage
-        (``dfx_forward_tangent_multi``): ``state0_dots`` (batch, n_dirs, 2, nb, 3) or None, ``params_dots`` a list of ``n_dirs`` dicts of
-        arrays by ``dfx_params`` field name (or None).  Returns (fields (batch, T, ...), fields_dots (batch, n_dirs, T, ...), stats)."""
-        if not self.has_forward_tangent_multi:
-            raise NotImplementedError(f"forward mode: the library {getattr(self.lib, '_name', self.lib)!r} has no dfx_forward_tangent_multi "
-                                      "(the CPU port of the oracle is reverse mode only; build the HIP engine)")
-        K = int(n_dirs)
-        if K < 1 or (params_dots is not None and len(params_dots) != K):
-            raise ValueError(f"forward_tangent_multi: need n_dirs >= 1 and one params_dot per direction (n_dirs={K})")
+    def _fixed_grid_args(self, state0, timepoints, steps_per_interval, step_times):
+        """(state0, timepoints, T, steps_per_interval, step_times, per_member) as the fixed-grid tangent entries take them."""
         B, nb = self.batch, self.n_blocks
         state0 = _f64(state0, (B, 2, nb, 3)) if state0 is not None else None
-        state0_dots = self._state0_dots(state0_dots, K)
         ts = _f64(timepoints)
         T = ts.shape[-1]
         spis = np.ascontiguousarray(np.broadcast_to(steps_per_interval, (max(T - 1, 0),)), dtype=np.int32)
@@ -536,6 +444,76 @@ class Engine:
             step_times = _f64(step_times, (B, n + 1))
         elif step_times is not None:
             step_times = _f64(step_times, (n + 1,))
+        return state0, ts, T, spis, step_times, per_member
+
+    def _dense_grid_args(self, who, state0, timepoints, step_times, n_steps):
+        """(state0, timepoints, T, step_times, n_steps) as the dense tangent entries take them."""
+        B, nb = self.batch, self.n_blocks
+        state0 = _f64(state0, (B, 2, nb, 3)) if state0 is not None else None
+        ts = _f64(timepoints)
+        if ts.ndim != 1:
+            raise ValueError(f"{who}: one row of timepoints for all members")
+        st_times = _f64(step_times)
+        ns = np.ascontiguousarray(n_steps, dtype=np.int64)
+        if st_times.ndim != 2 or st_times.shape[0] != B or ns.shape != (B,):
+            raise ValueError(f"{who}: step_times (batch={B}, stride) and n_steps (batch,)")
+        return state0, ts, len(ts), st_times, ns
+
+    @property
+    def has_forward_tangent(self):
+        return hasattr(self.lib, "dfx_forward_tangent")
+
+    def forward_tangent(self, state0, state0_dot, params_dot, timepoints, steps_per_interval, step_times=None):
+        """Primal fields and their directional derivative along (state0_dot, params_dot) of the fixed-grid solve (``dfx_forward_tangent``)
+        on the parameters of the last :meth:`set_params`.  ``params_dot``: arrays by ``dfx_params`` field name (a missing one: zero
+        tangent); ``timepoints`` (T,) or (batch, T) (then every member its own grid, as :meth:`forward`).  Returns (fields, fields_dot, stats)."""
+        self._need("dfx_forward_tangent")
+        B, nb = self.batch, self.n_blocks
+        state0, ts, T, spis, step_times, per_member = self._fixed_grid_args(state0, timepoints, steps_per_interval, step_times)
+        state0_dot = _f64(state0_dot, (B, 2, nb, 3)) if state0_dot is not None else None
+        p, keep = self._params_dots([params_dot], 1)
+        fields, fields_dot = np.empty((B, T, 2, nb, 3)), np.empty((B, T, 2, nb, 3))
+        st = dfx_stats()
+        self._check(self.lib.dfx_forward_tangent(self._h, _ptr(state0), _ptr(state0_dot), p, _ptr(ts), T, spis.ctypes.data_as(_ip),
+                                                 _ptr(step_times), int(per_member), _ptr(fields), _ptr(fields_dot), C.byref(st)),
+                    "dfx_forward_tangent")
+        return fields, fields_dot, _stats(st)
+
+    @property
+    def has_forward_tangent_dense(self):
+        return hasattr(self.lib, "dfx_forward_tangent_dense")
+
+    def forward_tangent_dense(self, state0, state0_dot, params_dot, timepoints, step_times, n_steps):
+        """Primal fields and their directional derivative of the ADAPTIVE solve's dense output on every member's own frozen accepted steps
+        (``dfx_forward_tangent_dense``): ``step_times`` (batch, stride) rows ``t_0 .. t_{N_m}``, ``n_steps`` (batch,)
+        (:func:`padded_step_times`), ``timepoints`` (T,).  Otherwise as :meth:`forward_tangent`.  Returns (fields, fields_dot, stats)."""
+        self._need("dfx_forward_tangent_dense")
+        B, nb = self.batch, self.n_blocks
+        state0, ts, T, st_times, ns = self._dense_grid_args("forward_tangent_dense", state0, timepoints, step_times, n_steps)
+        state0_dot = _f64(state0_dot, (B, 2, nb, 3)) if state0_dot is not None else None
+        p, keep = self._params_dots([params_dot], 1)
+        fields, fields_dot = np.empty((B, T, 2, nb, 3)), np.empty((B, T, 2, nb, 3))
+        st = dfx_stats()
+        self._check(self.lib.dfx_forward_tangent_dense(self._h, _ptr(state0), _ptr(state0_dot), p, _ptr(ts), T, _ptr(st_times),
+                                                       ns.ctypes.data_as(C.POINTER(C.c_int64)), st_times.shape[1], _ptr(fields),
+                                                       _ptr(fields_dot), C.byref(st)), "dfx_forward_tangent_dense")
+        return fields, fields_dot, _stats(st)
+
+    @property
+    def has_forward_tangent_multi(self):
+        return hasattr(self.lib, "dfx_forward_tangent_multi")
+
+    def forward_tangent_multi(self, state0, state0_dots, params_dots, n_dirs, timepoints, steps_per_interval, step_times=None):
+        """:meth:`forward_tangent` for ``n_dirs`` directions per member with the primal evaluated once per stage
+        (``dfx_forward_tangent_multi``): ``state0_dots`` (batch, n_dirs, 2, nb, 3) or None, ``params_dots`` a list of ``n_dirs`` dicts of
+        arrays by ``dfx_params`` field name (or None).  Returns (fields (batch, T, ...), fields_dots (batch, n_dirs, T, ...), stats)."""
+        self._need("dfx_forward_tangent_multi")
+        K = int(n_dirs)
+        if K < 1 or (params_dots is not None and len(params_dots) != K):
+            raise ValueError(f"forward_tangent_multi: need n_dirs >= 1 and one params_dot per direction (n_dirs={K})")
+        B, nb = self.batch, self.n_blocks
+        state0, ts, T, spis, step_times, per_member = self._fixed_grid_args(state0, timepoints, steps_per_interval, step_times)
+        state0_dots = self._state0_dots(state0_dots, K)
         p, keep = self._params_dots(params_dots, K)
         fields, fields_dots = np.empty((B, T, 2, nb, 3)), np.empty((B, K, T, 2, nb, 3))
         st = dfx_stats()
@@ -551,23 +529,13 @@ class Engine:
     def forward_tangent_dense_multi(self, state0, state0_dots, params_dots, n_dirs, timepoints, step_times, n_steps):
         """:meth:`forward_tangent_dense` for ``n_dirs`` directions per member (``dfx_forward_tangent_dense_multi``); arguments as
         :meth:`forward_tangent_multi` and :meth:`forward_tangent_dense`.  Returns (fields, fields_dots (batch, n_dirs, T, ...), stats)."""
-        if not self.has_forward_tangent_dense_multi:
-            raise NotImplementedError(f"forward mode: the library {getattr(self.lib, '_name', self.lib)!r} has no dfx_forward_tangent_dense_multi "
-                                      "(the CPU port of the oracle is reverse mode only; build the HIP engine)")
+        self._need("dfx_forward_tangent_dense_multi")
         K = int(n_dirs)
         if K < 1 or (params_dots is not None and len(params_dots) != K):
             raise ValueError(f"forward_tangent_dense_multi: need n_dirs >= 1 and one params_dot per direction (n_dirs={K})")
         B, nb = self.batch, self.n_blocks
-        state0 = _f64(state0, (B, 2, nb, 3)) if state0 is not None else None
+        state0, ts, T, st_times, ns = self._dense_grid_args("forward_tangent_dense_multi", state0, timepoints, step_times, n_steps)
         state0_dots = self._state0_dots(state0_dots, K)
-        ts = _f64(timepoints)
-        if ts.ndim != 1:
-            raise ValueError("forward_tangent_dense_multi: one row of timepoints for all members")
-        T = len(ts)
-        st_times = _f64(step_times)
-        ns = np.ascontiguousarray(n_steps, dtype=np.int64)
-        if st_times.ndim != 2 or st_times.shape[0] != B or ns.shape != (B,):
-            raise ValueError(f"forward_tangent_dense_multi: step_times (batch={B}, stride) and n_steps (batch,)")
         p, keep = self._params_dots(params_dots, K)
         fields, fields_dots = np.empty((B, T, 2, nb, 3)), np.empty((B, K, T, 2, nb, 3))
         st = dfx_stats()
@@ -833,9 +801,7 @@ class Engine:
         """Forward mode of :meth:`rhs` for ``n_dirs`` directions (``dfx_rhs_jvp``, the twin of :meth:`rhs_vjp`): ``y_dots``
         (batch, n_dirs, 2, nb, 3) or None, ``params_dots`` a list of ``n_dirs`` dicts of arrays by ``dfx_params`` field name (or None).
         Returns (dy (batch, 2, nb, 3), dy_dots (batch, n_dirs, 2, nb, 3)); rows of constrained DOFs are 0."""
-        if not self.has_rhs_jvp:
-            raise NotImplementedError(f"forward mode: the library {getattr(self.lib, '_name', self.lib)!r} has no dfx_rhs_jvp "
-                                      "(the CPU port of the oracle is reverse mode only; build the HIP engine)")
+        self._need("dfx_rhs_jvp")
         K = int(n_dirs)
         if params_dots is not None and len(params_dots) != K:
             raise ValueError(f"rhs_jvp: need one params_dot per direction (n_dirs={K})")

@@ -1,25 +1,45 @@
-// dfx_tangent.h -- the forward-mode (tangent) solve: one Runge-Kutta stage of the primal and of its directional derivative together.
+// dfx_tangent.h -- the forward-mode (tangent) solve: one Runge-Kutta stage of the primal and of K directional derivatives together.
 //
 // What it differentiates is the fixed-grid solve of dfx_forward_grid / dfx_forward_grid_members with its steps frozen -- the map dfx_adjoint
-// transposes.  One lane per (member, block):
-//   * the block's stage record and those of its partners are seeded as Dual numbers with the tangent stage state (seed_rec: the half-angle
-//     pair follows theta), and every per-ligament parameter as a Dual with its tangent (P = Dual): the epsilon parts of the forces that
-//     bond_grad_p / contact_grad / distance_contact_grad return are exactly  H_uu du + H_up dp  for the block's own DOFs;
+// transposes.  One lane per (member, block); the scalar is DualN<K>, one value and K epsilon parts, so every primal operation (the
+// half-angle records, atan2 / sqrt / rsqrt and their expansions, the branch decisions, every parameter and record load) happens once and
+// every epsilon operation K times.  The physics is not restated: bond_grad_p / contact_grad / distance_contact_grad (dfx_physics.h) are
+// instantiated with T = P = DualN<K>:
+//   * the block's stage record and those of its partners are seeded with the tangent stage states (seed_rec: the half-angle pair follows
+//     theta), and every per-ligament parameter with its tangents: the epsilon parts of the forces those functions return are exactly
+//     H_uu du + H_up dp  for the block's own DOFs, per direction;
 //   * DOF part, as fwd_dof (dfx_stage.h) plus its derivative: a = F / m  =>  da = (dF - a dm) / m, with F = F_load - dE/du - c v,
 //     dF = dF_load - (dE/du).e - dc v - c dv;  driven DOFs  du_c = sum coef (dg/dp . dp)  (eval_time_fn's gp),  loaded DOFs
-//     dF_load = sum load_coef (dg/dp . dp);  the RK combine of the next stage record is linear and takes the tangents alike.
+//     dF_load = sum load_coef (dg/dp . dp);  the RK combine of the next stage record is linear and takes every tangent alike.
 // Branch decisions (angle-contact window, closest edge of the distance-based contact, time-function phases) are taken on the primal values
-// only: the tangent follows the primal's branch, as the reverse sweep does.  Nothing is culled: every ligament is evaluated.
+// only: the tangents follow the primal's branch, as the reverse sweep does.  Nothing is culled: every ligament is evaluated.  No atomics,
+// nothing depends on the launch geometry.
 // The velocities of driven DOFs enter no force; their tangents are left at 0 here and the rows of prescribed DOFs in fields_dot are
-// assembled on the host (difflexmm_amd/dynamics.py, DynamicSolver.jvp).
+// assembled on the host (difflexmm_amd/dynamics.py, DynamicSolver.jvp_multi).
 //
-// dfx_forward_tangent_dense differentiates the ADAPTIVE solve instead -- the map dfx_adjoint transposes after dfx_forward_adaptive_keep: the
-// same stage kernel on every member's own frozen accepted steps (TanCtx::n_steps: a member that is done leaves; one more stage 0 at its
-// final state gives A_6 of its last step), and k_tan_dense forms the outputs inside the steps and their tangents by the quartic dense
-// output of the adaptive pass, which is linear in (q_n, v_n, A_0 .. A_6) with coefficients that hold primal step data only.
+// The dense pass (dfx_forward_tangent_dense[_multi]) differentiates the ADAPTIVE solve instead -- the map dfx_adjoint transposes after
+// dfx_forward_adaptive_keep: the same stage kernel on every member's own frozen accepted steps (TanCtx::n_steps: a member that is done
+// leaves; one more stage 0 at its final state, a step of size zero, gives A_6 of its last step), and k_tan_dense_multi forms the outputs
+// inside the steps and their tangents by the quartic dense output of the adaptive pass, which is linear in (q_n, v_n, A_0 .. A_6) with
+// coefficients that hold primal step data only.  A_0 of step n + 1 is A_6 of step n, so the place of A_0 alternates between rows 0 and 6
+// of A / DA with the step's parity (TanStage::a0) and nothing is copied.
 //
-// The parameter image is a plain per-slot layout of its own (value, then tangent), NOT the packed image of dfx_plan.h:pack_params, which
-// is not linear in the parameters (it stores 1/m, a dictionary of reference vectors, uniform stiffnesses once per member).
+// The parameter image is a plain per-slot layout of its own, NOT the packed image of dfx_plan.h:pack_params, which is not linear in the
+// parameters (it stores 1/m, a dictionary of reference vectors, uniform stiffnesses once per member).  Layouts (KC = the chunk width, a
+// template parameter; the host runs ceil(K / KC) passes, engine_tangent.hip):
+//   * parameter images, value then tangents -- the primal half once, then KC tangent halves:
+//       slot    9 * (1 + KC):  r(2) l(2) k(3) phi(2), then the same nine per direction
+//       block   6 * (1 + KC):  1/m(3) c(3), then d(1/m)(3) dc(3) per direction
+//       member  3 + kTanMemDir * KC:  contact(3), then dcontact(3) dfn_params per direction
+//       centre  2 * (1 + KC):  centroid(2), then its tangent per direction                        (distance-based contact)
+//   * primal records S / Y and A: B * nb * kRec and B * a_rows * nb * 3; tangent records and DA: one such plane per direction (d_plane /
+//     da_plane elements apart; tangent records hold q at 0..2, v at 5..7);
+//   * fields_dot of a pass: (B, KT, T, 2, nb, 3), KT = the directions of the pass.
+// A pass may hold several SLICES of KC directions each, one per blockIdx.y (TanSlices): every slice has an image of its own and its own
+// planes, and runs the same arithmetic; slice 0 alone stores the primal results (all slices compute the same ones).  Lattices too small to
+// fill the chip take all their directions as slices of width 1 in one pass -- the replicated-members form, which is cheaper there
+// (profiles/r09_tangent_multi.txt); everything else takes one slice of the widest width per pass.  A single direction is KC = 1 with one
+// slice in either form: dfx_forward_tangent and dfx_forward_tangent_dense are these kernels at that width.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,11 +47,85 @@
 
 namespace dfx {
 
-constexpr int kTanSlot = 18;     // per (member, slot): r(2) l(2) k(3) phi(2), then their tangents in the same order
-constexpr int kTanBlk = 12;      // per (member, block): 1/m(3), d(1/m)(3), c(3), dc(3)
-constexpr int kTanMem = 16;      // per member: contact(3), dcontact(3), dfn_params(DFX_MAX_FNS * DFX_FN_PARAMS)
-constexpr int kTanCen = 4;       // per (member, block): block centroid(2), its tangent(2)   (distance-based contact)
-static_assert(6 + DFX_MAX_FNS * DFX_FN_PARAMS <= kTanMem, "kTanMem");
+// ---------------------------------------------------------------------------------------
+// first-order forward-mode number with K epsilon parts
+// ---------------------------------------------------------------------------------------
+template <int K>
+struct DualN {
+  double v, e[K];
+  DFX_HD DualN() : v(0.0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) e[k] = 0.0;
+  }
+  DFX_HD DualN(double a) : v(a) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) e[k] = 0.0;
+  }
+};
+#define DFX_DN_EACH _Pragma("unroll") for (int k = 0; k < K; ++k)
+template <int K> DFX_HD DualN<K> operator+(DualN<K> a, DualN<K> b) { DualN<K> r; r.v = a.v + b.v; DFX_DN_EACH r.e[k] = a.e[k] + b.e[k]; return r; }
+template <int K> DFX_HD DualN<K> operator-(DualN<K> a, DualN<K> b) { DualN<K> r; r.v = a.v - b.v; DFX_DN_EACH r.e[k] = a.e[k] - b.e[k]; return r; }
+template <int K> DFX_HD DualN<K> operator-(DualN<K> a) { DualN<K> r; r.v = -a.v; DFX_DN_EACH r.e[k] = -a.e[k]; return r; }
+template <int K> DFX_HD DualN<K> operator*(DualN<K> a, DualN<K> b) {
+  DualN<K> r; r.v = a.v * b.v; DFX_DN_EACH r.e[k] = a.v * b.e[k] + a.e[k] * b.v; return r;
+}
+template <int K> DFX_HD DualN<K> operator*(double a, DualN<K> b) { DualN<K> r; r.v = a * b.v; DFX_DN_EACH r.e[k] = a * b.e[k]; return r; }
+template <int K> DFX_HD DualN<K> operator*(DualN<K> a, double b) { DualN<K> r; r.v = a.v * b; DFX_DN_EACH r.e[k] = a.e[k] * b; return r; }
+template <int K> DFX_HD DualN<K> operator+(DualN<K> a, double b) { a.v = a.v + b; return a; }
+template <int K> DFX_HD DualN<K> operator+(double a, DualN<K> b) { b.v = a + b.v; return b; }
+template <int K> DFX_HD DualN<K> operator-(DualN<K> a, double b) { a.v = a.v - b; return a; }
+template <int K> DFX_HD DualN<K> operator-(double a, DualN<K> b) { DualN<K> r; r.v = a - b.v; DFX_DN_EACH r.e[k] = -b.e[k]; return r; }
+template <int K> DFX_HD DualN<K> operator/(DualN<K> a, DualN<K> b) {
+  const double r = 1.0 / b.v, q = a.v * r;
+  DualN<K> o; o.v = q; DFX_DN_EACH o.e[k] = (a.e[k] - q * b.e[k]) * r; return o;
+}
+template <int K> DFX_HD DualN<K> operator/(double a, DualN<K> b) {
+  const double r = 1.0 / b.v, q = a * r;
+  DualN<K> o; o.v = q; DFX_DN_EACH o.e[k] = -q * b.e[k] * r; return o;
+}
+
+// what the physics templates look up by argument type
+template <int K> DFX_HD double val(DualN<K> a) { return a.v; }
+template <int K> DFX_HD double eps(DualN<K> a, int k) { return a.e[k]; }
+template <int K> DFX_HD DualN<K> trcp(DualN<K> a) {
+  const double r = trcp(a.v);
+  DualN<K> o; o.v = r; DFX_DN_EACH o.e[k] = -a.e[k] * r * r; return o;
+}
+template <int K> DFX_HD DualN<K> tsqrt(DualN<K> a) {
+  const double s = sqrt(a.v);
+  DualN<K> o; o.v = s; DFX_DN_EACH o.e[k] = 0.5 * a.e[k] / s; return o;
+}
+template <int K> DFX_HD DualN<K> trsqrt(DualN<K> a) {
+  const double r = trsqrt(a.v);
+  DualN<K> o; o.v = r; DFX_DN_EACH o.e[k] = -0.5 * a.e[k] * r * r * r; return o;
+}
+template <int K> DFX_HD DualN<K> tatan2(DualN<K> y, DualN<K> x) {
+  const double w = trcp(x.v * x.v + y.v * y.v);
+  DualN<K> o; o.v = fast_atan2(y.v, x.v); DFX_DN_EACH o.e[k] = (x.v * y.e[k] - y.v * x.e[k]) * w; return o;
+}
+template <int K> DFX_HD DualN<K> twrap(DualN<K> a) { a.v = twrap(a.v); return a; }
+
+// seed_rec for K directions: the half-angle pair follows theta in every one
+template <int K>
+DFX_HD BlockRec<DualN<K>> seed_rec(const BlockRec<double>& r, const double (&wx)[K], const double (&wy)[K], const double (&wth)[K]) {
+  BlockRec<DualN<K>> d;
+  d.x.v = r.x; d.y.v = r.y; d.th.v = r.th; d.ch.v = r.ch; d.sh.v = r.sh;
+  DFX_DN_EACH {
+    d.x.e[k] = wx[k]; d.y.e[k] = wy[k]; d.th.e[k] = wth[k];
+    d.ch.e[k] = -0.5 * r.sh * wth[k];
+    d.sh.e[k] = 0.5 * r.ch * wth[k];
+  }
+  return d;
+}
+
+constexpr int kTanSlotVals = 9;                                    // the primal half of a slot (and of every tangent half)
+constexpr int kTanBlkVals = 6;                                     // likewise of a block: 1/m(3), c(3)
+constexpr int kTanMemDir = 3 + DFX_MAX_FNS * DFX_FN_PARAMS;        // dcontact(3), dfn_params
+constexpr int kTanMaxWidth = 4;                                    // the widest chunk the library ships (profiles/r09_tangent_multi.txt)
+DFX_HD constexpr int tan_slot_n(int kc) { return kTanSlotVals * (1 + kc); }
+DFX_HD constexpr int tan_blk_n(int kc) { return kTanBlkVals * (1 + kc); }
+DFX_HD constexpr int tan_mem_n(int kc) { return 3 + kTanMemDir * kc; }
+DFX_HD constexpr int tan_cen_n(int kc) { return 2 * (1 + kc); }
 
 struct TanCtx {
   int B, nb, n_fns, n_stages;
@@ -39,10 +133,10 @@ struct TanCtx {
   const int32_t* block_special;  // nb (shared)
   const dfx_special* special;
   const TimeFn* fns;             // B * DFX_MAX_FNS (the primal time functions: dfx_set_params' upload)
-  const double* tp;              // B * n_slots * kTanSlot
-  const double* blk;             // B * nb * kTanBlk
-  const double* mem;             // B * kTanMem
-  const double* cen;             // B * nb * kTanCen, or null
+  const double* tp;              // slices * B * n_slots * tan_slot_n(KC)
+  const double* blk;             // slices * B * nb * tan_blk_n(KC)
+  const double* mem;             // slices * B * tan_mem_n(KC)
+  const double* cen;             // slices * B * nb * tan_cen_n(KC), or null
   const double* tgrid;           // n_grids * n_steps * 2: (t, h) of every step
   const double* t0;              // n_grids: the first output time
   long long grid_stride;         // elements between the grids of two members in tgrid (0: one grid)
@@ -52,16 +146,16 @@ struct TanCtx {
 };
 
 struct TanStage {
-  const double *S_in, *D_in;     // primal / tangent records of this stage, B * nb * kRec (tangent: q at 0..2, v at 5..7)
+  const double *S_in, *D_in;     // primal / tangent records of this stage (tangent: one plane per direction)
   const double *Y, *DY;          // step base
   double *S_out, *D_out;         // next stage records (stage s-1: the next step base)
-  double *A, *DA;                // stage accelerations and their tangents, B * a_rows * nb * 3
+  double *A, *DA;                // stage accelerations and their tangents (DA: one plane per direction)
   long long n;                   // step ordinal
   int i;                         // stage index
   int a0;                        // place of A_0 of this step: 0, or in the dense pass 0 / 6 by the step's parity (A_0 of step n + 1 is A_6 of step n)
 };
 
-// the dense output of step n (dfx_forward_tangent_dense): launched after stage 0 of step n + 1 has left A_6
+// the dense output of step n (the dense pass): launched after stage 0 of step n + 1 has left A_6
 struct TanDense {
   const double *Y0, *DY0;        // step base of step n (records)
   const double *Y1, *DY1;        // step base of step n + 1
@@ -69,77 +163,142 @@ struct TanDense {
   const int32_t* out_ptr;        // B * op_stride: outputs [out_ptr[n], out_ptr[n + 1]) lie in step n
   const double* theta;           // B * Tn: relative position of every output in its step
   const double* ts;              // Tn output times
-  double *fields, *fields_dot;   // B * Tn * 2 * nb * 3
+  double *fields, *fields_dot;   // B * Tn * 2 * nb * 3, and B * KT * Tn * 2 * nb * 3
   long long op_stride, n;
   int Tn, a0, a6;                // places of A_0 and A_6 of step n
   double cm[7], cma[7];          // mid-point weights (velocity / position form, Dopri of dfx_physics.h)
 };
 
-// (the kernels that are no templates are static: dfx_tangent_multi.h's translation unit reads this header too)
-DFX_HD BlockRec<Dual> tan_rec(const double* S, const double* D, int b) {
+// where the directions of a pass lie: planes of the tangent buffers, and the images of the slices
+struct TanSlices {
+  long long d_plane, da_plane;                         // elements between the planes of two directions in D_in / DY / D_out, and in DA
+  long long tp_plane, blk_plane, mem_plane, cen_plane; // elements between the images of two slices
+  int kt;                                              // directions of the pass: slices * KC
+};
+
+// what the kernels take: a stage / a dense output, and where its directions lie
+struct TanStageM {
+  TanStage s;
+  TanSlices sl;
+};
+
+struct TanDenseM {
+  TanDense d;
+  TanSlices sl;
+};
+
+template <int K>
+DFX_HD BlockRec<DualN<K>> tan_rec_n(const double* S, const double* D, long long plane, int b) {
   const BlockRec<double> r = load_rec(S, b);
-  const double* d = D + (size_t)b * kRec;
-  return seed_rec(r, d[0], d[1], d[2]);
+  double wx[K], wy[K], wth[K];
+  DFX_DN_EACH {
+    const double* d = D + (size_t)k * plane + (size_t)b * kRec;
+    wx[k] = d[0]; wy[k] = d[1]; wth[k] = d[2];
+  }
+  return seed_rec(r, wx, wy, wth);
 }
 
-DFX_HD Dual tan_par(const double* s, int j) { return Dual(s[j], s[9 + j]); }
+template <int K>
+DFX_HD DualN<K> tan_par_n(const double* s, int j) {
+  DualN<K> o; o.v = s[j];
+  DFX_DN_EACH o.e[k] = s[kTanSlotVals * (1 + k) + j];
+  return o;
+}
 
-// sum over f of coef_f * g_f(t) (and the tangent sum coef_f * dg_f/dp . dp_f)
-DFX_HD void tan_drive(const TanCtx& c, int m, const double* coef /* DFX_MAX_FNS */, double t, double& g_sum, double& gt_sum, double& dg_sum) {
-  g_sum = 0.0; gt_sum = 0.0; dg_sum = 0.0;
-  const double* dfn = c.mem + (size_t)m * kTanMem + 6;
+// value (vi) and K tangents (ti + stride * k) of one scalar of an image
+template <int K>
+DFX_HD DualN<K> tan_scalar_n(const double* p, int vi, int ti, int stride) {
+  DualN<K> o; o.v = p[vi];
+  DFX_DN_EACH o.e[k] = p[ti + stride * k];
+  return o;
+}
+
+// sum over f of coef_f * g_f(t), its time derivative, and per direction the tangent sum coef_f * dg_f/dp . dp_f; the time functions are
+// evaluated once
+template <int K>
+DFX_HD void tan_drive_n(const TanCtx& c, int m, const double* mem /* the member's image of this slice */, const double* coef /* DFX_MAX_FNS */,
+                        double t, double& g_sum, double& gt_sum, double (&dg_sum)[K]) {
+  g_sum = 0.0; gt_sum = 0.0;
+  DFX_DN_EACH dg_sum[k] = 0.0;
+  const double* dfn = mem + 3 + 3;
   for (int f = 0; f < c.n_fns; ++f) {
     if (coef[f] == 0.0) continue;
     double g, gt, gp[kMaxFnParams];
     eval_time_fn(c.fns[(size_t)m * DFX_MAX_FNS + f], t, g, gt, gp);
-    double dg = 0.0;
-    for (int k = 0; k < kMaxFnParams; ++k) dg += gp[k] * dfn[f * DFX_FN_PARAMS + k];
     g_sum += coef[f] * g;
     gt_sum += coef[f] * gt;
-    dg_sum += coef[f] * dg;
+    DFX_DN_EACH {
+      double dg = 0.0;
+      for (int j = 0; j < kMaxFnParams; ++j) dg += gp[j] * dfn[kTanMemDir * k + f * DFX_FN_PARAMS + j];
+      dg_sum[k] += coef[f] * dg;
+    }
   }
 }
 
-static __global__ void k_tan_init(TanCtx c, const double* state0, const double* state0_dot, double* S, double* D) {
+// state0_dot: (KT, B, 2, nb, 3) -- the directions of this pass (a padded direction is all zero), or null
+template <int K>
+__global__ void k_tan_init_multi(TanCtx c, const double* state0, const double* state0_dot, double* S, double* D, TanSlices sl) {
   const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= (long long)c.B * c.nb) return;
   const int m = (int)(gid / c.nb), b = (int)(gid % c.nb);
+  const int slice = blockIdx.y;
+  const long long d_plane = sl.d_plane;
+  const double* mem = c.mem + (size_t)slice * sl.mem_plane + (size_t)m * tan_mem_n(K);
+  D += (size_t)slice * K * d_plane;
+  if (state0_dot) state0_dot += (size_t)slice * K * c.B * 2 * c.nb * 3;
   const double t0 = c.t0[m * c.t0_stride];
   const int sidx = c.block_special[b];
-  double* r = S + (size_t)gid * kRec;
-  double* d = D + (size_t)gid * kRec;
+  double rr[kRec];
+  double* r = rr;
   const size_t nd = (size_t)c.nb * 3;
-  for (int k = 0; k < 3; ++k) {
-    double q = state0 ? state0[(size_t)m * 2 * nd + b * 3 + k] : 0.0;
-    double v = state0 ? state0[(size_t)m * 2 * nd + nd + b * 3 + k] : 0.0;
-    double dq = state0_dot ? state0_dot[(size_t)m * 2 * nd + b * 3 + k] : 0.0;
-    double dv = state0_dot ? state0_dot[(size_t)m * 2 * nd + nd + b * 3 + k] : 0.0;
-    if (sidx >= 0 && ((c.special[sidx].con_mask >> k) & 1)) {
-      tan_drive(c, m, c.special[sidx].con_coef[k], t0, q, v, dq);
-      dv = 0.0;
+  const size_t s0_plane = (size_t)c.B * 2 * nd;
+  for (int j = 0; j < 3; ++j) {
+    double q = state0 ? state0[(size_t)m * 2 * nd + b * 3 + j] : 0.0;
+    double v = state0 ? state0[(size_t)m * 2 * nd + nd + b * 3 + j] : 0.0;
+    double dq[K], dv[K];
+    DFX_DN_EACH {
+      dq[k] = state0_dot ? state0_dot[k * s0_plane + (size_t)m * 2 * nd + b * 3 + j] : 0.0;
+      dv[k] = state0_dot ? state0_dot[k * s0_plane + (size_t)m * 2 * nd + nd + b * 3 + j] : 0.0;
     }
-    r[k] = q; r[5 + k] = v;
-    d[k] = dq; d[5 + k] = dv;
+    if (sidx >= 0 && ((c.special[sidx].con_mask >> j) & 1)) {
+      tan_drive_n<K>(c, m, mem, c.special[sidx].con_coef[j], t0, q, v, dq);
+      DFX_DN_EACH dv[k] = 0.0;
+    }
+    r[j] = q; r[5 + j] = v;
+    DFX_DN_EACH {
+      double* d = D + (size_t)k * d_plane + (size_t)gid * kRec;
+      d[j] = dq[k]; d[5 + j] = dv[k];
+    }
   }
   double s, co;
   fast_sincos(0.5 * r[2], &s, &co);
   r[3] = co; r[4] = s;
-  d[3] = 0.0; d[4] = 0.0;
-}
-
-// node vectors of the bonded node, its next and its previous node on the block, as Duals (distance-based contact)
-template <int NPB>
-DFX_HD void tan_node_triple(const double* tp, int slot, Dual (&r)[3][2]) {
-  const int b = slot >> 2, k = slot & 3;
-  const int ks[3] = {k, (k + 1) % NPB, (k + NPB - 1) % NPB};
-  for (int i = 0; i < 3; ++i) {
-    const double* s = tp + (size_t)(b * kSlots + ks[i]) * kTanSlot;
-    r[i][0] = tan_par(s, 0); r[i][1] = tan_par(s, 1);
+  if (slice == 0) {
+    double* out = S + (size_t)gid * kRec;
+    for (int j = 0; j < kRec; ++j) out[j] = r[j];
+  }
+  DFX_DN_EACH {
+    double* d = D + (size_t)k * d_plane + (size_t)gid * kRec;
+    d[3] = 0.0; d[4] = 0.0;
   }
 }
 
-template <int MODEL, int CONTACT, int NPB>
-__global__ void __launch_bounds__(256) k_tan_stage(TanCtx c, Tableau T, TanStage st) {
+// node vectors of the bonded node, its next and its previous node on the block (distance-based contact)
+template <int NPB, int K>
+DFX_HD void tan_node_triple_n(const double* tp, int slot, DualN<K> (&r)[3][2]) {
+  const int b = slot >> 2, k = slot & 3;
+  const int ks[3] = {k, (k + 1) % NPB, (k + NPB - 1) % NPB};
+  for (int i = 0; i < 3; ++i) {
+    const double* s = tp + (size_t)(b * kSlots + ks[i]) * tan_slot_n(K);
+    r[i][0] = tan_par_n<K>(s, 0); r[i][1] = tan_par_n<K>(s, 1);
+  }
+}
+
+template <int MODEL, int CONTACT, int NPB, int KC>
+__global__ void __launch_bounds__(256) k_tan_stage_multi(TanCtx c, Tableau T, TanStageM sm) {
+  using D = DualN<KC>;
+  constexpr int K = KC;
+  const TanStage& st = sm.s;
   const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= (long long)c.B * c.nb) return;
   const int m = (int)(gid / c.nb), b = (int)(gid % c.nb);
@@ -150,125 +309,194 @@ __global__ void __launch_bounds__(256) k_tan_stage(TanCtx c, Tableau T, TanStage
     if (st.n > N || (st.n == N && st.i > 0)) return;
   }
   const size_t moff = (size_t)m * c.nb;                 // first block of this member in the record buffers
+  const TanSlices& sl = sm.sl;
+  const int slice = blockIdx.y;                         // this lane's KC directions: planes [slice * KC, (slice + 1) * KC), image `slice`
+  const bool first = slice == 0;                        // the slice that stores the primal results
+  const size_t doff = (size_t)slice * K * sl.d_plane, daoff = (size_t)slice * K * sl.da_plane;
   const double* S_in = st.S_in + moff * kRec;
-  const double* D_in = st.D_in + moff * kRec;
-  const double* tp = c.tp + moff * kSlots * kTanSlot;
-  const double* mem = c.mem + (size_t)m * kTanMem;
-  const BlockRec<Dual> o = tan_rec(S_in, D_in, b);
-  Dual f[3];
+  const double* D_in = st.D_in + doff + moff * kRec;
+  const double* tp = c.tp + (size_t)slice * sl.tp_plane + moff * kSlots * tan_slot_n(K);
+  const double* mem = c.mem + (size_t)slice * sl.mem_plane + (size_t)m * tan_mem_n(K);
+  const BlockRec<D> o = tan_rec_n<K>(S_in, D_in, sl.d_plane, b);
+  D f[3];
 #pragma unroll
-  for (int k = 0; k < NPB; ++k) {
-    const int slot = b * kSlots + k;
+  for (int kk = 0; kk < NPB; ++kk) {
+    const int slot = b * kSlots + kk;
     const int info = c.slot_info[slot];
     if (info < 0) continue;
     const int ps = info >> 1;
     const double sgn = (info & 1) ? 1.0 : -1.0;
-    const double* sp = tp + (size_t)slot * kTanSlot;
-    const double* pp = tp + (size_t)ps * kTanSlot;
-    const BlockRec<Dual> p = tan_rec(S_in, D_in, ps >> 2);
-    const Dual lx = tan_par(sp, 2), ly = tan_par(sp, 3);
-    const Dual l0 = tsqrt(lx * lx + ly * ly);
-    const Dual il0 = 1.0 / l0;
-    BondGrad<Dual> g;
-    bond_grad_p<MODEL, Dual, Dual>(o, p, tan_par(sp, 0), tan_par(sp, 1), tan_par(pp, 0), tan_par(pp, 1), lx, ly, l0, il0, tan_par(sp, 4),
-                                   tan_par(sp, 5), tan_par(sp, 6), sgn, g);
+    const double* sp = tp + (size_t)slot * tan_slot_n(K);
+    const double* pp = tp + (size_t)ps * tan_slot_n(K);
+    const BlockRec<D> p = tan_rec_n<K>(S_in, D_in, sl.d_plane, ps >> 2);
+    const D lx = tan_par_n<K>(sp, 2), ly = tan_par_n<K>(sp, 3);
+    const D l0 = tsqrt(lx * lx + ly * ly);
+    const D il0 = 1.0 / l0;
+    BondGrad<D> g;
+    bond_grad_p<MODEL, D, D>(o, p, tan_par_n<K>(sp, 0), tan_par_n<K>(sp, 1), tan_par_n<K>(pp, 0), tan_par_n<K>(pp, 1), lx, ly, l0, il0,
+                             tan_par_n<K>(sp, 4), tan_par_n<K>(sp, 5), tan_par_n<K>(sp, 6), sgn, g);
     f[0] = f[0] + g.fx; f[1] = f[1] + g.fy; f[2] = f[2] + g.fth;
-    const Dual am(mem[0], mem[3]), ac(mem[1], mem[4]), kc(mem[2], mem[5]);
     if (CONTACT == DFX_CONTACT_DISTANCE) {
-      Dual ro[3][2], rp[3][2];
-      tan_node_triple<NPB>(tp, slot, ro);
-      tan_node_triple<NPB>(tp, ps, rp);
-      const double* co = c.cen + (moff + b) * kTanCen;
-      const double* cp = c.cen + (moff + (ps >> 2)) * kTanCen;
-      DistContactGrad<Dual> dc;
-      distance_contact_grad<Dual, Dual>(o, p, Dual(co[0], co[2]), Dual(co[1], co[3]), Dual(cp[0], cp[2]), Dual(cp[1], cp[3]), ro, rp, info & 1,
-                                        am, ac, kc, dc);
+      const D am = tan_scalar_n<K>(mem, 0, 3, kTanMemDir), ac = tan_scalar_n<K>(mem, 1, 4, kTanMemDir), kc = tan_scalar_n<K>(mem, 2, 5, kTanMemDir);
+      D ro[3][2], rp[3][2];
+      tan_node_triple_n<NPB, K>(tp, slot, ro);
+      tan_node_triple_n<NPB, K>(tp, ps, rp);
+      const double* cen = c.cen + (size_t)slice * sl.cen_plane;
+      const double* co = cen + (moff + b) * tan_cen_n(K);
+      const double* cp = cen + (moff + (ps >> 2)) * tan_cen_n(K);
+      DistContactGrad<D> dc;
+      distance_contact_grad<D, D>(o, p, tan_scalar_n<K>(co, 0, 2, 2), tan_scalar_n<K>(co, 1, 3, 2), tan_scalar_n<K>(cp, 0, 2, 2),
+                                  tan_scalar_n<K>(cp, 1, 3, 2), ro, rp, info & 1, am, ac, kc, dc);
       f[0] = f[0] + dc.fx; f[1] = f[1] + dc.fy; f[2] = f[2] + dc.fth;
     } else if (CONTACT == DFX_CONTACT_ANGLE) {
-      ContactGrad<Dual> cg;
-      const Dual kap = sgn * (o.th - p.th);
-      contact_grad<Dual, Dual>(kap, tan_par(sp, 7), tan_par(sp, 8), am, ac, kc, cg);
+      const D am = tan_scalar_n<K>(mem, 0, 3, kTanMemDir), ac = tan_scalar_n<K>(mem, 1, 4, kTanMemDir), kc = tan_scalar_n<K>(mem, 2, 5, kTanMemDir);
+      ContactGrad<D> cg;
+      const D kap = sgn * (o.th - p.th);
+      contact_grad<D, D>(kap, tan_par_n<K>(sp, 7), tan_par_n<K>(sp, 8), am, ac, kc, cg);
       f[2] = f[2] + sgn * cg.dkap;
     }
   }
-  // DOF part (fwd_dof of dfx_stage.h and its derivative)
+  // DOF part (fwd_dof of dfx_stage.h and its derivative, the tangent lines once per direction)
   const double* tg = c.tgrid + (size_t)m * c.grid_stride + 2 * (size_t)st.n;
   const double t = tg[0], h = tg[1];
   const int i = st.i, r = i + 1;
   const double t_i = t + T.c[i] * h, t_next = t + T.c[r] * h;
   const int sidx = c.block_special[b];
-  const double* bk = c.blk + (moff + b) * kTanBlk;
+  const double* bk = c.blk + (size_t)slice * sl.blk_plane + (moff + b) * tan_blk_n(K);
   const size_t nd = (size_t)c.nb * 3;
   double* A = st.A + (size_t)m * c.a_rows * nd;
-  double* DA = st.DA + (size_t)m * c.a_rows * nd;
+  double* DA = st.DA + daoff + (size_t)m * c.a_rows * nd;
   const double* rin = S_in + (size_t)b * kRec;
   const double* din = D_in + (size_t)b * kRec;
   const double* yb = st.Y + (moff + b) * kRec;
-  const double* dyb = st.DY + (moff + b) * kRec;
+  const double* dyb = st.DY + doff + (moff + b) * kRec;
   double* ro = st.S_out + (moff + b) * kRec;
-  double* dro = st.D_out + (moff + b) * kRec;
+  double* dro = st.D_out + doff + (moff + b) * kRec;
+#pragma unroll
   for (int d = 0; d < 3; ++d) {
     const size_t dof = (size_t)b * 3 + d;
     bool constrained = false;
-    double fload = 0.0, dfload = 0.0, cnext = 0.0, cdnext = 0.0, dcnext = 0.0;
+    double fload = 0.0, cnext = 0.0, cdnext = 0.0;
+    double dfload[K], dcnext[K];
+    DFX_DN_EACH { dfload[k] = 0.0; dcnext[k] = 0.0; }
     if (sidx >= 0) {
       const dfx_special& sp = c.special[sidx];
       constrained = (sp.con_mask >> d) & 1;
       double unused;
-      if (constrained) tan_drive(c, m, sp.con_coef[d], t_next, cnext, cdnext, dcnext);
-      else tan_drive(c, m, sp.load_coef[d], t_i, fload, unused, dfload);
+      if (constrained) tan_drive_n<K>(c, m, mem, sp.con_coef[d], t_next, cnext, cdnext, dcnext);
+      else tan_drive_n<K>(c, m, mem, sp.load_coef[d], t_i, fload, unused, dfload);
     }
-    const double v_i = rin[5 + d], dv_i = din[5 + d];
-    const double inv_m = bk[d], dinv_m = bk[3 + d], damp = bk[6 + d], ddamp = bk[9 + d];
-    const double a = constrained ? 0.0 : (fload - f[d].v - damp * v_i) * inv_m;
-    // a = F / m: da = dF / m + F d(1/m)
-    const double da = constrained ? 0.0 : (dfload - f[d].e - ddamp * v_i - damp * dv_i) * inv_m + (fload - f[d].v - damp * v_i) * dinv_m;
-    A[(size_t)(i ? i : st.a0) * nd + dof] = a;
-    DA[(size_t)(i ? i : st.a0) * nd + dof] = da;
-    double sv = T.a[r][i] * a, sq = T.aa[r][i] * a, dsv = T.a[r][i] * da, dsq = T.aa[r][i] * da;
+    const double v_i = rin[5 + d];
+    const double inv_m = bk[d], damp = bk[3 + d];
+    const double F = fload - f[d].v - damp * v_i;
+    const double a = constrained ? 0.0 : F * inv_m;
+    const size_t arow = (size_t)(i ? i : st.a0) * nd + dof;
+    if (first) A[arow] = a;
+    double sv = T.a[r][i] * a, sq = T.aa[r][i] * a;
+    double dsv[K], dsq[K];
+    DFX_DN_EACH {
+      const double dv_i = din[(size_t)k * sl.d_plane + 5 + d];
+      const double dinv_m = bk[kTanBlkVals * (1 + k) + d], ddamp = bk[kTanBlkVals * (1 + k) + 3 + d];
+      // a = F / m: da = dF / m + F d(1/m)
+      const double da = constrained ? 0.0 : (dfload[k] - f[d].e[k] - ddamp * v_i - damp * dv_i) * inv_m + F * dinv_m;
+      DA[(size_t)k * sl.da_plane + arow] = da;
+      dsv[k] = T.a[r][i] * da; dsq[k] = T.aa[r][i] * da;
+    }
     for (int l = 0; l < i; ++l) {
-      const size_t row = l ? l : st.a0;
-      const double al = A[row * nd + dof], dal = DA[row * nd + dof];
+      const size_t row = (size_t)(l ? l : st.a0) * nd + dof;
+      const double al = A[row];
       sv += T.a[r][l] * al; sq += T.aa[r][l] * al;
-      dsv += T.a[r][l] * dal; dsq += T.aa[r][l] * dal;
+      DFX_DN_EACH {
+        const double dal = DA[(size_t)k * sl.da_plane + row];
+        dsv[k] += T.a[r][l] * dal; dsq[k] += T.aa[r][l] * dal;
+      }
     }
     double qnext = yb[d] + h * (T.c[r] * yb[5 + d] + h * sq);
     double vnext = yb[5 + d] + h * sv;
-    double dqnext = dyb[d] + h * (T.c[r] * dyb[5 + d] + h * dsq);
-    double dvnext = dyb[5 + d] + h * dsv;
-    if (constrained) { qnext = cnext; vnext = cdnext; dqnext = dcnext; dvnext = 0.0; }
-    ro[d] = qnext; ro[5 + d] = vnext;
-    dro[d] = dqnext; dro[5 + d] = dvnext;
+    if (constrained) { qnext = cnext; vnext = cdnext; }
+    if (first) { ro[d] = qnext; ro[5 + d] = vnext; }
+    DFX_DN_EACH {
+      const double* dy = dyb + (size_t)k * sl.d_plane;
+      double dqnext = dy[d] + h * (T.c[r] * dy[5 + d] + h * dsq[k]);
+      double dvnext = dy[5 + d] + h * dsv[k];
+      if (constrained) { dqnext = dcnext[k]; dvnext = 0.0; }
+      double* dr = dro + (size_t)k * sl.d_plane;
+      dr[d] = dqnext; dr[5 + d] = dvnext;
+      if (d == 2) { dr[3] = 0.0; dr[4] = 0.0; }
+    }
     if (d == 2) {
       double s, co;
       fast_sincos(0.5 * qnext, &s, &co);
-      ro[3] = co; ro[4] = s;
-      dro[3] = 0.0; dro[4] = 0.0;
+      if (first) { ro[3] = co; ro[4] = s; }
     }
   }
 }
 
-// row k of fields and fields_dot (B, T, 2, nb, 3) from the step-base records
-static __global__ void k_tan_snapshot(int B, int nb, int Tn, int k, const double* S, const double* D, double* fields, double* fields_dot) {
+// row j of fields (B, T, 2, nb, 3) and of this pass's fields_dot (B, KT, T, 2, nb, 3) from the step-base records
+template <int K>
+__global__ void k_tan_snapshot_multi(int B, int nb, int Tn, int j, const double* S, const double* D, TanSlices sl, double* fields,
+                                     double* fields_dot) {
   const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= (long long)B * nb) return;
   const int m = (int)(gid / nb), b = (int)(gid % nb);
+  const int slice = blockIdx.y;
   const size_t nd = (size_t)nb * 3;
-  const size_t row = ((size_t)m * Tn + k) * 2 * nd;
+  const size_t row = ((size_t)m * Tn + j) * 2 * nd;
   const double* r = S + (size_t)gid * kRec;
-  const double* d = D + (size_t)gid * kRec;
-  for (int j = 0; j < 3; ++j) {
-    fields[row + b * 3 + j] = r[j];
-    fields[row + nd + b * 3 + j] = r[5 + j];
-    fields_dot[row + b * 3 + j] = d[j];
-    fields_dot[row + nd + b * 3 + j] = d[5 + j];
+  if (slice == 0)
+    for (int q = 0; q < 3; ++q) {
+      fields[row + b * 3 + q] = r[q];
+      fields[row + nd + b * 3 + q] = r[5 + q];
+    }
+  DFX_DN_EACH {
+    const double* d = D + (size_t)(slice * K + k) * sl.d_plane + (size_t)gid * kRec;
+    const size_t drow = (((size_t)m * sl.kt + slice * K + k) * Tn + j) * 2 * nd;
+    for (int q = 0; q < 3; ++q) {
+      fields_dot[drow + b * 3 + q] = d[q];
+      fields_dot[drow + nd + b * 3 + q] = d[5 + q];
+    }
+  }
+}
+
+// The output of ONE right-hand-side evaluation (dfx_rhs_jvp) from what k_tan_init_multi and stage 0 of a step of size zero left behind: the
+// step-base records Y / DY (velocities and their tangents) and row 0 of A / DA (accelerations and their tangents).  dy (B, 2, nb, 3) and this
+// pass's dy_dots (B, KT, 2, nb, 3) are laid out as k_tan_snapshot_multi lays out one row of fields / fields_dot; the rows of prescribed DOFs
+// are 0 (the stage already stores a = da = 0 there; their velocity is c'(t) in the records and is masked here).
+template <int K>
+__global__ void k_tan_rhs_out_multi(TanCtx c, const double* Y, const double* DY, const double* A, const double* DA, TanSlices sl, double* dy,
+                                    double* dy_dots) {
+  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= (long long)c.B * c.nb) return;
+  const int m = (int)(gid / c.nb), b = (int)(gid % c.nb);
+  const int slice = blockIdx.y;
+  const size_t nd = (size_t)c.nb * 3;
+  const size_t arow = (size_t)m * c.a_rows * nd + (size_t)b * 3;
+  const size_t row = (size_t)m * 2 * nd;
+  const int sidx = c.block_special[b];
+  const int con_mask = sidx >= 0 ? c.special[sidx].con_mask : 0;
+  const double* r = Y + (size_t)gid * kRec;
+  if (slice == 0)
+    for (int q = 0; q < 3; ++q) {
+      dy[row + b * 3 + q] = ((con_mask >> q) & 1) ? 0.0 : r[5 + q];
+      dy[row + nd + b * 3 + q] = A[arow + q];
+    }
+  DFX_DN_EACH {
+    const double* d = DY + (size_t)(slice * K + k) * sl.d_plane + (size_t)gid * kRec;
+    const double* da = DA + (size_t)(slice * K + k) * sl.da_plane + arow;
+    const size_t drow = ((size_t)m * sl.kt + slice * K + k) * 2 * nd;
+    for (int q = 0; q < 3; ++q) {
+      dy_dots[drow + b * 3 + q] = ((con_mask >> q) & 1) ? 0.0 : d[5 + q];
+      dy_dots[drow + nd + b * 3 + q] = da[q];
+    }
   }
 }
 
 // rows [out_ptr[n], out_ptr[n + 1]) of fields and fields_dot from the dense output of step n: the quartic of the adaptive pass (k_prepare
-// of dfx_kernels.h, the same expressions in the same order) on (q_n, q_n+1, q_mid, v_n, v_n+1) and on (v_n, v_n+1, v_mid, A_0, A_6), and
-// the same linear formula on their tangents -- its coefficients hold primal step data only (h, theta).  One lane per (member, block).
-static __global__ void __launch_bounds__(256) k_tan_dense(TanCtx c, TanDense dn) {
+// of dfx_kernels.h, the same expressions in the same order) on (q_n, q_n+1, q_mid, v_n, v_n+1) and on (v_n, v_n+1, v_mid, A_0, A_6), once,
+// and the same linear formula on every tangent -- its coefficients hold primal step data only (h, theta).  One lane per (member, block).
+template <int K>
+__global__ void __launch_bounds__(256) k_tan_dense_multi(TanCtx c, TanDenseM dm) {
+  const TanDense& dn = dm.d;
   const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= (long long)c.B * c.nb) return;
   const int m = (int)(gid / c.nb), b = (int)(gid % c.nb);
@@ -276,43 +504,68 @@ static __global__ void __launch_bounds__(256) k_tan_dense(TanCtx c, TanDense dn)
   const int32_t* op = dn.out_ptr + (size_t)m * dn.op_stride;
   const int lo = op[dn.n], hi = op[dn.n + 1];
   if (hi <= lo) return;
+  const TanSlices& sl = dm.sl;
+  const int slice = blockIdx.y;
+  const double* mem = c.mem + (size_t)slice * sl.mem_plane + (size_t)m * tan_mem_n(K);
   const double h = c.tgrid[(size_t)m * c.grid_stride + 2 * (size_t)dn.n + 1];
   const size_t nd = (size_t)c.nb * 3;
   const double* A = dn.A + (size_t)m * c.a_rows * nd;
-  const double* DA = dn.DA + (size_t)m * c.a_rows * nd;
+  const double* DA = dn.DA + (size_t)slice * K * sl.da_plane + (size_t)m * c.a_rows * nd;
   const double* y0 = dn.Y0 + (size_t)gid * kRec;
-  const double* dy0 = dn.DY0 + (size_t)gid * kRec;
   const double* y1 = dn.Y1 + (size_t)gid * kRec;
-  const double* dy1 = dn.DY1 + (size_t)gid * kRec;
   const int sidx = c.block_special[b];
   for (int d = 0; d < 3; ++d) {
     const size_t dof = (size_t)b * 3 + d;
     const bool constrained = sidx >= 0 && ((c.special[sidx].con_mask >> d) & 1);
     const double qn = y0[d], vn = y0[5 + d], q1 = y1[d], v1 = y1[5 + d];
-    const double dqn = dy0[d], dvn = dy0[5 + d], dq1 = dy1[d], dv1 = dy1[5 + d];
     const double a0 = A[(size_t)dn.a0 * nd + dof], a6 = A[(size_t)dn.a6 * nd + dof];
-    const double da0 = DA[(size_t)dn.a0 * nd + dof], da6 = DA[(size_t)dn.a6 * nd + dof];
     double sm = dn.cm[0] * a0 + dn.cm[6] * a6, sma = dn.cma[0] * a0 + dn.cma[6] * a6;
-    double dsm = dn.cm[0] * da0 + dn.cm[6] * da6, dsma = dn.cma[0] * da0 + dn.cma[6] * da6;
     for (int l = 1; l < 6; ++l) {
-      const double al = A[(size_t)l * nd + dof], dal = DA[(size_t)l * nd + dof];
+      const double al = A[(size_t)l * nd + dof];
       sm += dn.cm[l] * al; sma += dn.cma[l] * al;
-      dsm += dn.cm[l] * dal; dsma += dn.cma[l] * dal;
     }
     const double qmid = qn + h * (0.5 * vn + h * sma), vmid = vn + h * sm;
-    const double dqmid = dqn + h * (0.5 * dvn + h * dsma), dvmid = dvn + h * dsm;
+    double dqn[K], dvn[K], dq1[K], dv1[K], da0[K], da6[K], dqmid[K], dvmid[K];
+    DFX_DN_EACH {
+      const double* dy0 = dn.DY0 + (size_t)(slice * K + k) * sl.d_plane + (size_t)gid * kRec;
+      const double* dy1 = dn.DY1 + (size_t)(slice * K + k) * sl.d_plane + (size_t)gid * kRec;
+      const double* DAk = DA + (size_t)k * sl.da_plane;
+      dqn[k] = dy0[d]; dvn[k] = dy0[5 + d]; dq1[k] = dy1[d]; dv1[k] = dy1[5 + d];
+      da0[k] = DAk[(size_t)dn.a0 * nd + dof]; da6[k] = DAk[(size_t)dn.a6 * nd + dof];
+      double dsm = dn.cm[0] * da0[k] + dn.cm[6] * da6[k], dsma = dn.cma[0] * da0[k] + dn.cma[6] * da6[k];
+      for (int l = 1; l < 6; ++l) {
+        const double dal = DAk[(size_t)l * nd + dof];
+        dsm += dn.cm[l] * dal; dsma += dn.cma[l] * dal;
+      }
+      dqmid[k] = dqn[k] + h * (0.5 * dvn[k] + h * dsma);
+      dvmid[k] = dvn[k] + h * dsm;
+    }
     for (int kk = lo; kk < hi; ++kk) {
       const double r = dn.theta[(size_t)m * dn.Tn + kk];
       double oq = dopri_dense(qn, q1, qmid, vn, v1, h, r), ov = dopri_dense(vn, v1, vmid, a0, a6, h, r);
-      double doq = dopri_dense(dqn, dq1, dqmid, dvn, dv1, h, r), dov = dopri_dense(dvn, dv1, dvmid, da0, da6, h, r);
-      if (constrained) { tan_drive(c, m, c.special[sidx].con_coef[d], dn.ts[kk], oq, ov, doq); dov = 0.0; }
+      double doq[K], dov[K];
+      DFX_DN_EACH {
+        doq[k] = dopri_dense(dqn[k], dq1[k], dqmid[k], dvn[k], dv1[k], h, r);
+        dov[k] = dopri_dense(dvn[k], dv1[k], dvmid[k], da0[k], da6[k], h, r);
+      }
+      if (constrained) {
+        tan_drive_n<K>(c, m, mem, c.special[sidx].con_coef[d], dn.ts[kk], oq, ov, doq);
+        DFX_DN_EACH dov[k] = 0.0;
+      }
       const size_t row = ((size_t)m * dn.Tn + kk) * 2 * nd;
-      dn.fields[row + dof] = oq;
-      dn.fields[row + nd + dof] = ov;
-      dn.fields_dot[row + dof] = doq;
-      dn.fields_dot[row + nd + dof] = dov;
+      if (slice == 0) {
+        dn.fields[row + dof] = oq;
+        dn.fields[row + nd + dof] = ov;
+      }
+      DFX_DN_EACH {
+        const size_t drow = (((size_t)m * sl.kt + slice * K + k) * dn.Tn + kk) * 2 * nd;
+        dn.fields_dot[drow + dof] = doq[k];
+        dn.fields_dot[drow + nd + dof] = dov[k];
+      }
     }
   }
 }
+
+#undef DFX_DN_EACH
 
 }  // namespace dfx

@@ -473,7 +473,8 @@ class DynamicSolver:
         """Forward-mode derivative of the FIXED-GRID solve (``adaptive=True``: of the adaptive solve itself, see below):
         ``fields, fields_dot = jvp(state0, timepoints, control_params, state0_dot, control_params_dot)``,
         ``fields_dot = d fields / d(state0, control_params) . (state0_dot, control_params_dot)`` with the steps frozen
-        (``dfx_forward_tangent``: one stage launch per Runge-Kutta stage computes the primal and the tangent together).  This is the map
+        (one stage launch per Runge-Kutta stage computes the primal and the tangent together: the kernels of :meth:`jvp_multi` at one
+        direction, and this call is ``jvp_multi`` with ``tangents=[(state0_dot, control_params_dot)]``, column 0).  This is the map
         :meth:`vjp` transposes: on the same grid  ``sum(fields_bar * fields_dot) == <vjp(fields_bar), tangent>``.
 
         * ``control_params_dot``: a ``ControlParams``-shaped tree of tangents (the shape :meth:`vjp` returns), or a list of them, one per
@@ -491,8 +492,8 @@ class DynamicSolver:
           ``grid_refine > 1`` or per-member ``timepoints`` -- ``ValueError``): the map differentiated is the reference's call,
           ``solve_dynamics(state0, timepoints, control_params)``.  The adaptive pass runs first (keeping its accepted steps where the
           library and the physics allow it), then the tangent pass takes every member over ITS OWN accepted steps, frozen, and forms the
-          outputs and their tangents inside the steps by the controller's quartic dense output (``dfx_forward_tangent_dense``).  ``fields``
-          are the fields of that call to rounding, and ``fields_dot`` is the transpose of what :meth:`vjp` computes on the
+          outputs and their tangents inside the steps by the controller's quartic dense output (``dfx_forward_tangent_dense_multi``).
+          ``fields`` are the fields of that call to rounding, and ``fields_dot`` is the transpose of what :meth:`vjp` computes on the
           ``"adaptive-records"`` path: when the steps were kept (``self.stats["kept_trajectory"]``), ``vjp`` may follow this call directly
           and differentiates the same solve.  Step sizes and accept / reject decisions are not differentiated.  ``self.stats`` reports
           ``step_control="adaptive-dense"`` and ``steps_per_member``.
@@ -503,70 +504,9 @@ class DynamicSolver:
 
         The solver's trajectory checkpoint is not kept by this call (``adaptive=True`` apart): a ``vjp`` must follow a solve with
         ``keep_trajectory=True``."""
-        if adaptive:
-            grids = [name for name, on in (("steps_per_interval", steps_per_interval is not None), ("step_times", step_times is not None),
-                                           ("a default grid of the solver", self.steps_per_interval is not None),
-                                           ("grid_refine > 1", self.grid_refine > 1), ("per-member timepoints", np.ndim(timepoints) == 2)) if on]
-            if grids:
-                raise ValueError("DynamicSolver.jvp: adaptive=True differentiates the adaptive solve on its own accepted steps and takes no grid "
-                                 f"(got {', '.join(grids)})")
-        if not self.engine.has_forward_tangent or (adaptive and not self.engine.has_forward_tangent_dense):
-            lib = self.engine.lib
-            raise NotImplementedError(f"DynamicSolver.jvp: the library {getattr(lib, '_name', lib)!r} has no dfx_forward_tangent "
-                                      "(forward mode runs on the HIP engine only; the CPU port of the oracle is reverse mode only)")
-        cps, flats = self.prepare(control_params)
-        self._last = None                   # (dfx_set_params dropped the handle's checkpoint)
-        dots = self._member_tangents(control_params_dot)
-        tflats = [self._flatten_tangent(cp, cd) for cp, cd in zip(cps, dots)]
-        params_dot = {k: np.stack([f[k] for f in tflats]) for k in tflats[0]}
-        ts = np.asarray(timepoints, dtype=float)
-        B, nb = self.batch, self.n_blocks
-
-        def members(x):
-            if x is None:
-                return None
-            x = np.asarray(x, dtype=float)
-            return np.broadcast_to(x, (B,) + x.shape) if x.ndim == 3 else x
-        s0, s0d = members(state0), members(state0_dot)
-        spi = steps_per_interval if steps_per_interval is not None else self.steps_per_interval
-        control = "fixed"
-        if adaptive:
-            # What the tangent pass refuses (extra ligaments, a tableau without dense output) is refused before the adaptive pass is paid
-            # for: the same entry point on the initial state alone, one timepoint and no step.  Then the adaptive pass, its accepted steps
-            # kept for a vjp of the same solve where the kept-steps path serves the physics, and the tangent pass over every member's own
-            # step boundaries.
-            self.engine.forward_tangent_dense(s0, None, None, ts[:1], np.full((B, 1), ts[0]), np.zeros(B, dtype=np.int64))
-            kept, primal, astats = False, None, None
-            if self.engine.can_keep_adaptive and os.environ.get("DFX_ADAPTIVE_RECORDS", "1") != "0":
-                try:
-                    primal, astats = self.engine.forward_adaptive(s0, ts, self.rtol, self.atol, max_attempts=self.max_attempts, keep_trajectory=True)
-                    kept = True
-                except RuntimeError as e:
-                    if "forward_adaptive_keep:" not in str(e):
-                        raise
-            if not kept:
-                primal, astats = self.engine.forward_adaptive(s0, ts, self.rtol, self.atol, max_attempts=self.max_attempts)
-            self.adaptive_stats = astats
-            grid, n_steps = _b.padded_step_times([self.engine.adaptive_step_times(m) for m in range(B)], ts[0])
-            fields, fields_dot, stats = self.engine.forward_tangent_dense(s0, s0d, params_dot, ts, grid, n_steps)
-            if kept:        # as a differentiable solve leaves it: vjp reverses the adaptive pass above
-                self._last = (cps, flats, ts)
-                self._last_fields = primal
-            self.stats = dict(stats, steps_per_interval=None, step_times=grid, step_control="adaptive-dense",
-                              steps_per_member=[int(n) for n in n_steps], kept_trajectory=kept)
-        else:
-            if spi is None:
-                if ts.ndim == 2:
-                    raise ValueError("per-member timepoints need steps_per_interval (the adaptive controller chooses one grid per call)")
-                spi, step_times = self.adaptive_grid(np.zeros((B, 2, nb, 3)) if s0 is None else s0, ts, flats)
-                control = "adaptive-grid"
-            fields, fields_dot, stats = self.engine.forward_tangent(s0, s0d, params_dot, ts, spi, step_times=step_times)
-            self.stats = dict(stats, steps_per_interval=spi, step_times=step_times, step_control=control)
-        for m, (cp, cd) in enumerate(zip(cps, dots)):
-            self._prescribed_tangent_rows(fields_dot[m], cp, cd, ts[m] if ts.ndim == 2 else ts)
-        if self.batch == 1 and not isinstance(control_params, list):
-            return fields[0], fields_dot[0]
-        return fields, fields_dot
+        fields, fields_dot = self.jvp_multi(state0, timepoints, control_params, [(state0_dot, control_params_dot)],
+                                            steps_per_interval=steps_per_interval, step_times=step_times, adaptive=adaptive, _who="jvp")
+        return fields, (fields_dot[0] if fields_dot.ndim == 5 else fields_dot[:, 0])
 
     def _prescribed_tangent_rows(self, fields_dot_m, cp, cd, ts_m):
         """The rows of PRESCRIBED DOFs of one member's ``fields_dot`` (T, 2, nb, 3) along one direction ``cd``, in place:
@@ -597,7 +537,8 @@ class DynamicSolver:
             raise ValueError(f"expected {self.batch} tangents, got {len(dots)}")
         return dots
 
-    def jvp_multi(self, state0, timepoints, control_params, tangents, steps_per_interval=None, step_times=None, adaptive=False):
+    def jvp_multi(self, state0, timepoints, control_params, tangents, steps_per_interval=None, step_times=None, adaptive=False,
+                  _who="jvp_multi"):
         """:meth:`jvp` along K directions in one pass: ``fields, fields_dot = jvp_multi(state0, timepoints, control_params, tangents)``
         with ``tangents`` a list of K pairs ``(state0_dot, control_params_dot)`` (either element may be None: zero; ``control_params_dot``
         follows :meth:`jvp`'s rules -- None leaves, missing keys, a list of one tree per member when batch > 1).  The stage kernel carries
@@ -606,26 +547,28 @@ class DynamicSolver:
         direction, and a solver of batch 1 returns a whole Jacobian over a few leaves.  ``fields`` is what :meth:`jvp` returns;
         ``fields_dot`` has a direction axis in front of T: (K, T, 2, nb, 3) for a single design, (batch, K, T, 2, nb, 3) otherwise, and
         ``fields_dot[..., k, :, :, :, :]`` is :meth:`jvp` along ``tangents[k]`` to rounding.  Grid semantics, ``adaptive=True`` (a
-        ``ValueError`` with a grid of any kind), ``self.stats`` and "``vjp`` may follow on the kept solve" are :meth:`jvp`'s."""
+        ``ValueError`` with a grid of any kind), ``self.stats`` and "``vjp`` may follow on the kept solve" are :meth:`jvp`'s.
+        (``_who``: the public method the call came through, for the error texts.)"""
+        who = f"DynamicSolver.{_who}"
         if adaptive:
             grids = [name for name, on in (("steps_per_interval", steps_per_interval is not None), ("step_times", step_times is not None),
                                            ("a default grid of the solver", self.steps_per_interval is not None),
                                            ("grid_refine > 1", self.grid_refine > 1), ("per-member timepoints", np.ndim(timepoints) == 2)) if on]
             if grids:
-                raise ValueError("DynamicSolver.jvp_multi: adaptive=True differentiates the adaptive solve on its own accepted steps and takes "
+                raise ValueError(f"{who}: adaptive=True differentiates the adaptive solve on its own accepted steps and takes "
                                  f"no grid (got {', '.join(grids)})")
         tangents = list(tangents) if tangents is not None else []
         if not tangents:
-            raise ValueError("DynamicSolver.jvp_multi: need at least one (state0_dot, control_params_dot) pair")
+            raise ValueError(f"{who}: need at least one (state0_dot, control_params_dot) pair")
         for tg in tangents:
             if not (isinstance(tg, (tuple, list)) and not isinstance(tg, ControlParams) and len(tg) == 2):
-                raise ValueError("DynamicSolver.jvp_multi: every tangent is a pair (state0_dot, control_params_dot)")
+                raise ValueError(f"{who}: every tangent is a pair (state0_dot, control_params_dot)")
         K = len(tangents)
         dots = [self._member_tangents(cd) for _, cd in tangents]            # [direction][member]
         engine = self.engine
         if not engine.has_forward_tangent_multi or (adaptive and not engine.has_forward_tangent_dense_multi):
             lib = engine.lib
-            raise NotImplementedError(f"DynamicSolver.jvp_multi: the library {getattr(lib, '_name', lib)!r} has no dfx_forward_tangent_multi "
+            raise NotImplementedError(f"{who}: the library {getattr(lib, '_name', lib)!r} has no dfx_forward_tangent{'' if _who == 'jvp' else '_multi'} "
                                       "(forward mode runs on the HIP engine only; the CPU port of the oracle is reverse mode only)")
         cps, flats = self.prepare(control_params)
         self._last = None                   # (dfx_set_params dropped the handle's checkpoint)
@@ -651,8 +594,10 @@ class DynamicSolver:
         spi = steps_per_interval if steps_per_interval is not None else self.steps_per_interval
         control = "fixed"
         if adaptive:
-            # as jvp(adaptive=True): the refusals first (the same entry on the initial state alone), the adaptive pass with its steps kept
-            # where the physics allows it, then the tangent pass over every member's own accepted steps
+            # What the tangent pass refuses (extra ligaments, a tableau without dense output) is refused before the adaptive pass is paid
+            # for: the same entry point on the initial state alone, one timepoint and no step.  Then the adaptive pass, its accepted steps
+            # kept for a vjp of the same solve where the kept-steps path serves the physics, and the tangent pass over every member's own
+            # step boundaries.
             engine.forward_tangent_dense_multi(s0, None, None, 1, ts[:1], np.full((B, 1), ts[0]), np.zeros(B, dtype=np.int64))
             kept, primal, astats = False, None, None
             if engine.can_keep_adaptive and os.environ.get("DFX_ADAPTIVE_RECORDS", "1") != "0":

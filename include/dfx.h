@@ -234,7 +234,8 @@ int dfx_adjoint(dfx_handle* h, const double* fields_bar, dfx_grads* grads, dfx_s
  * params_dot has the shapes of dfx_params; a NULL array (or params_dot == NULL, state0_dot == NULL) is a zero tangent.  The primal
  * parameters are the ones dfx_set_params left on the handle; state0 == NULL: at rest.  The rows of PRESCRIBED DOFs in fields_dot hold the
  * tangent of c(t) in the position rows and 0 in the velocity rows (the caller assembles dc'/dp . dp if it needs them).
- * One stage launch per Runge-Kutta stage, primal and tangent in one pass (Dual numbers); supported: every bond model, no / angle-based /
+ * One stage launch per Runge-Kutta stage, primal and tangent in one pass (dual numbers).  This entry and dfx_forward_tangent_dense are
+ * the _multi entries below with one direction ((batch, 1, ...) is (batch, ...)); supported: every bond model, no / angle-based /
  * distance-based contact, 3 and 4 nodes per block; nodes with more than one ligament return 1.  The call keeps its buffers to itself: the
  * trajectory checkpoint and the resident history of the last dfx_forward are left untouched, so a later dfx_adjoint still reverses THAT
  * solve.  Non-finite values in fields or fields_dot: return 3. */
@@ -271,12 +272,12 @@ int dfx_dense_output_map(const double* step_times, const int64_t* n_steps, int64
  * its compiled chunk widths, the spare directions of the last pass zero).  state0_dots (batch, n_dirs, 2, n_blocks, 3) or NULL;
  * params_dots: n_dirs entries, each with the shapes and the NULL rules of dfx_forward_tangent's params_dot (params_dots == NULL: every
  * parameter tangent zero).  fields (batch, T, 2, n_blocks, 3) comes from the first pass; fields_dots (batch, n_dirs, T, 2, n_blocks, 3),
- * column k = what dfx_forward_tangent / dfx_forward_tangent_dense return for direction k, to the rounding of a differently contracted
- * epsilon arithmetic.  Contracts, return codes and refusals are those of the single-direction entries; n_dirs < 1 returns 1.  The device
+ * column k = what dfx_forward_tangent / dfx_forward_tangent_dense return for direction k: the two single-direction entries are the
+ * _multi entries with one direction.  Contracts, return codes and refusals are theirs; n_dirs < 1 returns 1.  The device
  * buffers of the call hold one pass (they do not grow with n_dirs) and are all allocated before the first pass: a failed allocation is
  * return 2 with nothing left behind.  stats->launches and kernel_ms cover all passes.  Where batch * n_blocks * n_dirs <= 65536 (too few
  * lanes to give every SIMD a wave) all directions run in ONE pass instead, spread over lanes at width 1, which is the cheaper form there;
- * the environment variable DFX_TANGENT_MULTI_FORM=chunked|spread forces either form. */
+ * the environment variable DFX_TANGENT_MULTI_FORM=chunked|spread forces either form (one direction is one pass of width 1 in both). */
 int dfx_forward_tangent_multi(dfx_handle* h, const double* state0, const double* state0_dots, const dfx_params* params_dots,
                               int32_t n_dirs, const double* timepoints, int32_t n_timepoints, const int32_t* steps_per_interval,
                               const double* step_times, int32_t per_member_times,

@@ -1,4 +1,5 @@
-"""-m gpu: forward mode (DynamicSolver.jvp -> dfx_forward_tangent) against torch.autograd through the oracle's fixed-grid solve, as the
+"""-m gpu: forward mode (DynamicSolver.jvp -> jvp_multi along one direction -> dfx_forward_tangent_multi, the kernels of dfx_tangent.h at
+width 1) against torch.autograd through the oracle's fixed-grid solve, as the
 transpose of the discrete adjoint at size, against central differences at size, and its grid semantics."""
 import numpy as np
 import pytest

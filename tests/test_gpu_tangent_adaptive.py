@@ -1,4 +1,5 @@
-"""-m gpu: forward mode through the adaptive solve (DynamicSolver.jvp(adaptive=True) -> dfx_forward_tangent_dense): its fields are the
+"""-m gpu: forward mode through the adaptive solve (DynamicSolver.jvp(adaptive=True) -> jvp_multi along one direction ->
+dfx_forward_tangent_dense_multi; the single-direction entry dfx_forward_tangent_dense is that one at n_dirs = 1): its fields are the
 fields of the default call, its tangent is torch.autograd through the oracle's replay of the engine's own accepted steps with the dense
 output, it is the transpose of vjp on the SAME solve, and its contract.  Host side: tests/test_tangent_adaptive_host.py."""
 import math

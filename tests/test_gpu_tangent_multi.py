@@ -3,8 +3,15 @@ dfx_forward_tangent_dense_multi): its columns are the single-direction ``jvp``'s
 of ``vjp``; batch x directions; the adaptive form; a batch-1 Jacobian against central differences; its contract.  Host side:
 tests/test_tangent_multi_host.py.
 
+``jvp`` is ``jvp_multi`` along one direction, and dfx_forward_tangent / dfx_forward_tangent_dense are the ``_multi`` entries at
+n_dirs = 1: ONE set of kernels (dfx_tangent.h), instantiated 1, 2 and 4 wide.  "Against ``jvp``" below therefore compares the 4- and
+2-wide instances (the chunked form at K >= 2) with the 1-wide one; the K = 1 and the spread-form cases compare the 1-wide kernel with
+itself and pass trivially -- they stay as checks of the host's pass planning, slicing and column placement.  The independent check of the
+1-wide kernel is the oracle: test_gpu_tangent.py, test_gpu_tangent_adaptive.py and test_gpu_tangent_param_shapes.py through ``jvp``.
+Section 8 pins the single-direction C entries to the n_dirs = 1 ones bit for bit.
+
 Tolerances are the suite's: 1e-13 for the primal fields of two kernels that evaluate the same expressions, 1e-12 (the
-RHS-level figure) for a column against the single-direction kernel -- the K-wide epsilon arithmetic is contracted differently --,
+RHS-level figure) for a column against the 1-wide kernel -- the K-wide epsilon arithmetic is contracted differently --,
 RTOL_GRAD against autograd, 1e-11 for the transposition identity, 1e-6 against central differences.  Worst cases measured on the MI355X
 are in profiles/r09_tangent_multi.txt."""
 import numpy as np
@@ -425,3 +432,41 @@ def test_extra_ligaments_are_refused_before_any_pass():
     c2 = _case("quads", 4, True, False, seed=12)
     _, fdots = c2.solver.jvp_multi(y0, ts, c2.cp, tangents, steps_per_interval=4)
     assert np.abs(fdots).max() > 0 and relerr(fdots[1], 2.0 * fdots[0]) < 1e-12
+
+
+# ---- 8. the single-direction entries are the n_dirs = 1 ones ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("lattice", ["quads", "kagome"])
+def test_single_direction_entries_are_the_multi_entries_at_one_direction(lattice):
+    """dfx_forward_tangent / dfx_forward_tangent_dense against dfx_forward_tangent_multi / dfx_forward_tangent_dense_multi at n_dirs = 1,
+    to the bit: the same kernels on the same image, not two that agree to rounding.  4 x 4 quads and the 4-cell kagome lattice (4 and 3
+    nodes per block), nonlinear ligaments, angle contact, a driven block, per-bond parameters, a non-zero state0_dot."""
+    c = _case(lattice, 4, True, True, "dopri5")
+    rng = np.random.default_rng(3)
+    c.cp = _per_bond(c)
+    cp, inertia = _explicit_inertia(c)
+    s, e = c.solver, c.solver.engine
+    ts = np.linspace(0, 3e-4, 4)
+    y0, y0d = c.random_state(0.05, 0.02, 5.0)[None], c.random_state(0.05, 0.02, 5.0)[None]
+    cps, _ = s.prepare(cp)
+    params_dot = {k: v[None] for k, v in s._flatten_tangent(cps[0], _tangent_tree(c, rng, inertia)).items()}
+    assert all(np.abs(params_dot[k]).max() > 0 for k in ("k_bond", "reference_vector", "void_angle0", "fn_params"))
+
+    def same(one, multi, what):
+        (f1, d1, st1), (fm, dm_, stm) = one, multi
+        assert dm_.shape == (1, 1) + d1.shape[1:]
+        assert np.abs(d1).max() > 0 and np.all(np.isfinite(d1))
+        assert np.array_equal(f1, fm), (lattice, what, "fields", relerr(fm, f1))
+        assert np.array_equal(d1, dm_[:, 0]), (lattice, what, "fields_dot", relerr(dm_[:, 0], d1))
+        for key in ("steps", "rhs_evals", "launches"):
+            assert st1[key] == stm[key], (lattice, what, key, st1[key], stm[key])
+        return st1
+    st = same(e.forward_tangent(y0, y0d, params_dot, ts, 4), e.forward_tangent_multi(y0, y0d[:, None], [params_dot], 1, ts, 4), "fixed grid")
+    assert st["steps"] == 12 and st["rhs_evals"] == 12 * 6 and st["launches"] == 2 + 12 * 6 + 3
+    # the accepted steps of one adaptive pass
+    s.rtol = s.atol = 1e-5
+    s(y0[0], ts, cp)
+    assert s.stats["step_control"] == "adaptive"
+    grid, ns = b.padded_step_times([e.adaptive_step_times(0)], ts[0])
+    st = same(e.forward_tangent_dense(y0, y0d, params_dot, ts, grid, ns),
+              e.forward_tangent_dense_multi(y0, y0d[:, None], [params_dot], 1, ts, grid, ns), "dense")
+    assert st["steps"] == ns[0] > 0 and st["rhs_evals"] == 6 * ns[0] + 1

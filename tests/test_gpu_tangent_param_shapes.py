@@ -1,15 +1,15 @@
 """-m gpu: forward mode (jvp, jvp(adaptive=True), jvp_multi) on the non-uniform parameter images of tests/param_shapes.py.
 
-The tangent kernels do not read the packed image: tangent_image (engine_tangent.hip) and multi_image (engine_tangent_multi.hip) rebuild a
-per-slot image from it on the host and branch on the flags pack_params derives from the DATA -- the reference vector out of the member's
+The tangent kernels do not read the packed image: multi_image (engine_tangent.hip; jvp takes it at one direction) rebuilds a
+per-slot image from it on the host and branches on the flags pack_params derives from the DATA -- the reference vector out of the member's
 dictionary or out of p_l, the stiffnesses out of the member's constants or out of p_k, damping per block and DOF.  Every other forward-mode
 test runs on a uniform image (k_uniform, a dictionary of at most four entries, one damping value on every block).  Here, at the sizes, grid,
 seed and ShapeCases of tests/test_gpu_param_shapes.py (13 x 13 quads, 11 x 11 kagome: member boundaries inside a wave, a partial last wave):
 
   a. every image against torch.autograd.functional.jvp through the oracle, member by member, along ``all`` (every leaf) and ``leaf`` (only
      the leaf the shape is named after: its column would sit decades under the all-leaf column) -- RTOL_TRAJ fields, RTOL_GRAD tangents;
-  b. jvp_multi, both forms of a pass, K = 3 (all, leaf, all - leaf) and K = 5: columns equal the single-direction jvp (1e-12; 1e-13 fields)
-     and are linear in the direction;
+  b. jvp_multi, both forms of a pass, K = 3 (all, leaf, all - leaf) and K = 5: columns equal the single-direction jvp (1e-12; 1e-13 fields;
+     the 4- and 2-wide kernels against the 1-wide one) and are linear in the direction;
   c. ten members of 49 blocks with stiffnesses of their own (490 threads): the transposition identity with vjp on the same solve per
      member (1e-11), jvp and jvp_multi in both forms, and members 0 and 9 against the oracle;
   d. jvp(adaptive=True) on the images of test_param_shape_adaptive_loop_and_stage_controller, members leaving the dense pass on their own

@@ -186,14 +186,14 @@ def test_widest_stage_kernel_has_no_scratch_traffic(tmp_path):
     """The widest shipped k_tan_stage_multi<nonlinear, angle contact, 4, KC>: no scratch instruction, no scratch segment (the rule the
     shipped widths were chosen by: profiles/r09_tangent_multi.txt)."""
     csrc = os.path.join(ROOT, "difflexmm_amd", "csrc")
-    src = open(os.path.join(csrc, "engine_tangent_multi.hip")).read()
+    src = open(os.path.join(csrc, "engine_tangent.hip")).read()
     widths = [int(w) for w in re.search(r"constexpr int kWidths\[\] = \{([^}]*)\}", src).group(1).split(",")]
     kc = max(widths)
-    hdr = open(os.path.join(csrc, "dfx_tangent_multi.h")).read()
+    hdr = open(os.path.join(csrc, "dfx_tangent.h")).read()
     assert int(re.search(r"constexpr int kTanMaxWidth = (\d+);", hdr).group(1)) == kc
     out = tmp_path / "tangent_multi.s"
     subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-mllvm", "-disable-machine-licm", "-S", "--cuda-device-only",
-                           "-o", str(out), os.path.join(csrc, "engine_tangent_multi.hip")], stderr=subprocess.DEVNULL)
+                           "-o", str(out), os.path.join(csrc, "engine_tangent.hip")], stderr=subprocess.DEVNULL)
     txt = out.read_text()
     name = f"_ZN3dfx17k_tan_stage_multiILi1ELi1ELi4ELi{kc}EEEvNS_6TanCtxENS_7TableauENS_9TanStageME"
     i = txt.index("\n" + name + ":")

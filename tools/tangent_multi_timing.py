@@ -3,7 +3,8 @@
        x K lanes do not fill the chip, all directions spread over lanes in one pass (width 1);
   (a') the chunked form forced (DFX_TANGENT_MULTI_FORM=chunked), to show what the choice is worth;
 against the two ways K directions were had before it --
-  (b1) K calls of DynamicSolver.jvp on the same solver, one direction each;
+  (b1) K calls of DynamicSolver.jvp on the same solver: K passes of width 1 (jvp is jvp_multi along one direction; in
+       profiles/r09_tangent_multi.txt it was still a single-direction kernel of its own);
   (b2) one jvp on a solver of batch x K members, every design replicated K times (where batch x K <= --max-members, default 64: the host
        side of wider replicated ensembles takes longer than the measurement is worth)
 -- on tools/tangent_timing.py's two configurations:

@@ -1,5 +1,5 @@
-"""What a tangent stage costs: DynamicSolver.jvp (primal + one tangent direction per member, dfx_forward_tangent) against the plain
-fixed-grid forward solve solve_dynamics(..., steps_per_interval=...) on the same grid, at
+"""What a tangent stage costs: DynamicSolver.jvp (primal + one tangent direction per member: jvp_multi along one direction, the
+K-direction kernels of dfx_tangent.h at width 1) against the plain fixed-grid forward solve solve_dynamics(..., steps_per_interval=...) on the same grid, at
   * 128 x 128 quads with angle contact, 16 members, 250 dopri5 steps;
   * the paper's lattice (24 x 16 quads, spacing 15 mm, contact -15 / -10 deg, damping), 1 member, 250 steps.
 Prints device ms per step of both (HIP events around the stage launches), the wall time per call, and the ratio.
