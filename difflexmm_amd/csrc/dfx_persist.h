@@ -80,8 +80,8 @@ struct LigRes {
   double am, ac, kc, phi1, phi2, kap_safe, phi_min;      // angle contact
   int info, pslot;
 };
-template <int CONTACT>
-__device__ __forceinline__ void load_lig_res(const DevCtx& c, const MemberBases& B, int slot, LigRes& g) {
+template <int CONTACT, class Ctx /* DevCtx or PersistCtx */>
+__device__ __forceinline__ void load_lig_res(const Ctx& c, const MemberBases& B, int slot, LigRes& g) {
   g.info = ldg<int>(c.slot_info, (u32)slot * 4);
   g.pslot = g.info < 0 ? slot : (g.info >> 1);          // a slot without a ligament watches its own block
   g.sgn = (g.info & 1) ? 1.0 : -1.0;
@@ -105,6 +105,16 @@ __device__ __forceinline__ void load_lig_res(const DevCtx& c, const MemberBases&
     const double2 ph = ldg<double2>(B.p_phi, (u32)slot * 16);
     g.phi1 = ph.x; g.phi2 = ph.y;
   }
+}
+// a per-lane value the compiler must take as new where this stands: what is computed from it stays where it is written
+__device__ __forceinline__ int fresh_v(int x) { asm volatile("" : "+v"(x)); return x; }
+// uniform bases of member `um` of a launch (PersistCtx: every array starts at the launch's first member)
+__device__ __forceinline__ MemberBases persist_bases(const PersistCtx& c, u32 um) {
+  MemberBases B{};
+  const u32 ps = um * (u32)c.n_slots;
+  B.p_r = c.p_r + (size_t)(ps * 2); B.p_phi = c.p_phi + (size_t)(ps * 2); B.p_l = c.p_l + (size_t)(ps * 2); B.p_k = c.p_k + (size_t)(ps * 4);
+  B.cst = c.cst + (size_t)(um * 16); B.l_dict = c.l_dict + (size_t)(um * 1024); B.p_lidx = c.p_lidx + (size_t)ps;
+  return B;
 }
 // the partner's ring record of stage ordinal t: polled until none of its four doubles is poison; false: gave up
 __device__ __forceinline__ bool ring_wait(const double* place, u32 byte_off, double (&r)[4], int t_ord, int* give_up, int limit) {
@@ -180,25 +190,25 @@ __device__ __forceinline__ LanePos wave_lane_pos(int w, int n_blocks) {
 #define DFX_PERSIST_OCC
 #endif
 template <int MODEL, int CONTACT, int NPB>
-__global__ __launch_bounds__(kPersistThreads) DFX_PERSIST_OCC void k_fwd_persist(DevCtx c, PersistCoef pc, PersistArgs pa) {
+__global__ __launch_bounds__(kPersistThreads) DFX_PERSIST_OCC void k_fwd_persist(PersistCtx c, PersistFwdTab pc, PersistArgs pa) {
   int ml, w;
   if (!persist_wave(pa, ml, w)) return;
-  const int m = c.m0 + ml;
   const LanePos lp = wave_lane_pos<NPB>(w, c.n_blocks);
   if (!lp.valid) return;
   const int slot = lp.slot, b = lp.b, k = lp.k, kd = k < 3 ? k : 2;
+  const u32 um = (u32)ml;                  // the member's number inside the launch (PersistCtx)
   const u32 nd = (u32)c.n_blocks * 3;
   const int s = c.s;
   const Seg sg = *c.cur;
-  const MemberBases B = member_bases(c, m);
+  const MemberBases B = persist_bases(c, um);
   LigRes g;
   load_lig_res<CONTACT>(c, B, slot, g);
   const int info = g.info, pslot = g.pslot;
   // ---- resident per DOF lane
   const int dof = b * 3 + kd;
   const u32 o_dof = (u32)dof * 8, o_rec = ((u32)b * kPos + kd) * 8, o_chunk = ((u32)b * kPos + 2 * (k & 1)) * 8;
-  const double damp = c.damping_uniform ? B.cst[6 + kd] : ldg<double>(c.damping + (size_t)((u32)m * nd), o_dof);
-  const double invm = ldg<double>(c.inv_m + (size_t)((u32)m * nd), o_dof);
+  const double damp = c.damping_uniform ? B.cst[6 + kd] : ldg<double>(c.damping + (size_t)(um * nd), o_dof);
+  const double invm = ldg<double>(c.inv_m + (size_t)(um * nd), o_dof);
   const int sidx = ldg<int>(c.block_special, (u32)b * 4);
   const bool constrained = k < 3 && sidx >= 0 && ((c.special[sidx >= 0 ? sidx : 0].con_mask >> k) & 1);
   // a driven / loaded DOF's coefficients of the <= 2 time functions, resident (prescribed motion: con_coef, load: load_coef -- a DOF is one or
@@ -210,11 +220,16 @@ __global__ __launch_bounds__(kPersistThreads) DFX_PERSIST_OCC void k_fwd_persist
     tf_coef[f] = (k < 3 && sidx >= 0 && f < c.n_fns) ? (constrained ? c.special[sidx].con_coef[k][f] : c.special[sidx].load_coef[k][f]) : 0.0;
   const bool recs = c.rps > 1;
   const long long n0 = sg.base_step;
+  const size_t blk = (size_t)((u32)c.n_blocks * (u32)kStep);            // doubles of one record
+  const size_t rec_step = (size_t)(u32)c.batch * blk;                     // ... between consecutive records of one member
+  double* const traj_m = c.traj ? c.traj + (size_t)um * blk : nullptr;        // (forward only: no checkpoint, nothing is built on a null base)
+  double* const POSm = c.POS + (size_t)(um * (u32)c.nbuf * (u32)c.n_blocks * (u32)kPos);
+  double* const VELm = c.VEL + (size_t)(um * (u32)c.nbuf * nd);
   double qn, vn;
   BlockRec<double> o;
   {
-    const double* P0 = pos_in(c, m, recs ? -1 : 0, n0);
-    const double* V0 = vel_in(c, m, recs ? -1 : 0, n0);
+    const double* P0 = recs ? traj_m + (size_t)((u32)n0 * (u32)c.rps) * rec_step : POSm;
+    const double* V0 = recs ? P0 + (size_t)((u32)c.n_blocks * (u32)kPos) : VELm;
     const double2 a0 = ldg<double2>(P0, (u32)b * kPos * 8), a1 = ldg<double2>(P0, (u32)b * kPos * 8 + 16);
     o.x = a0.x; o.y = a0.y; o.th = a1.x; o.sh = a1.y;
     qn = ldg<double>(P0, o_rec);
@@ -224,13 +239,26 @@ __global__ __launch_bounds__(kPersistThreads) DFX_PERSIST_OCC void k_fwd_persist
 #pragma unroll
   for (int l = 0; l < kPersistStages; ++l) al[l] = 0.0;
   // ---- the ring: per-lane byte offsets inside a place; a place of all members is ring_stride doubles
-  const size_t ring_stride = (size_t)c.batch * c.n_blocks * kPos;
-  const u32 r_own = ((u32)m * (u32)c.n_blocks + (u32)b) * (kPos * 8) + 16u * (u32)(k & 1);
-  const u32 r_par = ((u32)m * (u32)c.n_blocks + (u32)(pslot >> 2)) * (kPos * 8);
+  const size_t ring_stride = (size_t)((u32)c.batch * (u32)c.n_blocks * (u32)kPos);
+  const u32 r_own = (um * (u32)c.n_blocks + (u32)b) * (kPos * 8) + 16u * (u32)(k & 1);
+  const u32 r_par = (um * (u32)c.n_blocks + (u32)(pslot >> 2)) * (kPos * 8);
   if (k < 2) ring_store(pa.ring, r_own, k == 0 ? o.x : o.th, k == 0 ? o.y : o.sh);      // ordinal 0
   const int total = pa.n_steps * s;
   int t_ord = 0;
   double v_i = vn;
+  // ---- what moves with the stage ordinal, stepped: the record a stage writes (records level: record i + 1 of step n -- consecutive but
+  // for the gap between the s stage records and the rps records of a step), the row of the time-function table (a constrained DOF reads
+  // the NEXT row: in its lane offset), the place in the stage checkpoint, the ring place
+  // (state level, c.rps == 1: only the last stage of a step stores, into the state of step n + 1 -- the pointer moves once per step)
+  const int keep = recs ? 2 : (c.traj ? 1 : 0);                           // what a stage leaves in the trajectory checkpoint
+  double* tr = keep ? traj_m + ((size_t)((u32)n0 * (u32)c.rps) + 1) * rec_step : nullptr;
+  const size_t rec_adv = recs ? rec_step : 0, rec_gap = recs ? (size_t)(u32)(c.rps - s) * rec_step : (keep ? rec_step : 0);
+  const u32 o_vrec = (u32)c.n_blocks * (kPos * 8) + o_dof;                // the DOF's velocity inside a record
+  const double* ft = c.fn_tab ? c.fn_tab + ((size_t)um * kMaxGraphSteps * kFnRows) * (DFX_MAX_FNS * kFnEntry) : nullptr;
+  const int ft_row = c.fn_tab ? DFX_MAX_FNS * kFnEntry : 0;               // doubles between consecutive rows (no table: the pointer stays null)
+  const u32 z_row = constrained ? (u32)(DFX_MAX_FNS * kFnEntry * 8) : 0u;
+  double* Am = c.AD ? c.AD + (size_t)um * c.ad_stride + (size_t)n0 * ((u32)(s - 1) * nd) : nullptr;
+  const double* place = pa.ring;                                           // ring place of ordinal t_ord
 #ifdef DFX_PERSIST_TIMING
   unsigned acc_t[6] = {0, 0, 0, 0, 0, 0};
   unsigned long long t_prev = tick();
@@ -239,22 +267,28 @@ __global__ __launch_bounds__(kPersistThreads) DFX_PERSIST_OCC void k_fwd_persist
   for (int j = 0; j < pa.n_steps; ++j) {
     const long long n = n0 + j;
     double h = sg.h;
-    if (c.t_steps) { const double* ts = steps_of(c, m); h = ts[n + 1] - ts[n]; }
-    double* Am = c.AD ? c.AD + (size_t)m * c.ad_stride + (size_t)n * ((u32)(s - 1) * nd) : nullptr;
+    if (c.t_steps) { const double* ts = c.t_steps + (size_t)um * (size_t)c.ts_stride; h = ts[n + 1] - ts[n]; }
     // (one copy of the stage body, the stage index a run-time value: unrolled six times the register allocator kept 200 registers live
     // and the launch lost its second and third wave per SIMD)
 #pragma unroll 1
     for (int i = 0; i < s; ++i) {
       {
+        // ---- the stage's coefficients: one row (PersistFwdTab), asked for here
+        const double* row = pc.row[i];
+        double cv[kPersistStages - 1], cq[kPersistStages - 1];
+#pragma unroll
+        for (int l = 0; l < kPersistStages - 1; ++l) { cv[l] = row[l]; cq[l] = row[kPersistStages - 1 + l]; }
+        const double cv_i = row[10], cq_i = row[11], c_next = row[12];
         // ---- what does not need the partner's record, in front of the poll (a wave alone on its SIMD has nothing else to do while it
         // waits): the own half-angle cosine, the Runge-Kutta sums over the EARLIER stages' accelerations, the load of a loaded block
         o.ch = half_cos(o.th, o.sh);
         double sv = 0.0, sq = 0.0, fload = 0.0;
 #pragma unroll
         for (int l = 0; l < kPersistStages - 1; ++l) {
-          const double a_l = l < i ? al[l] : 0.0;         // (the stage kernels add exact zeros for l >= i as well)
-          sv += pc.cv[i][l] * a_l;
-          sq += pc.cq[i][l] * a_l;
+          // (a stage l >= i has weight zero in the row, as the stage kernels add exact zeros for it; al[l] is finite from the start -- in a
+          // member that has overflowed, zero times a stale infinity is NaN where the stage kernels keep a zero: that member is lost either way)
+          sv += cv[l] * al[l];
+          sq += cq[l] * al[l];
         }
         // the time functions' table values a driven / loaded DOF needs (prescribed value and rate at the NEXT stage time, or the load at this
         // one): ASKED FOR here, used after the poll -- the two round trips overlap
@@ -262,19 +296,17 @@ __global__ __launch_bounds__(kPersistThreads) DFX_PERSIST_OCC void k_fwd_persist
 #pragma unroll
         for (int f = 0; f < DFX_MAX_FNS; ++f) { tv0[f] = 0.0; tv1[f] = 0.0; }
         if (k < 3 && sidx >= 0) {
-          const double* ft = fn_tab_row(c, m, j, constrained ? i + 1 : i);
-          const u32 z = lane_zero();
+          const u32 z = lane_zero() + z_row;
 #pragma unroll
           for (int f = 0; f < DFX_MAX_FNS; ++f)
             if (f < c.n_fns) { tv0[f] = fn_tab_get(ft, f, 0, z); if (constrained) tv1[f] = fn_tab_get(ft, f, 1, z); }
         }
         DFX_TICK(0)
         // ---- the partner's record of this stage
-        const double* place = pa.ring + (size_t)(t_ord % kPRing) * ring_stride;
         double pr[4];
         if (!ring_wait(place, r_par, pr, t_ord, pa.give_up, pa.spin_limit)) return;
         DFX_TICK(1)
-        if (k < 2 && t_ord + kPAhead <= total) ring_poison(pa.ring + (size_t)((t_ord + kPAhead) % kPRing) * ring_stride, r_own);
+        if (k < 2 && t_ord + kPAhead <= total) ring_poison(pa.ring + (size_t)(((u32)t_ord + kPAhead) & (kPRing - 1)) * ring_stride, r_own);
         BlockRec<double> p;
         p.x = pr[0]; p.y = pr[1]; p.th = pr[2]; p.sh = pr[3];
         p.ch = half_cos(p.th, p.sh);
@@ -305,13 +337,13 @@ __global__ __launch_bounds__(kPersistThreads) DFX_PERSIST_OCC void k_fwd_persist
         double qnext = 0.0, vnext = 0.0;
         if (k < 3) {
           const double a = constrained ? 0.0 : (fload - dE - damp * v_i) * invm;
-          if (Am && i < s - 1) stg<double>(Am + (size_t)i * nd, o_dof, a);
+          if (Am && i < s - 1) stg<double>(Am, o_dof, a);
           // (the stage kernels' order: the earlier stages' terms first -- summed above --, the own term last)
-          sv += pc.cv[i][i] * a;
-          sq += pc.cq[i][i] * a;
+          sv += cv_i * a;
+          sq += cq_i * a;
 #pragma unroll
           for (int l = 0; l < kPersistStages; ++l) al[l] = l == i ? a : al[l];
-          qnext = qn + h * (pc.c[i + 1] * vn + h * sq);
+          qnext = qn + h * (c_next * vn + h * sq);
           vnext = vn + h * sv;
           if (constrained) { qnext = q_pre; vnext = v_pre; }
         }
@@ -322,26 +354,32 @@ __global__ __launch_bounds__(kPersistThreads) DFX_PERSIST_OCC void k_fwd_persist
         fast_sincos(0.5 * th2, &sn, &cs);
         o.x = x0; o.y = y1; o.th = th2; o.sh = sn;
         ++t_ord;
+        place = pa.ring + (size_t)((u32)t_ord & (kPRing - 1)) * ring_stride;
         DFX_TICK(4)
         const bool last = i == s - 1;
-        if (k < 2) ring_store(pa.ring + (size_t)(t_ord % kPRing) * ring_stride, r_own, k == 0 ? x0 : th2, k == 0 ? y1 : sn);
+        if (k < 2) ring_store(const_cast<double*>(place), r_own, k == 0 ? x0 : th2, k == 0 ? y1 : sn);
         if (k < 3) {
           const double2 chunk = k == 0 ? make_double2(x0, y1) : make_double2(th2, sn);
-          if (recs || (last && c.traj)) {
-            double* tr = recs ? traj_rec(c, m, -2 - i, n) : traj_rec(c, m, -1, n + 1);
+          if (keep > (last ? 0 : 1)) {
             if (k < 2) stg<double2>(tr, o_chunk, chunk);
-            stg<double>(tr + (size_t)c.n_blocks * kPos, o_dof, vnext);
+            stg<double>(tr, o_vrec, vnext);
           }
-          if (last && !recs && j == pa.n_steps - 1) {      // the segment's last state, for k_snapshot and the next segment
-            if (k < 2) stg<double2>(c.POS + (size_t)((u32)m * (u32)c.nbuf * (u32)c.n_blocks * kPos), o_chunk, chunk);
-            stg<double>(c.VEL + (size_t)((u32)m * (u32)c.nbuf * nd), o_dof, vnext);
+          if (last && keep < 2 && j == pa.n_steps - 1) {      // the segment's last state, for k_snapshot and the next segment
+            if (k < 2) stg<double2>(POSm, o_chunk, chunk);
+            stg<double>(VELm, o_dof, vnext);
           }
         }
         v_i = vnext;
         if (last) { qn = qnext; vn = vnext; }
         DFX_TICK(5)
+        // ---- on to the next stage: one record, one table row, one place in the stage checkpoint
+        tr += rec_adv;
+        ft += ft_row;
+        if (Am && i < s - 1) Am += nd;
       }
     }
+    tr += rec_gap;
+    ft += (kFnRows - s) * ft_row;
   }
 #ifdef DFX_PERSIST_TIMING
   if (pa.dbg && (threadIdx.x & 63) == 0) {
@@ -370,38 +408,39 @@ __global__ __launch_bounds__(kPersistThreads) DFX_PERSIST_OCC void k_fwd_persist
 // (k_adj_begin, a stage launch, or this kernel) left it -- DevCtx::W -- and the last one leaves its own there, with lambda in LAM and
 // the accumulators in their arrays: segments run by this kernel and by stage launches can alternate.
 
-// (three workgroups per compute unit: 168 registers; the allocator's own choice is 170-172, the limit costs two 8-byte spills of
-// epilogue pointers OUTSIDE the stage loop)
+// (three workgroups per compute unit: <= 168 registers.  The loop takes PersistCtx, not DevCtx, steps its addresses with the stage
+// ordinal and makes its four Kbar sums where they are written: 159 registers, no scratch, no scalar register spilled inside a stage
+// -- tests/test_persist_loop_budget.py, profiles/r14_persist_lean.txt)
 //   DENSE: the sweep of an adaptive solve that kept its accepted steps (dfx_dense.h): every member its own number of steps N_m -- a wave
 //   runs the steps n <= N_m of the segment, of step N_m only stage 0 (the evaluation at the final state, a step of size zero) -- and the
 //   outputs' cotangents enter through the dense output (the same sums as in adj_stage_body<..., DENSE = 1>).  Builds of their own
 //   (k_adj_dense_loop, dfx_persist_dense.hip): the fixed-grid kernels carry none of it.
 template <int MODEL, int CONTACT, int NPB, int DENSE>
-__device__ __forceinline__ void adj_persist_body(const DevCtx& c, const PersistAdjCoef& pc, const PersistArgs& pa, const DenseCtx& dn) {
+__device__ __forceinline__ void adj_persist_body(const PersistCtx& c, const PersistAdjTab& pc, const PersistArgs& pa, const DenseCtx& dn) {
   int ml, w;
   if (!persist_wave(pa, ml, w)) return;
-  const int m = c.m0 + ml;
   const LanePos lp = wave_lane_pos<NPB>(w, c.n_blocks);
   if (!lp.valid) return;
   const int slot = lp.slot, b = lp.b, k = lp.k, kd = k < 3 ? k : 2;
+  const u32 um = (u32)ml;                  // the member's number inside the launch: every base of PersistCtx points at the launch's first member
   const u32 nd = (u32)c.n_blocks * 3, nd6 = (u32)c.n_blocks * 6;
   const int s = c.s;
   const Seg sg = *c.cur;
   long long n_m = 0;
   int j_top = pa.n_steps - 1;
   if constexpr (DENSE) {
-    n_m = dn.n_acc[m];
+    n_m = dn.n_acc[c.m0 + ml];
     if (n_m - sg.base_step < (long long)j_top) j_top = (int)(n_m - sg.base_step);
     if (j_top < 0) return;                      // this member's sweep starts in an earlier segment
   }
-  const MemberBases B = member_bases(c, m);
+  const MemberBases B = persist_bases(c, um);
   LigRes g;
   load_lig_res<CONTACT>(c, B, slot, g);
   const int info = g.info, pslot = g.pslot;
   const int dof = b * 3 + kd;
   const u32 o_dof = (u32)dof * 8, o_b6 = ((u32)b * 6 + 2 * kd) * 8;
-  const double damp = c.damping_uniform ? B.cst[6 + kd] : ldg<double>(c.damping + (size_t)((u32)m * nd), o_dof);
-  const double invm = ldg<double>(c.inv_m + (size_t)((u32)m * nd), o_dof);
+  const double damp = c.damping_uniform ? B.cst[6 + kd] : ldg<double>(c.damping + (size_t)(um * nd), o_dof);
+  const double invm = ldg<double>(c.inv_m + (size_t)(um * nd), o_dof);
   const int sidx = ldg<int>(c.block_special, (u32)b * 4);
   const bool constrained = k < 3 && sidx >= 0 && ((c.special[sidx >= 0 ? sidx : 0].con_mask >> k) & 1);
   double tf_coef[DFX_MAX_FNS];      // k_fwd_persist: a driven / loaded DOF's coefficients of the time functions, resident
@@ -409,12 +448,12 @@ __device__ __forceinline__ void adj_persist_body(const DevCtx& c, const PersistA
   for (int f = 0; f < DFX_MAX_FNS; ++f)
     tf_coef[f] = (k < 3 && sidx >= 0 && f < c.n_fns) ? (constrained ? c.special[sidx].con_coef[k][f] : c.special[sidx].load_coef[k][f]) : 0.0;
   // ---- resident: lambda, accumulators
-  double* LAMm = c.LAM + (size_t)((u32)m * nd6);
-  const u32 ms = (u32)m * (u32)c.n_slots;
+  double* LAMm = c.LAM + (size_t)(um * nd6);
+  const u32 ms = um * (u32)c.n_slots;
   double* grm = c.g_r + (size_t)(ms * 2);
   double* gpm = c.g_phi + (size_t)ms;
-  double* bmm = c.blk_m + (size_t)((u32)m * nd);
-  double* bcm = c.blk_c ? c.blk_c + (size_t)((u32)m * nd) : nullptr;
+  double* bmm = c.blk_m + (size_t)(um * nd);
+  double* bcm = c.blk_c ? c.blk_c + (size_t)(um * nd) : nullptr;
   // The later stages' Ybar (five (q, v) pairs per DOF) and the four accumulators are touched once or twice per stage: they live in LDS,
   // one private place per lane (no lane reads another lane's: no barrier, no fence) -- 30 registers less, which is what lets three
   // workgroups of this kernel share a compute unit (171-198 VGPRs before, two workgroups)
@@ -423,18 +462,36 @@ __device__ __forceinline__ void adj_persist_body(const DevCtx& c, const PersistA
   __shared__ double s_acc[3][kPersistThreads];        // void angle, inertia, damping
   __shared__ double2 s_lam[kPersistThreads];
   const int tid = (int)threadIdx.x;
+  // (every Ybar place is read at every stage and weighted by the stage's row of PersistAdjTab: zero where a later stage does not enter the
+  // sums, so a place must hold a finite number from the start)
+#pragma unroll
+  for (int jj = 0; jj < kPersistStages - 1; ++jj) s_yb[jj][tid] = make_double2(0.0, 0.0);
   s_racc[tid] = ldg<double2>(grm, (u32)slot * 16);
   s_lam[tid] = ldg<double2>(LAMm, o_b6);
   s_acc[0][tid] = CONTACT == 1 ? ldg<double>(gpm, (u32)slot * 8) : 0.0;
   s_acc[1][tid] = ldg<double>(bmm, o_dof);
   s_acc[2][tid] = bcm ? ldg<double>(bcm, o_dof) : 0.0;
   bool phi_any = false;
+  // where a DOF of a driven / loaded block adds to the time functions' parameter gradients, when they are asked for
+  double* const fn_gq = (c.fn_g && k < 3 && sidx >= 0) ? c.fn_g + (((size_t)um * c.n_special + sidx) * DFX_MAX_FNS) * DFX_FN_PARAMS : nullptr;
   // ---- the ring
-  const size_t ring_stride = (size_t)c.batch * c.n_blocks * kPos;
-  const u32 r_own = ((u32)m * (u32)c.n_blocks + (u32)b) * (kPos * 8) + 16u * (u32)(k & 1);
-  const u32 r_par = ((u32)m * (u32)c.n_blocks + (u32)(pslot >> 2)) * (kPos * 8);
+  const size_t ring_stride = (size_t)((u32)c.batch * (u32)c.n_blocks * (u32)kPos);
+  const u32 r_own = (um * (u32)c.n_blocks + (u32)b) * (kPos * 8) + 16u * (u32)(k & 1);
+  const u32 r_par = (um * (u32)c.n_blocks + (u32)(pslot >> 2)) * (kPos * 8);
   const int total = DENSE ? (j_top + 1) * s - ((sg.base_step + j_top == n_m) ? s - 1 : 0) : pa.n_steps * s;
   int t_ord = 0;
+  // ---- what moves with the stage ordinal, stepped (consecutive stages to run -- (n, i) -> (n, i - 1), (n, 0) -> (n - 1, s - 1) -- are
+  // consecutive records of the checkpoint but for the gap between the s stage records and the rps records of a step, consecutive rows
+  // of the time-function table but for the rows a step does not use, and alternate in the parity buffer of W):
+  const int i_top = (DENSE && sg.base_step + j_top == n_m) ? 0 : s - 1;      // DENSE: of step N_m only stage 0 runs
+  const size_t rec_step = (size_t)((u32)c.batch * ((u32)c.n_blocks * (u32)kStep));     // doubles between consecutive records of one member
+  const u32 o_vel = (u32)c.n_blocks * (kPos * 8) + o_dof;                              // the DOF's velocity inside a record
+  const double* rec = c.traj + (size_t)((((u32)(sg.base_step + j_top) * (u32)c.rps + (u32)i_top) * (u32)c.batch + um)) * (size_t)((u32)c.n_blocks * (u32)kStep);
+  const size_t rec_gap = (size_t)(u32)(c.rps - s) * rec_step;
+  const double* ft = c.fn_tab ? c.fn_tab + (((size_t)um * kMaxGraphSteps + (u32)j_top) * kFnRows + (u32)i_top) * (DFX_MAX_FNS * kFnEntry) : nullptr;
+  const int ft_row = c.fn_tab ? DFX_MAX_FNS * kFnEntry : 0;               // doubles between consecutive rows (no table: the pointer stays null)
+  int win = (int)(((sg.base_step + j_top) * s + i_top) & 1);
+  const double* place = pa.ring;                                                      // ring place of ordinal t_ord
 #ifdef DFX_PERSIST_TIMING
   unsigned acc_t[6] = {0, 0, 0, 0, 0, 0};
   unsigned long long t_prev = tick();
@@ -443,40 +500,54 @@ __device__ __forceinline__ void adj_persist_body(const DevCtx& c, const PersistA
   for (int j = j_top; j >= 0; --j) {
     const long long n = sg.base_step + j;
     double h = sg.h, h_before = (sg.j0 + j) == 0 ? sg.h_prev : sg.h;
-    if (c.t_steps) { const double* ts = steps_of(c, m); h = ts[n + 1] - ts[n]; h_before = n > 0 ? ts[n] - ts[n - 1] : 0.0; }
+    if (c.t_steps) { const double* ts = c.t_steps + (size_t)um * (size_t)c.ts_stride; h = ts[n + 1] - ts[n]; h_before = n > 0 ? ts[n] - ts[n - 1] : 0.0; }
+    // the first step of an interval adds the interval's own cotangent to lambda (its stage 0): fetched per step, not inside the stage loop
+    // (a free DOF's two words; zero elsewhere -- a constrained DOF's lambda is set to zero behind the sum)
+    const bool first = !DENSE && (sg.j0 + j) == 0 && c.G;
+    double g0q = 0.0, g0v = 0.0;
+    if (first && k < 3 && !constrained) {
+      const double* G = c.G + ((size_t)sg.interval * c.batch + um) * (size_t)nd6;
+      g0q = G[b * 6 + k]; g0v = G[b * 6 + 3 + k];
+    }
 #pragma unroll 1
     for (int i = (DENSE && n == n_m) ? 0 : s - 1; i >= 0; --i) {
-      const int win = (int)((n * s + i) & 1);
+      // ---- the stage's coefficients: one row, asked for here, waited for where the sums begin
+      const double* row = pc.row[i];
+      double cf[kPersistStages - 1], cu[kPersistStages - 1];
+#pragma unroll
+      for (int jj = 0; jj < kPersistStages - 1; ++jj) { cf[jj] = row[jj]; cu[jj] = row[kPersistStages - 1 + jj]; }
+      const double col_s = row[10], cur_s = row[11], col_i = row[12];
       // ---- the records this stage linearises about (checkpoint), in flight while the partner's w is polled
-      const double* POSin = traj_rec(c, m, -1 - i, n);
+      const double* POSin = rec;
       const double2 o0 = ldg<double2>(POSin, (u32)b * (kPos * 8)), o1 = ldg<double2>(POSin, (u32)b * (kPos * 8) + 16);
       const double2 q0 = ldg<double2>(POSin, (u32)(pslot >> 2) * (kPos * 8)), q1 = ldg<double2>(POSin, (u32)(pslot >> 2) * (kPos * 8) + 16);
-      const double v_i = ldg<double>(POSin + (size_t)c.n_blocks * kPos, o_dof);
+      const double v_i = ldg<double>(POSin, o_vel);
       // ---- Kbar sums over the later stages' Ybar, the own w and its broadcasts (k_adj_stage, records build): none of it needs the
-      // partner's w or the records still in flight -- in front of the poll
+      // partner's w or the records still in flight -- in front of the poll.  (A stage that does not enter has weight zero: PersistAdjTab.
+      // The stage kernels add an exact zero for it; here a stale place times zero is that zero only while the place is finite -- in a member
+      // whose Ybar has overflowed it is NaN, one stage before the NaN would have reached the sums anyway: such a member's gradient is lost either way.
+      //       // DENSE: the evaluation at the final state, stage 0 of the zero-size step N_m, is the first stage a wave runs -- every place still zero)
       double sq = 0.0, sv = 0.0, sqc = 0.0, svc = 0.0;
 #pragma unroll
       for (int jj = 1; jj < kPersistStages; ++jj) {
-        // (DENSE: the evaluation at the final state, stage 0 of the zero-size step N_m, has no later stages -- their places hold nothing yet)
-        const bool on = jj > i && jj < s && !(DENSE && n == n_m);
-        const double2 y = on ? s_yb[jj - 1][tid] : make_double2(0.0, 0.0);
-        const double cf = i > 0 ? pc.col[i][jj] : 1.0;
-        sq += cf * y.x;
-        sv += cf * y.y;
-        sqc += pc.cur[i][jj] * y.x;
-        svc += pc.cur[i][jj] * y.y;
+        const double2 y = s_yb[jj - 1][tid];
+        sq += cf[jj - 1] * y.x;
+        sv += cf[jj - 1] * y.y;
+        sqc += cu[jj - 1] * y.x;
+        svc += cu[jj - 1] * y.y;
       }
+      // (made HERE: left to the compiler, three of the sums sink into the epilogue and keep the five Ybar pairs and the row's twenty
+      // coefficients in registers across the whole stage)
+      asm volatile("" : "+v"(sq), "+v"(sv), "+v"(sqc), "+v"(svc));
       // the load of a loaded DOF at this stage time (tabulated per segment): fetched here, in front of the poll
       double tv0[DFX_MAX_FNS];
 #pragma unroll
       for (int f = 0; f < DFX_MAX_FNS; ++f) tv0[f] = 0.0;
       if (k < 3 && sidx >= 0 && !constrained) {
-        const double* ft = fn_tab_row(c, m, j, i);
         const u32 z = lane_zero();
 #pragma unroll
         for (int f = 0; f < DFX_MAX_FNS; ++f) if (f < c.n_fns) tv0[f] = fn_tab_get(ft, f, 0, z);
       }
-      const double col_s = pc.col[i][s], cur_s = pc.cur[i][s], col_i = pc.col[i][i];
       const double2 lam = s_lam[tid];
       const double lq = lam.x, lv = lam.y;
       double w_d = (h * (cur_s * lv + svc)) * invm;
@@ -485,13 +556,14 @@ __device__ __forceinline__ void adj_persist_body(const DevCtx& c, const PersistA
       double e_own_q = 0.0, e_nxt_v = 0.0, gs_q = 0.0, gs_v = 0.0;
       if constexpr (DENSE) {
         if (!constrained) {
+          const int m = c.m0 + ml;
           const int* op = dn.out_ptr + (size_t)m * dn.stride;
           const int lo = op[n], hi = op[n + 1], plo = n > 0 ? op[n - 1] : lo;
           const double* dwm = dn.dw + (size_t)m * dn.n_out * 8;
           const u32 o_g = ((u32)b * 6 + kd) * 8;
           double e_own_v = 0.0;
           for (int kk = lo; kk < hi; ++kk) {
-            const double* Gk = c.G + ((size_t)kk * c.batch + m) * (size_t)nd6;
+            const double* Gk = c.G + ((size_t)kk * c.batch + um) * (size_t)nd6;
             const double gq = ldg<double>(Gk, o_g), gv = ldg<double>(Gk, o_g + 24);
             const double* wt = dwm + (size_t)kk * 8;
             e_own_q += wt[i] * gq; e_own_v += wt[i] * gv;
@@ -502,7 +574,7 @@ __device__ __forceinline__ void adj_persist_body(const DevCtx& c, const PersistA
           if (i <= 1) {
             double e6q = 0.0, e6v = 0.0, e5v = 0.0;
             for (int kk = plo; kk < lo; ++kk) {
-              const double* Gk = c.G + ((size_t)kk * c.batch + m) * (size_t)nd6;
+              const double* Gk = c.G + ((size_t)kk * c.batch + um) * (size_t)nd6;
               const double gq = ldg<double>(Gk, o_g), gv = ldg<double>(Gk, o_g + 24);
               const double* wt = dwm + (size_t)kk * 8;
               e6q += wt[6] * gq; e6v += wt[6] * gv;
@@ -513,7 +585,7 @@ __device__ __forceinline__ void adj_persist_body(const DevCtx& c, const PersistA
           }
           if (i == 0 && n == 0)
             for (int kk = 0; kk < lo; ++kk) {
-              const double* Gk = c.G + ((size_t)kk * c.batch + m) * (size_t)nd6;
+              const double* Gk = c.G + ((size_t)kk * c.batch + um) * (size_t)nd6;
               gs_q += ldg<double>(Gk, o_g); gs_v += ldg<double>(Gk, o_g + 24);
             }
           w_d += e_own_v * invm;
@@ -523,13 +595,14 @@ __device__ __forceinline__ void adj_persist_body(const DevCtx& c, const PersistA
       double wp[4];
       DFX_TICK(0)
       if (t_ord == 0) {
-        const double* Win = c.W + (size_t)(((u32)m * 2 + (u32)win) * nd);
+        const double* Win = c.W + (size_t)((um * 2 + (u32)win) * nd);
         const u32 pb = (u32)(pslot >> 2) * 24;
         const double2 wxy = ldg<double2>(Win, pb);
         wp[0] = wxy.x; wp[1] = wxy.y; wp[2] = ldg<double>(Win, pb + 16);
-      } else if (!ring_wait(pa.ring + (size_t)(t_ord % kPRing) * ring_stride, r_par, wp, t_ord, pa.give_up, pa.spin_limit)) return;
+      } else if (!ring_wait(place, r_par, wp, t_ord, pa.give_up, pa.spin_limit)) return;
       DFX_TICK(1)
-      if (k < 2 && t_ord + kPAhead < total) ring_poison(pa.ring + (size_t)((t_ord + kPAhead) % kPRing) * ring_stride, r_own);
+      // (the place of ordinal t + kPAhead: half a ring further on)
+      if (k < 2 && t_ord + kPAhead < total) ring_poison(pa.ring + (size_t)(((u32)t_ord + kPAhead) & (kPRing - 1)) * ring_stride, r_own);
       BlockRec<double> o, p;
       o.x = o0.x; o.y = o0.y; o.th = o1.x; o.sh = o1.y; o.ch = half_cos(o.th, o.sh);
       p.x = q0.x; p.y = q0.y; p.th = q1.x; p.sh = q1.y; p.ch = half_cos(p.th, p.sh);
@@ -563,14 +636,17 @@ __device__ __forceinline__ void adj_persist_body(const DevCtx& c, const PersistA
         double fload = 0.0;
 #pragma unroll
         for (int f = 0; f < DFX_MAX_FNS; ++f) if (!constrained) fload += tf_coef[f] * tv0[f];
-        if (c.fn_g && sidx >= 0) {        // gradients w.r.t. the time functions' parameters (asked for explicitly: not the design loop's path)
-          const double* ft = fn_tab_row(c, m, j, i);
+        // gradients w.r.t. the time functions' parameters (asked for explicitly: not the design loop's path).  A rare path: its lane
+        // predicate is made here, from a value the compiler has to take as new at every stage -- hoisted, it is a lane mask the loop has no
+        // scalar registers for (spilled and re-read at every stage)
+        double* const fq = fn_gq;
+        if (fresh_v(fq != nullptr)) {
 #pragma unroll
           for (int f = 0; f < DFX_MAX_FNS; ++f) {
             const double coef = f < c.n_fns ? (constrained ? -hw * tf_coef[f] : w_d * tf_coef[f]) : 0.0;
             if (coef != 0.0) {
               const u32 z = lane_zero();
-              double* q = c.fn_g + (((size_t)m * c.n_special + sidx) * DFX_MAX_FNS + f) * DFX_FN_PARAMS;
+              double* q = fq + f * DFX_FN_PARAMS;
               for (int kk = 0; kk < DFX_FN_PARAMS; ++kk) acc_add(q + kk, coef * fn_tab_get(ft, f, 2 + kk, z));
             }
           }
@@ -592,11 +668,8 @@ __device__ __forceinline__ void adj_persist_body(const DevCtx& c, const PersistA
         } else {
           double nlq = lq + (ybq + sq), nlv = lv + (ybv + sv);
           if constexpr (DENSE) { nlq += gs_q; nlv += gs_v; }
-          const bool first = !DENSE && (sg.j0 + j) == 0;
-          if (first && c.G && !constrained) {
-            const double* G = c.G + ((size_t)sg.interval * c.batch + m) * (size_t)nd6;
-            nlq += G[b * 6 + k]; nlv += G[b * 6 + 3 + k];
-          }
+          // (the first step of an interval: once per interval -- a rare path, see above)
+          if (first) { nlq += g0q; nlv += g0v; }
           if (constrained) { nlq = 0.0; nlv = 0.0; }
           s_lam[tid] = make_double2(nlq, nlv);
           kv = h_before * col_s * nlv;
@@ -607,13 +680,20 @@ __device__ __forceinline__ void adj_persist_body(const DevCtx& c, const PersistA
       DFX_TICK(3)
       // ---- w of the next stage to run: into the ring, or -- last stage of the launch -- where the next launch reads it
       ++t_ord;
+      place = pa.ring + (size_t)((u32)t_ord & (kPRing - 1)) * ring_stride;
       if (t_ord < total) {
         const double w1 = blk_bcast<NPB, 1>(w_next, k), w2 = blk_bcast<NPB, 2>(w_next, k);
-        if (k < 2) ring_store(pa.ring + (size_t)(t_ord % kPRing) * ring_stride, r_own, k == 0 ? w_next : w2, k == 0 ? w1 : 0.0);
+        if (k < 2) ring_store(const_cast<double*>(place), r_own, k == 0 ? w_next : w2, k == 0 ? w1 : 0.0);
       } else if (k < 3) {
-        stg<double>(c.W + (size_t)(((u32)m * 2 + (u32)(win ^ 1)) * nd), o_dof, w_next);
+        stg<double>(c.W + (size_t)((um * 2 + (u32)(win ^ 1)) * nd), o_dof, w_next);
       }
+      // ---- on to the next stage to run: one record, one table row, the other parity
+      rec -= rec_step;
+      ft -= ft_row;
+      win ^= 1;
     }
+    rec -= rec_gap;
+    ft -= (kFnRows - s) * ft_row;
   }
 #ifdef DFX_PERSIST_TIMING
   if (pa.dbg && (threadIdx.x & 63) == 0) {
@@ -632,7 +712,7 @@ __device__ __forceinline__ void adj_persist_body(const DevCtx& c, const PersistA
 }
 
 template <int MODEL, int CONTACT, int NPB>
-__global__ __launch_bounds__(kPersistThreads) __attribute__((amdgpu_waves_per_eu(3))) void k_adj_persist(DevCtx c, PersistAdjCoef pc, PersistArgs pa) {
+__global__ __launch_bounds__(kPersistThreads) __attribute__((amdgpu_waves_per_eu(3))) void k_adj_persist(PersistCtx c, PersistAdjTab pc, PersistArgs pa) {
   adj_persist_body<MODEL, CONTACT, NPB, 0>(c, pc, pa, DenseCtx{});
 }
 

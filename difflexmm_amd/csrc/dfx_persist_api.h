@@ -3,6 +3,7 @@
 // -mllvm -disable-machine-licm.  Their stage loop is the first long loop around the ligament arithmetic, and the machine-level
 // loop-invariant code motion hoists every fp64 literal of that arithmetic (the polynomial coefficients of atan2 / sincos, ~80
 // registers of v_mov) out of it: 203 VGPRs and two waves per SIMD instead of 108 and four (profiles/r05_persistent_kernels.txt).
+// (Included behind dfx_kernels.h: PersistCtx names dfx::Seg and dfx_special.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,7 +19,7 @@ constexpr int kSpinLimit = 1 << 23; // polls (>= 0.5 us each) before a wave give
 // the store is complete (the owner's next poll waits for it) before a neighbour can ask -- and the ring is longer than that look-ahead
 static_assert(kPAhead >= 2 && kPRing >= kPAhead + 1, "hand-off ring: re-poison at least two ordinals ahead, ring longer than the look-ahead");
 
-struct PersistCoef {            // the whole tableau in acceleration form, by value (scalar loads at compile-time offsets)
+struct PersistCoef {            // the whole tableau in acceleration form (host side: persist_fwd_tab cuts the loop's rows out of it)
   double cv[kPersistStages][kPersistStages];
   double cq[kPersistStages][kPersistStages];
   double c[kPersistStages + 1];
@@ -35,10 +36,41 @@ struct PersistArgs {
 };
 
 
-struct PersistAdjCoef {         // AdjCoef of every stage
-  double col[kPersistStages][kPersistStages + 1];
-  double cur[kPersistStages][kPersistStages + 1];
-  double c[kPersistStages];
+// The reverse loop's coefficients as it consumes them: ONE row of 16 doubles per stage, fetched by one group of scalar loads at the top of
+// the stage.  The structure of the sums is baked into the numbers: a later stage jj that does not enter stage i's sums (jj <= i, jj >= s)
+// has coefficient 0 -- the loop reads every Ybar place (zeroed at the start of a launch, finite ever after) and multiplies, no selects;
+// stage 0 takes the later stages' Ybar with weight 1 (the sum that enters lambda).
+//   row[i] = { cf[1..5] | cur[1..5] | col[s] | cur[s] | col[i] | 0 0 0 },   cf[jj] = jj > i && jj < s ? (i > 0 ? col[i][jj] : 1) : 0
+constexpr int kAdjRow = 16;
+struct PersistAdjTab { double row[kPersistStages][kAdjRow]; };
+// the forward loop's, likewise: an earlier stage l >= i has weight 0 (its acceleration's place holds a finite number from the start)
+//   row[i] = { cv[i][0..4] | cq[i][0..4] | cv[i][i] | cq[i][i] | c[i+1] | 0 0 0 },   cv[i][l], cq[i][l] = 0 for l >= i
+struct PersistFwdTab { double row[kPersistStages][kAdjRow]; };
+static_assert((kPRing & (kPRing - 1)) == 0, "the ring place of a stage ordinal is taken with a mask");
+
+// What the persistent loops (forward and reverse) read of the engine's context, built by the host per launch (engine_launch.hip, persist_ctx): every
+// per-member array already points at the launch's first member, so the kernel indexes with the member's number inside the launch.
+// DevCtx by value is ~80 fields; what the stage loop needs of it did not fit the scalar registers and was spilled to vector lanes and
+// re-read, or re-loaded from the argument segment, at every stage (profiles/r14_persist_lean.txt).
+struct PersistCtx {
+  int n_blocks, n_slots, n_fns, batch, s, rps, n_special, m0;
+  int k_uniform, damping_uniform, l_dict_on, nbuf;
+  const int32_t* slot_info;
+  const int32_t* block_special;
+  const dfx_special* special;
+  const double *p_r, *p_l, *p_k, *p_phi, *l_dict, *cst, *inv_m, *damping;
+  const uint8_t* p_lidx;
+  const double* fn_tab;
+  const dfx::Seg* cur;
+  const double* t_steps;
+  long long ts_stride;
+  double* traj;
+  double *POS, *VEL, *AD;       // forward: stage buffers (buffer 0 = the step state), stage checkpoint or null
+  long long ad_stride;
+  double *LAM, *W;
+  const double* G;
+  double *g_r, *g_phi, *blk_m, *blk_c, *fn_g;
+  int* touch;
 };
 
 // kernels by (bond model, contact, lanes per block); nullptr: no such build

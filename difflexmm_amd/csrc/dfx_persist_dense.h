@@ -345,7 +345,7 @@ __global__ __launch_bounds__(kPersistThreads) void k_adaptive_fwd_loop(DevCtx c,
 
 // the reverse sweep of the kept steps without kernel boundaries: adj_persist_body<..., DENSE = 1> (dfx_persist.h)
 template <int MODEL, int CONTACT, int NPB>
-__global__ __launch_bounds__(kPersistThreads) DFX_DENSE_OCC void k_adj_dense_loop(DevCtx c, PersistAdjCoef pc, PersistArgs pa,
+__global__ __launch_bounds__(kPersistThreads) DFX_DENSE_OCC void k_adj_dense_loop(PersistCtx c, PersistAdjTab pc, PersistArgs pa,
                                                                                                            DenseCtx dn) {
   adj_persist_body<MODEL, CONTACT, NPB, 1>(c, pc, pa, dn);
 }

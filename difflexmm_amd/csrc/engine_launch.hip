@@ -496,19 +496,69 @@ static void launch_persist(dfx_handle* h, const void* fn, hipStream_t st, void**
   fl.push_back({ev, st, need});
   h->launches++;
 }
+// the reverse loop's coefficients, one row per stage (dfx_persist_api.h, PersistAdjTab): AdjCoef of stage i with the structure of the
+// stage's sums written into the numbers
+static PersistAdjTab persist_adj_tab(const Tableau& T) {
+  PersistAdjTab t;
+  memset(&t, 0, sizeof(t));
+  const int s = T.s;
+  for (int i = 0; i < s && i < kPersistStages; ++i) {
+    const AdjCoef ac = adj_coef(T, i);
+    for (int jj = 1; jj < kPersistStages; ++jj) {
+      const bool on = jj > i && jj < s;
+      t.row[i][jj - 1] = on ? (i > 0 ? ac.col[jj] : 1.0) : 0.0;
+      t.row[i][kPersistStages - 1 + jj - 1] = on ? ac.cur[jj] : 0.0;
+    }
+    t.row[i][10] = ac.col[s]; t.row[i][11] = ac.cur[s]; t.row[i][12] = ac.col[i];
+  }
+  return t;
+}
+static PersistFwdTab persist_fwd_tab(const Tableau& T) {
+  const PersistCoef pc = persist_coef(T);
+  PersistFwdTab t;
+  memset(&t, 0, sizeof(t));
+  for (int i = 0; i < T.s && i < kPersistStages; ++i) {
+    for (int l = 0; l < kPersistStages - 1 && l < i; ++l) { t.row[i][l] = pc.cv[i][l]; t.row[i][kPersistStages - 1 + l] = pc.cq[i][l]; }
+    t.row[i][10] = pc.cv[i][i]; t.row[i][11] = pc.cq[i][i]; t.row[i][12] = pc.c[i + 1];
+  }
+  return t;
+}
+// what the loops read of the context of a launch whose first member is cc.m0 (dfx_persist_api.h, PersistCtx): every per-member
+// array moved on to that member (the strides are those of the stage kernels: member_bases, traj_rec, fn_tab_row, dfx_kernels.h)
+template <class P> static P* persist_at(P* p, size_t elems) { return p ? p + elems : p; }
+static PersistCtx persist_ctx(const DevCtx& cc) {
+  PersistCtx p;
+  memset(&p, 0, sizeof(p));
+  const size_t m0 = (size_t)cc.m0, nd = (size_t)cc.n_blocks * 3, ns = (size_t)cc.n_slots;
+  p.n_blocks = cc.n_blocks; p.n_slots = cc.n_slots; p.n_fns = cc.n_fns; p.batch = cc.batch; p.s = cc.s; p.rps = cc.rps;
+  p.n_special = cc.n_special; p.m0 = cc.m0;
+  p.k_uniform = cc.k_uniform; p.damping_uniform = cc.damping_uniform; p.l_dict_on = cc.l_dict_on;
+  p.slot_info = cc.slot_info; p.block_special = cc.block_special; p.special = cc.special;
+  p.p_r = persist_at(cc.p_r, m0 * ns * 2); p.p_l = persist_at(cc.p_l, m0 * ns * 2); p.p_k = persist_at(cc.p_k, m0 * ns * 4);
+  p.p_phi = persist_at(cc.p_phi, m0 * ns * 2); p.l_dict = persist_at(cc.l_dict, m0 * 1024); p.cst = persist_at(cc.cst, m0 * 16);
+  p.p_lidx = persist_at(cc.p_lidx, m0 * ns);
+  p.inv_m = persist_at(cc.inv_m, m0 * nd); p.damping = persist_at(cc.damping, m0 * nd);
+  p.fn_tab = persist_at(cc.fn_tab, m0 * kMaxGraphSteps * kFnRows * (DFX_MAX_FNS * kFnEntry));
+  p.cur = cc.cur;
+  p.t_steps = persist_at(cc.t_steps, m0 * (size_t)cc.ts_stride); p.ts_stride = cc.ts_stride;
+  p.traj = persist_at(cc.traj, m0 * (size_t)cc.n_blocks * kStep);
+  p.nbuf = cc.nbuf; p.ad_stride = cc.ad_stride;
+  p.POS = persist_at(cc.POS, m0 * cc.nbuf * (size_t)cc.n_blocks * kPos); p.VEL = persist_at(cc.VEL, m0 * cc.nbuf * nd);
+  p.AD = persist_at(cc.AD, m0 * (size_t)cc.ad_stride);
+  p.LAM = persist_at(cc.LAM, m0 * nd * 2); p.W = persist_at(cc.W, m0 * 2 * nd); p.G = persist_at(cc.G, m0 * nd * 2);
+  p.g_r = persist_at(cc.g_r, m0 * ns * 2); p.g_phi = persist_at(cc.g_phi, m0 * ns);
+  p.blk_m = persist_at(cc.blk_m, m0 * nd); p.blk_c = persist_at(cc.blk_c, m0 * nd);
+  p.fn_g = persist_at(cc.fn_g, m0 * (size_t)cc.n_special * DFX_MAX_FNS * DFX_FN_PARAMS);
+  p.touch = cc.touch;
+  return p;
+}
 // one segment of the group's members: the first ring places poisoned, then the whole segment in one launch per `per_launch` members
 static void launch_segment_persist(dfx_handle* h, const DevCtx& c, hipStream_t st, int nm, int n_steps, bool reverse, double* ring = nullptr) {
   if (!ring) ring = h->d_ring.p;
   const int npb = h->persist_npb, per = reverse ? h->persist_adj_members : h->persist_fwd_members;
   const void* fn = reverse ? dfx_persist::adj_kernel(h->pl.model, h->pl.contact, npb) : dfx_persist::fwd_kernel(h->pl.model, h->pl.contact, npb);
-  PersistCoef pcf = persist_coef(h->pl.tab);
-  PersistAdjCoef pca;
-  memset(&pca, 0, sizeof(pca));
-  for (int i = 0; i < h->pl.tab.s && i < kPersistStages; ++i) {
-    const AdjCoef ac = adj_coef(h->pl.tab, i);
-    for (int jj = 0; jj <= kPersistStages; ++jj) { pca.col[i][jj] = ac.col[jj]; pca.cur[i][jj] = ac.cur[jj]; }
-    pca.c[i] = ac.c_i;
-  }
+  PersistFwdTab pcf = persist_fwd_tab(h->pl.tab);
+  PersistAdjTab pca = persist_adj_tab(h->pl.tab);
   const int n_chunks = (nm + per - 1) / per;      // members that do not fit at once: launches of balanced widths
   for (int k = 0, off = 0; k < n_chunks; off += chunk_members(nm, n_chunks, k++)) {
     const int cnt = chunk_members(nm, n_chunks, k);
@@ -520,12 +570,14 @@ static void launch_segment_persist(dfx_handle* h, const DevCtx& c, hipStream_t s
     dfx_persist::launch_ring_poison(st, ring, h->pl.batch, h->pl.n_blocks, cc.m0, cnt, kPos);
     h->launches++;
     PersistArgs pa;
-    pa.ring = ring; pa.give_up = persist_give_up_word(h); pa.n_steps = n_steps; pa.nm = cnt; pa.waves_per_member = h->persist_wpm; pa.spin_limit = persist_spin_limit(h); pa.xcd_wg = xcd_wg;
+    pa.give_up = persist_give_up_word(h); pa.n_steps = n_steps; pa.nm = cnt; pa.waves_per_member = h->persist_wpm; pa.spin_limit = persist_spin_limit(h); pa.xcd_wg = xcd_wg;
 #ifdef DFX_PERSIST_TIMING
     pa.dbg = ((reverse ? getenv("DFX_TIMING_REVERSE") != nullptr : getenv("DFX_TIMING_REVERSE") == nullptr) && grid <= 8192) ? persist_dbg_buffer() : nullptr;
 #endif
-    void* args_f[] = {&cc, &pcf, &pa};
-    void* args_r[] = {&cc, &pca, &pa};
+    pa.ring = ring + (size_t)cc.m0 * h->pl.n_blocks * kPos;       // (the loops count their members from the launch's first one, in the ring too)
+    PersistCtx pcx = persist_ctx(cc);
+    void* args_f[] = {&pcx, &pcf, &pa};
+    void* args_r[] = {&pcx, &pca, &pa};
     launch_persist(h, fn, st, reverse ? args_r : args_f, grid, per_cu * persist_wg_slots(fn));
   }
 }
@@ -598,13 +650,7 @@ bool persist_plan_adj_dense(dfx_handle* h, const DevCtx& c) {
 void launch_adj_dense_persist(dfx_handle* h, const DevCtx& c, hipStream_t st, int n_steps, DenseCtx dn) {
   const int npb = h->persist_npb, per = h->persist_adj_members, nm = h->pl.batch;
   const void* fn = dfx_persist::adj_dense_kernel(h->pl.model, h->pl.contact, npb);
-  PersistAdjCoef pca;
-  memset(&pca, 0, sizeof(pca));
-  for (int i = 0; i < h->pl.tab.s && i < kPersistStages; ++i) {
-    const AdjCoef ac = adj_coef(h->pl.tab, i);
-    for (int jj = 0; jj <= kPersistStages; ++jj) { pca.col[i][jj] = ac.col[jj]; pca.cur[i][jj] = ac.cur[jj]; }
-    pca.c[i] = ac.c_i;
-  }
+  PersistAdjTab pca = persist_adj_tab(h->pl.tab);
   const int n_chunks = (nm + per - 1) / per, even = (nm + n_chunks - 1) / n_chunks;
   for (int off = 0; off < nm; off += even) {
     const int cnt = std::min(even, nm - off);
@@ -616,11 +662,13 @@ void launch_adj_dense_persist(dfx_handle* h, const DevCtx& c, hipStream_t st, in
     dfx_persist::launch_ring_poison(st, h->d_ring.p, h->pl.batch, h->pl.n_blocks, cc.m0, cnt, kPos);
     h->launches++;
     PersistArgs pa;
-    pa.ring = h->d_ring.p; pa.give_up = persist_give_up_word(h); pa.n_steps = n_steps; pa.nm = cnt; pa.waves_per_member = h->persist_wpm; pa.spin_limit = persist_spin_limit(h); pa.xcd_wg = xcd_wg;
+    pa.ring = h->d_ring.p + (size_t)cc.m0 * h->pl.n_blocks * kPos;
+    pa.give_up = persist_give_up_word(h); pa.n_steps = n_steps; pa.nm = cnt; pa.waves_per_member = h->persist_wpm; pa.spin_limit = persist_spin_limit(h); pa.xcd_wg = xcd_wg;
 #ifdef DFX_PERSIST_TIMING
     pa.dbg = nullptr;
 #endif
-    void* args[] = {&cc, &pca, &pa, &dn};
+    PersistCtx pcx = persist_ctx(cc);
+    void* args[] = {&pcx, &pca, &pa, &dn};
     launch_persist(h, fn, st, args, grid, per_cu * persist_wg_slots(fn));
   }
 }
