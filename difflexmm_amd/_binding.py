@@ -67,7 +67,8 @@ COMM_EXPORTS = ["dfx_comm_unique_id", "dfx_comm_init", "dfx_comm_destroy", "dfx_
                 "dfx_gather_objectives", "dfx_reduce_grads", "dfx_comm_allreduce", "dfx_comm_barrier", "dfx_comm_last_error",
                 "dfx_mem_info", "dfx_device_synchronize", "dfx_kinetic_value_and_grad_device", "dfx_download", "dfx_forward_kinetic_value_and_grad",
                 "dfx_forward_tangent", "dfx_forward_tangent_dense", "dfx_dense_output_map", "dfx_forward_tangent_multi",
-                "dfx_forward_tangent_dense_multi", "dfx_rhs_jvp", "dfx_objective_value", "dfx_objective_value_and_grad"]
+                "dfx_forward_tangent_dense_multi", "dfx_rhs_jvp", "dfx_objective_value", "dfx_objective_value_and_grad",
+                "dfx_strain_objective_value", "dfx_strain_objective_value_and_grad"]
 EXPORTS = EXPORTS + COMM_EXPORTS
 
 
@@ -149,6 +150,10 @@ def declare(lib):
         lib.dfx_objective_value.argtypes = [H, C.c_int32, _dp, C.c_int32, _dp, _dp, C.c_int32, _dp]
         lib.dfx_objective_value_and_grad.argtypes = [H, C.c_int32, _dp, C.c_int32, _dp, _dp, C.c_int32, _dp, C.POINTER(dfx_grads),
                                                      C.POINTER(dfx_grads), C.c_int32, C.POINTER(dfx_stats)]
+    if hasattr(lib, "dfx_strain_objective_value_and_grad"):
+        lib.dfx_strain_objective_value.argtypes = [H, _dp, C.c_int32, _dp, _dp, _dp]
+        lib.dfx_strain_objective_value_and_grad.argtypes = [H, _dp, C.c_int32, _dp, _dp, _dp, C.POINTER(dfx_grads), C.POINTER(dfx_grads),
+                                                            C.c_int32, C.POINTER(dfx_stats)]
     if hasattr(lib, "dfx_comm_init"):
         lib.dfx_comm_unique_id.argtypes = [C.c_char_p]
         lib.dfx_comm_init.argtypes = [C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(H)]
@@ -754,6 +759,65 @@ class Engine:
         st = dfx_stats()
         self._check(self.lib.dfx_objective_value_and_grad(self._h, int(kind), _ptr(w), wpm, _ptr(tau), _ptr(lev), lpm, _ptr(obj), C.byref(want),
                                                           C.byref(views), int(bool(device)), C.byref(st)), "dfx_objective_value_and_grad")
+        if device:
+            return obj, {n: DeviceArray(self, C.cast(getattr(views, n), C.c_void_p).value, sh[n]) for n in names}, _stats(st)
+        out = {}
+        for n in names:
+            a = np.ctypeslib.as_array(getattr(views, n), shape=sh[n])
+            a.flags.writeable = False
+            out[n] = a
+        return obj, out, _stats(st)
+
+    # -- ligament strain-energy objective on the device-resident history ----------------------------------
+    @property
+    def has_strain_objective(self):
+        return hasattr(self.lib, "dfx_strain_objective_value_and_grad")
+
+    def _strain_objective_args(self, bond_weights, time_weights, parts):
+        """The array arguments of ``dfx_strain_objective_value[_and_grad]``: bond weights (n_bonds,) or (batch, n_bonds), time weights (T,)
+        or None, the four part coefficients (c_stretch, c_shear, c_bend, c_contact)."""
+        if not self.has_strain_objective:
+            raise NotImplementedError(f"strain-energy objective: the library {getattr(self.lib, '_name', self.lib)!r} has no "
+                                      "dfx_strain_objective_value_and_grad (a stale libdfx.so, or the CPU port of the oracle; build the HIP engine)")
+        B, nbd = self.batch, self.n_bonds
+        w = _f64(bond_weights)
+        if w.shape not in ((nbd,), (B, nbd)):
+            raise ValueError(f"bond_weights must be ({nbd},) or ({B}, {nbd}), got {w.shape}")
+        tau = None
+        if time_weights is not None:
+            tau = _f64(time_weights)
+            if self.n_timepoints is not None and tau.shape != (self.n_timepoints,):
+                raise ValueError(f"time_weights must be ({self.n_timepoints},), got {tau.shape}")
+        c = _f64(parts)
+        if c.shape != (4,):
+            raise ValueError(f"parts must be (c_stretch, c_shear, c_bend, c_contact), got shape {c.shape}")
+        return w, int(w.ndim == 2), tau, c
+
+    def strain_objective_value(self, bond_weights, time_weights=None, parts=(1.0, 1.0, 1.0, 0.0)):
+        """(batch,) weighted ligament strain energy (``dfx_strain_objective_value``) on the resident history of the last forward pass."""
+        w, wpm, tau, c = self._strain_objective_args(bond_weights, time_weights, parts)
+        obj = np.zeros(self.batch)
+        self._check(self.lib.dfx_strain_objective_value(self._h, _ptr(w), wpm, _ptr(tau), _ptr(c), _ptr(obj)), "dfx_strain_objective_value")
+        return obj
+
+    def strain_objective_value_and_grad(self, bond_weights, time_weights=None, parts=(1.0, 1.0, 1.0, 0.0), which=ALL_GRADS, device=False):
+        """Value (batch,) and the requested gradients of the weighted ligament strain energy in ONE call
+        (``dfx_strain_objective_value_and_grad``): the ligament forces are formed on the device as the cotangent of the reverse sweep, the
+        explicit node-vector / void-angle / per-ligament terms are added behind it.  Results as :meth:`objective_value_and_grad`."""
+        w, wpm, tau, c = self._strain_objective_args(bond_weights, time_weights, parts)
+        sh = self.shapes()
+        want, views = dfx_grads(), dfx_grads()
+        names = [n for n in which if not (n == "fn_params" and self.n_fns == 0) and not (n == "contact" and not self.contact)
+                 and not (n == "void_angle0" and self.contact != CONTACT_ANGLE)
+                 and not (n == "block_centroids" and self.contact != CONTACT_DISTANCE)]
+        flag = np.zeros(1)
+        for n in names:
+            setattr(want, n, _ptr(flag))
+        obj = np.zeros(self.batch)
+        st = dfx_stats()
+        self._check(self.lib.dfx_strain_objective_value_and_grad(self._h, _ptr(w), wpm, _ptr(tau), _ptr(c), _ptr(obj), C.byref(want),
+                                                                 C.byref(views), int(bool(device)), C.byref(st)),
+                    "dfx_strain_objective_value_and_grad")
         if device:
             return obj, {n: DeviceArray(self, C.cast(getattr(views, n), C.c_void_p).value, sh[n]) for n in names}, _stats(st)
         out = {}

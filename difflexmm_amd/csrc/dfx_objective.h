@@ -13,6 +13,20 @@
 //                         same bits
 //   k_objective_explicit  after the sweep: the direct dependence on the inertia (into blk_m) and, for the angular kind, on the block
 //                         centroids (into g_c), one lane per (member, listed block), output times in order
+//
+// The ligament strain-energy objective (dfx_strain_objective_value[_and_grad]) is a weighted sum over LIGAMENTS and output times,
+//   J_m = sum_k tau_k sum_bonds w_mb [ c_stretch E_stretch + c_shear E_shear + c_bend E_bend + c_contact E_contact ](bond; u_k, params_m)
+// The bond energy is linear in its three stiffnesses and the contact penalty in k_contact, so the weighted energy of a ligament is the plain
+// energy evaluated with (c_stretch k_stretch, c_shear k_shear, c_bend k_rot) and c_contact k_contact, times w tau: ONE evaluation of
+// bond_grad / contact_grad (dfx_physics.h) gives the value and every first derivative.  The host turns the bond weights into slot weights
+// (both end slots of a ligament carry its weight) and lists the blocks that own a weighted end; an item is one (output time k, listed
+// block j) pair of one member, its four slots on the four lanes of a DPP quad.
+//   k_strain_objective           every lane whose slot carries a weighted ligament evaluates its OWN side of it in gather form (as the forward
+//                                stage does: no atomics), the quad adds dE/d(x, y, theta) in the fixed order of quad_sum and lane 0 stores rows
+//                                0..2 of G[(k, m, b)]; a ligament's energy is counted on its end-0 lane; partials / k_objective_finish as above
+//   k_strain_objective_explicit  after the sweep: d J / d(own node vector) into g_r, the two void-angle terms into g_phi (phi1 on the end-0
+//                                slot, phi2 on the end-1 slot, as the reverse stage), and on end-0 slots d J / d(reference vector, stiffnesses,
+//                                contact constants) into g_b when the call collects them; one lane per (member, listed slot), output times in order
 #pragma once
 #include "dfx_kernels.h"
 
@@ -128,6 +142,125 @@ __global__ __launch_bounds__(64) void k_objective_explicit(DevCtx c, ObjArgs a) 
     double* gc = c.g_c + ((size_t)m * c.n_blocks + b) * 2;
     gc[0] += cx; gc[1] += cy;
   }
+}
+
+// ---- ligament strain energy ------------------------------------------------------------------------------------------------------
+constexpr int kObjStrain = 2;              // ObjJob::kind of a strain call (not a DFX_OBJ_* kind: the entries of its own set it)
+constexpr int kObjQuads = kObjThreads / 4;  // items per workgroup
+
+// ObjArgs of a strain call: blocks = listed blocks, w = SLOT weights (w_members * n_slots: both end slots of a ligament carry its weight),
+// lever = the four part coefficients (c_stretch, c_shear, c_bend, c_contact)
+struct StrainLig {
+  BondGrad<double> g;
+  ContactGrad<double> cg;       // zeros unless CONTACT == 1 and c_contact != 0
+  double sgn;
+  bool end0;
+};
+
+// one side of the ligament on `slot` at output time k of member m, stiffnesses scaled by the part coefficients; parameters from the
+// resident images as k_response reads them
+template <int MODEL, int CONTACT>
+__device__ __forceinline__ void strain_eval(const DevCtx& c, const MemberBases& B, const double* f, int slot, int info, const double* parts,
+                                            StrainLig& S) {
+  const int b = slot >> 2, ps = info >> 1, pb = ps >> 2;
+  BlockRec<double> o, p;
+  o.x = f[(size_t)b * 3]; o.y = f[(size_t)b * 3 + 1]; o.th = f[(size_t)b * 3 + 2];
+  p.x = f[(size_t)pb * 3]; p.y = f[(size_t)pb * 3 + 1]; p.th = f[(size_t)pb * 3 + 2];
+  fast_sincos(0.5 * o.th, &o.sh, &o.ch);
+  fast_sincos(0.5 * p.th, &p.sh, &p.ch);
+  const double2 ro = ldg<double2>(B.p_r, (u32)slot * 16), rp = ldg<double2>(B.p_r, (u32)ps * 16);
+  double lx, ly, l0, il0, ks, ksh, kr;
+  if (c.l_dict_on) {
+    const int li = B.p_lidx[slot];
+    lx = B.l_dict[li * 4]; ly = B.l_dict[li * 4 + 1]; l0 = B.l_dict[li * 4 + 2]; il0 = B.l_dict[li * 4 + 3];
+  } else {
+    lx = B.p_l[(size_t)slot * 2]; ly = B.p_l[(size_t)slot * 2 + 1]; l0 = sqrt(lx * lx + ly * ly); il0 = 1.0 / l0;
+  }
+  if (c.k_uniform) { ks = B.cst[3]; ksh = B.cst[4]; kr = B.cst[5]; }
+  else { ks = B.p_k[(size_t)slot * 4]; ksh = B.p_k[(size_t)slot * 4 + 1]; kr = B.p_k[(size_t)slot * 4 + 2]; }
+  S.sgn = (info & 1) ? 1.0 : -1.0;
+  S.end0 = !(info & 1);
+  bond_grad<MODEL, double>(o, p, ro.x, ro.y, rp.x, rp.y, lx, ly, l0, il0, parts[0] * ks, parts[1] * ksh, parts[2] * kr, S.sgn, S.g);
+  S.cg.dkap = S.cg.p1 = S.cg.p2 = S.cg.am = S.cg.ac = S.cg.kc = S.cg.e = 0.0;
+  if (CONTACT == 1 && parts[3] != 0.0) {
+    const double2 ph = ldg<double2>(B.p_phi, (u32)slot * 16);
+    contact_grad<double>(S.sgn * (o.th - p.th), ph.x, ph.y, B.cst[0], B.cst[1], parts[3] * B.cst[2], S.cg);
+  }
+}
+
+// grid (chunks of kObjQuads items, members): a wave never spans two members, the four slots of an item sit in one DPP quad
+template <int MODEL, int CONTACT>
+__global__ __launch_bounds__(kObjThreads) void k_strain_objective(DevCtx c, ObjArgs a, double* G, double* partial) {
+  const int m = blockIdx.y;
+  const long long total = (long long)c.n_timepoints * a.n_act;
+  const long long item = (long long)blockIdx.x * kObjQuads + (threadIdx.x >> 2);
+  const int kk = threadIdx.x & 3;
+  const bool valid = item < total;
+  double val = 0.0, fx = 0.0, fy = 0.0, fth = 0.0;
+  int k = 0, b = 0;
+  if (valid) {
+    k = (int)(item / a.n_act);
+    b = a.blocks[(int)(item % a.n_act)];
+    const int slot = b * 4 + kk;
+    const int info = c.slot_info[slot];
+    const double tw = (a.tau ? a.tau[k] : 1.0) * a.w[(size_t)m * a.w_stride + slot];
+    if (info >= 0 && tw != 0.0) {
+      const MemberBases B = member_bases(c, m);
+      const size_t nd = (size_t)c.n_blocks * 3;
+      StrainLig S;
+      strain_eval<MODEL, CONTACT>(c, B, a.fields + ((size_t)m * c.n_timepoints + k) * nd * 2, slot, info, a.lever, S);
+      fx = tw * S.g.fx; fy = tw * S.g.fy; fth = tw * (S.g.fth + S.sgn * S.cg.dkap);
+      if (S.end0) val = tw * (S.g.e + S.cg.e);
+    }
+  }
+  // every lane of the quad takes part (lanes without a weighted ligament, and the lanes of a padded item, add zeros)
+  fx = quad_sum(fx); fy = quad_sum(fy); fth = quad_sum(fth);
+  if (valid && G && kk == 0) {
+    double* g = G + ((size_t)k * c.batch + m) * ((size_t)c.n_blocks * 6) + (size_t)b * 6;
+    g[0] = fx; g[1] = fy; g[2] = fth;
+  }
+  __shared__ double red[kObjWaves];
+  val = obj_wave_sum(val);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = val;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = red[0];
+    for (int wv = 1; wv < kObjWaves; ++wv) s += red[wv];
+    partial[(size_t)m * gridDim.x + blockIdx.x] = s;
+  }
+}
+
+// grid (chunks of 64 listed slots, members); every accumulator entry touched belongs to one lane
+template <int MODEL, int CONTACT>
+__global__ __launch_bounds__(64) void k_strain_objective_explicit(DevCtx c, ObjArgs a) {
+  const int m = blockIdx.y;
+  const int idx = blockIdx.x * 64 + threadIdx.x;
+  if (idx >= a.n_act * 4) return;
+  const int slot = a.blocks[idx >> 2] * 4 + (idx & 3);
+  const int info = c.slot_info[slot];
+  const double w = a.w[(size_t)m * a.w_stride + slot];
+  if (info < 0 || w == 0.0) return;
+  const MemberBases B = member_bases(c, m);
+  const size_t nd = (size_t)c.n_blocks * 3;
+  const bool bonds = c.g_b && !(info & 1);
+  double rx = 0.0, ry = 0.0, phi = 0.0, q[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int k = 0; k < c.n_timepoints; ++k) {
+    const double tw = (a.tau ? a.tau[k] : 1.0) * w;
+    if (tw == 0.0) continue;
+    StrainLig S;
+    strain_eval<MODEL, CONTACT>(c, B, a.fields + ((size_t)m * c.n_timepoints + k) * nd * 2, slot, info, a.lever, S);
+    rx += tw * S.g.rx; ry += tw * S.g.ry;
+    phi += tw * (S.end0 ? S.cg.p1 : S.cg.p2);
+    if (bonds) {
+      q[0] += tw * S.g.lx; q[1] += tw * S.g.ly;
+      q[2] += tw * (a.lever[0] * S.g.ks); q[3] += tw * (a.lever[1] * S.g.ksh); q[4] += tw * (a.lever[2] * S.g.kr);
+      q[5] += tw * S.cg.am; q[6] += tw * S.cg.ac; q[7] += tw * (a.lever[3] * S.cg.kc);
+    }
+  }
+  const size_t ms = (size_t)m * c.n_slots + slot;
+  c.g_r[ms * 2] += rx; c.g_r[ms * 2 + 1] += ry;
+  if (CONTACT == 1 && phi != 0.0) { c.g_phi[ms] += phi; c.touch[0] = 1; }
+  if (bonds) for (int i = 0; i < 8; ++i) c.g_b[ms * 8 + i] += q[i];
 }
 
 }  // namespace

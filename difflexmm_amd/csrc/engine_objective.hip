@@ -1,6 +1,8 @@
 // engine_objective.hip -- libdfx host side: weighted kinetic-energy and angular-momentum objectives evaluated and differentiated on the
 // device-resident history (dfx_objective_value, dfx_objective_value_and_grad).  "Fill the cotangent buffer G, reduce the value" before the
 // reverse sweep, "add the explicit d objective / d parameters" after it: the sweep itself is run_adjoint, unchanged.
+// The ligament strain-energy objective (dfx_strain_objective_value[_and_grad]) takes the same route with kernels of its own: its cotangent
+// on the fields is the weighted ligament force, its explicit terms reach node vectors, void angles and the per-ligament parameters.
 // (shared declarations in dfx_engine.h, the kernels in dfx_objective.h)
 #include "dfx_engine.h"
 #include "dfx_objective.h"
@@ -89,11 +91,114 @@ int launch_objective(dfx_handle* h, const ObjJob& j, double* G, double* objectiv
   return 0;
 }
 
+// ---- ligament strain energy: bond weights -> slot weights (both end slots of a ligament carry its weight), listed blocks = the blocks that
+// own a weighted end; the part coefficients travel in the lever buffer
+int prepare_strain(dfx_handle* h, const char* who, const double* bw, int32_t w_per_member, const double* tau, const double* parts, ObjHost& out) {
+  const Plan& pl = h->pl;
+  const size_t B = pl.batch, nb = pl.n_blocks, NS = pl.n_slots, nbd = pl.n_bonds;
+  const int Tn = (int)h->ts.size();
+  if (!bw) { h->err = std::string(who) + ": bond_weights is NULL"; return 1; }
+  if (!parts) { h->err = std::string(who) + ": parts4 is NULL"; return 1; }
+  if (pl.n_ovf) {
+    h->err = std::string(who) + ": nodes with more than one ligament (a general bond list with extra ligaments) are not supported by the strain-energy objective";
+    return 1;
+  }
+  const size_t wm = w_per_member ? B : 1;
+  for (size_t i = 0; i < wm * nbd; ++i)
+    if (!std::isfinite(bw[i])) { h->err = std::string(who) + ": non-finite bond weight"; return 1; }
+  for (int k = 0; tau && k < Tn; ++k)
+    if (!std::isfinite(tau[k])) { h->err = std::string(who) + ": non-finite time weight"; return 1; }
+  for (int i = 0; i < 4; ++i)
+    if (!std::isfinite(parts[i])) { h->err = std::string(who) + ": non-finite part coefficient"; return 1; }
+  if (parts[3] != 0.0 && pl.contact != DFX_CONTACT_ANGLE) {
+    h->err = std::string(who) + ": c_contact != 0 needs a lattice with the angle contact (the distance-based contact energy is not part of this objective)";
+    return 1;
+  }
+  std::vector<double> sw(wm * NS, 0.0);
+  std::vector<char> listed(nb, 0);
+  for (size_t sl = 0; sl < NS; ++sl) {
+    if (pl.slot_info[sl] < 0) continue;
+    const size_t bond = (size_t)pl.slot_bond[sl];
+    for (size_t m = 0; m < wm; ++m) {
+      const double v = bw[m * nbd + bond];
+      sw[m * NS + sl] = v;
+      if (v != 0.0) listed[sl >> 2] = 1;
+    }
+  }
+  out.blocks.clear();
+  for (size_t b = 0; b < nb; ++b) if (listed[b]) out.blocks.push_back((int32_t)b);
+  out.job.kind = kObjStrain;
+  out.job.n_act = (int)out.blocks.size();
+  out.job.w_stride = w_per_member ? (int)NS : 0;
+  out.job.lever_stride = 0;
+  out.job.has_tau = tau != nullptr;
+  HIP_OK(h->d_obj_blocks.ensure(std::max<size_t>(1, out.blocks.size())));
+  HIP_OK(h->d_obj_w.ensure(sw.size()));
+  HIP_OK(h->d_obj_lever.ensure(4));
+  HIP_OK(h->d_obj.ensure(B));
+  if (!out.blocks.empty())
+    HIP_OK(hipMemcpyAsync(h->d_obj_blocks.p, out.blocks.data(), sizeof(int32_t) * out.blocks.size(), hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipMemcpyAsync(h->d_obj_w.p, sw.data(), sizeof(double) * sw.size(), hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipMemcpyAsync(h->d_obj_lever.p, parts, sizeof(double) * 4, hipMemcpyHostToDevice, h->stream));
+  if (tau) {
+    HIP_OK(h->d_obj_tau.ensure(Tn));
+    HIP_OK(hipMemcpyAsync(h->d_obj_tau.p, tau, sizeof(double) * Tn, hipMemcpyHostToDevice, h->stream));
+  }
+  HIP_OK(hipStreamSynchronize(h->stream));       // the slot weights are a local of this function
+  return 0;
+}
+
+ObjArgs strain_args(const dfx_handle* h, const ObjJob& j) {
+  ObjArgs a;
+  a.fields = h->d_fields.p; a.blocks = h->d_obj_blocks.p; a.w = h->d_obj_w.p;
+  a.tau = j.has_tau ? h->d_obj_tau.p : nullptr;
+  a.lever = h->d_obj_lever.p;
+  a.n_act = j.n_act; a.w_stride = j.w_stride; a.lever_stride = 0;
+  return a;
+}
+
+// the build of a strain kernel for the handle's bond model; the angle contact only where the lattice has it (c_contact != 0 is refused elsewhere)
+#define DFX_STRAIN_LAUNCH(KERNEL, GRID, BLOCK, ...)                                                                               \
+  do {                                                                                                                             \
+    const bool ang_ = h->pl.contact == DFX_CONTACT_ANGLE;                                                                          \
+    switch (h->pl.model) {                                                                                                         \
+      case kNonlinear: if (ang_) hipLaunchKernelGGL((KERNEL<kNonlinear, 1>), GRID, BLOCK, 0, h->stream, __VA_ARGS__);              \
+        else hipLaunchKernelGGL((KERNEL<kNonlinear, 0>), GRID, BLOCK, 0, h->stream, __VA_ARGS__); break;                           \
+      case kLinearized: if (ang_) hipLaunchKernelGGL((KERNEL<kLinearized, 1>), GRID, BLOCK, 0, h->stream, __VA_ARGS__);            \
+        else hipLaunchKernelGGL((KERNEL<kLinearized, 0>), GRID, BLOCK, 0, h->stream, __VA_ARGS__); break;                          \
+      case kSimpleSpring: if (ang_) hipLaunchKernelGGL((KERNEL<kSimpleSpring, 1>), GRID, BLOCK, 0, h->stream, __VA_ARGS__);        \
+        else hipLaunchKernelGGL((KERNEL<kSimpleSpring, 0>), GRID, BLOCK, 0, h->stream, __VA_ARGS__); break;                        \
+      default: if (ang_) hipLaunchKernelGGL((KERNEL<kStretchTorsion, 1>), GRID, BLOCK, 0, h->stream, __VA_ARGS__);                 \
+        else hipLaunchKernelGGL((KERNEL<kStretchTorsion, 0>), GRID, BLOCK, 0, h->stream, __VA_ARGS__); break;                      \
+    }                                                                                                                              \
+  } while (0)
+
+// ligament forces into G (may be null: value only), the value into d_obj and, when given, into pinned host memory
+int launch_strain(dfx_handle* h, const ObjJob& j, double* G, double* objective_host) {
+  const size_t B = h->pl.batch;
+  const long long items = (long long)h->ts.size() * j.n_act;
+  const unsigned chunks = (unsigned)std::max<long long>(1, (items + kObjQuads - 1) / kObjQuads);
+  HIP_OK(h->d_obj_part.ensure(B * chunks));
+  DevCtx c = make_ctx(h);
+  const ObjArgs a = strain_args(h, j);
+  const dim3 grid(chunks, (unsigned)B);
+  DFX_STRAIN_LAUNCH(k_strain_objective, grid, dim3(kObjThreads), c, a, G, h->d_obj_part.p);
+  hipLaunchKernelGGL(k_objective_finish, dim3((unsigned)B), dim3(kObjThreads), 0, h->stream, (const double*)h->d_obj_part.p, (int)chunks, h->d_obj.p,
+                     objective_host);
+  return 0;
+}
+
 }  // namespace
 
 void launch_objective_explicit(dfx_handle* h, const DevCtx& c) {
   const ObjJob& j = *h->obj_job;
   if (j.n_act == 0) return;
+  if (j.kind == kObjStrain) {
+    const ObjArgs a = strain_args(h, j);
+    const dim3 grid((unsigned)((j.n_act * 4 + 63) / 64), (unsigned)h->pl.batch);
+    DFX_STRAIN_LAUNCH(k_strain_objective_explicit, grid, dim3(64), c, a);
+    return;
+  }
   const ObjArgs a = obj_args(h, j);
   const dim3 grid((unsigned)((j.n_act + 63) / 64), (unsigned)h->pl.batch);
   if (j.kind == DFX_OBJ_KINETIC) hipLaunchKernelGGL(k_objective_explicit<DFX_OBJ_KINETIC>, grid, dim3(64), 0, h->stream, c, a);
@@ -147,6 +252,50 @@ int dfx_objective_value_and_grad(dfx_handle* h, int32_t kind, const double* bloc
   // one launch: accumulators and cotangents cleared, cursors at the last segment (as the kinetic entries)
   if (zero_grad_accumulators(h, h->d_G.p, B * Tn * nb * 6, (int)h->segs.size())) return 2;
   if (int rc = launch_objective(h, oh.job, h->d_G.p, objective ? reinterpret_cast<double*>(h->obj_stage.p) : nullptr)) return rc;
+  if (int rc = run_adjoint(h, want, nullptr, views, stats, false, 0, true)) return rc;
+  if (objective) memcpy(objective, h->obj_stage.p, sizeof(double) * B);
+  return 0;
+}
+
+int dfx_strain_objective_value(dfx_handle* h, const double* bond_weights, int32_t weights_per_member, const double* time_weights,
+                               const double* parts4, double* objective) {
+  HIP_OK(hipSetDevice(h->device));
+  if (!h->have_fields || !h->have_params) { h->err = "strain_objective_value: run forward first"; return 1; }
+  if (!objective) { h->err = "strain_objective_value: objective is NULL"; return 1; }
+  ObjHost oh;
+  if (int rc = prepare_strain(h, "strain_objective_value", bond_weights, weights_per_member, time_weights, parts4, oh)) return rc;
+  if (int rc = launch_strain(h, oh.job, nullptr, nullptr)) return rc;
+  HIP_OK(hipMemcpyAsync(objective, h->d_obj.p, sizeof(double) * h->pl.batch, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int dfx_strain_objective_value_and_grad(dfx_handle* h, const double* bond_weights, int32_t weights_per_member, const double* time_weights,
+                                        const double* parts4, double* objective, const dfx_grads* want, dfx_grads* views, int32_t device_views,
+                                        dfx_stats* stats) {
+  HIP_OK(hipSetDevice(h->device));
+  if (!h->have_traj || !h->have_fields) { h->err = "strain_objective_value_and_grad: run forward with keep_trajectory=1 first"; return 1; }
+  if (h->ck->writer != h) { h->err = std::string("strain_objective_value_and_grad: ") + kStaleCheckpoint; return 1; }
+  const Plan& pl = h->pl;
+  const size_t B = pl.batch, nb = pl.n_blocks;
+  const int Tn = (int)h->ts.size();
+  ObjHost oh;
+  if (int rc = prepare_strain(h, "strain_objective_value_and_grad", bond_weights, weights_per_member, time_weights, parts4, oh)) return rc;
+  if (ensure_adjoint_buffers(h)) return 2;
+  HIP_OK(h->d_G.ensure(B * Tn * nb * 6));
+  if (objective) HIP_OK(h->obj_stage.ensure(sizeof(double) * B));
+  // as dfx_objective_value_and_grad: what the sweep consults on the handle for this call is taken back on every way out
+  struct Scope {
+    dfx_handle* h;
+    ~Scope() { h->obj_job = nullptr; h->obj_centroids = false; h->device_views = false; }
+  } scope{h};
+  h->obj_centroids = false;
+  h->obj_job = &oh.job;
+  h->device_views = device_views != 0;
+  set_grad_wishes(h, want);
+  if (zero_grad_accumulators(h, h->d_G.p, B * Tn * nb * 6, (int)h->segs.size())) return 2;
+  if (int rc = launch_strain(h, oh.job, h->d_G.p, objective ? reinterpret_cast<double*>(h->obj_stage.p) : nullptr)) return rc;
   if (int rc = run_adjoint(h, want, nullptr, views, stats, false, 0, true)) return rc;
   if (objective) memcpy(objective, h->obj_stage.p, sizeof(double) * B);
   return 0;

@@ -792,6 +792,24 @@ class DynamicSolver:
         self.adjoint_stats = stats
         return obj, grads
 
+    def strain_objective_value(self, spec):
+        """(batch,) value of a weighted ligament strain-energy objective (``objective.StrainObjectiveSpec``) on the device-resident history
+        of the last solve (any forward pass: no kept trajectory needed)."""
+        return self.engine.strain_objective_value(spec.bond_weights, spec.time_weights, spec.parts)
+
+    def strain_objective_value_and_raw(self, spec, which=("centroid_node_vectors", "void_angle0", "inertia"), device=False):
+        """The weighted ligament strain energy (``objective.StrainObjectiveSpec``) of the last kept solve, evaluated and differentiated on
+        the device beside :meth:`objective_value_and_raw`: the history stays in HBM, the ligament forces are formed there as the cotangent
+        of the reverse sweep, and the explicit node-vector, void-angle and (when ``which`` names ``reference_vector`` / ``k_bond`` /
+        ``contact``) per-ligament terms are already in the raw gradients returned.  As with :meth:`vjp_raw`, ``fn_params`` holds what the
+        sweep accumulates: the direct dependence of a prescribed output DOF on its drive is not in it."""
+        which = tuple(w for w in which if not (w == "void_angle0" and self.spec.contact != _b.CONTACT_ANGLE))
+        if self.spec.contact == _b.CONTACT_DISTANCE and "block_centroids" not in which:
+            which = which + ("block_centroids",)
+        obj, grads, stats = self.engine.strain_objective_value_and_grad(spec.bond_weights, spec.time_weights, spec.parts, which=which, device=device)
+        self.adjoint_stats = stats
+        return obj, grads
+
     @staticmethod
     def _bond_params_bar(bp, kb, refv_bar, like):
         """Gradient tree with the structure of the bond parameters that were passed in (LigamentParams /

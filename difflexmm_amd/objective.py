@@ -1,6 +1,7 @@
 """Cross-correlation measures between recorded signals -- the names of ``difflexmm/objective.py`` (post-processing of space-time
 records in the notebooks; host code, SciPy where the reference uses ``jax.scipy.signal``) -- and the weighted objectives the engine
-evaluates and differentiates on the device-resident history (``ObjectiveSpec``; ``include/dfx.h``: ``dfx_objective_value_and_grad``)."""
+evaluates and differentiates on the device-resident history (``ObjectiveSpec``; ``include/dfx.h``: ``dfx_objective_value_and_grad``;
+``StrainObjectiveSpec``: ``dfx_strain_objective_value_and_grad``)."""
 from typing import Any, NamedTuple
 
 import numpy as np
@@ -115,3 +116,93 @@ def host_value_and_cotangent(spec, fields, inertia):
     if single:
         return float(value[0]), fb[0], m_bar[0], cen_bar[0]
     return value, fb, m_bar, cen_bar
+
+
+# ---- ligament strain energy on the device-resident history ---------------------------------------------------------------------------
+class StrainObjectiveSpec:
+    """The elastic energy stored in weighted ligaments (``include/dfx.h``: ``dfx_strain_objective_value[_and_grad]``):
+
+        J_m = sum_k tau_k sum_bonds w_mb [ c_stretch E_stretch + c_shear E_shear + c_bend E_bend + c_contact E_contact ](bond; u_k, params_m)
+
+    ``bond_weights`` (n_bonds,) or (batch, n_bonds), in the order of the problem's bond list; ``time_weights`` (T,) or None = all ones;
+    ``parts`` = (c_stretch, c_shear, c_bend, c_contact).  The arrays are converted and their shapes checked here (``ValueError``); their
+    lengths against a solve are checked where the spec is used."""
+    __slots__ = ("bond_weights", "time_weights", "parts")
+
+    def __init__(self, bond_weights, time_weights=None, parts=(1.0, 1.0, 1.0, 0.0)):
+        w = np.array(bond_weights, dtype=float)
+        if w.ndim not in (1, 2) or w.shape[-1] == 0:
+            raise ValueError(f"bond_weights must be (n_bonds,) or (batch, n_bonds), got {w.shape}")
+        tau = None
+        if time_weights is not None:
+            tau = np.array(time_weights, dtype=float)
+            if tau.ndim != 1:
+                raise ValueError(f"time_weights must be (T,), got {tau.shape}")
+        c = np.array(parts, dtype=float)
+        if c.shape != (4,) or not np.isfinite(c).all():
+            raise ValueError(f"parts must be four finite numbers (c_stretch, c_shear, c_bend, c_contact), got {parts!r}")
+        self.bond_weights, self.time_weights, self.parts = w, tau, tuple(float(x) for x in c)
+
+    def __repr__(self):
+        return f"StrainObjectiveSpec(bond_weights={self.bond_weights.shape}, time_weights={self.time_weights!r}, parts={self.parts})"
+
+
+def bond_weights_from_blocks(bond_connectivity, n_nodes_per_block, target_blocks_list, weights, ends="both"):
+    """Weights of target regions -> weights of bonds.  A bond belongs to a target when both (``ends="both"``) or any (``ends="any"``) of its
+    end blocks are in it; ``bond_connectivity`` (n_bonds, 2) node ids, node n on block n // n_nodes_per_block.  ``weights``: one row
+    (n_targets,) -> (n_bonds,), or one row per member (batch, n_targets) -> (batch, n_bonds).  Overlapping targets add, as in
+    ``block_weights_from_targets``."""
+    if ends not in ("both", "any"):
+        raise ValueError(f"ends must be 'both' or 'any', got {ends!r}")
+    bonds = np.asarray(bond_connectivity, dtype=np.int64).reshape(-1, 2)
+    blocks = bonds // int(n_nodes_per_block)
+    n_blocks = int(blocks.max()) + 1 if blocks.size else 0
+    w = np.asarray(weights, dtype=float)
+    if w.shape[-1:] != (len(target_blocks_list),) or w.ndim not in (1, 2):
+        raise ValueError(f"weights must be ({len(target_blocks_list)},) or (batch, {len(target_blocks_list)}), got {w.shape}")
+    out = np.zeros(w.shape[:-1] + (len(bonds),))
+    for i, tb in enumerate(target_blocks_list):
+        tb = np.asarray(tb, dtype=np.int64).reshape(-1)
+        if tb.size and (tb.min() < 0 or tb.max() >= n_blocks):
+            raise ValueError(f"target {i}: block out of range [0, {n_blocks})")
+        inside = np.isin(blocks, tb)
+        member = inside.all(1) if ends == "both" else inside.any(1)
+        out[..., member] += w[..., i:i + 1]
+    return out
+
+
+def host_strain_value(spec, fields, centroid_node_vectors, bond_connectivity, reference_bond_vectors, k_stretch, k_shear, k_rot):
+    """NumPy value of the three ligament parts of a ``StrainObjectiveSpec`` for nonlinear ligaments, from the strains of
+    ``energy.compute_ligament_strains_history`` as ``compute_response_data`` forms them: 1/2 k (strain |l0|)^2 for the axial and shear
+    strain, 1/2 k_rot (theta_2 - theta_1)^2.  ``fields`` (batch, T, 2, n_blocks, 3) or (T, 2, n_blocks, 3); ``centroid_node_vectors`` with
+    or without the member axis; stiffnesses scalars or (n_bonds,).  The contact part has no host formula here: ``parts[3]`` must be 0.
+    Returns (batch,) or a float."""
+    from .energy import compute_ligament_strains_history
+    f = np.asarray(fields, dtype=float)
+    single = f.ndim == 4
+    if single:
+        f = f[None]
+    B, T = f.shape[:2]
+    c = np.asarray(spec.parts, dtype=float)
+    if c.shape != (4,):
+        raise ValueError(f"parts must be (c_stretch, c_shear, c_bend, c_contact), got {spec.parts!r}")
+    if c[3] != 0.0:
+        raise ValueError("host_strain_value: the contact part is evaluated on the device only (parts[3] must be 0)")
+    refv = np.asarray(reference_bond_vectors, dtype=float)
+    nbd = len(np.asarray(bond_connectivity))
+    w = np.asarray(spec.bond_weights, dtype=float)
+    if w.shape not in ((nbd,), (B, nbd)):
+        raise ValueError(f"bond_weights must be ({nbd},) or ({B}, {nbd}), got {w.shape}")
+    w = np.broadcast_to(w, (B, nbd))
+    tau = np.ones(T) if spec.time_weights is None else np.asarray(spec.time_weights, dtype=float)
+    if tau.shape != (T,):
+        raise ValueError(f"time_weights must be ({T},), got {tau.shape}")
+    cnv = np.asarray(centroid_node_vectors, dtype=float)
+    cnv = np.broadcast_to(cnv, (B,) + cnv.shape[-3:])
+    l0 = np.linalg.norm(np.broadcast_to(refv, (nbd, 2)), axis=-1)
+    out = np.zeros(B)
+    for m in range(B):
+        axial, shear, bending = compute_ligament_strains_history(f[m, :, 0], cnv[m], bond_connectivity, refv)
+        e = c[0] * 0.5 * k_stretch * (axial * l0) ** 2 + c[1] * 0.5 * k_shear * (shear * l0) ** 2 + c[2] * 0.5 * k_rot * bending ** 2
+        out[m] = tau @ (e @ w[m])
+    return float(out[0]) if single else out

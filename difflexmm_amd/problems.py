@@ -984,6 +984,56 @@ class TargetAngularMomentum:
         return val, design_gradients(fw, [design], raw)[0]
 
 
+class TargetStrainEnergy:
+    """objective(design) = weights @ [elastic energy stored in the ligaments of every target region, summed over the output times]: the
+    quantity ``compute_response_data`` reports as strain_energy_{stretch,shear,bending} (plus, with ``parts[3] != 0``, the angle-contact
+    penalty), as an objective -- minimised to protect a region, maximised to concentrate deformation in it.  A ligament belongs to a region
+    when both (``ends="both"``) or any (``ends="any"``) of its end blocks do; ``parts`` = (c_stretch, c_shear, c_bend, c_contact) weighs
+    the four parts of every ligament's energy.
+    Device only: value and gradient are ``dfx_strain_objective_value[_and_grad]`` (``objective.StrainObjectiveSpec``) -- the cotangent of
+    this objective is the ligament force, which the engine alone computes.  There is NO host gradient path; the CPU port of the oracle
+    cannot serve this class.  A list of designs runs as one ensemble (``run_ensemble_optimization`` accepts the class)."""
+
+    def __init__(self, forward, target_sizes, target_shifts, weights, parts=(1.0, 1.0, 1.0, 0.0), ends="both"):
+        from .objective import StrainObjectiveSpec, bond_weights_from_blocks
+        self.forward = forward
+        if not getattr(forward, "is_setup", False):
+            forward.setup()
+        pick = kagome_target_blocks if isinstance(forward.geometry, KagomeGeometry) else quads_target_blocks
+        self.target_sizes, self.target_shifts = tuple(map(tuple, target_sizes)), tuple(map(tuple, target_shifts))
+        if len(self.target_sizes) != len(self.target_shifts) or len(weights) != len(self.target_sizes):
+            raise ValueError("target_sizes, target_shifts and weights must have the same length")
+        self.weights, self.ends = np.asarray(weights, dtype=float), ends
+        self.target_blocks_list = [pick(forward.geometry, ts, sh) for ts, sh in zip(self.target_sizes, self.target_shifts)]
+        self.bond_weights = bond_weights_from_blocks(forward.bond_connectivity, forward.geometry.n_npb, self.target_blocks_list, self.weights,
+                                                     ends=ends)
+        self.spec = StrainObjectiveSpec(self.bond_weights, None, parts)
+        self.parts = self.spec.parts
+
+    def value(self, design):
+        """One design -> float, a list of ``forward.batch`` designs (or a multiple of it) -> (n,) array; no trajectory is kept."""
+        fw = self.forward
+        parts = _in_batches(fw, design, self.value)
+        if parts is not None:
+            return np.concatenate(parts)
+        fw.solve(design, keep_trajectory=False, want_fields=False)
+        obj = np.asarray(fw.solve_dynamics.strain_objective_value(self.spec), dtype=float)
+        return obj if isinstance(design, list) else float(obj[0])
+
+    def value_and_grad(self, design):
+        """Return shapes as ``TargetKineticEnergy.value_and_grad``; only the parameter groups a design reaches are differentiated."""
+        fw = self.forward
+        parts = _in_batches(fw, design, self.value_and_grad)
+        if parts is not None:
+            return np.concatenate([p[0] for p in parts]), [g for p in parts for g in p[1]]
+        many = isinstance(design, list)
+        fw.solve(design, keep_trajectory=True, want_fields=False)
+        obj, raw = fw.solve_dynamics.strain_objective_value_and_raw(self.spec)
+        grads = design_gradients(fw, design if many else [design], raw)
+        obj = np.asarray(obj, dtype=float)
+        return (obj, grads) if many else (float(obj[0]), grads[0])
+
+
 class MultiInputTargetKineticEnergy:
     """weights @ [target kinetic energy of every forward problem], all sharing one design
     (problems/quads_focusing_multi_input.py:43-86).  The forward problems differ in their boundary conditions

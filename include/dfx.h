@@ -349,6 +349,32 @@ int dfx_objective_value_and_grad(dfx_handle* h, int32_t kind, const double* bloc
                                  const double* time_weights, const double* lever0, int32_t lever_per_member,
                                  double* objective, const dfx_grads* want, dfx_grads* views, int32_t device_views, dfx_stats* stats);
 
+/* The elastic energy stored in the ligaments as an objective on the device-resident history (HIP library only): for member m, with bond
+ * weights w_mb, output-time weights tau_k and four part coefficients c = parts4 = (c_stretch, c_shear, c_bend, c_contact),
+ *   J_m = sum_k tau_k sum_bonds w_mb [ c_stretch E_stretch + c_shear E_shear + c_bend E_bend + c_contact E_contact ](bond; u_k, params_m)
+ * E_stretch, E_shear, E_bend: the three terms of the handle's bond model (for nonlinear ligaments what dfx_response_data writes; a part a
+ * model does not have contributes nothing), E_contact: the angle-contact penalty of the bond's two void angles, u_k the displacement part
+ * of the history.  The energies are linear in the stiffnesses, so J is the plain energy with (c_stretch k_stretch, c_shear k_shear,
+ * c_bend k_rot) and c_contact k_contact: one evaluation gives the value and every first derivative.
+ * bond_weights: (batch, n_bonds) when weights_per_member != 0, else (n_bonds,), in the order of the problem's bond list; bonds whose weight
+ * is zero in every member cost nothing.  time_weights: NULL = all ones, else EXACTLY T doubles.  objective: (batch,), may be NULL in the
+ * gradient call.  dfx_strain_objective_value works after any forward pass; dfx_strain_objective_value_and_grad needs the kept trajectory
+ * and equals dfx_adjoint on the fields_bar of this formula (the weighted ligament force on the position rows; velocity rows zero) PLUS the
+ * explicit terms: d J / d centroid_node_vectors, d J / d void_angle0 and -- when want asks for them -- d J / d(reference_vector, k_bond,
+ * contact).  As with dfx_adjoint, the direct dependence of a PRESCRIBED output DOF on the parameters of its time function is not part of
+ * fn_params (the caller adds it from fields_bar; solve_dynamics.vjp does).  want / views / device_views / stats, the sweep forms, the
+ * two-level fixed-order sum of the value and the refusals of a missing trajectory or a stale shared checkpoint are those of
+ * dfx_objective_value_and_grad; without reference_vector / k_bond / contact in `want` the reverse sweep runs the same builds as for the
+ * kinetic kinds.
+ * Return 1 (dfx_last_error says why): a NULL bond_weights / parts4 (/ objective in the value call), a non-finite weight or part,
+ * c_contact != 0 on a lattice without the angle contact (the distance-based contact energy is not part of this objective), nodes with
+ * more than one ligament. */
+int dfx_strain_objective_value(dfx_handle* h, const double* bond_weights, int32_t weights_per_member, const double* time_weights,
+                               const double* parts4, double* objective);
+int dfx_strain_objective_value_and_grad(dfx_handle* h, const double* bond_weights, int32_t weights_per_member, const double* time_weights,
+                                        const double* parts4, double* objective, const dfx_grads* want, dfx_grads* views,
+                                        int32_t device_views, dfx_stats* stats);
+
 /* Post-processing of the last forward solve on its device-resident history (problems/quads_focusing.py:319-372 with
  * energy.py:522-534): strain energies of every ligament 1/2 k (strain |l0|)^2 for the axial, shear and bending strain of
  * the NONLINEAR kinematics, (batch, T, n_bonds) each, and the kinetic energy of every block sum_d m_d v_d^2 / 2,
