@@ -21,6 +21,7 @@
 #include <string>
 #include <vector>
 
+#include "dfx_builds.h"
 #include "dfx_kernels.h"
 #include "dfx_persist_api.h"
 #ifdef DFX_EXPERIMENTAL
@@ -241,8 +242,7 @@ void setup_lig(dfx_handle* h);
 int lig_pack(dfx_handle* h);
 bool lig_fwd_ok(const dfx_handle* h, const DevCtx& c, int mode);
 bool lig_adj_ok(const dfx_handle* h, const DevCtx& c, int wbuf, int local_only);
-bool pack3(const dfx_handle* h);
-int kernel_build_code(const dfx_handle* h, const DevCtx& c, bool tile);
+int kernel_build_code(const dfx_handle* h, const DevCtx& c, bool tile, bool reverse);
 void launch_fwd(dfx_handle* h, const DevCtx& c, hipStream_t st, dim3 grid, int i, int j, int in_buf, int out_buf, int y_buf, int mode);
 void launch_fwd(dfx_handle* h, const DevCtx& c, int i, int j, int in_buf, int out_buf, int y_buf, int mode);
 void launch_adj(dfx_handle* h, const DevCtx& c, hipStream_t st, dim3 grid, int i, int j, int in_buf, int wbuf, int local_only);

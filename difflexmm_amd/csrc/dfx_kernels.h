@@ -709,7 +709,7 @@ __global__ __launch_bounds__(kThreads) DFX_FWD_OCC void k_fwd_stage(DevCtx c_arg
   static_assert(NPB == 4 || CONTACT != 2, "distance-based contact uses the quad mapping");
   const int i = ISTAGE >= 0 ? ISTAGE : i_arg;
   // The per-stage builds are also the builds of the COMMON parameter shape, which the launch code checks before it takes them
-  // (hot_shape in dfx_engine.hip): uniform stiffnesses and damping, the reference-vector dictionary in LDS, equal steps, records read
+  // (stage_build_ok in dfx_builds.h): uniform stiffnesses and damping, the reference-vector dictionary in LDS, equal steps, records read
   // from and written to the trajectory checkpoint.  What is a run-time flag in the generic builds is a constant here.
   DevCtx c = c_arg;
   if (ISTAGE >= 0) {

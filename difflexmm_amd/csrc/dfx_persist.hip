@@ -5,32 +5,21 @@
 #include <cstdint>
 #include <cstring>
 
+#include "dfx_dispatch.h"
 #include "dfx_kernels.h"
 #include "dfx_persist.h"
 
 namespace dfx_persist {
 
-template <int MODEL, int CONTACT>
-static const void* fwd_kernel_t(int npb) {
-  if (npb == 3) return (const void*)k_fwd_persist<MODEL, CONTACT, 3>;
-  return (const void*)k_fwd_persist<MODEL, CONTACT, 4>;
-}
 const void* fwd_kernel(int model, int contact, int npb) {
-  if (contact != 0 && contact != 1) return nullptr;
-  if (model == kNonlinear) return contact ? fwd_kernel_t<kNonlinear, 1>(npb) : fwd_kernel_t<kNonlinear, 0>(npb);
-  if (model == kLinearized) return contact ? fwd_kernel_t<kLinearized, 1>(npb) : fwd_kernel_t<kLinearized, 0>(npb);
-  return nullptr;
-}
-template <int MODEL, int CONTACT>
-static const void* adj_kernel_t(int npb) {
-  if (npb == 3) return (const void*)k_adj_persist<MODEL, CONTACT, 3>;
-  return (const void*)k_adj_persist<MODEL, CONTACT, 4>;
+  const void* fn = nullptr;
+  with_physics<loop_physics>(model, contact, [&](auto M, auto C) { fn = npb == 3 ? (const void*)k_fwd_persist<M(), C(), 3> : (const void*)k_fwd_persist<M(), C(), 4>; });
+  return fn;
 }
 const void* adj_kernel(int model, int contact, int npb) {
-  if (contact != 0 && contact != 1) return nullptr;
-  if (model == kNonlinear) return contact ? adj_kernel_t<kNonlinear, 1>(npb) : adj_kernel_t<kNonlinear, 0>(npb);
-  if (model == kLinearized) return contact ? adj_kernel_t<kLinearized, 1>(npb) : adj_kernel_t<kLinearized, 0>(npb);
-  return nullptr;
+  const void* fn = nullptr;
+  with_physics<loop_physics>(model, contact, [&](auto M, auto C) { fn = npb == 3 ? (const void*)k_adj_persist<M(), C(), 3> : (const void*)k_adj_persist<M(), C(), 4>; });
+  return fn;
 }
 void launch_ring_poison(hipStream_t st, double* ring, int batch, int n_blocks, int m0, int nm, int width) {
   const int per_member = n_blocks * width;

@@ -6,27 +6,21 @@
 #include <cstdint>
 #include <cstring>
 
+#include "dfx_dispatch.h"
 #include "dfx_kernels.h"
 #include "dfx_persist_dense.h"
 
 namespace dfx_persist {
 
 const void* adaptive_fwd_kernel(int model, int contact) {
-  if (contact != 0 && contact != 1) return nullptr;
-  if (model == kNonlinear) return contact ? (const void*)k_adaptive_fwd_loop<kNonlinear, 1> : (const void*)k_adaptive_fwd_loop<kNonlinear, 0>;
-  if (model == kLinearized) return contact ? (const void*)k_adaptive_fwd_loop<kLinearized, 1> : (const void*)k_adaptive_fwd_loop<kLinearized, 0>;
-  return nullptr;
-}
-template <int MODEL, int CONTACT>
-static const void* adj_dense_kernel_t(int npb) {
-  if (npb == 3) return (const void*)k_adj_dense_loop<MODEL, CONTACT, 3>;
-  return (const void*)k_adj_dense_loop<MODEL, CONTACT, 4>;
+  const void* fn = nullptr;
+  with_physics<loop_physics>(model, contact, [&](auto M, auto C) { fn = (const void*)k_adaptive_fwd_loop<M(), C()>; });
+  return fn;
 }
 const void* adj_dense_kernel(int model, int contact, int npb) {
-  if (contact != 0 && contact != 1) return nullptr;
-  if (model == kNonlinear) return contact ? adj_dense_kernel_t<kNonlinear, 1>(npb) : adj_dense_kernel_t<kNonlinear, 0>(npb);
-  if (model == kLinearized) return contact ? adj_dense_kernel_t<kLinearized, 1>(npb) : adj_dense_kernel_t<kLinearized, 0>(npb);
-  return nullptr;
+  const void* fn = nullptr;
+  with_physics<loop_physics>(model, contact, [&](auto M, auto C) { fn = npb == 3 ? (const void*)k_adj_dense_loop<M(), C(), 3> : (const void*)k_adj_dense_loop<M(), C(), 4>; });
+  return fn;
 }
 
 }  // namespace dfx_persist

@@ -79,12 +79,8 @@ int dfx_create(const dfx_problem* problem, dfx_handle** out) {
     const long long waves = (long long)h->pl.batch * ((h->pl.n_slots + 63) / 64);
     int want = e ? atoi(e) : (problem->streams > 0 ? problem->streams : (waves >= 2048 ? 2 : 1));
     // solves that fit the persistent stage loop (dfx_persist.h) run all their members in ONE launch per segment
-    if (!e && problem->streams <= 0 && want > 1 && persist_shape_ok(h)) {
-      h->persist_npb = (h->pl.n_npb == 3 && pack3(h)) ? 3 : 4;
-      // (both sweeps must fit: a solve whose reverse sweep keeps the stage launches keeps its two member groups too)
-      if (persist_members_ok(h, persist_members_that_fit(h, dfx_persist::fwd_kernel(h->pl.model, h->pl.contact, h->persist_npb), h->persist_npb)) &&
-          persist_members_ok(h, persist_members_that_fit(h, dfx_persist::adj_kernel(h->pl.model, h->pl.contact, h->persist_npb), h->persist_npb))) want = 1;
-    }
+    // (both sweeps must fit: a solve whose reverse sweep keeps the stage launches keeps its two member groups too)
+    if (!e && problem->streams <= 0 && want > 1 && persist_would_serve(h)) want = 1;
     int ng = std::max(1, std::min({want, h->pl.batch, kMaxGroups}));
     (void)hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming);
     (void)hipEventCreateWithFlags(&h->ev_fork2, hipEventDisableTiming);
@@ -426,11 +422,7 @@ int dfx_energy(dfx_handle* h, const double* u, double* energy) {
   HIP_OK(hipMemcpyAsync(h->d_POS.p, S.data(), sizeof(double) * S.size(), hipMemcpyHostToDevice, h->stream));
   HIP_OK(h->d_tmp.ensure(B * pl.n_slots));
   DevCtx c = make_ctx(h);
-#define DFX_EN_CASE(M) case M: if (pl.contact == 2) hipLaunchKernelGGL((k_energy<M, 2>), slot_grid(h), dim3(kThreads), 0, h->stream, c, h->d_tmp.p); \
-    else if (pl.contact) hipLaunchKernelGGL((k_energy<M, 1>), slot_grid(h), dim3(kThreads), 0, h->stream, c, h->d_tmp.p); \
-    else hipLaunchKernelGGL((k_energy<M, 0>), slot_grid(h), dim3(kThreads), 0, h->stream, c, h->d_tmp.p); break;
-  switch (pl.model) { DFX_EN_CASE(kNonlinear) DFX_EN_CASE(kLinearized) DFX_EN_CASE(kSimpleSpring) DFX_EN_CASE(kStretchTorsion) }
-#undef DFX_EN_CASE
+  with_physics<all_physics>(pl.model, pl.contact, [&](auto M, auto C) { hipLaunchKernelGGL((k_energy<M(), C()>), slot_grid(h), dim3(kThreads), 0, h->stream, c, h->d_tmp.p); });
   std::vector<double> e(B * pl.n_slots);
   HIP_OK(hipMemcpyAsync(e.data(), h->d_tmp.p, sizeof(double) * e.size(), hipMemcpyDeviceToHost, h->stream));
   HIP_OK(hipStreamSynchronize(h->stream));

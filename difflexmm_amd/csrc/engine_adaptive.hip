@@ -272,11 +272,7 @@ static int forward_adaptive_impl(dfx_handle* h, const double* state0, const doub
     if (p < 5) { launch_fwd(h, cc, st, grid, p + 1, 0, keep ? -1 - (p + 1) : inb[p + 1], keep ? -2 - (p + 1) : outb[p + 1], keep ? -1 : 0, 0); return; }
     if (p == 5) {
       const int eb = keep ? -7 : 3, yb = keep ? -1 : 0;
-#define DFX_ERR_CASE(M) case M: if (pl.contact == 2) hipLaunchKernelGGL((k_fwd_stage<M, 2>), grid, dim3(kThreads), 0, st, cc, sc_err, 6, 0, eb, -1, yb, 2); \
-    else if (pl.contact) hipLaunchKernelGGL((k_fwd_stage<M, 1>), grid, dim3(kThreads), 0, st, cc, sc_err, 6, 0, eb, -1, yb, 2); \
-    else hipLaunchKernelGGL((k_fwd_stage<M, 0>), grid, dim3(kThreads), 0, st, cc, sc_err, 6, 0, eb, -1, yb, 2); break;
-      switch (pl.model) { DFX_ERR_CASE(kNonlinear) DFX_ERR_CASE(kLinearized) DFX_ERR_CASE(kSimpleSpring) DFX_ERR_CASE(kStretchTorsion) }
-#undef DFX_ERR_CASE
+      with_physics<all_physics>(pl.model, pl.contact, [&](auto M, auto C) { hipLaunchKernelGGL((k_fwd_stage<M(), C()>), grid, dim3(kThreads), 0, st, cc, sc_err, 6, 0, eb, -1, yb, 2); });
     } else if (p == 6) hipLaunchKernelGGL(k_control, dim3(nm), dim3(kThreads), 0, st, cc, n_partials, 2.0 * (double)n_free, Tn, ar);
     else hipLaunchKernelGGL(k_prepare, grid, dim3(kThreads), 0, st, cc, dc, Tn, keep ? 1 : 0);
     h->launches++;

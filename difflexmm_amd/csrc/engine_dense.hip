@@ -6,16 +6,13 @@
 
 using namespace dfx_persist;
 
-template <int MODEL, int CONTACT>
-static void launch_adj_dense_t(const DevCtx& c, hipStream_t st, dim3 grid, const AdjCoef& ac, const DenseCtx& dn, int i, int j) {
-  if (c.g_b) hipLaunchKernelGGL((k_adj_stage_dense<MODEL, CONTACT, 1>), grid, dim3(kThreads), 0, st, c, ac, dn, i, j);
-  else hipLaunchKernelGGL((k_adj_stage_dense<MODEL, CONTACT, 0>), grid, dim3(kThreads), 0, st, c, ac, dn, i, j);
-}
+// (the kept adaptive solve serves the loop physics only: dfx_forward_adaptive_keep refuses the rest)
 static void launch_adj_dense(dfx_handle* h, const DevCtx& c, hipStream_t st, dim3 grid, const DenseCtx& dn, int i, int j) {
   const AdjCoef ac = adj_coef(h->pl.tab, i);
-  const bool con = h->pl.contact != 0;
-  if (h->pl.model == kNonlinear) { if (con) launch_adj_dense_t<kNonlinear, 1>(c, st, grid, ac, dn, i, j); else launch_adj_dense_t<kNonlinear, 0>(c, st, grid, ac, dn, i, j); }
-  else { if (con) launch_adj_dense_t<kLinearized, 1>(c, st, grid, ac, dn, i, j); else launch_adj_dense_t<kLinearized, 0>(c, st, grid, ac, dn, i, j); }
+  with_physics<loop_physics>(h->pl.model, h->pl.contact, [&](auto M, auto C) {
+    if (c.g_b) hipLaunchKernelGGL((k_adj_stage_dense<M(), C(), 1>), grid, dim3(kThreads), 0, st, c, ac, dn, i, j);
+    else hipLaunchKernelGGL((k_adj_stage_dense<M(), C(), 0>), grid, dim3(kThreads), 0, st, c, ac, dn, i, j);
+  });
   h->launches++;
 }
 

@@ -399,7 +399,7 @@ int forward_grid_impl(dfx_handle* h, const double* state0, const double* timepoi
   h->fwd_stats.streams = (int64_t)h->groups.size();
   h->fwd_stats.stage_checkpoint = c.AD ? 1 : 0;
   h->fwd_stats.checkpoint_records = h->segments ? 2 : (c.rps > 1 ? 1 : 0);
-  h->fwd_stats.tile_kernels = h->persist_fwd ? 3 : kernel_build_code(h, c, h->lig_fwd_used);
+  h->fwd_stats.tile_kernels = h->persist_fwd ? 3 : kernel_build_code(h, c, h->lig_fwd_used, false);
   if (h->defer_forward_sync) return 0;          // the fused call goes on enqueueing the reverse sweep; finish_forward after its last wait
   HIP_OK(hipStreamSynchronize(h->stream));
   HIP_OK(hipGetLastError());

@@ -52,7 +52,7 @@ DevCtx make_ctx(dfx_handle* h) {
   // (general bond lists run the one reverse build that has them)
   c.g_r = h->d_g_r.p; c.g_phi = h->d_g_phi.p; c.g_b = (h->want_bond_grads || pl.n_ovf) ? h->d_g_b.p : nullptr;
   c.touch = h->d_touch.p;
-  c.lam_pairs = (c.g_b || c.AD) ? 0 : 1;      // the REBUILD builds of the reverse stage (launch_adj_t) keep the scalar layout
+  c.lam_pairs = (c.g_b || c.AD) ? 0 : 1;      // the REBUILD builds of the reverse stage (launch_adj) keep the scalar layout
   c.blk_m = h->d_blk_m.p; c.blk_c = h->want_damping_grads ? h->d_blk_c.p : nullptr;
   c.fn_g = h->want_fn_grads ? h->d_fn_g.p : nullptr;
   return c;
@@ -114,158 +114,98 @@ int pair_state_buf(const dfx_handle* h, long long n) {
 // 3-node blocks: the two stage kernels pack five triangles per 16 lanes (lane_pos<3>) instead of leaving every fourth lane idle --
 // 20 blocks per wave instead of 16.  Fixed grid only (the adaptive controller's error reduction keeps the quad mapping), not with the
 // distance-based contact; reverse: the records build.  DFX_PACK3=0 keeps the quad mapping (A/B measurements).
-bool pack3(const dfx_handle* h) {
+static bool pack3(const dfx_handle* h) {
   const char* e = getenv("DFX_PACK3");
   return h->pl.n_npb == 3 && !h->adaptive && !(e && e[0] == '0');
 }
-// The per-stage builds of the stage kernels (template parameter ISTAGE) assume the common parameter shape and compile its run-time flags
-// away: uniform stiffnesses and damping, the reference-vector dictionary in LDS, equal steps, no stage checkpoint, no adaptive clock,
-// records read from / written to the trajectory checkpoint (the caller checks the buffer arguments).
-static bool hot_shape(const DevCtx& c) {
-  return c.k_uniform && c.l_dict_on && c.l_dict_lds && c.damping_uniform && !c.t_steps && !c.AD && !c.clock;
-}
-// the per-stage builds (stage index, common parameter shape and -- where the records live in the checkpoint -- the buffer arguments as
-// compile-time constants) of the write-through table kernels, quad mapping (NPB = 4) or packed triangles (NPB = 3); false: not applicable
-template <int MODEL, int CONTACT, int NPB>
-static bool launch_fwd_hot(dfx_handle* h, const DevCtx& c, hipStream_t st, dim3 grid, int i, int j, int in_buf, int out_buf, int y_buf, int mode) {
-  if constexpr ((MODEL == kNonlinear || MODEL == kLinearized) && CONTACT != 2) {
-    if (!h->wt || !h->stage_builds || !hot_shape(c)) return false;
-    const StageCoef scf = stage_coef(h->pl.tab, i);
-    const bool recs = c.rps > 1 && in_buf == -1 - i && out_buf == -2 - i && y_buf == -1 && mode == 0;
-#define DFX_FWD_I(I)                                                                                                              \
-  case I:                                                                                                                         \
-    if (recs)                                                                                                                     \
-      hipLaunchKernelGGL((k_fwd_stage<MODEL, CONTACT, NPB, 1, 0, 1, I, 1>), grid, dim3(kThreads), 0, st, c, scf, i, j, in_buf, out_buf, \
-                         y_buf, mode);                                                                                            \
-    else                                                                                                                          \
-      hipLaunchKernelGGL((k_fwd_stage<MODEL, CONTACT, NPB, 1, 0, 1, I, 0>), grid, dim3(kThreads), 0, st, c, scf, i, j, in_buf, out_buf, \
-                         y_buf, mode);                                                                                            \
-    return true;
-    switch (i) { DFX_FWD_I(0) DFX_FWD_I(1) DFX_FWD_I(2) DFX_FWD_I(3) DFX_FWD_I(4) DFX_FWD_I(5) default: break; }
-#undef DFX_FWD_I
-  }
-  return false;
-}
-// the reverse per-stage builds live in a translation unit of their own (stage_builds_adj.hip: compiled with its own scheduling strategy)
-namespace dfx_hot {
-bool launch_adj_stage_build(int model, int contact, int npb, hipStream_t st, dim3 grid, const DevCtx& c, const AdjCoef& acf, int i, int j, int in_buf, int wbuf,
-                            int local_only, const StageCoef& rc, int rb);
-}
-template <int MODEL, int CONTACT, int NPB>
-static bool launch_adj_hot(dfx_handle* h, const DevCtx& c, hipStream_t st, dim3 grid, int i, int j, int in_buf, int wbuf, int local_only, const StageCoef& rc,
-    int rb) {
-  if constexpr ((MODEL == kNonlinear || MODEL == kLinearized) && CONTACT != 2) {
-    if (!h->wt || !h->stage_builds || !(c.k_uniform && c.l_dict_on && c.l_dict_lds && c.damping_uniform && !c.t_steps)) return false;
-    return dfx_hot::launch_adj_stage_build(MODEL, CONTACT, NPB, st, grid, c, adj_coef(h->pl.tab, i), i, j, in_buf, wbuf, local_only, rc, rb);
-  }
-  return false;
+// what the build selection (dfx_builds.h) reads of a handle and a launch context
+static BuildQuery build_query(const dfx_handle* h, const DevCtx& c) {
+  BuildQuery q;
+  q.model = h->pl.model; q.contact = h->pl.contact; q.n_npb = h->pl.n_npb; q.n_ovf = h->pl.n_ovf; q.s = h->pl.tab.s;
+  q.pack3 = pack3(h); q.wt = h->wt; q.stage_builds = h->stage_builds;
+  q.k_uniform = c.k_uniform; q.l_dict_on = c.l_dict_on; q.l_dict_lds = c.l_dict_lds; q.damping_uniform = c.damping_uniform;
+  q.t_steps = c.t_steps != nullptr; q.AD = c.AD != nullptr; q.clock = c.clock != nullptr;
+  q.records = c.rps > 1; q.fn_tab = c.fn_tab != nullptr; q.g_b = c.g_b != nullptr;
+  return q;
 }
 // what dfx_stats.tile_kernels reports: 1 tile kernels, 2 the per-stage / common-shape builds of the slot kernels, 0 their generic builds
-int kernel_build_code(const dfx_handle* h, const DevCtx& c, bool tile) {
-  if (tile) return 1;
-  const bool model_ok = (h->pl.model == kNonlinear || h->pl.model == kLinearized) && h->pl.contact != DFX_CONTACT_DISTANCE;
-  const bool quad_or_packed = !h->pl.n_ovf && (h->pl.n_npb == 4 || pack3(h));
-  return (model_ok && quad_or_packed && h->wt && h->stage_builds && c.fn_tab && hot_shape(c) && h->pl.tab.s <= 6) ? 2 : 0;
-}
-template <int MODEL, int CONTACT>
-static void launch_fwd_t(dfx_handle* h, const DevCtx& c, hipStream_t st, dim3 grid, int i, int j, int in_buf, int out_buf, int y_buf, int mode) {
-#ifdef DFX_EXPERIMENTAL
-  if constexpr (CONTACT != 2) {
-    if (lig_fwd_ok(h, c, mode)) {
-      const dim3 tg(h->lig.n_wg, grid.y);
-      hipLaunchKernelGGL((k_fwd_tile<MODEL, CONTACT>), tg, dim3(64 * kTileWaves), 0, st, c, h->lig, stage_coef(h->pl.tab, i), i, j, in_buf, out_buf,
-                         y_buf, mode);
-      return;
-    }
-  }
-#endif
-  if (h->pl.n_ovf) {       // general bond lists: the build that walks a node's extra ligaments (quad mapping, in-kernel time functions)
-    if constexpr (CONTACT != 2)
-      hipLaunchKernelGGL((k_fwd_stage<MODEL, CONTACT, 4, 0, 1>), grid, dim3(kThreads), 0, st, c, stage_coef(h->pl.tab, i), i, j, in_buf, out_buf, y_buf, mode);
-    return;
-  }
-  const bool tab = c.fn_tab != nullptr && !c.clock;        // the segment's time-function table is there: the build that reads it
-  if (CONTACT != 2 && pack3(h) && !(mode & 2)) {
-    if constexpr (CONTACT != 2) {
-      if (tab && launch_fwd_hot<MODEL, CONTACT, 3>(h, c, st, dim3(c.n_wg3, grid.y), i, j, in_buf, out_buf, y_buf, mode)) return;
-      if (tab) hipLaunchKernelGGL((k_fwd_stage<MODEL, CONTACT, 3, 1>), dim3(c.n_wg3, grid.y), dim3(kThreads), 0, st, c, stage_coef(h->pl.tab, i), i, j,
-          in_buf, out_buf, y_buf, mode);
-      else hipLaunchKernelGGL((k_fwd_stage<MODEL, CONTACT, 3, 0>), dim3(c.n_wg3, grid.y), dim3(kThreads), 0, st, c, stage_coef(h->pl.tab, i), i, j, in_buf,
-          out_buf, y_buf, mode);
-    }
-    return;
-  }
-  if (tab && h->wt) {
-    if (launch_fwd_hot<MODEL, CONTACT, 4>(h, c, st, grid, i, j, in_buf, out_buf, y_buf, mode)) return;
-    hipLaunchKernelGGL((k_fwd_stage<MODEL, CONTACT, 4, 1, 0, 1>), grid, dim3(kThreads), 0, st, c, stage_coef(h->pl.tab, i), i, j, in_buf, out_buf, y_buf, mode);
-  }
-  else if (tab) hipLaunchKernelGGL((k_fwd_stage<MODEL, CONTACT, 4, 1>), grid, dim3(kThreads), 0, st, c, stage_coef(h->pl.tab, i), i, j, in_buf, out_buf,
-      y_buf, mode);
-  else hipLaunchKernelGGL((k_fwd_stage<MODEL, CONTACT, 4, 0>), grid, dim3(kThreads), 0, st, c, stage_coef(h->pl.tab, i), i, j, in_buf, out_buf, y_buf, mode);
-}
+int kernel_build_code(const dfx_handle* h, const DevCtx& c, bool tile, bool reverse) { return tile ? 1 : build_code(build_query(h, c), reverse); }
+
+// One stage launch: select the build (dfx_builds.h), then instantiate it.  The switches below list exactly the builds the library ships.
 void launch_fwd(dfx_handle* h, const DevCtx& c, hipStream_t st, dim3 grid, int i, int j, int in_buf, int out_buf, int y_buf, int mode) {
-  const Plan& pl = h->pl;
-#define DFX_FWD_CASE(M) case M: if (pl.contact == 2) launch_fwd_t<M, 2>(h, c, st, grid, i, j, in_buf, out_buf, y_buf, mode); \
-    else if (pl.contact) launch_fwd_t<M, 1>(h, c, st, grid, i, j, in_buf, out_buf, y_buf, mode); else launch_fwd_t<M, 0>(h, c, st, grid, i, j, in_buf, \
-    out_buf, y_buf, mode); break;
-  switch (pl.model) { DFX_FWD_CASE(kNonlinear) DFX_FWD_CASE(kLinearized) DFX_FWD_CASE(kSimpleSpring) DFX_FWD_CASE(kStretchTorsion) }
-#undef DFX_FWD_CASE
   h->launches++;
+  const FwdBuild b = select_fwd_build(build_query(h, c), i, in_buf, out_buf, y_buf, mode);
+  const StageCoef scf = stage_coef(h->pl.tab, i);
+  const dim3 g = b.packed_grid ? dim3(c.n_wg3, grid.y) : grid;
+  with_physics<all_physics>(h->pl.model, h->pl.contact, [&](auto M, auto C) {
+    constexpr int MODEL = M(), CONTACT = C();
+    auto go = [&](auto* k) { hipLaunchKernelGGL(k, g, dim3(kThreads), 0, st, c, scf, i, j, in_buf, out_buf, y_buf, mode); };
+#ifdef DFX_EXPERIMENTAL
+    if constexpr (CONTACT != 2) {
+      if (lig_fwd_ok(h, c, mode)) {
+        const dim3 tg(h->lig.n_wg, grid.y);
+        hipLaunchKernelGGL((k_fwd_tile<MODEL, CONTACT>), tg, dim3(64 * kTileWaves), 0, st, c, h->lig, scf, i, j, in_buf, out_buf, y_buf, mode);
+        return;
+      }
+    }
+#endif
+    auto stage_build = [&](auto NPB) {
+      with_index<kStageBuilds>(b.istage, [&](auto I) {
+        b.recs ? go(k_fwd_stage<MODEL, CONTACT, NPB(), 1, 0, 1, I(), 1>) : go(k_fwd_stage<MODEL, CONTACT, NPB(), 1, 0, 1, I(), 0>);
+      });
+    };
+    if constexpr (CONTACT != 2) {
+      if (b.ovf) return go(k_fwd_stage<MODEL, CONTACT, 4, 0, 1>);
+      if (b.npb == 3) {
+        if constexpr (loop_physics(MODEL, CONTACT)) if (b.istage >= 0) return stage_build(int_c<3>{});
+        return b.tab ? go(k_fwd_stage<MODEL, CONTACT, 3, 1>) : go(k_fwd_stage<MODEL, CONTACT, 3, 0>);
+      }
+    }
+    if (b.npb != 4) return;
+    if constexpr (loop_physics(MODEL, CONTACT)) if (b.istage >= 0) return stage_build(int_c<4>{});
+    if (b.wt) go(k_fwd_stage<MODEL, CONTACT, 4, 1, 0, 1>);
+    else b.tab ? go(k_fwd_stage<MODEL, CONTACT, 4, 1>) : go(k_fwd_stage<MODEL, CONTACT, 4, 0>);
+  });
 }
 void launch_fwd(dfx_handle* h, const DevCtx& c, int i, int j, int in_buf, int out_buf, int y_buf, int mode) {
   launch_fwd(h, c, h->stream, slot_grid(h), i, j, in_buf, out_buf, y_buf, mode);
 }
-template <int MODEL, int CONTACT>
-static void launch_adj_t(dfx_handle* h, const DevCtx& c, hipStream_t st, dim3 grid, int i, int j, int in_buf, int wbuf, int local_only) {
-  // stage checkpoint: which record this launch rebuilds for the launch after it (0: none)
-  const int s = h->pl.tab.s;
-  const int rb = (c.AD && !local_only) ? (i >= 2 ? i - 1 : (i == 0 ? s - 1 : 0)) : 0;
-  const StageCoef rc = stage_coef(h->pl.tab, rb > 0 ? rb - 1 : 0);
-#ifdef DFX_EXPERIMENTAL
-  if constexpr (CONTACT != 2) {
-    if (lig_adj_ok(h, c, wbuf, local_only)) {
-      const dim3 tg(h->lig.n_wg, grid.y);
-      hipLaunchKernelGGL((k_adj_tile<MODEL, CONTACT>), tg, dim3(64 * kTileWaves), 0, st, c, h->lig, adj_coef(h->pl.tab, i), i, j, in_buf);
-      return;
-    }
-  }
-#endif
-  if (h->pl.n_ovf) {       // general bond lists: one build for every checkpoint level (per-ligament gradients on, rebuild on)
-    if constexpr (CONTACT != 2)
-      hipLaunchKernelGGL((k_adj_stage<MODEL, CONTACT, 1, 1, 4, 0, 1>), grid, dim3(kThreads), 0, st, c, adj_coef(h->pl.tab, i), i, j, in_buf, wbuf, local_only,
-          rc, rb);
-  }
-  else if (c.g_b) hipLaunchKernelGGL((k_adj_stage<MODEL, CONTACT, 1, 1>), grid, dim3(kThreads), 0, st, c, adj_coef(h->pl.tab, i), i, j, in_buf, wbuf,
-      local_only, rc, rb);
-  else if (c.AD) hipLaunchKernelGGL((k_adj_stage_rb<MODEL, CONTACT>), grid, dim3(kThreads), 0, st, c, adj_coef(h->pl.tab, i), i, j, in_buf, wbuf, local_only,
-      rc, rb);
-  else if (CONTACT != 2 && pack3(h)) {
-    if constexpr (CONTACT != 2) {
-      if (c.fn_tab && !local_only && launch_adj_hot<MODEL, CONTACT, 3>(h, c, st, dim3(c.n_wg3, grid.y), i, j, in_buf, wbuf, local_only, rc, rb)) return;
-      if (c.fn_tab && !local_only) hipLaunchKernelGGL((k_adj_stage<MODEL, CONTACT, 0, 0, 3, 1>), dim3(c.n_wg3, grid.y), dim3(kThreads), 0, st, c,
-          adj_coef(h->pl.tab, i), i, j, in_buf, wbuf, local_only, rc, rb);
-      else hipLaunchKernelGGL((k_adj_stage<MODEL, CONTACT, 0, 0, 3, 0>), dim3(c.n_wg3, grid.y), dim3(kThreads), 0, st, c, adj_coef(h->pl.tab, i), i, j,
-          in_buf, wbuf, local_only, rc, rb);
-    }
-  }
-  else if (c.fn_tab && !local_only && h->wt) {
-    if (launch_adj_hot<MODEL, CONTACT, 4>(h, c, st, grid, i, j, in_buf, wbuf, local_only, rc, rb)) return;
-    hipLaunchKernelGGL((k_adj_stage<MODEL, CONTACT, 0, 0, 4, 1, 0, 1>), grid, dim3(kThreads), 0, st, c, adj_coef(h->pl.tab, i), i, j, in_buf, wbuf,
-        local_only, rc, rb);
-  }
-  else if (c.fn_tab && !local_only) hipLaunchKernelGGL((k_adj_stage<MODEL, CONTACT, 0, 0, 4, 1>), grid, dim3(kThreads), 0, st, c, adj_coef(h->pl.tab, i), i,
-      j, in_buf, wbuf, local_only, rc, rb);
-  else hipLaunchKernelGGL((k_adj_stage<MODEL, CONTACT, 0, 0, 4, 0>), grid, dim3(kThreads), 0, st, c, adj_coef(h->pl.tab, i), i, j, in_buf, wbuf, local_only,
-      rc, rb);
+// the reverse per-stage builds live in a translation unit of their own (stage_builds_adj.hip: compiled with its own scheduling strategy)
+namespace dfx_hot {
+void launch_adj_stage_build(int model, int contact, int npb, hipStream_t st, dim3 grid, const DevCtx& c, const AdjCoef& acf, int i, int j, int in_buf, int wbuf,
+                            int local_only, const StageCoef& rc, int rb);
 }
 void launch_adj(dfx_handle* h, const DevCtx& c, hipStream_t st, dim3 grid, int i, int j, int in_buf, int wbuf, int local_only) {
-  const Plan& pl = h->pl;
-#define DFX_ADJ_CASE(M) case M: if (pl.contact == 2) launch_adj_t<M, 2>(h, c, st, grid, i, j, in_buf, wbuf, local_only); \
-    else if (pl.contact) launch_adj_t<M, 1>(h, c, st, grid, i, j, in_buf, wbuf, local_only); else launch_adj_t<M, 0>(h, c, st, grid, i, j, in_buf, wbuf, \
-    local_only); break;
-  switch (pl.model) { DFX_ADJ_CASE(kNonlinear) DFX_ADJ_CASE(kLinearized) DFX_ADJ_CASE(kSimpleSpring) DFX_ADJ_CASE(kStretchTorsion) }
-#undef DFX_ADJ_CASE
   h->launches++;
+  // stage checkpoint: which record this launch rebuilds for the launch after it (0: none)
+  const int rb = (c.AD && !local_only) ? (i >= 2 ? i - 1 : (i == 0 ? h->pl.tab.s - 1 : 0)) : 0;
+  const StageCoef rc = stage_coef(h->pl.tab, rb > 0 ? rb - 1 : 0);
+  const AdjCoef acf = adj_coef(h->pl.tab, i);
+  const AdjBuild b = select_adj_build(build_query(h, c), i, local_only);
+  const dim3 g = b.packed_grid ? dim3(c.n_wg3, grid.y) : grid;
+  with_physics<all_physics>(h->pl.model, h->pl.contact, [&](auto M, auto C) {
+    constexpr int MODEL = M(), CONTACT = C();
+    auto go = [&](auto* k) { hipLaunchKernelGGL(k, g, dim3(kThreads), 0, st, c, acf, i, j, in_buf, wbuf, local_only, rc, rb); };
+#ifdef DFX_EXPERIMENTAL
+    if constexpr (CONTACT != 2) {
+      if (lig_adj_ok(h, c, wbuf, local_only)) {
+        const dim3 tg(h->lig.n_wg, grid.y);
+        hipLaunchKernelGGL((k_adj_tile<MODEL, CONTACT>), tg, dim3(64 * kTileWaves), 0, st, c, h->lig, acf, i, j, in_buf);
+        return;
+      }
+    }
+#endif
+    if (b.istage >= 0) return dfx_hot::launch_adj_stage_build(MODEL, CONTACT, b.npb, st, g, c, acf, i, j, in_buf, wbuf, local_only, rc, rb);
+    if constexpr (CONTACT != 2) if (b.kind == kAdjOvf) return go(k_adj_stage<MODEL, CONTACT, 1, 1, 4, 0, 1>);
+    if (b.kind == kAdjBondGrads) return go(k_adj_stage<MODEL, CONTACT, 1, 1>);
+    if (b.kind == kAdjRebuild) return go(k_adj_stage_rb<MODEL, CONTACT>);
+    if constexpr (CONTACT != 2) {
+      if (b.npb == 3) return b.tab ? go(k_adj_stage<MODEL, CONTACT, 0, 0, 3, 1>) : go(k_adj_stage<MODEL, CONTACT, 0, 0, 3, 0>);
+    }
+    if (b.npb != 4) return;
+    if (b.wt) go(k_adj_stage<MODEL, CONTACT, 0, 0, 4, 1, 0, 1>);
+    else b.tab ? go(k_adj_stage<MODEL, CONTACT, 0, 0, 4, 1>) : go(k_adj_stage<MODEL, CONTACT, 0, 0, 4, 0>);
+  });
 }
 void launch_adj(dfx_handle* h, const DevCtx& c, int i, int j, int in_buf, int wbuf, int local_only) {
   launch_adj(h, c, h->stream, slot_grid(h), i, j, in_buf, wbuf, local_only);
@@ -397,9 +337,9 @@ static bool persist_adj_members_ok(const dfx_handle* h, const void* fn, int per_
   const long long room = (long long)persist_cap(fn) * h->n_cu * 4;
   return 2LL * chunk_members(nm, n_chunks, n_chunks - 1) * h->persist_wpm >= room;
 }
-// would both sweeps of a fixed-grid solve of this handle run the persistent loop?  (asked before the context exists: the checkpoint choice)
+// would both sweeps of a fixed-grid solve run the persistent loop?  (asked before the context exists -- the checkpoint choice -- and at creation, before the groups do)
 bool persist_would_serve(dfx_handle* h) {
-  if (!persist_shape_ok(h) || h->adaptive || h->groups.size() != 1) return false;
+  if (!persist_shape_ok(h) || h->adaptive || h->groups.size() > 1) return false;
   const int npb = (h->pl.n_npb == 3 && pack3(h)) ? 3 : 4;
   return persist_members_ok(h, persist_members_that_fit(h, dfx_persist::fwd_kernel(h->pl.model, h->pl.contact, npb), npb)) &&
          persist_members_ok(h, persist_members_that_fit(h, dfx_persist::adj_kernel(h->pl.model, h->pl.contact, npb), npb));

@@ -157,21 +157,11 @@ ObjArgs strain_args(const dfx_handle* h, const ObjJob& j) {
   return a;
 }
 
-// the build of a strain kernel for the handle's bond model; the angle contact only where the lattice has it (c_contact != 0 is refused elsewhere)
-#define DFX_STRAIN_LAUNCH(KERNEL, GRID, BLOCK, ...)                                                                               \
-  do {                                                                                                                             \
-    const bool ang_ = h->pl.contact == DFX_CONTACT_ANGLE;                                                                          \
-    switch (h->pl.model) {                                                                                                         \
-      case kNonlinear: if (ang_) hipLaunchKernelGGL((KERNEL<kNonlinear, 1>), GRID, BLOCK, 0, h->stream, __VA_ARGS__);              \
-        else hipLaunchKernelGGL((KERNEL<kNonlinear, 0>), GRID, BLOCK, 0, h->stream, __VA_ARGS__); break;                           \
-      case kLinearized: if (ang_) hipLaunchKernelGGL((KERNEL<kLinearized, 1>), GRID, BLOCK, 0, h->stream, __VA_ARGS__);            \
-        else hipLaunchKernelGGL((KERNEL<kLinearized, 0>), GRID, BLOCK, 0, h->stream, __VA_ARGS__); break;                          \
-      case kSimpleSpring: if (ang_) hipLaunchKernelGGL((KERNEL<kSimpleSpring, 1>), GRID, BLOCK, 0, h->stream, __VA_ARGS__);        \
-        else hipLaunchKernelGGL((KERNEL<kSimpleSpring, 0>), GRID, BLOCK, 0, h->stream, __VA_ARGS__); break;                        \
-      default: if (ang_) hipLaunchKernelGGL((KERNEL<kStretchTorsion, 1>), GRID, BLOCK, 0, h->stream, __VA_ARGS__);                 \
-        else hipLaunchKernelGGL((KERNEL<kStretchTorsion, 0>), GRID, BLOCK, 0, h->stream, __VA_ARGS__); break;                      \
-    }                                                                                                                              \
-  } while (0)
+// the build of a strain kernel for the handle's bond model; the angle contact only where the lattice has it (c_contact != 0 is refused
+// elsewhere), so the distance-based contact takes the CONTACT = 0 build
+template <class F> void with_strain_physics(const dfx_handle* h, F&& f) {
+  with_physics<all_physics>(h->pl.model, h->pl.contact == DFX_CONTACT_ANGLE ? 1 : 0, [&](auto M, auto C) { if constexpr (C() != DFX_CONTACT_DISTANCE) f(M, C); });
+}
 
 // ligament forces into G (may be null: value only), the value into d_obj and, when given, into pinned host memory
 int launch_strain(dfx_handle* h, const ObjJob& j, double* G, double* objective_host) {
@@ -182,7 +172,7 @@ int launch_strain(dfx_handle* h, const ObjJob& j, double* G, double* objective_h
   DevCtx c = make_ctx(h);
   const ObjArgs a = strain_args(h, j);
   const dim3 grid(chunks, (unsigned)B);
-  DFX_STRAIN_LAUNCH(k_strain_objective, grid, dim3(kObjThreads), c, a, G, h->d_obj_part.p);
+  with_strain_physics(h, [&](auto M, auto C) { hipLaunchKernelGGL((k_strain_objective<M(), C()>), grid, dim3(kObjThreads), 0, h->stream, c, a, G, h->d_obj_part.p); });
   hipLaunchKernelGGL(k_objective_finish, dim3((unsigned)B), dim3(kObjThreads), 0, h->stream, (const double*)h->d_obj_part.p, (int)chunks, h->d_obj.p,
                      objective_host);
   return 0;
@@ -196,7 +186,7 @@ void launch_objective_explicit(dfx_handle* h, const DevCtx& c) {
   if (j.kind == kObjStrain) {
     const ObjArgs a = strain_args(h, j);
     const dim3 grid((unsigned)((j.n_act * 4 + 63) / 64), (unsigned)h->pl.batch);
-    DFX_STRAIN_LAUNCH(k_strain_objective_explicit, grid, dim3(64), c, a);
+    with_strain_physics(h, [&](auto M, auto C) { hipLaunchKernelGGL((k_strain_objective_explicit<M(), C()>), grid, dim3(64), 0, h->stream, c, a); });
     return;
   }
   const ObjArgs a = obj_args(h, j);

@@ -430,7 +430,7 @@ int run_adjoint(dfx_handle* h, const dfx_grads* want, dfx_grads* grads, dfx_grad
     stats->stage_kernel_us = h->n_total ? 1e3 * ms / (double)(h->n_total * pl.tab.s * 2) : 0.0;
     stats->stage_checkpoint = c.AD ? 1 : 0;
     stats->checkpoint_records = h->segments ? 2 : (c.rps > 1 ? 1 : 0);
-    stats->tile_kernels = h->persist_adj ? 3 : ((c.g_b || c.AD) ? 0 : kernel_build_code(h, c, h->lig_adj_used));
+    stats->tile_kernels = h->persist_adj ? 3 : ((c.g_b || c.AD) ? 0 : kernel_build_code(h, c, h->lig_adj_used, true));
   }
   return 0;
 }

@@ -67,31 +67,19 @@ void launch_rhs_out(dim3 grid, hipStream_t s, const TanCtx& c, const MultiBufs& 
                      (const double*)d.DA.p, sl, d.fields.p, d.fields_dot.p);
 }
 
-template <int MODEL, int CONTACT, int KC>
-MultiKernels pick_npb(int npb) {
-  return {npb == 3 ? launch_stage<MODEL, CONTACT, 3, KC> : launch_stage<MODEL, CONTACT, 4, KC>, launch_init<KC>, launch_snapshot<KC>, launch_dense<KC>,
-          launch_rhs_out<KC>};
-}
-template <int MODEL, int KC>
-MultiKernels pick_contact(int contact, int npb) {
-  if (contact == DFX_CONTACT_DISTANCE) return pick_npb<MODEL, DFX_CONTACT_DISTANCE, KC>(npb);
-  if (contact == DFX_CONTACT_ANGLE) return pick_npb<MODEL, DFX_CONTACT_ANGLE, KC>(npb);
-  return pick_npb<MODEL, DFX_CONTACT_NONE, KC>(npb);
-}
 template <int KC>
-MultiKernels pick_model(int model, int contact, int npb) {
-  switch (model) {
-    case kNonlinear: return pick_contact<kNonlinear, KC>(contact, npb);
-    case kLinearized: return pick_contact<kLinearized, KC>(contact, npb);
-    case kSimpleSpring: return pick_contact<kSimpleSpring, KC>(contact, npb);
-    default: return pick_contact<kStretchTorsion, KC>(contact, npb);
-  }
+MultiKernels pick_physics(int model, int contact, int npb) {
+  MultiKernels k = {};
+  with_physics<all_physics>(model, contact, [&](auto M, auto C) {
+    k = {npb == 3 ? launch_stage<M(), C(), 3, KC> : launch_stage<M(), C(), 4, KC>, launch_init<KC>, launch_snapshot<KC>, launch_dense<KC>, launch_rhs_out<KC>};
+  });
+  return k;
 }
 MultiKernels pick_kernels(int model, int contact, int npb, int kc) {
   switch (kc) {
-    case 4: return pick_model<4>(model, contact, npb);
-    case 2: return pick_model<2>(model, contact, npb);
-    default: return pick_model<1>(model, contact, npb);
+    case 4: return pick_physics<4>(model, contact, npb);
+    case 2: return pick_physics<2>(model, contact, npb);
+    default: return pick_physics<1>(model, contact, npb);
   }
 }
 

@@ -10,34 +10,19 @@
 #include <cstdint>
 #include <cstring>
 
+#include "dfx_builds.h"
 #include "dfx_kernels.h"
 
 namespace dfx_hot {
 
-template <int MODEL, int CONTACT, int NPB>
-static bool adj_t(hipStream_t st, dim3 grid, const DevCtx& c, const AdjCoef& acf, int i, int j, int in_buf, int wbuf, int local_only,
-                  const StageCoef& rc, int rb) {
-#define DFX_ADJ_I(I) case I: hipLaunchKernelGGL((k_adj_stage<MODEL, CONTACT, 0, 0, NPB, 1, 0, 1, I>), grid, dim3(kThreads), 0, st, c, acf, i, j, in_buf, \
-    wbuf, local_only, rc, rb); return true;
-  switch (i) { DFX_ADJ_I(0) DFX_ADJ_I(1) DFX_ADJ_I(2) DFX_ADJ_I(3) DFX_ADJ_I(4) DFX_ADJ_I(5) default: break; }
-#undef DFX_ADJ_I
-  return false;
-}
-template <int MODEL, int CONTACT>
-static bool adj_n(int npb, hipStream_t st, dim3 grid, const DevCtx& c, const AdjCoef& acf, int i, int j, int in_buf, int wbuf, int local_only,
-                  const StageCoef& rc, int rb) {
-  return npb == 3 ? adj_t<MODEL, CONTACT, 3>(st, grid, c, acf, i, j, in_buf, wbuf, local_only, rc, rb)
-                  : adj_t<MODEL, CONTACT, 4>(st, grid, c, acf, i, j, in_buf, wbuf, local_only, rc, rb);
-}
-// false: no per-stage build for this (model, contact, lanes per block, stage) -- the caller launches the generic build
-bool launch_adj_stage_build(int model, int contact, int npb, hipStream_t st, dim3 grid, const DevCtx& c, const AdjCoef& acf, int i, int j, int in_buf, int wbuf,
+// the launch switch: the caller has selected a per-stage build (select_adj_build, dfx_builds.h), so the build exists
+void launch_adj_stage_build(int model, int contact, int npb, hipStream_t st, dim3 grid, const DevCtx& c, const AdjCoef& acf, int i, int j, int in_buf, int wbuf,
                             int local_only, const StageCoef& rc, int rb) {
-  if (contact != 0 && contact != 1) return false;
-  if (model == kNonlinear) return contact ? adj_n<kNonlinear, 1>(npb, st, grid, c, acf, i, j, in_buf, wbuf, local_only, rc, rb)
-                                          : adj_n<kNonlinear, 0>(npb, st, grid, c, acf, i, j, in_buf, wbuf, local_only, rc, rb);
-  if (model == kLinearized) return contact ? adj_n<kLinearized, 1>(npb, st, grid, c, acf, i, j, in_buf, wbuf, local_only, rc, rb)
-                                           : adj_n<kLinearized, 0>(npb, st, grid, c, acf, i, j, in_buf, wbuf, local_only, rc, rb);
-  return false;
+  auto go = [&](auto* k) { hipLaunchKernelGGL(k, grid, dim3(kThreads), 0, st, c, acf, i, j, in_buf, wbuf, local_only, rc, rb); };
+  with_physics<loop_physics>(model, contact, [&](auto M, auto C) {
+    auto stage_build = [&](auto NPB) { with_index<kStageBuilds>(i, [&](auto I) { go(k_adj_stage<M(), C(), 0, 0, NPB(), 1, 0, 1, I()>); }); };
+    npb == 3 ? stage_build(int_c<3>{}) : stage_build(int_c<4>{});
+  });
 }
 
 }  // namespace dfx_hot

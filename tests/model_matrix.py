@@ -44,7 +44,7 @@ _EN = {"nonlinear": (en_mod.ligament_energy, OE.ligament_energy), "linearized": 
 
 def loop_serves(model, contact):
     """The physics the persistent loops and the kept adaptive steps serve (engine_launch.hip persist_shape_ok, engine_adaptive.hip): the
-    two ligament models, without contact or with angle contact.  Also what the per-stage builds exist for (kernel_build_code)."""
+    two ligament models, without contact or with angle contact.  Also what the per-stage builds exist for (dfx_builds.h, stage_build_ok)."""
     return model in ("nonlinear", "linearized") and contact != "distance"
 
 

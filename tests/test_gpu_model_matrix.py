@@ -2,7 +2,7 @@
 
 The kernels are compiled once per (MODEL, CONTACT) pair -- nonlinear / linearised ligaments, the simple spring, the stretching + torsional
 spring, each with no contact, angle contact and distance contact -- and again per NPB, TAB, WT, ISTAGE, RECS, BOND_GRADS, REBUILD and for
-the persistent and adaptive loops (engine_launch.hip launch_fwd_t / launch_adj_t / persist_shape_ok / kernel_build_code,
+the persistent and adaptive loops (dfx_builds.h select_fwd_build / select_adj_build / build_code, engine_launch.hip persist_shape_ok,
 stage_builds_adj.hip, dfx_persist.hip, dfx_persist_dense.hip, engine_adaptive.hip).  The rest of the suite takes nonlinear ligaments with
 angle contact everywhere and the other pairs on 4 x 4 blocks, undamped, on the default arm.  Here all 24 lattice x model x contact
 combinations run on 13 x 13 quads (676 slots) and 11 x 11 kagome (242 triangles) -- a partial last wave --, damped, on
@@ -13,6 +13,7 @@ combinations run on 13 x 13 quads (676 slots) and 11 x 11 kagome (242 triangles)
   stage_notab  DFX_PERSIST=0 DFX_WT=0 DFX_FN_TABLE=0    the TAB = 0 builds (time functions evaluated in the kernel)
   persistent   DFX_PERSIST=1                            the persistent loops (also at the segments level), or their fallback
   quadmap      DFX_PERSIST=0 DFX_WT=0 DFX_PACK3=0       kagome without distance contact: NPB = 4 on triangles
+  quadmap_wt   DFX_PERSIST=0 DFX_WT=1 DFX_PACK3=0       kagome, the ligament models without distance contact: the NPB = 4 ISTAGE builds on triangles
 
 each against torch.autograd through the oracle on every leaf the model has (fields RTOL_TRAJ -- 1e-9 with distance contact, the bar of
 test_distance_contact.py --, gradients RTOL_GRAD, member by member), against the stage arm (fields 1e-13, gradients 1e-11; equality where
@@ -38,7 +39,8 @@ SPI = 8
 TS_ADAPTIVE = np.linspace(0.0, 3e-4, 7)
 STAGE = {"DFX_PERSIST": "0", "DFX_WT": "0"}
 ARMS = {"stage": STAGE, "stage_wt": {"DFX_PERSIST": "0", "DFX_WT": "1"}, "stage_notab": dict(STAGE, DFX_FN_TABLE="0"),
-        "persistent": {"DFX_PERSIST": "1"}, "quadmap": dict(STAGE, DFX_PACK3="0")}
+        "persistent": {"DFX_PERSIST": "1"}, "quadmap": dict(STAGE, DFX_PACK3="0"),
+        "quadmap_wt": {"DFX_PERSIST": "0", "DFX_WT": "1", "DFX_PACK3": "0"}}
 LEVELS = ("records", "stages", "state", "segments")
 SWITCHES = ("DFX_PERSIST", "DFX_WT", "DFX_FN_TABLE", "DFX_PACK3", "DFX_CHECKPOINT", "DFX_STAGE_CHECKPOINT", "DFX_STAGE_BUILDS", "DFX_DICT_LDS",
             "DFX_ADAPTIVE_RECORDS", "DFX_PERSIST_MAX_WG", "DFX_PERSIST_CHUNKS", "DFX_STREAMS", "DFX_EAGER_STEPS")
@@ -86,7 +88,7 @@ def _codes(eng):
 
 def _check_codes(arm, level, mc, eng):
     """The build code the dispatch implies (engine_launch.hip): 3 the persistent loops (persist_shape_ok: the ligament models without
-    distance contact; the reverse loop at the records and segments levels), 2 the per-stage builds (kernel_build_code: the same physics, write-
+    distance contact; the reverse loop at the records and segments levels), 2 the per-stage builds (build_code, dfx_builds.h: the same physics, write-
     through stores, the table, the common parameter shape -- the ``uniform`` image), 0 the generic builds."""
     fwd, raw, tree = _codes(eng)
     what = (arm, level, mc.model, mc.contact, fwd, raw, tree)
@@ -94,7 +96,7 @@ def _check_codes(arm, level, mc, eng):
     assert eng["fwd_stats_again"]["tile_kernels"] == fwd, what
     if arm == "persistent" and serves:
         assert fwd == 3 and raw == 3, what
-    elif arm == "stage_wt":
+    elif arm in ("stage_wt", "quadmap_wt"):
         want = 2 if serves and mc.image == "uniform" else 0
         assert fwd == want and raw == want and tree == 0, what          # (the build that accumulates ligament gradients has no per-stage twin)
     else:
@@ -124,6 +126,8 @@ def test_fixed_grid_on_every_arm_and_level(lattice, model, contact):
         runs.append(("persistent", "segments"))
     if lattice == "kagome" and contact != "distance":
         runs.append(("quadmap", None))
+        if serves:
+            runs.append(("quadmap_wt", None))
     for arm, level in runs:
         mc_arm, eng = _run(lattice, model, contact, dict(ARMS[arm], **({"DFX_CHECKPOINT": level} if level else {})))
         _check_codes(arm, level, mc_arm, eng)

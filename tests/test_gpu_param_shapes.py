@@ -75,7 +75,7 @@ def _codes(eng):
 
 
 def common_shape(sc):
-    """The parameter shape the per-stage builds compile in (engine_launch.hip, hot_shape): every member's stiffnesses and damping uniform
+    """The parameter shape the per-stage builds compile in (dfx_builds.h, stage_build_ok): every member's stiffnesses and damping uniform
     (each member its own values) and every member's dictionary in LDS."""
     return sc.expect["k_uniform"] and sc.expect["damping_uniform"] and sc.dict_layout == "lds"
 
