@@ -68,7 +68,8 @@ COMM_EXPORTS = ["dfx_comm_unique_id", "dfx_comm_init", "dfx_comm_destroy", "dfx_
                 "dfx_mem_info", "dfx_device_synchronize", "dfx_kinetic_value_and_grad_device", "dfx_download", "dfx_forward_kinetic_value_and_grad",
                 "dfx_forward_tangent", "dfx_forward_tangent_dense", "dfx_dense_output_map", "dfx_forward_tangent_multi",
                 "dfx_forward_tangent_dense_multi", "dfx_rhs_jvp", "dfx_objective_value", "dfx_objective_value_and_grad",
-                "dfx_strain_objective_value", "dfx_strain_objective_value_and_grad"]
+                "dfx_strain_objective_value", "dfx_strain_objective_value_and_grad", "dfx_signal_values", "dfx_signal_misfit_value",
+                "dfx_signal_misfit_value_and_grad"]
 EXPORTS = EXPORTS + COMM_EXPORTS
 
 
@@ -154,6 +155,12 @@ def declare(lib):
         lib.dfx_strain_objective_value.argtypes = [H, _dp, C.c_int32, _dp, _dp, _dp]
         lib.dfx_strain_objective_value_and_grad.argtypes = [H, _dp, C.c_int32, _dp, _dp, _dp, C.POINTER(dfx_grads), C.POINTER(dfx_grads),
                                                             C.c_int32, C.POINTER(dfx_stats)]
+    if hasattr(lib, "dfx_signal_misfit_value_and_grad"):
+        terms = [C.c_int32, _ip, _ip, _ip, _dp, C.c_int32]
+        lib.dfx_signal_values.argtypes = [H] + terms + [_dp]
+        lib.dfx_signal_misfit_value.argtypes = [H] + terms + [_dp, C.c_int32, _dp, _dp, _dp]
+        lib.dfx_signal_misfit_value_and_grad.argtypes = [H] + terms + [_dp, C.c_int32, _dp, _dp, _dp, C.POINTER(dfx_grads), C.POINTER(dfx_grads),
+                                                                        C.c_int32, C.POINTER(dfx_stats)]
     if hasattr(lib, "dfx_comm_init"):
         lib.dfx_comm_unique_id.argtypes = [C.c_char_p]
         lib.dfx_comm_init.argtypes = [C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(H)]
@@ -818,6 +825,81 @@ class Engine:
         self._check(self.lib.dfx_strain_objective_value_and_grad(self._h, _ptr(w), wpm, _ptr(tau), _ptr(c), _ptr(obj), C.byref(want),
                                                                  C.byref(views), int(bool(device)), C.byref(st)),
                     "dfx_strain_objective_value_and_grad")
+        if device:
+            return obj, {n: DeviceArray(self, C.cast(getattr(views, n), C.c_void_p).value, sh[n]) for n in names}, _stats(st)
+        out = {}
+        for n in names:
+            a = np.ctypeslib.as_array(getattr(views, n), shape=sh[n])
+            a.flags.writeable = False
+            out[n] = a
+        return obj, out, _stats(st)
+
+    # -- signal misfit on the device-resident history ---------------------------------------------------------
+    @property
+    def has_signal_misfit(self):
+        return hasattr(self.lib, "dfx_signal_misfit_value_and_grad")
+
+    def _signal_terms(self, terms, n_signals):
+        """The term arrays of ``dfx_signal_*``: ``terms`` is a sequence of (signal, block, component, coef)."""
+        if not self.has_signal_misfit:
+            raise NotImplementedError(f"signal misfit: the library {getattr(self.lib, '_name', self.lib)!r} has no "
+                                      "dfx_signal_misfit_value_and_grad (a stale libdfx.so, or the CPU port of the oracle; build the HIP engine)")
+        t = np.asarray(terms, dtype=float).reshape(-1, 4)
+        idx = [np.ascontiguousarray(t[:, i], dtype=np.int32) for i in range(3)]
+        coef = np.ascontiguousarray(t[:, 3], dtype=np.float64)
+        return (len(t), idx[0].ctypes.data_as(_ip), idx[1].ctypes.data_as(_ip), idx[2].ctypes.data_as(_ip), _ptr(coef), int(n_signals)), (idx, coef)
+
+    def _signal_targets(self, n_signals, targets, signal_weights, time_weights):
+        B, T, ns = self.batch, self.n_timepoints, int(n_signals)
+        tg = _f64(targets)
+        if tg.ndim not in (2, 3) or tg.shape[-1] != ns or (tg.ndim == 3 and tg.shape[0] != B) or (T is not None and tg.shape[-2] != T):
+            raise ValueError(f"targets must be ({T}, {ns}) or ({B}, {T}, {ns}), got {tg.shape}")
+        om = tau = None
+        if signal_weights is not None:
+            om = _f64(signal_weights)
+            if om.shape != (ns,):
+                raise ValueError(f"signal_weights must be ({ns},), got {om.shape}")
+        if time_weights is not None:
+            tau = _f64(time_weights)
+            if T is not None and tau.shape != (T,):
+                raise ValueError(f"time_weights must be ({T},), got {tau.shape}")
+        return tg, int(tg.ndim == 3), om, tau
+
+    def signal_values(self, terms, n_signals):
+        """(batch, T, n_signals) signals (``dfx_signal_values``) on the resident history of the last forward pass: linear combinations of
+        displacement (components 0..2), velocity (3..5) and elastic-force (6..8) components of blocks."""
+        args, keep = self._signal_terms(terms, n_signals)
+        out = np.zeros((self.batch, self.n_timepoints or 1, max(int(n_signals), 1)))       # (no forward pass yet: the library refuses before it writes)
+        self._check(self.lib.dfx_signal_values(self._h, *args, _ptr(out)), "dfx_signal_values")
+        return out
+
+    def signal_misfit_value(self, terms, n_signals, targets, signal_weights=None, time_weights=None):
+        """(batch,) least-squares misfit of the signals against ``targets`` (``dfx_signal_misfit_value``)."""
+        args, keep = self._signal_terms(terms, n_signals)
+        tg, tpm, om, tau = self._signal_targets(n_signals, targets, signal_weights, time_weights)
+        obj = np.zeros(self.batch)
+        self._check(self.lib.dfx_signal_misfit_value(self._h, *args, _ptr(tg), tpm, _ptr(om), _ptr(tau), _ptr(obj)), "dfx_signal_misfit_value")
+        return obj
+
+    def signal_misfit_value_and_grad(self, terms, n_signals, targets, signal_weights=None, time_weights=None, which=ALL_GRADS, device=False):
+        """Value (batch,) and the requested gradients of the signal misfit in ONE call (``dfx_signal_misfit_value_and_grad``): channels,
+        signals and residual cotangents are formed on the device, force terms add the Hessian-vector product K w to the cotangent of the
+        reverse sweep and their mixed second derivatives behind it.  Results as :meth:`objective_value_and_grad`."""
+        args, keep = self._signal_terms(terms, n_signals)
+        tg, tpm, om, tau = self._signal_targets(n_signals, targets, signal_weights, time_weights)
+        sh = self.shapes()
+        want, views = dfx_grads(), dfx_grads()
+        names = [n for n in which if not (n == "fn_params" and self.n_fns == 0) and not (n == "contact" and not self.contact)
+                 and not (n == "void_angle0" and self.contact != CONTACT_ANGLE)
+                 and not (n == "block_centroids" and self.contact != CONTACT_DISTANCE)]
+        flag = np.zeros(1)
+        for n in names:
+            setattr(want, n, _ptr(flag))
+        obj = np.zeros(self.batch)
+        st = dfx_stats()
+        self._check(self.lib.dfx_signal_misfit_value_and_grad(self._h, *args, _ptr(tg), tpm, _ptr(om), _ptr(tau), _ptr(obj), C.byref(want),
+                                                              C.byref(views), int(bool(device)), C.byref(st)),
+                    "dfx_signal_misfit_value_and_grad")
         if device:
             return obj, {n: DeviceArray(self, C.cast(getattr(views, n), C.c_void_p).value, sh[n]) for n in names}, _stats(st)
         out = {}

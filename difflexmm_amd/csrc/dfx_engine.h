@@ -145,6 +145,13 @@ struct dfx_handle {
   DevBuf<double> d_obj_w, d_obj_tau, d_obj_lever, d_obj_part;
   const ObjJob* obj_job = nullptr;
   bool obj_centroids = false;
+  // dfx_signal_* (engine_objective.hip): the compacted specification (index tables, coefficients | targets | signal weights), the force
+  // channels, the signals, their residual cotangents and the direction w of the call; sig: how many of each (the explicit terms behind the
+  // sweep read it)
+  DevBuf<int32_t> d_sig_tab;
+  DevBuf<double> d_sig_coef, d_sig_chan, d_sig_S, d_sig_c, d_sig_w;
+  struct SigJob { int n_fb = 0, n_set = 0, n_sig = 0, n_uc = 0, n_terms = 0, n_blocks = 0; bool has_target = false, has_omega = false, has_tau = false;
+                  long long target_stride = 0; } sig;
   std::vector<double> ts;
   std::vector<int> spis;           // RK steps in each output interval (fixed grid)
   std::vector<long long> step0;    // first step ordinal of each interval

@@ -27,8 +27,25 @@
 //   k_strain_objective_explicit  after the sweep: d J / d(own node vector) into g_r, the two void-angle terms into g_phi (phi1 on the end-0
 //                                slot, phi2 on the end-1 slot, as the reverse stage), and on end-0 slots d J / d(reference vector, stiffnesses,
 //                                contact constants) into g_b when the call collects them; one lane per (member, listed slot), output times in order
+//
+// The signal misfit (dfx_signal_values, dfx_signal_misfit_value[_and_grad]): a signal is a linear combination of displacement, velocity and
+// elastic-force components of listed blocks, J_m = 1/2 sum_k tau_k sum_s omega_s (S_mks - Starget_mks)^2.  The per-ligament arithmetic is
+// dfx_signal.h (host and device).  FORCE blocks are the blocks with a force term; the SET holds them and the blocks bonded to them.
+//   k_signal_channels   items (output k, force block j), the four slots of an item on one DPP quad: each lane its own side of its ligament
+//                       in gather form, quad_sum gives dE/d(x, y, theta) of the block, lane 0 stores the three channels
+//   k_signal_residual   one lane per (member, output, signal): the signal's terms in list order (field terms straight from the history)
+//                       give S; the residual cotangent c = tau omega (S - Starget) is stored beside it; value partials / k_objective_finish
+//   k_signal_direction  one lane per (member, output, distinct (block, component)): sum coef c over the terms that name it, in list order --
+//                       a field component goes to its own row of G, a force component into the direction w
+//   k_signal_cotangent  items (output k, block j of the set): Dual records seeded with w on the own and the partner block, the quad-summed
+//                       epsilon parts of dE/d(x, y, theta) are (K w) on the block: ADDED to rows 0..2 of G[(k, m, b)] by lane 0
+//   k_signal_explicit   after the sweep: one lane per (member, slot of the set), output times in order: the epsilon parts of dE/d(node
+//                       vector) into g_r, of dE/dphi1 (end-0 slot) / dE/dphi2 (end-1 slot) into g_phi, and on end-0 slots of dE/d(reference
+//                       vector, stiffnesses, contact constants) into g_b when the call collects them
+// No atomics anywhere: the same history gives the same bits.
 #pragma once
 #include "dfx_kernels.h"
+#include "dfx_signal.h"
 
 namespace {
 
@@ -256,6 +273,205 @@ __global__ __launch_bounds__(64) void k_strain_objective_explicit(DevCtx c, ObjA
       q[2] += tw * (a.lever[0] * S.g.ks); q[3] += tw * (a.lever[1] * S.g.ksh); q[4] += tw * (a.lever[2] * S.g.kr);
       q[5] += tw * S.cg.am; q[6] += tw * S.cg.ac; q[7] += tw * (a.lever[3] * S.cg.kc);
     }
+  }
+  const size_t ms = (size_t)m * c.n_slots + slot;
+  c.g_r[ms * 2] += rx; c.g_r[ms * 2 + 1] += ry;
+  if (CONTACT == 1 && phi != 0.0) { c.g_phi[ms] += phi; c.touch[0] = 1; }
+  if (bonds) for (int i = 0; i < 8; ++i) c.g_b[ms * 8 + i] += q[i];
+}
+
+// ---- signal misfit ------------------------------------------------------------------------------------------------------------------
+constexpr int kObjSignal = 3;              // ObjJob::kind of a signal-misfit call
+
+struct SigArgs {
+  const double* fields;       // batch * T * n_blocks*6
+  const int32_t* fblocks;     // n_fb force blocks
+  const int32_t* fmap;        // n_blocks: index of the block in fblocks, or -1
+  const int32_t* set;         // n_set blocks: force blocks and the blocks bonded to them
+  const int32_t* sig_ptr;     // n_sig + 1: the terms of signal s, in list order
+  const int32_t* term_src;    // >= 0: offset of a field component inside one output time of the history; < 0: -(1 + channel)
+  const double* term_coef;
+  const int32_t* uc_ptr;      // n_uc + 1: the terms that name distinct (block, component) number i, in list order
+  const int32_t* uc_dst;      // >= 0: b*6 + row inside G of one (output, member); < 0: -(1 + channel) inside w
+  const int32_t* uc_sig;      // signal of each such term
+  const double* uc_coef;
+  const double* target;       // (T, n_sig), members target_stride apart (0: shared); null: signal values only
+  const double* omega;        // n_sig or null
+  const double* tau;          // T or null
+  double *chan, *S, *cres, *w;  // batch * T * (n_fb*3 | n_sig | n_sig | n_fb*3)
+  long long target_stride;
+  int n_fb, n_set, n_sig, n_uc;
+};
+
+// what one side of the ligament on `slot` reads at one output time (f: the member's history at that time), as strain_eval
+__device__ __forceinline__ void signal_load(const DevCtx& c, const MemberBases& B, const double* f, int slot, int info, int contact, SignalLigIn& in) {
+  const int b = slot >> 2, ps = info >> 1, pb = ps >> 2;
+  in.o.x = f[(size_t)b * 3]; in.o.y = f[(size_t)b * 3 + 1]; in.o.th = f[(size_t)b * 3 + 2];
+  in.p.x = f[(size_t)pb * 3]; in.p.y = f[(size_t)pb * 3 + 1]; in.p.th = f[(size_t)pb * 3 + 2];
+  fast_sincos(0.5 * in.o.th, &in.o.sh, &in.o.ch);
+  fast_sincos(0.5 * in.p.th, &in.p.sh, &in.p.ch);
+  const double2 ro = ldg<double2>(B.p_r, (u32)slot * 16), rp = ldg<double2>(B.p_r, (u32)ps * 16);
+  in.rox = ro.x; in.roy = ro.y; in.rpx = rp.x; in.rpy = rp.y;
+  if (c.l_dict_on) {
+    const int li = B.p_lidx[slot];
+    in.lx = B.l_dict[li * 4]; in.ly = B.l_dict[li * 4 + 1]; in.l0 = B.l_dict[li * 4 + 2]; in.il0 = B.l_dict[li * 4 + 3];
+  } else {
+    in.lx = B.p_l[(size_t)slot * 2]; in.ly = B.p_l[(size_t)slot * 2 + 1]; in.l0 = sqrt(in.lx * in.lx + in.ly * in.ly); in.il0 = 1.0 / in.l0;
+  }
+  if (c.k_uniform) { in.ks = B.cst[3]; in.ksh = B.cst[4]; in.kr = B.cst[5]; }
+  else { in.ks = B.p_k[(size_t)slot * 4]; in.ksh = B.p_k[(size_t)slot * 4 + 1]; in.kr = B.p_k[(size_t)slot * 4 + 2]; }
+  in.sgn = (info & 1) ? 1.0 : -1.0;
+  in.phi1 = in.phi2 = in.am = in.ac = in.kc = 0.0;
+  if (contact) {
+    const double2 ph = ldg<double2>(B.p_phi, (u32)slot * 16);
+    in.phi1 = ph.x; in.phi2 = ph.y; in.am = B.cst[0]; in.ac = B.cst[1]; in.kc = B.cst[2];
+  }
+}
+
+// grid (chunks of kObjQuads items, members)
+template <int MODEL, int CONTACT>
+__global__ __launch_bounds__(kObjThreads) void k_signal_channels(DevCtx c, SigArgs a) {
+  const int m = blockIdx.y;
+  const long long total = (long long)c.n_timepoints * a.n_fb;
+  const long long item = (long long)blockIdx.x * kObjQuads + (threadIdx.x >> 2);
+  const int kk = threadIdx.x & 3;
+  const bool valid = item < total;
+  double fx = 0.0, fy = 0.0, fth = 0.0;
+  if (valid) {
+    const int k = (int)(item / a.n_fb);
+    const int slot = a.fblocks[(int)(item % a.n_fb)] * 4 + kk;
+    const int info = c.slot_info[slot];
+    if (info >= 0) {
+      SignalLigIn in;
+      signal_load(c, member_bases(c, m), a.fields + ((size_t)m * c.n_timepoints + k) * ((size_t)c.n_blocks * 6), slot, info, CONTACT, in);
+      signal_lig_force<MODEL, CONTACT>(in, fx, fy, fth);
+    }
+  }
+  // every lane of the quad takes part (slots without a ligament and the lanes of a padded item add zeros)
+  fx = quad_sum(fx); fy = quad_sum(fy); fth = quad_sum(fth);
+  if (valid && kk == 0) {
+    double* ch = a.chan + ((size_t)m * total + (size_t)item) * 3;
+    ch[0] = fx; ch[1] = fy; ch[2] = fth;
+  }
+}
+
+// grid (chunks of kObjThreads (output, signal) pairs, members)
+__global__ __launch_bounds__(kObjThreads) void k_signal_residual(DevCtx c, SigArgs a, double* partial) {
+  const int m = blockIdx.y;
+  const long long total = (long long)c.n_timepoints * a.n_sig;
+  const long long item = (long long)blockIdx.x * kObjThreads + threadIdx.x;
+  double val = 0.0;
+  if (item < total) {
+    const int k = (int)(item / a.n_sig), s = (int)(item % a.n_sig);
+    const double* f = a.fields + ((size_t)m * c.n_timepoints + k) * ((size_t)c.n_blocks * 6);
+    const double* ch = a.chan + ((size_t)m * c.n_timepoints + k) * ((size_t)a.n_fb * 3);
+    double S = 0.0;
+    for (int t = a.sig_ptr[s]; t < a.sig_ptr[s + 1]; ++t) {
+      const int src = a.term_src[t];
+      S += a.term_coef[t] * (src >= 0 ? f[src] : ch[-1 - src]);
+    }
+    const size_t at = (size_t)m * total + (size_t)item;
+    a.S[at] = S;
+    if (a.target) {
+      const double r = S - a.target[(size_t)m * a.target_stride + (size_t)item];
+      const double cr = (a.tau ? a.tau[k] : 1.0) * (a.omega ? a.omega[s] : 1.0) * r;
+      a.cres[at] = cr;
+      val = 0.5 * cr * r;
+    }
+  }
+  if (!partial) return;
+  __shared__ double red[kObjWaves];
+  val = obj_wave_sum(val);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = val;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = red[0];
+    for (int wv = 1; wv < kObjWaves; ++wv) s += red[wv];
+    partial[(size_t)m * gridDim.x + blockIdx.x] = s;
+  }
+}
+
+// grid (chunks of kObjThreads (output, distinct (block, component)) pairs, members); every entry of G / w written belongs to one lane
+__global__ __launch_bounds__(kObjThreads) void k_signal_direction(DevCtx c, SigArgs a, double* G) {
+  const int m = blockIdx.y;
+  const long long total = (long long)c.n_timepoints * a.n_uc;
+  const long long item = (long long)blockIdx.x * kObjThreads + threadIdx.x;
+  if (item >= total) return;
+  const int k = (int)(item / a.n_uc), i = (int)(item % a.n_uc);
+  const double* cr = a.cres + ((size_t)m * c.n_timepoints + k) * (size_t)a.n_sig;
+  double v = 0.0;
+  for (int t = a.uc_ptr[i]; t < a.uc_ptr[i + 1]; ++t) v += a.uc_coef[t] * cr[a.uc_sig[t]];
+  const int dst = a.uc_dst[i];
+  if (dst >= 0) G[((size_t)k * c.batch + m) * ((size_t)c.n_blocks * 6) + dst] = v;
+  else a.w[((size_t)m * c.n_timepoints + k) * ((size_t)a.n_fb * 3) + (-1 - dst)] = v;
+}
+
+// the direction on block b at one (member, output): w of a force block, zero elsewhere
+__device__ __forceinline__ bool signal_seed(const SigArgs& a, const double* wk, int b, double* w3) {
+  const int j = a.fmap[b];
+  w3[0] = j >= 0 ? wk[j * 3] : 0.0; w3[1] = j >= 0 ? wk[j * 3 + 1] : 0.0; w3[2] = j >= 0 ? wk[j * 3 + 2] : 0.0;
+  return w3[0] != 0.0 || w3[1] != 0.0 || w3[2] != 0.0;
+}
+
+// grid (chunks of kObjQuads items, members): runs behind k_signal_direction on the same stream (it adds to rows that kernel may have set)
+template <int MODEL, int CONTACT>
+__global__ __launch_bounds__(kObjThreads) void k_signal_cotangent(DevCtx c, SigArgs a, double* G) {
+  const int m = blockIdx.y;
+  const long long total = (long long)c.n_timepoints * a.n_set;
+  const long long item = (long long)blockIdx.x * kObjQuads + (threadIdx.x >> 2);
+  const int kk = threadIdx.x & 3;
+  const bool valid = item < total;
+  double hx = 0.0, hy = 0.0, hth = 0.0;
+  int k = 0, b = 0;
+  if (valid) {
+    k = (int)(item / a.n_set);
+    b = a.set[(int)(item % a.n_set)];
+    const int slot = b * 4 + kk;
+    const int info = c.slot_info[slot];
+    if (info >= 0) {
+      const double* wk = a.w + ((size_t)m * c.n_timepoints + k) * ((size_t)a.n_fb * 3);
+      double wo[3], wp[3];
+      const bool so = signal_seed(a, wk, b, wo), sp = signal_seed(a, wk, info >> 3, wp);
+      if (so || sp) {
+        SignalLigIn in;
+        SignalLigOut out;
+        signal_load(c, member_bases(c, m), a.fields + ((size_t)m * c.n_timepoints + k) * ((size_t)c.n_blocks * 6), slot, info, CONTACT, in);
+        signal_lig_eps<MODEL, CONTACT>(in, wo, wp, out);
+        hx = out.hx; hy = out.hy; hth = out.hth;
+      }
+    }
+  }
+  hx = quad_sum(hx); hy = quad_sum(hy); hth = quad_sum(hth);
+  if (valid && kk == 0) {
+    double* g = G + ((size_t)k * c.batch + m) * ((size_t)c.n_blocks * 6) + (size_t)b * 6;
+    g[0] += hx; g[1] += hy; g[2] += hth;
+  }
+}
+
+// grid (chunks of 64 slots of the set, members); every accumulator entry touched belongs to one lane
+template <int MODEL, int CONTACT>
+__global__ __launch_bounds__(64) void k_signal_explicit(DevCtx c, SigArgs a) {
+  const int m = blockIdx.y;
+  const int idx = blockIdx.x * 64 + threadIdx.x;
+  if (idx >= a.n_set * 4) return;
+  const int b = a.set[idx >> 2], slot = b * 4 + (idx & 3);
+  const int info = c.slot_info[slot];
+  if (info < 0) return;
+  const MemberBases B = member_bases(c, m);
+  const bool end0 = !(info & 1), bonds = c.g_b && end0;
+  double rx = 0.0, ry = 0.0, phi = 0.0, q[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int k = 0; k < c.n_timepoints; ++k) {
+    const double* wk = a.w + ((size_t)m * c.n_timepoints + k) * ((size_t)a.n_fb * 3);
+    double wo[3], wp[3];
+    const bool so = signal_seed(a, wk, b, wo), sp = signal_seed(a, wk, info >> 3, wp);
+    if (!so && !sp) continue;
+    SignalLigIn in;
+    SignalLigOut out;
+    signal_load(c, B, a.fields + ((size_t)m * c.n_timepoints + k) * ((size_t)c.n_blocks * 6), slot, info, CONTACT, in);
+    signal_lig_eps<MODEL, CONTACT>(in, wo, wp, out);
+    rx += out.rx; ry += out.ry;
+    phi += end0 ? out.p1 : out.p2;
+    if (bonds) for (int i = 0; i < 8; ++i) q[i] += out.q[i];
   }
   const size_t ms = (size_t)m * c.n_slots + slot;
   c.g_r[ms * 2] += rx; c.g_r[ms * 2 + 1] += ry;

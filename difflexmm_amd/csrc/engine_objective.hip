@@ -3,6 +3,8 @@
 // reverse sweep, "add the explicit d objective / d parameters" after it: the sweep itself is run_adjoint, unchanged.
 // The ligament strain-energy objective (dfx_strain_objective_value[_and_grad]) takes the same route with kernels of its own: its cotangent
 // on the fields is the weighted ligament force, its explicit terms reach node vectors, void angles and the per-ligament parameters.
+// The signal misfit (dfx_signal_values, dfx_signal_misfit_value[_and_grad]) likewise: force channels, signals and residual cotangents on the
+// device, the Hessian-vector product K w of its force terms added to the cotangent, mixed second derivatives behind the sweep.
 // (shared declarations in dfx_engine.h, the kernels in dfx_objective.h)
 #include "dfx_engine.h"
 #include "dfx_objective.h"
@@ -178,11 +180,175 @@ int launch_strain(dfx_handle* h, const ObjJob& j, double* G, double* objective_h
   return 0;
 }
 
+// ---- signal misfit: the term list compacted into index tables.  FORCE blocks: the blocks with a force term (components 6..8); the SET: those
+// and the blocks bonded to them (every ligament with an end on a force block is evaluated from both of its ends)
+struct SigTerms { int32_t n; const int32_t *signal, *block, *comp; const double* coef; int32_t n_signals; };
+
+int prepare_signal(dfx_handle* h, const char* who, const SigTerms& t, const double* targets, int32_t targets_per_member, const double* omega,
+                   const double* tau, bool want_target) {
+  const Plan& pl = h->pl;
+  const size_t B = pl.batch, nb = pl.n_blocks;
+  const int Tn = (int)h->ts.size(), ns = t.n_signals;
+  const std::string w(who);
+  if (ns <= 0) { h->err = w + ": n_signals must be positive"; return 1; }
+  if (t.n <= 0 || !t.signal || !t.block || !t.comp || !t.coef) { h->err = w + ": an empty term list (a NULL term array, or n_terms <= 0)"; return 1; }
+  if (want_target && !targets) { h->err = w + ": targets is NULL"; return 1; }
+  std::vector<int> count(ns, 0);
+  bool force = false;
+  for (int i = 0; i < t.n; ++i) {
+    if (t.signal[i] < 0 || t.signal[i] >= ns) { h->err = w + ": term " + std::to_string(i) + " names signal " + std::to_string(t.signal[i]) + " out of range (n_signals = " + std::to_string(ns) + ")"; return 1; }
+    if (t.block[i] < 0 || (size_t)t.block[i] >= nb) { h->err = w + ": term " + std::to_string(i) + " names block " + std::to_string(t.block[i]) + " out of range (n_blocks = " + std::to_string(nb) + ")"; return 1; }
+    if (t.comp[i] < 0 || t.comp[i] > 8) { h->err = w + ": term " + std::to_string(i) + " names component " + std::to_string(t.comp[i]) + " out of range (0..2 displacement, 3..5 velocity, 6..8 elastic force)"; return 1; }
+    if (!std::isfinite(t.coef[i])) { h->err = w + ": non-finite coefficient"; return 1; }
+    ++count[t.signal[i]];
+    force = force || t.comp[i] >= 6;
+  }
+  for (int s = 0; s < ns; ++s)
+    if (!count[s]) { h->err = w + ": signal " + std::to_string(s) + " is empty (no term names it)"; return 1; }
+  if (force && pl.contact == DFX_CONTACT_DISTANCE) {
+    h->err = w + ": force components need the ligament and angle-contact energy (the distance-based contact energy is not part of the signal channels)";
+    return 1;
+  }
+  if (force && pl.n_ovf) {
+    h->err = w + ": nodes with more than one ligament (a general bond list with extra ligaments) are not supported by the force components of a signal";
+    return 1;
+  }
+  const size_t n_tg = want_target ? (targets_per_member ? B : 1) * (size_t)Tn * ns : 0;
+  for (size_t i = 0; i < n_tg; ++i)
+    if (!std::isfinite(targets[i])) { h->err = w + ": non-finite target"; return 1; }
+  for (int s = 0; want_target && omega && s < ns; ++s)
+    if (!std::isfinite(omega[s])) { h->err = w + ": non-finite signal weight"; return 1; }
+  for (int k = 0; want_target && tau && k < Tn; ++k)
+    if (!std::isfinite(tau[k])) { h->err = w + ": non-finite time weight"; return 1; }
+  // force blocks and the set
+  std::vector<int32_t> fmap(nb, -1), fblocks, set;
+  std::vector<char> in_f(nb, 0), in_set(nb, 0);
+  for (int i = 0; i < t.n; ++i) if (t.comp[i] >= 6) in_f[t.block[i]] = 1;
+  for (size_t b = 0; b < nb; ++b) {
+    if (!in_f[b]) continue;
+    fmap[b] = (int32_t)fblocks.size();
+    fblocks.push_back((int32_t)b);
+    in_set[b] = 1;
+    for (int kk = 0; kk < 4; ++kk) {
+      const int info = pl.slot_info[b * 4 + kk];
+      if (info >= 0) in_set[info >> 3] = 1;
+    }
+  }
+  for (size_t b = 0; b < nb; ++b) if (in_set[b]) set.push_back((int32_t)b);
+  // the terms by signal, list order kept
+  std::vector<int32_t> sig_ptr(ns + 1, 0), term_src(t.n);
+  std::vector<double> term_coef(t.n);
+  for (int s = 0; s < ns; ++s) sig_ptr[s + 1] = sig_ptr[s] + count[s];
+  {
+    std::vector<int32_t> at(sig_ptr.begin(), sig_ptr.end() - 1);
+    for (int i = 0; i < t.n; ++i) {
+      const int c = t.comp[i], b = t.block[i], o = at[t.signal[i]]++;
+      term_src[o] = c < 3 ? b * 3 + c : c < 6 ? (int)nb * 3 + b * 3 + (c - 3) : -1 - (fmap[b] * 3 + (c - 6));
+      term_coef[o] = t.coef[i];
+    }
+  }
+  // the terms by distinct (block, component), list order kept; all three components of a force block are listed (w is written whole)
+  std::map<std::pair<int, int>, std::vector<int>> by_dof;
+  for (int32_t b : fblocks) for (int c = 6; c < 9; ++c) by_dof[{b, c}];
+  for (int i = 0; i < t.n; ++i) by_dof[{t.block[i], t.comp[i]}].push_back(i);
+  std::vector<int32_t> uc_ptr(1, 0), uc_dst, uc_sig;
+  std::vector<double> uc_coef;
+  for (const auto& e : by_dof) {
+    const int b = e.first.first, c = e.first.second;
+    uc_dst.push_back(c < 6 ? b * 6 + c : -1 - (fmap[b] * 3 + (c - 6)));
+    for (int i : e.second) { uc_sig.push_back(t.signal[i]); uc_coef.push_back(t.coef[i]); }
+    uc_ptr.push_back((int32_t)uc_sig.size());
+  }
+  dfx_handle::SigJob& J = h->sig;
+  J.n_fb = (int)fblocks.size(); J.n_set = (int)set.size(); J.n_sig = ns; J.n_uc = (int)uc_dst.size(); J.n_terms = t.n; J.n_blocks = (int)nb;
+  J.has_target = want_target; J.has_omega = want_target && omega; J.has_tau = want_target && tau;
+  J.target_stride = targets_per_member ? (long long)Tn * ns : 0;
+  // one int table and one double table, in the order sig_args reads them
+  std::vector<int32_t> tab;
+  for (const std::vector<int32_t>* v : {&fblocks, &fmap, &set, &sig_ptr, &term_src, &uc_ptr, &uc_dst, &uc_sig}) tab.insert(tab.end(), v->begin(), v->end());
+  std::vector<double> dbl(term_coef);
+  dbl.insert(dbl.end(), uc_coef.begin(), uc_coef.end());
+  if (J.has_omega) dbl.insert(dbl.end(), omega, omega + ns);
+  if (J.has_tau) dbl.insert(dbl.end(), tau, tau + Tn);
+  if (want_target) dbl.insert(dbl.end(), targets, targets + n_tg);
+  HIP_OK(h->d_sig_tab.ensure(tab.size()));
+  HIP_OK(h->d_sig_coef.ensure(dbl.size()));
+  HIP_OK(h->d_sig_chan.ensure(B * Tn * (size_t)J.n_fb * 3));
+  HIP_OK(h->d_sig_w.ensure(B * Tn * (size_t)J.n_fb * 3));
+  HIP_OK(h->d_sig_S.ensure(B * Tn * (size_t)ns));
+  HIP_OK(h->d_sig_c.ensure(B * Tn * (size_t)ns));
+  HIP_OK(h->d_obj.ensure(B));
+  HIP_OK(hipMemcpyAsync(h->d_sig_tab.p, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipMemcpyAsync(h->d_sig_coef.p, dbl.data(), sizeof(double) * dbl.size(), hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));       // the tables are locals of this function
+  return 0;
+}
+
+SigArgs sig_args(const dfx_handle* h) {
+  const dfx_handle::SigJob& J = h->sig;
+  const int Tn = (int)h->ts.size();
+  SigArgs a;
+  a.fields = h->d_fields.p;
+  const int32_t* ip = h->d_sig_tab.p;
+  a.fblocks = ip; ip += J.n_fb;
+  a.fmap = ip; ip += J.n_blocks;
+  a.set = ip; ip += J.n_set;
+  a.sig_ptr = ip; ip += J.n_sig + 1;
+  a.term_src = ip; ip += J.n_terms;
+  a.uc_ptr = ip; ip += J.n_uc + 1;
+  a.uc_dst = ip; ip += J.n_uc;
+  a.uc_sig = ip;
+  const double* dp = h->d_sig_coef.p;
+  a.term_coef = dp; dp += J.n_terms;
+  a.uc_coef = dp; dp += J.n_terms;
+  a.omega = J.has_omega ? dp : nullptr; dp += J.has_omega ? J.n_sig : 0;
+  a.tau = J.has_tau ? dp : nullptr; dp += J.has_tau ? Tn : 0;
+  a.target = J.has_target ? dp : nullptr;
+  a.chan = h->d_sig_chan.p; a.S = h->d_sig_S.p; a.cres = h->d_sig_c.p; a.w = h->d_sig_w.p;
+  a.target_stride = J.target_stride;
+  a.n_fb = J.n_fb; a.n_set = J.n_set; a.n_sig = J.n_sig; a.n_uc = J.n_uc;
+  return a;
+}
+
+// channels, signals and (with targets) residual cotangents and the value into d_obj / pinned host memory; with G the cotangent of the sweep
+int launch_signal(dfx_handle* h, double* G, double* objective_host) {
+  const dfx_handle::SigJob& J = h->sig;
+  const size_t B = h->pl.batch;
+  const long long Tn = (long long)h->ts.size();
+  DevCtx c = make_ctx(h);
+  const SigArgs a = sig_args(h);
+  auto chunks_of = [](long long items, int per) { return (unsigned)std::max<long long>(1, (items + per - 1) / per); };
+  if (J.n_fb) {
+    const dim3 grid(chunks_of(Tn * J.n_fb, kObjQuads), (unsigned)B);
+    with_strain_physics(h, [&](auto M, auto C) { hipLaunchKernelGGL((k_signal_channels<M(), C()>), grid, dim3(kObjThreads), 0, h->stream, c, a); });
+  }
+  const unsigned chunks = chunks_of(Tn * J.n_sig, kObjThreads);
+  if (J.has_target) HIP_OK(h->d_obj_part.ensure(B * chunks));
+  hipLaunchKernelGGL(k_signal_residual, dim3(chunks, (unsigned)B), dim3(kObjThreads), 0, h->stream, c, a, J.has_target ? h->d_obj_part.p : nullptr);
+  if (J.has_target)
+    hipLaunchKernelGGL(k_objective_finish, dim3((unsigned)B), dim3(kObjThreads), 0, h->stream, (const double*)h->d_obj_part.p, (int)chunks, h->d_obj.p,
+                       objective_host);
+  if (G) {
+    hipLaunchKernelGGL(k_signal_direction, dim3(chunks_of(Tn * J.n_uc, kObjThreads), (unsigned)B), dim3(kObjThreads), 0, h->stream, c, a, G);
+    if (J.n_set) {
+      const dim3 grid(chunks_of(Tn * J.n_set, kObjQuads), (unsigned)B);
+      with_strain_physics(h, [&](auto M, auto C) { hipLaunchKernelGGL((k_signal_cotangent<M(), C()>), grid, dim3(kObjThreads), 0, h->stream, c, a, G); });
+    }
+  }
+  return 0;
+}
+
 }  // namespace
 
 void launch_objective_explicit(dfx_handle* h, const DevCtx& c) {
   const ObjJob& j = *h->obj_job;
   if (j.n_act == 0) return;
+  if (j.kind == kObjSignal) {
+    const SigArgs a = sig_args(h);
+    const dim3 grid((unsigned)((a.n_set * 4 + 63) / 64), (unsigned)h->pl.batch);
+    with_strain_physics(h, [&](auto M, auto C) { hipLaunchKernelGGL((k_signal_explicit<M(), C()>), grid, dim3(64), 0, h->stream, c, a); });
+    return;
+  }
   if (j.kind == kObjStrain) {
     const ObjArgs a = strain_args(h, j);
     const dim3 grid((unsigned)((j.n_act * 4 + 63) / 64), (unsigned)h->pl.batch);
@@ -286,6 +452,68 @@ int dfx_strain_objective_value_and_grad(dfx_handle* h, const double* bond_weight
   set_grad_wishes(h, want);
   if (zero_grad_accumulators(h, h->d_G.p, B * Tn * nb * 6, (int)h->segs.size())) return 2;
   if (int rc = launch_strain(h, oh.job, h->d_G.p, objective ? reinterpret_cast<double*>(h->obj_stage.p) : nullptr)) return rc;
+  if (int rc = run_adjoint(h, want, nullptr, views, stats, false, 0, true)) return rc;
+  if (objective) memcpy(objective, h->obj_stage.p, sizeof(double) * B);
+  return 0;
+}
+
+int dfx_signal_values(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block, const int32_t* term_component,
+                      const double* term_coef, int32_t n_signals, double* values) {
+  HIP_OK(hipSetDevice(h->device));
+  if (!h->have_fields || !h->have_params) { h->err = "signal_values: run forward first"; return 1; }
+  if (!values) { h->err = "signal_values: values is NULL"; return 1; }
+  const SigTerms t{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
+  if (int rc = prepare_signal(h, "signal_values", t, nullptr, 0, nullptr, nullptr, false)) return rc;
+  if (int rc = launch_signal(h, nullptr, nullptr)) return rc;
+  HIP_OK(hipMemcpyAsync(values, h->d_sig_S.p, sizeof(double) * h->pl.batch * h->ts.size() * (size_t)n_signals, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int dfx_signal_misfit_value(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block, const int32_t* term_component,
+                            const double* term_coef, int32_t n_signals, const double* targets, int32_t targets_per_member,
+                            const double* signal_weights, const double* time_weights, double* objective) {
+  HIP_OK(hipSetDevice(h->device));
+  if (!h->have_fields || !h->have_params) { h->err = "signal_misfit_value: run forward first"; return 1; }
+  if (!objective) { h->err = "signal_misfit_value: objective is NULL"; return 1; }
+  const SigTerms t{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
+  if (int rc = prepare_signal(h, "signal_misfit_value", t, targets, targets_per_member, signal_weights, time_weights, true)) return rc;
+  if (int rc = launch_signal(h, nullptr, nullptr)) return rc;
+  HIP_OK(hipMemcpyAsync(objective, h->d_obj.p, sizeof(double) * h->pl.batch, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int dfx_signal_misfit_value_and_grad(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block,
+                                     const int32_t* term_component, const double* term_coef, int32_t n_signals, const double* targets,
+                                     int32_t targets_per_member, const double* signal_weights, const double* time_weights, double* objective,
+                                     const dfx_grads* want, dfx_grads* views, int32_t device_views, dfx_stats* stats) {
+  HIP_OK(hipSetDevice(h->device));
+  if (!h->have_traj || !h->have_fields) { h->err = "signal_misfit_value_and_grad: run forward with keep_trajectory=1 first"; return 1; }
+  if (h->ck->writer != h) { h->err = std::string("signal_misfit_value_and_grad: ") + kStaleCheckpoint; return 1; }
+  const Plan& pl = h->pl;
+  const size_t B = pl.batch, nb = pl.n_blocks;
+  const int Tn = (int)h->ts.size();
+  const SigTerms t{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
+  if (int rc = prepare_signal(h, "signal_misfit_value_and_grad", t, targets, targets_per_member, signal_weights, time_weights, true)) return rc;
+  if (ensure_adjoint_buffers(h)) return 2;
+  HIP_OK(h->d_G.ensure(B * Tn * nb * 6));
+  if (objective) HIP_OK(h->obj_stage.ensure(sizeof(double) * B));
+  // as dfx_objective_value_and_grad: what the sweep consults on the handle for this call is taken back on every way out
+  struct Scope {
+    dfx_handle* h;
+    ~Scope() { h->obj_job = nullptr; h->obj_centroids = false; h->device_views = false; }
+  } scope{h};
+  ObjJob job;
+  job.kind = kObjSignal; job.n_act = h->sig.n_set; job.w_stride = job.lever_stride = 0; job.has_tau = h->sig.has_tau;
+  h->obj_centroids = false;
+  h->obj_job = &job;
+  h->device_views = device_views != 0;
+  set_grad_wishes(h, want);
+  if (zero_grad_accumulators(h, h->d_G.p, B * Tn * nb * 6, (int)h->segs.size())) return 2;
+  if (int rc = launch_signal(h, h->d_G.p, objective ? reinterpret_cast<double*>(h->obj_stage.p) : nullptr)) return rc;
   if (int rc = run_adjoint(h, want, nullptr, views, stats, false, 0, true)) return rc;
   if (objective) memcpy(objective, h->obj_stage.p, sizeof(double) * B);
   return 0;

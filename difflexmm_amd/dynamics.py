@@ -810,6 +810,30 @@ class DynamicSolver:
         self.adjoint_stats = stats
         return obj, grads
 
+    def signal_values(self, spec):
+        """(batch, T, n_signals) signals of an ``objective.SignalSpec`` on the device-resident history of the last solve (any forward
+        pass): field components are read from the history, force components are the elastic force dE/d(x, y, theta) on the block,
+        evaluated there -- no second handle, no upload of states."""
+        return self.engine.signal_values(spec.terms, spec.n_signals)
+
+    def signal_misfit_value(self, spec):
+        """(batch,) least-squares misfit of an ``objective.SignalSpec`` against its targets on the device-resident history."""
+        return self.engine.signal_misfit_value(spec.terms, spec.n_signals, spec.targets, spec.omega, spec.tau)
+
+    def signal_misfit_value_and_raw(self, spec, which=("centroid_node_vectors", "void_angle0", "inertia"), device=False):
+        """The signal misfit (``objective.SignalSpec``) of the last kept solve, evaluated and differentiated on the device beside
+        :meth:`strain_objective_value_and_raw`: the residual cotangent and, for force terms, the Hessian-vector product that carries it
+        onto the fields are formed in HBM; the mixed second derivatives of the force terms (node vectors, void angles and, when ``which``
+        names them, ``reference_vector`` / ``k_bond`` / ``contact``) are already in the raw gradients returned.  As with :meth:`vjp_raw`,
+        ``fn_params`` holds what the sweep accumulates: the direct dependence of a prescribed output DOF on its drive is not in it."""
+        which = tuple(w for w in which if not (w == "void_angle0" and self.spec.contact != _b.CONTACT_ANGLE))
+        if self.spec.contact == _b.CONTACT_DISTANCE and "block_centroids" not in which:
+            which = which + ("block_centroids",)
+        obj, grads, stats = self.engine.signal_misfit_value_and_grad(spec.terms, spec.n_signals, spec.targets, spec.omega, spec.tau, which=which,
+                                                                     device=device)
+        self.adjoint_stats = stats
+        return obj, grads
+
     @staticmethod
     def _bond_params_bar(bp, kb, refv_bar, like):
         """Gradient tree with the structure of the bond parameters that were passed in (LigamentParams /

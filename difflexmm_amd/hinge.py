@@ -125,6 +125,19 @@ class _HingeBase:
         applied_u = self.applied_displacement(solution_data.timepoints, **control_params.constraint_params)
         return np.array([applied_u, force_history * self.force_multiplier])
 
+    def reaction_signal(self, targets=None, omega=None):
+        """The (multiplied) reaction force as an ``objective.SignalSpec``: force_multiplier * the sum of the elastic force on the driven
+        top-row DOFs, one signal."""
+        from .objective import SignalSpec
+        return SignalSpec.force_sum(self.reaction_block_DOF_pairs, self.force_multiplier, targets, omega)
+
+    def force_displacement_device(self, control_params):
+        """:meth:`force_displacement` of the LAST solve of ``solve_dynamics`` (:meth:`solve` with these parameters), evaluated on that
+        solve's own handle from its device-resident history (``DynamicSolver.signal_values``): no second handle, no upload of states."""
+        force_history = self.solve_dynamics.signal_values(self.reaction_signal())[0, :, 0]
+        applied_u = self.applied_displacement(self.timepoints, **control_params.constraint_params)
+        return np.array([applied_u, force_history])
+
     def force_vjp(self, solution_data, control_params, force_bar):
         """Cotangent ``force_bar`` (T,) of the (multiplied) force history -> (cotangent of the fields, explicit d/d(k_stretch, k_shear,
         k_rot)): one batched Hessian-vector call.  With w = -force_bar * mult * m on the reaction DOFs as cotangent of the accelerations,
@@ -298,10 +311,12 @@ class HingeResponseError:
         self.target_forces = np.array([resample(u, f, n) for u, f, _ in self.target_responses.values()])
         self.is_setup = True
 
-    def compute_fitted_responses(self, k_values):
+    def compute_fitted_responses(self, k_values, on_device=False):
         for p in self.forward_problems:
             if not p.is_setup:
                 p.setup()
+        if on_device:
+            return {p.loading_type: p.force_displacement_device(p.solve(k_values)[1]) for p in self.forward_problems}
         return {p.loading_type: p.force_displacement(*p.solve(k_values)) for p in self.forward_problems}
 
     def objective_fn(self, k_values):
@@ -323,6 +338,23 @@ class HingeResponseError:
             fields_bar, explicit = p.force_vjp(sol, cp, 2.0 * (forces - target) / total)
             implicit = p.solve_dynamics.vjp_raw(fields_bar, which=("k_bond",))["k_bond"]
             grad += explicit + np.asarray(implicit, dtype=float)[0].sum(0)
+        return value, tuple(grad)
+
+    def value_and_grad_device(self, k_values):
+        """:meth:`value_and_grad` with the misfit evaluated and differentiated on the kept solve of every test (one
+        ``signal_misfit_value_and_grad`` call each, omega = 2 / total and coef = force_multiplier): the history is not downloaded, no
+        second handle is loaded, the Hessian-vector product and the explicit stiffness term are formed on the device."""
+        if not self.is_setup:
+            self.setup_objective()
+        total = self.target_forces.size
+        value, grad = 0.0, np.zeros(3)
+        for p, target in zip(self.forward_problems, self.target_forces):
+            cp = p.control_params(k_values)
+            p.solve_dynamics(p.state0, p.timepoints, cp, keep_trajectory=True, want_fields=False)
+            spec = p.reaction_signal(np.asarray(target, dtype=float)[:, None], omega=[2.0 / total])
+            v, raw = p.solve_dynamics.signal_misfit_value_and_raw(spec, which=("k_bond",))
+            value += float(v[0])
+            grad += np.asarray(raw["k_bond"], dtype=float)[0].sum(0)
         return value, tuple(grad)
 
     def residuals_and_jacobian(self, k_values):
@@ -357,14 +389,17 @@ class HingeResponseError:
                                       max_evaluations=n_iterations)
         self.fitted_responses = self.compute_fitted_responses(tuple(float(a) for a in history["x"][-1]))
 
-    def run_optimization_GD(self, initial_guess, n_iterations, step_size, lower_bound=None, upper_bound=None, verbose=False):
-        self.objective_values, self.design_values = naive_GD(self.value_and_grad, initial_guess, step_size, n_iterations, lower_bound,
+    def run_optimization_GD(self, initial_guess, n_iterations, step_size, lower_bound=None, upper_bound=None, verbose=False, on_device=False):
+        """``on_device=True``: every evaluation is :meth:`value_and_grad_device`."""
+        self.objective_values, self.design_values = naive_GD(self.value_and_grad_device if on_device else self.value_and_grad, initial_guess, step_size, n_iterations, lower_bound,
                                                              upper_bound, verbose)
-        self.fitted_responses = self.compute_fitted_responses(self.design_values[-1])
+        self.fitted_responses = self.compute_fitted_responses(self.design_values[-1], on_device)
 
-    def run_optimization_nlopt(self, initial_guess, n_iterations, max_time=None, lower_bound=None, upper_bound=None, verbose=False):
+    def run_optimization_nlopt(self, initial_guess, n_iterations, max_time=None, lower_bound=None, upper_bound=None, verbose=False,
+                               on_device=False):
         """:668-721 with the method of moving asymptotes of ``difflexmm_amd.optimize`` where the reference calls NLopt's LD_MMA
-        (minimisation, bounds, at most ``n_iterations`` evaluations)."""
+        (minimisation, bounds, at most ``n_iterations`` evaluations).  ``on_device=True``: every evaluation is
+        :meth:`value_and_grad_device`."""
         import time
         from .optimize import mma_minimize
         t0 = time.perf_counter()
@@ -375,7 +410,7 @@ class HingeResponseError:
         def fun(x):
             if max_time is not None and self.objective_values and time.perf_counter() - t0 > max_time:
                 raise _TimeUp
-            v, g = self.value_and_grad(tuple(x))
+            v, g = (self.value_and_grad_device if on_device else self.value_and_grad)(tuple(x))
             self.objective_values.append(v)
             self.design_values.append(tuple(float(a) for a in x))
             if verbose:
@@ -385,7 +420,7 @@ class HingeResponseError:
             mma_minimize(fun, np.asarray(initial_guess, dtype=float), lower=lower_bound, upper=upper_bound, maxeval=n_iterations)
         except _TimeUp:
             pass
-        self.fitted_responses = self.compute_fitted_responses(self.design_values[-1])
+        self.fitted_responses = self.compute_fitted_responses(self.design_values[-1], on_device)
 
     def to_dict(self):
         return dict(forward_problems=[p.to_dict() for p in self.forward_problems], target_responses=self.target_responses,

@@ -1,7 +1,7 @@
 """Cross-correlation measures between recorded signals -- the names of ``difflexmm/objective.py`` (post-processing of space-time
 records in the notebooks; host code, SciPy where the reference uses ``jax.scipy.signal``) -- and the weighted objectives the engine
 evaluates and differentiates on the device-resident history (``ObjectiveSpec``; ``include/dfx.h``: ``dfx_objective_value_and_grad``;
-``StrainObjectiveSpec``: ``dfx_strain_objective_value_and_grad``)."""
+``StrainObjectiveSpec``: ``dfx_strain_objective_value_and_grad``; ``SignalSpec``: ``dfx_signal_misfit_value_and_grad``)."""
 from typing import Any, NamedTuple
 
 import numpy as np
@@ -206,3 +206,103 @@ def host_strain_value(spec, fields, centroid_node_vectors, bond_connectivity, re
         e = c[0] * 0.5 * k_stretch * (axial * l0) ** 2 + c[1] * 0.5 * k_shear * (shear * l0) ** 2 + c[2] * 0.5 * k_rot * bending ** 2
         out[m] = tau @ (e @ w[m])
     return float(out[0]) if single else out
+
+
+# ---- signal misfit on the device-resident history -------------------------------------------------------------------------------------
+DISPLACEMENT, VELOCITY, FORCE = 0, 3, 6          # first component of each kind: + 0, 1, 2 for x, y, theta
+
+
+class SignalSpec:
+    """A least-squares misfit between target histories and signals that are linear combinations of displacement, velocity and elastic-force
+    components of blocks (``include/dfx.h``: ``dfx_signal_values``, ``dfx_signal_misfit_value[_and_grad]``):
+
+        S_mks = sum over the terms of signal s: coef * channel(block, component; fields_mk, params_m)
+        J_m   = 1/2 sum_k tau_k sum_s omega_s (S_mks - Starget_mks)^2
+
+    ``terms``: a sequence of (signal, block, component, coef); component 0..2 displacement x, y, theta, 3..5 velocity, 6..8 the elastic force
+    dE/d(x, y, theta) on the block; a signal adds its terms in list order.  ``targets`` (T, n_signals) shared or (batch, T, n_signals), or
+    None for a spec that only evaluates signals; ``omega`` (n_signals,) or None = ones; ``tau`` (T,) or None = ones.  Shapes are checked here
+    (``ValueError``); block numbers and lengths against a solve are checked where the spec is used."""
+    __slots__ = ("terms", "n_signals", "targets", "omega", "tau")
+
+    def __init__(self, terms, n_signals=None, targets=None, omega=None, tau=None):
+        t = np.array(terms, dtype=float)
+        if t.ndim != 2 or t.shape[1] != 4 or len(t) == 0:
+            raise ValueError(f"terms must be a non-empty sequence of (signal, block, component, coef), got shape {t.shape}")
+        if not np.isfinite(t).all() or (t[:, :3] != np.round(t[:, :3])).any():
+            raise ValueError("terms: signal, block and component must be integers and every coefficient finite")
+        if (t[:, :3] < 0).any() or (t[:, 2] > 8).any():
+            raise ValueError("terms: signal and block must be >= 0 and component in 0..8 (0..2 displacement, 3..5 velocity, 6..8 force)")
+        ns = int(t[:, 0].max()) + 1 if n_signals is None else int(n_signals)
+        if ns <= 0 or t[:, 0].max() >= ns:
+            raise ValueError(f"terms name signal {int(t[:, 0].max())} but n_signals = {ns}")
+        empty = sorted(set(range(ns)) - set(int(x) for x in t[:, 0]))
+        if empty:
+            raise ValueError(f"signals without terms: {empty}")
+        tg = None
+        if targets is not None:
+            tg = np.array(targets, dtype=float)
+            if tg.ndim not in (2, 3) or tg.shape[-1] != ns:
+                raise ValueError(f"targets must be (T, {ns}) or (batch, T, {ns}), got {tg.shape}")
+        om = None
+        if omega is not None:
+            om = np.array(omega, dtype=float)
+            if om.shape != (ns,):
+                raise ValueError(f"omega must be ({ns},), got {om.shape}")
+        ta = None
+        if tau is not None:
+            ta = np.array(tau, dtype=float)
+            if ta.ndim != 1 or (tg is not None and ta.shape[0] != tg.shape[-2]):
+                raise ValueError(f"tau must be (T,){'' if tg is None else f' with T = {tg.shape[-2]}'}, got {ta.shape}")
+        self.terms = [(int(a), int(b), int(c), float(d)) for a, b, c, d in t]
+        self.n_signals, self.targets, self.omega, self.tau = ns, tg, om, ta
+
+    def __repr__(self):
+        return (f"SignalSpec({len(self.terms)} terms, n_signals={self.n_signals}, targets={None if self.targets is None else self.targets.shape}, "
+                f"omega={self.omega!r}, tau={self.tau!r})")
+
+    @property
+    def has_force(self):
+        return any(c >= FORCE for _, _, c, _ in self.terms)
+
+    @classmethod
+    def fields_of(cls, block_dofs, kind="displacement", targets=None, omega=None, tau=None):
+        """One signal per (block, dof) of the displacement (``kind="displacement"``) or velocity (``"velocity"``) history: tracked block
+        motions.  ``block_dofs``: a sequence of (block, dof), dof 0, 1, 2 = x, y, theta."""
+        if kind not in ("displacement", "velocity"):
+            raise ValueError(f"kind must be 'displacement' or 'velocity', got {kind!r}")
+        base = DISPLACEMENT if kind == "displacement" else VELOCITY
+        bd = np.array(block_dofs, dtype=np.int64).reshape(-1, 2)
+        if len(bd) == 0 or (bd[:, 1] < 0).any() or (bd[:, 1] > 2).any():
+            raise ValueError("block_dofs must be a non-empty sequence of (block, dof) with dof in 0..2")
+        return cls([(s, int(b), base + int(d), 1.0) for s, (b, d) in enumerate(bd)], len(bd), targets, omega, tau)
+
+    @classmethod
+    def force_sum(cls, block_dofs, scale=1.0, targets=None, omega=None, tau=None):
+        """ONE signal: ``scale`` times the sum of the elastic force on the listed (block, dof) pairs -- the reaction force on a set of driven
+        DOFs (``hinge_characterization.py``: force_multiplier * sum of the reaction on the driven DOFs)."""
+        bd = np.array(block_dofs, dtype=np.int64).reshape(-1, 2)
+        if len(bd) == 0 or (bd[:, 1] < 0).any() or (bd[:, 1] > 2).any():
+            raise ValueError("block_dofs must be a non-empty sequence of (block, dof) with dof in 0..2")
+        return cls([(0, int(b), FORCE + int(d), float(scale)) for b, d in bd], 1, targets, omega, tau)
+
+    def with_targets(self, targets, omega=None, tau=None):
+        """The same terms against other targets and weights."""
+        return SignalSpec(self.terms, self.n_signals, targets, omega, tau)
+
+
+def host_signal_values(spec, fields):
+    """NumPy restatement of the signals of a ``SignalSpec`` whose terms are field components (displacement, velocity): ``fields``
+    (batch, T, 2, n_blocks, 3) -> (batch, T, n_signals), or (T, 2, n_blocks, 3) -> (T, n_signals).  Force components have no host path
+    (``ValueError``): they are evaluated on the device, that is the point of ``DynamicSolver.signal_values``."""
+    f = np.asarray(fields, dtype=float)
+    if f.ndim not in (4, 5) or f.shape[-3] != 2 or f.shape[-1] != 3:
+        raise ValueError(f"fields must be (batch, T, 2, n_blocks, 3) or (T, 2, n_blocks, 3), got {f.shape}")
+    if spec.has_force:
+        raise ValueError("host_signal_values: force components are evaluated on the device only (DynamicSolver.signal_values)")
+    out = np.zeros(f.shape[:-3] + (spec.n_signals,))
+    for s, b, c, coef in spec.terms:
+        if b >= f.shape[-2]:
+            raise ValueError(f"block {b} out of range [0, {f.shape[-2]})")
+        out[..., s] += coef * f[..., c // 3, b, c % 3]
+    return out

@@ -1034,6 +1034,80 @@ class TargetStrainEnergy:
         return (obj, grads) if many else (float(obj[0]), grads[0])
 
 
+class TargetSignalMisfit:
+    """objective(design) = 1/2 sum_k tau_k sum_s omega_s (S_ks(design) - Starget_ks)^2 for an ``objective.SignalSpec``: signals that are
+    linear combinations of displacement, velocity and elastic-force components of blocks against target histories -- waveform shaping, a
+    calibration against tracked block motions, a reaction force against a measured one.  A list of designs runs as one ensemble (targets
+    (T, n_signals) shared or (len(designs), T, n_signals); ``run_ensemble_optimization`` accepts the class) on the device
+    (``dfx_signal_misfit_value_and_grad``); one design takes the host path -- signals of field components only: the history is downloaded
+    and the cotangent built in NumPy -- unless ``on_device``.  Force components have no host path."""
+
+    def __init__(self, forward, spec):
+        self.forward, self.spec = forward, spec
+        if spec.targets is None:
+            raise ValueError("TargetSignalMisfit: the SignalSpec has no targets")
+        if not getattr(forward, "is_setup", False):
+            forward.setup()
+        nb = forward.geometry.n_blocks
+        if max(b for _, b, _, _ in spec.terms) >= nb:
+            raise ValueError(f"TargetSignalMisfit: a term names a block out of range [0, {nb})")
+
+    def _chunk_spec(self, i, n):
+        """the spec of designs i .. i + n of a longer list (per-member targets are cut alike)"""
+        sp = self.spec
+        return sp if sp.targets.ndim == 2 else sp.with_targets(sp.targets[i:i + n], sp.omega, sp.tau)
+
+    def _device(self, design, grad):
+        fw = self.forward
+        many = isinstance(design, list)
+        if many and self.spec.targets.ndim == 3 and len(self.spec.targets) != len(design):
+            raise ValueError(f"{len(design)} designs against targets for {len(self.spec.targets)} members")
+        if many and len(design) != fw.batch:
+            if len(design) == 0 or len(design) % fw.batch:
+                raise ValueError(f"{len(design)} designs for a forward problem built with batch={fw.batch}: pass batch designs, or a multiple of it")
+            parts = [TargetSignalMisfit(fw, self._chunk_spec(i, fw.batch))._device(design[i:i + fw.batch], grad) for i in range(0, len(design), fw.batch)]
+            if not grad:
+                return np.concatenate(parts)
+            return np.concatenate([p[0] for p in parts]), [g for p in parts for g in p[1]]
+        fw.solve(design, keep_trajectory=grad, want_fields=False)
+        if not grad:
+            obj = np.asarray(fw.solve_dynamics.signal_misfit_value(self.spec), dtype=float)
+            return obj if many else float(obj[0])
+        obj, raw = fw.solve_dynamics.signal_misfit_value_and_raw(self.spec)
+        grads = design_gradients(fw, design if many else [design], raw)
+        obj = np.asarray(obj, dtype=float)
+        return (obj, grads) if many else (float(obj[0]), grads[0])
+
+    def _host(self, design, grad):
+        from .objective import host_signal_values
+        sp, fw = self.spec, self.forward
+        if sp.has_force:
+            raise ValueError("TargetSignalMisfit: force components are evaluated on the device only: pass on_device=True (or a list of designs)")
+        sol = fw.solve(design, keep_trajectory=grad)
+        S = host_signal_values(sp, sol.fields)
+        T = S.shape[0]
+        tg = sp.targets if sp.targets.ndim == 2 else sp.targets[0]
+        tau = np.ones(T) if sp.tau is None else sp.tau
+        om = np.ones(sp.n_signals) if sp.omega is None else sp.omega
+        c = tau[:, None] * om[None, :] * (S - tg)
+        val = float(0.5 * np.sum(c * (S - tg)))
+        if not grad:
+            return val
+        fb = np.zeros_like(sol.fields)
+        for s, b, comp, coef in sp.terms:
+            fb[:, comp // 3, b, comp % 3] += coef * c[:, s]
+        raw = {k: np.array(v, dtype=float) for k, v in fw.solve_dynamics.vjp_raw(fb).items()}
+        return val, design_gradients(fw, [design], raw)[0]
+
+    def value(self, design, on_device=False):
+        """One design -> float, a list of designs -> (n,) array."""
+        return self._device(design, False) if on_device or isinstance(design, list) else self._host(design, False)
+
+    def value_and_grad(self, design, on_device=False):
+        """Return shapes as ``TargetKineticEnergy.value_and_grad``; only the parameter groups a design reaches are differentiated."""
+        return self._device(design, True) if on_device or isinstance(design, list) else self._host(design, True)
+
+
 class MultiInputTargetKineticEnergy:
     """weights @ [target kinetic energy of every forward problem], all sharing one design
     (problems/quads_focusing_multi_input.py:43-86).  The forward problems differ in their boundary conditions

@@ -2,11 +2,13 @@
 curves of a tension, a compression and a shear test.  No measured curves ship with this repository, so the "experiment" is the response
 of a sample with known stiffnesses; the fit starts elsewhere and must walk towards them.
 
-    python examples/hinge_fit.py [--iterations 12] [--cells 3] [--method mma|lm]
+    python examples/hinge_fit.py [--iterations 12] [--cells 3] [--method mma|lm] [--on-device]
 
 --method mma (the default) is the reference's loop: the method of moving asymptotes on the reverse-mode gradient.  --method lm treats the
 fit as the least-squares problem it is: Levenberg-Marquardt on the residual Jacobian, which forward mode delivers in one pass per test
-(an addition, HingeResponseError.run_optimization_lm).
+(an addition, HingeResponseError.run_optimization_lm).  --on-device (with mma) evaluates and differentiates the misfit on the kept solve
+of every test (HingeResponseError.value_and_grad_device: the signal misfit of include/dfx.h): the histories stay on the device and the
+second, reaction-force handle is not used.
 """
 import argparse
 import math
@@ -43,6 +45,7 @@ def main():
     ap.add_argument("--cells", type=int, default=3)
     ap.add_argument("--timepoints", type=int, default=21)
     ap.add_argument("--method", choices=("mma", "lm"), default="mma")
+    ap.add_argument("--on-device", action="store_true", help="mma: the misfit and its gradient on the kept solve of every test")
     a = ap.parse_args()
     fit = build_fit(a.cells, a.timepoints)
     t0 = time.perf_counter()
@@ -50,8 +53,8 @@ def main():
         fit.run_optimization_lm(START, a.iterations, lower_bound=LOWER, upper_bound=UPPER)
         what = "3 forward-mode solves with 3 tangents each"
     else:
-        fit.run_optimization_nlopt(START, a.iterations, lower_bound=LOWER, upper_bound=UPPER)
-        what = "3 forward + 3 reverse solves each"
+        fit.run_optimization_nlopt(START, a.iterations, lower_bound=LOWER, upper_bound=UPPER, on_device=a.on_device)
+        what = "3 forward + 3 reverse solves each" + (", misfit on the device" if a.on_device else "")
     wall = time.perf_counter() - t0
     best = int(np.argmin(fit.objective_values))
     print(f"{len(fit.objective_values)} evaluations ({what}) in {wall:.2f} s")

@@ -375,6 +375,43 @@ int dfx_strain_objective_value_and_grad(dfx_handle* h, const double* bond_weight
                                         const double* parts4, double* objective, const dfx_grads* want, dfx_grads* views,
                                         int32_t device_views, dfx_stats* stats);
 
+/* Signal misfit on the device-resident history (HIP library only): a least-squares misfit between target histories and signals that are
+ * linear combinations of displacement, velocity and elastic-force components of chosen blocks -- the objective of the hinge
+ * characterisation (problems/hinge_characterization.py: the reaction force on the driven DOFs against a measured one), of a calibration
+ * against tracked block motions and of waveform shaping.  For member m, output time k and signal s
+ *   S_mks = sum over the terms of signal s: coef * channel(block, component; fields_mk, params_m)
+ *   J_m   = 1/2 sum_k tau_k sum_s omega_s (S_mks - Starget_mks)^2
+ * component 0..2: the displacement x, y, theta of the block; 3..5: its velocity; 6..8: the elastic force dE/d(x, y, theta) on it, E the
+ * ligament plus angle-contact energy the handle was created with, at output configuration k with member m's parameters, prescribed DOFs at
+ * the values the fields hold (no damping, no loading, no velocity: what dfx_rhs gives for a state at rest, times the inertia, with the sign
+ * of an energy gradient).
+ * Terms are parallel arrays of n_terms entries (term_signal in 0..n_signals-1, term_block, term_component, term_coef); a signal adds its
+ * terms in list order.  targets: (batch, T, n_signals) when targets_per_member != 0, else (T, n_signals); signal_weights omega: (n_signals,)
+ * or NULL = ones; time_weights tau: EXACTLY T doubles or NULL = ones.
+ * dfx_signal_values writes S (batch, T, n_signals) and dfx_signal_misfit_value J (batch,) after any forward pass.
+ * dfx_signal_misfit_value_and_grad needs the kept trajectory and equals dfx_adjoint on the fields_bar of these formulas -- coef * c on the
+ * row of a field term, c = tau omega (S - Starget), and for force terms the Hessian-vector product K(u_k) w on the position rows, w = sum
+ * coef * c on the listed force DOFs -- PLUS the explicit terms of the force channels, the mixed derivatives d(w . grad E)/dp:
+ * centroid_node_vectors, void_angle0 and, when `want` asks for them, reference_vector, k_bond, contact.  Both come from one dual-number
+ * evaluation of the ligament gradient.  As with dfx_adjoint and the other device objectives, the direct dependence of a PRESCRIBED output
+ * DOF on the parameters of its time function is not part of fn_params (the caller adds it from fields_bar; for a force term on or next to
+ * a driven block that is (K w) on the driven DOF times d drive / d parameter).  want / views / device_views / stats, the sweep forms, the
+ * fixed-order sum of the value (no atomics: the same history gives the same bits) and the refusals of a missing trajectory or a stale
+ * shared checkpoint are those of dfx_strain_objective_value_and_grad; without reference_vector / k_bond / contact in `want` the reverse
+ * sweep runs the same builds as for the kinetic kinds.  Signals of field components alone work for every physics the sweep serves.
+ * Return 1 (dfx_last_error says why): no forward pass (no kept trajectory for the gradient call), a signal, block or component out of
+ * range, a signal without terms, a NULL or non-finite argument, force components on a problem with the distance-based contact or with
+ * nodes that carry more than one ligament. */
+int dfx_signal_values(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block, const int32_t* term_component,
+                      const double* term_coef, int32_t n_signals, double* values);
+int dfx_signal_misfit_value(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block,
+                            const int32_t* term_component, const double* term_coef, int32_t n_signals, const double* targets,
+                            int32_t targets_per_member, const double* signal_weights, const double* time_weights, double* objective);
+int dfx_signal_misfit_value_and_grad(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block,
+                                     const int32_t* term_component, const double* term_coef, int32_t n_signals, const double* targets,
+                                     int32_t targets_per_member, const double* signal_weights, const double* time_weights,
+                                     double* objective, const dfx_grads* want, dfx_grads* views, int32_t device_views, dfx_stats* stats);
+
 /* Post-processing of the last forward solve on its device-resident history (problems/quads_focusing.py:319-372 with
  * energy.py:522-534): strain energies of every ligament 1/2 k (strain |l0|)^2 for the axial, shear and bending strain of
  * the NONLINEAR kinematics, (batch, T, n_bonds) each, and the kinetic energy of every block sum_d m_d v_d^2 / 2,
