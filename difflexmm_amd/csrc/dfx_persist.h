@@ -77,7 +77,7 @@ __global__ __launch_bounds__(kThreads) void k_ring_poison(double* ring, int batc
 // what a lane keeps about its slot's ligament for the whole launch (the stage kernels load this at every stage: issue_lane / resolve_lane)
 struct LigRes {
   double rox, roy, rpx, rpy, lx, ly, l0, il0, ks, ksh, kr, sgn;
-  double am, ac, kc, phi1, phi2, kap_safe, phi_min;      // angle contact
+  double am, ac, kc, phi1, phi2, kap_safe;               // angle contact
   int info, pslot;
 };
 template <int CONTACT, class Ctx /* DevCtx or PersistCtx */>
@@ -99,12 +99,17 @@ __device__ __forceinline__ void load_lig_res(const Ctx& c, const MemberBases& B,
   }
   if (c.k_uniform) { g.ks = B.cst[3]; g.ksh = B.cst[4]; g.kr = B.cst[5]; }
   else { g.ks = ldg<double>(B.p_k, (u32)slot * 32); g.ksh = ldg<double>(B.p_k, (u32)slot * 32 + 8); g.kr = ldg<double>(B.p_k, (u32)slot * 32 + 16); }
-  g.am = g.ac = g.kc = g.phi1 = g.phi2 = g.kap_safe = g.phi_min = 0.0;
+  g.am = g.ac = g.kc = g.phi1 = g.phi2 = g.kap_safe = 0.0;
   if (CONTACT == 1) {
-    g.am = B.cst[0]; g.ac = B.cst[1]; g.kc = B.cst[2]; g.kap_safe = B.cst[9]; g.phi_min = B.cst[10];
+    g.am = B.cst[0]; g.ac = B.cst[1]; g.kc = B.cst[2]; g.kap_safe = B.cst[9];
     const double2 ph = ldg<double2>(B.p_phi, (u32)slot * 16);
     g.phi1 = ph.x; g.phi2 = ph.y;
   }
+}
+// a pointer moved on by a stride kept in BYTES: the loops step their addresses once per stage, and a stride in elements is shifted again
+// at every step (the loops are built without machine-level loop-invariant code motion)
+template <class T> __device__ __forceinline__ T* step_bytes(T* p, long long bytes) {
+  return (T*)((const char*)p + bytes);
 }
 // a per-lane value the compiler must take as new where this stands: what is computed from it stays where it is written
 __device__ __forceinline__ int fresh_v(int x) { asm volatile("" : "+v"(x)); return x; }
@@ -143,6 +148,28 @@ __device__ __forceinline__ unsigned long long tick() {
 #else
 #define DFX_TICK(k)
 #endif
+
+// The wave's issue priority while it computes: the member's rank (dfx_persist_prio.h), the same on every SIMD the member has waves on.
+// s_setprio takes an immediate and ignores EXEC, so the rank -- wave-uniform, in a scalar register -- is switched over: a scalar compare and
+// branch around one s_setprio each.  Raised from the poll to the publish, the part of a stage the member's neighbours wait for; back at 0
+// behind the publish and in front of every poll: a wave that spins never outranks one that computes.  (Raised for the whole stage but the
+// poll pays a third of it: profiles/r18_persist_priority.txt.)
+__device__ __forceinline__ int prio_rank(const PersistArgs& pa, int ml) {
+  return __builtin_amdgcn_readfirstlane(persist_prio(pa.prio != 0, ml, pa.prio, pa.xcd_wg));
+}
+__device__ __forceinline__ void prio_raise(int& rank) {
+  // (the rank taken as new here: compared once outside the loop, the three outcomes are lane masks the loop has no scalar registers for.
+  // Step by step: nested ifs without an else lower to one compare and one branch per level)
+  asm volatile("" : "+s"(rank));
+  if (rank >= 1) {
+    __builtin_amdgcn_s_setprio(1);
+    if (rank >= 2) {
+      __builtin_amdgcn_s_setprio(2);
+      if (rank >= 3) __builtin_amdgcn_s_setprio(3);
+    }
+  }
+}
+__device__ __forceinline__ void prio_drop() { __builtin_amdgcn_s_setprio(0); }
 
 // which member and which of its waves this wave is.  Dense: waves packed one after the other.  XCD-aware (pa.xcd_wg workgroups per member, small
 // lattices): the dispatcher deals workgroups round-robin over the eight XCDs (tools/mock/handoff_scope_mock.hip: workgroup b on XCD b % 8,
@@ -195,6 +222,7 @@ __global__ __launch_bounds__(kPersistThreads) DFX_PERSIST_OCC void k_fwd_persist
   if (!persist_wave(pa, ml, w)) return;
   const LanePos lp = wave_lane_pos<NPB>(w, c.n_blocks);
   if (!lp.valid) return;
+  int rank = prio_rank(pa, ml);
   const int slot = lp.slot, b = lp.b, k = lp.k, kd = k < 3 ? k : 2;
   const u32 um = (u32)ml;                  // the member's number inside the launch (PersistCtx)
   const u32 nd = (u32)c.n_blocks * 3;
@@ -252,12 +280,13 @@ __global__ __launch_bounds__(kPersistThreads) DFX_PERSIST_OCC void k_fwd_persist
   // (state level, c.rps == 1: only the last stage of a step stores, into the state of step n + 1 -- the pointer moves once per step)
   const int keep = recs ? 2 : (c.traj ? 1 : 0);                           // what a stage leaves in the trajectory checkpoint
   double* tr = keep ? traj_m + ((size_t)((u32)n0 * (u32)c.rps) + 1) * rec_step : nullptr;
-  const size_t rec_adv = recs ? rec_step : 0, rec_gap = recs ? (size_t)(u32)(c.rps - s) * rec_step : (keep ? rec_step : 0);
+  const size_t rec_adv = (recs ? rec_step : 0) * 8, rec_gap = (recs ? (size_t)(u32)(c.rps - s) * rec_step : (keep ? rec_step : 0)) * 8;     // bytes
   const u32 o_vrec = (u32)c.n_blocks * (kPos * 8) + o_dof;                // the DOF's velocity inside a record
   const double* ft = c.fn_tab ? c.fn_tab + ((size_t)um * kMaxGraphSteps * kFnRows) * (DFX_MAX_FNS * kFnEntry) : nullptr;
-  const int ft_row = c.fn_tab ? DFX_MAX_FNS * kFnEntry : 0;               // doubles between consecutive rows (no table: the pointer stays null)
+  const int ft_row = c.fn_tab ? DFX_MAX_FNS * kFnEntry * 8 : 0;           // bytes between consecutive rows (no table: the pointer stays null)
   const u32 z_row = constrained ? (u32)(DFX_MAX_FNS * kFnEntry * 8) : 0u;
   double* Am = c.AD ? c.AD + (size_t)um * c.ad_stride + (size_t)n0 * ((u32)(s - 1) * nd) : nullptr;
+  const int am_adv = c.AD ? (int)(nd * 8) : 0;                             // bytes between consecutive stages of the stage checkpoint
   const double* place = pa.ring;                                           // ring place of ordinal t_ord
 #ifdef DFX_PERSIST_TIMING
   unsigned acc_t[6] = {0, 0, 0, 0, 0, 0};
@@ -304,7 +333,9 @@ __global__ __launch_bounds__(kPersistThreads) DFX_PERSIST_OCC void k_fwd_persist
         DFX_TICK(0)
         // ---- the partner's record of this stage
         double pr[4];
+        prio_drop();
         if (!ring_wait(place, r_par, pr, t_ord, pa.give_up, pa.spin_limit)) return;
+        prio_raise(rank);
         DFX_TICK(1)
         if (k < 2 && t_ord + kPAhead <= total) ring_poison(pa.ring + (size_t)(((u32)t_ord + kPAhead) & (kPRing - 1)) * ring_stride, r_own);
         BlockRec<double> p;
@@ -323,12 +354,14 @@ __global__ __launch_bounds__(kPersistThreads) DFX_PERSIST_OCC void k_fwd_persist
           bond_grad<MODEL, double>(o, p, g.rox, g.roy, g.rpx, g.rpy, g.lx, g.ly, g.l0, g.il0, g.ks, g.ksh, g.kr, g.sgn, bg);
           fx = bg.fx; fy = bg.fy; fth = bg.fth;
           if (CONTACT == 1) {
-            // the stage kernels fetch a ligament's own void angles only beyond the culling bound and evaluate the member's smallest
-            // one otherwise (exact zeros either way); the same selection keeps the two forms equal bit for bit
-            const bool far = !(fabs(o.th - p.th) <= g.kap_safe);
-            ContactGrad<double> cg;
-            contact_grad<double>(g.sgn * (o.th - p.th), far ? g.phi1 : g.phi_min, far ? g.phi2 : g.phi_min, g.am, g.ac, g.kc, cg);
-            fth += g.sgn * cg.dkap;
+            // inside the culling bound the penalty and its derivatives are exactly zero (dfx_plan.h, kappa_safe): the stage kernels
+            // evaluate a stand-in void angle there to add those zeros, the loop adds nothing -- equal but for the sign of a zero.  A wave
+            // with no ligament beyond the bound skips the block
+            if (!(fabs(o.th - p.th) <= g.kap_safe)) {
+              ContactGrad<double> cg;
+              contact_grad<double>(g.sgn * (o.th - p.th), g.phi1, g.phi2, g.am, g.ac, g.kc, cg);
+              fth += g.sgn * cg.dkap;
+            }
           }
         }
         DFX_TICK(2)
@@ -358,6 +391,7 @@ __global__ __launch_bounds__(kPersistThreads) DFX_PERSIST_OCC void k_fwd_persist
         DFX_TICK(4)
         const bool last = i == s - 1;
         if (k < 2) ring_store(const_cast<double*>(place), r_own, k == 0 ? x0 : th2, k == 0 ? y1 : sn);
+        prio_drop();
         if (k < 3) {
           const double2 chunk = k == 0 ? make_double2(x0, y1) : make_double2(th2, sn);
           if (keep > (last ? 0 : 1)) {
@@ -373,13 +407,13 @@ __global__ __launch_bounds__(kPersistThreads) DFX_PERSIST_OCC void k_fwd_persist
         if (last) { qn = qnext; vn = vnext; }
         DFX_TICK(5)
         // ---- on to the next stage: one record, one table row, one place in the stage checkpoint
-        tr += rec_adv;
-        ft += ft_row;
-        if (Am && i < s - 1) Am += nd;
+        tr = step_bytes(tr, rec_adv);
+        ft = step_bytes(ft, ft_row);
+        Am = step_bytes(Am, i < s - 1 ? am_adv : 0);
       }
     }
-    tr += rec_gap;
-    ft += (kFnRows - s) * ft_row;
+    tr = step_bytes(tr, rec_gap);
+    ft = step_bytes(ft, (kFnRows - s) * ft_row);
   }
 #ifdef DFX_PERSIST_TIMING
   if (pa.dbg && (threadIdx.x & 63) == 0) {
@@ -421,6 +455,7 @@ __device__ __forceinline__ void adj_persist_body(const PersistCtx& c, const Pers
   if (!persist_wave(pa, ml, w)) return;
   const LanePos lp = wave_lane_pos<NPB>(w, c.n_blocks);
   if (!lp.valid) return;
+  int rank = prio_rank(pa, ml);
   const int slot = lp.slot, b = lp.b, k = lp.k, kd = k < 3 ? k : 2;
   const u32 um = (u32)ml;                  // the member's number inside the launch: every base of PersistCtx points at the launch's first member
   const u32 nd = (u32)c.n_blocks * 3, nd6 = (u32)c.n_blocks * 6;
@@ -471,7 +506,7 @@ __device__ __forceinline__ void adj_persist_body(const PersistCtx& c, const Pers
   s_acc[0][tid] = CONTACT == 1 ? ldg<double>(gpm, (u32)slot * 8) : 0.0;
   s_acc[1][tid] = ldg<double>(bmm, o_dof);
   s_acc[2][tid] = bcm ? ldg<double>(bcm, o_dof) : 0.0;
-  bool phi_any = false;
+  int phi_any = 0;      // (a lane's word, not a bool: a lane mask carried around the stage loop costs seven scalar instructions per stage)
   // where a DOF of a driven / loaded block adds to the time functions' parameter gradients, when they are asked for
   double* const fn_gq = (c.fn_g && k < 3 && sidx >= 0) ? c.fn_g + (((size_t)um * c.n_special + sidx) * DFX_MAX_FNS) * DFX_FN_PARAMS : nullptr;
   // ---- the ring
@@ -484,12 +519,12 @@ __device__ __forceinline__ void adj_persist_body(const PersistCtx& c, const Pers
   // consecutive records of the checkpoint but for the gap between the s stage records and the rps records of a step, consecutive rows
   // of the time-function table but for the rows a step does not use, and alternate in the parity buffer of W):
   const int i_top = (DENSE && sg.base_step + j_top == n_m) ? 0 : s - 1;      // DENSE: of step N_m only stage 0 runs
-  const size_t rec_step = (size_t)((u32)c.batch * ((u32)c.n_blocks * (u32)kStep));     // doubles between consecutive records of one member
+  const size_t rec_step = (size_t)((u32)c.batch * ((u32)c.n_blocks * (u32)kStep)) * 8;  // bytes between consecutive records of one member
   const u32 o_vel = (u32)c.n_blocks * (kPos * 8) + o_dof;                              // the DOF's velocity inside a record
   const double* rec = c.traj + (size_t)((((u32)(sg.base_step + j_top) * (u32)c.rps + (u32)i_top) * (u32)c.batch + um)) * (size_t)((u32)c.n_blocks * (u32)kStep);
   const size_t rec_gap = (size_t)(u32)(c.rps - s) * rec_step;
   const double* ft = c.fn_tab ? c.fn_tab + (((size_t)um * kMaxGraphSteps + (u32)j_top) * kFnRows + (u32)i_top) * (DFX_MAX_FNS * kFnEntry) : nullptr;
-  const int ft_row = c.fn_tab ? DFX_MAX_FNS * kFnEntry : 0;               // doubles between consecutive rows (no table: the pointer stays null)
+  const int ft_row = c.fn_tab ? DFX_MAX_FNS * kFnEntry * 8 : 0;           // bytes between consecutive rows (no table: the pointer stays null)
   int win = (int)(((sg.base_step + j_top) * s + i_top) & 1);
   const double* place = pa.ring;                                                      // ring place of ordinal t_ord
 #ifdef DFX_PERSIST_TIMING
@@ -594,12 +629,14 @@ __device__ __forceinline__ void adj_persist_body(const PersistCtx& c, const Pers
       const double wox = blk_bcast<NPB, 0>(w_d, k), woy = blk_bcast<NPB, 1>(w_d, k), woth = blk_bcast<NPB, 2>(w_d, k);
       double wp[4];
       DFX_TICK(0)
+      prio_drop();
       if (t_ord == 0) {
         const double* Win = c.W + (size_t)((um * 2 + (u32)win) * nd);
         const u32 pb = (u32)(pslot >> 2) * 24;
         const double2 wxy = ldg<double2>(Win, pb);
         wp[0] = wxy.x; wp[1] = wxy.y; wp[2] = ldg<double>(Win, pb + 16);
       } else if (!ring_wait(place, r_par, wp, t_ord, pa.give_up, pa.spin_limit)) return;
+      prio_raise(rank);
       DFX_TICK(1)
       // (the place of ordinal t + kPAhead: half a ring further on)
       if (k < 2 && t_ord + kPAhead < total) ring_poison(pa.ring + (size_t)(((u32)t_ord + kPAhead) & (kPRing - 1)) * ring_stride, r_own);
@@ -607,7 +644,7 @@ __device__ __forceinline__ void adj_persist_body(const PersistCtx& c, const Pers
       o.x = o0.x; o.y = o0.y; o.th = o1.x; o.sh = o1.y; o.ch = half_cos(o.th, o.sh);
       p.x = q0.x; p.y = q0.y; p.th = q1.x; p.sh = q1.y; p.ch = half_cos(p.th, p.sh);
       // ---- Hessian-vector product + mixed parameter derivatives of this slot
-      double hx = 0.0, hy = 0.0, hth = 0.0, ex = 0.0, ey = 0.0, eth = 0.0, d_rx = 0.0, d_ry = 0.0, d_phi = 0.0;
+      double hx = 0.0, hy = 0.0, hth = 0.0, ex = 0.0, ey = 0.0, eth = 0.0, d_rx = 0.0, d_ry = 0.0;
       if (info >= 0) {
         // (the Hessian-vector product written out by hand, as in the records build of the stage kernel: bond_hvp / contact_hvp, dfx_physics.h)
         BondHvp hv;
@@ -616,17 +653,19 @@ __device__ __forceinline__ void adj_persist_body(const PersistCtx& c, const Pers
         ex = hv.fx; ey = hv.fy; eth = hv.fth;
         d_rx = hv.rx; d_ry = hv.ry;
         if (CONTACT == 1) {
-          const bool far = !(fabs(o.th - p.th) <= g.kap_safe);
-          double dk, dke, p1e, p2e;
-          contact_hvp(g.sgn * (o.th - p.th), g.sgn * (woth - wp[2]), far ? g.phi1 : g.phi_min, far ? g.phi2 : g.phi_min, g.am, g.ac, g.kc, dk, dke, p1e, p2e);
-          hth += g.sgn * dke;
-          eth += g.sgn * dk;
-          d_phi = (info & 1) ? p2e : p1e;
+          // (only beyond the culling bound, as in k_fwd_persist: exact zeros otherwise)
+          if (!(fabs(o.th - p.th) <= g.kap_safe)) {
+            double dk, dke, p1e, p2e;
+            contact_hvp(g.sgn * (o.th - p.th), g.sgn * (woth - wp[2]), g.phi1, g.phi2, g.am, g.ac, g.kc, dk, dke, p1e, p2e);
+            hth += g.sgn * dke;
+            eth += g.sgn * dk;
+            const double d_phi = (info & 1) ? p2e : p1e;
+            if (d_phi != 0.0) { s_acc[0][tid] -= d_phi; phi_any = fresh_v(1); }
+          }
         }
         const double2 r_old = s_racc[tid];
         s_racc[tid] = make_double2(r_old.x - d_rx, r_old.y - d_ry);
       }
-      if (CONTACT == 1 && d_phi != 0.0) { s_acc[0][tid] -= d_phi; phi_any = true; }
       DFX_TICK(2)
       const double hw = blk_reduce3<NPB>(hx, hy, hth, k);
       const double dE = blk_reduce3<NPB>(ex, ey, eth, k);
@@ -684,16 +723,17 @@ __device__ __forceinline__ void adj_persist_body(const PersistCtx& c, const Pers
       if (t_ord < total) {
         const double w1 = blk_bcast<NPB, 1>(w_next, k), w2 = blk_bcast<NPB, 2>(w_next, k);
         if (k < 2) ring_store(const_cast<double*>(place), r_own, k == 0 ? w_next : w2, k == 0 ? w1 : 0.0);
+        prio_drop();
       } else if (k < 3) {
         stg<double>(c.W + (size_t)((um * 2 + (u32)(win ^ 1)) * nd), o_dof, w_next);
       }
       // ---- on to the next stage to run: one record, one table row, the other parity
-      rec -= rec_step;
-      ft -= ft_row;
+      rec = step_bytes(rec, -(long long)rec_step);
+      ft = step_bytes(ft, -ft_row);
       win ^= 1;
     }
-    rec -= rec_gap;
-    ft -= (kFnRows - s) * ft_row;
+    rec = step_bytes(rec, -(long long)rec_gap);
+    ft = step_bytes(ft, -(kFnRows - s) * ft_row);
   }
 #ifdef DFX_PERSIST_TIMING
   if (pa.dbg && (threadIdx.x & 63) == 0) {

@@ -6,6 +6,7 @@
 // (Included behind dfx_kernels.h: PersistCtx names dfx::Seg and dfx_special.)
 #pragma once
 #include <hip/hip_runtime.h>
+#include "dfx_persist_prio.h"
 
 namespace dfx_persist {
 
@@ -30,6 +31,7 @@ struct PersistArgs {
   int n_steps, nm, waves_per_member;
   int spin_limit;               // polls before a wave gives up (kSpinLimit; the test hook dfx_test_set_spin_limit makes it tiny)
   int xcd_wg;                   // > 0: workgroups per member, every member on ONE XCD (workgroup b sits on XCD b % 8: persist_wave); 0: waves packed densely
+  int prio;                     // member-ranked issue priority (dfx_persist_prio.h): 0: off, else the launch's workgroups per compute unit
 #ifdef DFX_PERSIST_TIMING
   unsigned* dbg;                // diagnostic build: 8 words per wave (six phase sums, total ticks, stages)
 #endif

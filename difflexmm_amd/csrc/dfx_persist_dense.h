@@ -219,10 +219,12 @@ __global__ __launch_bounds__(kPersistThreads) void k_adaptive_fwd_loop(DevCtx c,
         bond_grad<MODEL, double>(o, p, g.rox, g.roy, g.rpx, g.rpy, g.lx, g.ly, g.l0, g.il0, g.ks, g.ksh, g.kr, g.sgn, bg);
         fx = bg.fx; fy = bg.fy; fth = bg.fth;
         if (CONTACT == 1) {
-          const bool far = !(fabs(o.th - p.th) <= g.kap_safe);
-          ContactGrad<double> cg;
-          contact_grad<double>(g.sgn * (o.th - p.th), far ? g.phi1 : g.phi_min, far ? g.phi2 : g.phi_min, g.am, g.ac, g.kc, cg);
-          fth += g.sgn * cg.dkap;
+          // (only beyond the culling bound, as in k_fwd_persist: exact zeros otherwise)
+          if (!(fabs(o.th - p.th) <= g.kap_safe)) {
+            ContactGrad<double> cg;
+            contact_grad<double>(g.sgn * (o.th - p.th), g.phi1, g.phi2, g.am, g.ac, g.kc, cg);
+            fth += g.sgn * cg.dkap;
+          }
         }
       }
       const double dE = blk_reduce3<4>(fx, fy, fth, k);

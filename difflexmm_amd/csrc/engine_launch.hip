@@ -316,6 +316,11 @@ static int persist_adj_max_chunks() {
   const char* e = getenv("DFX_PERSIST_ADJ_CHUNKS");
   return e ? std::max(1, atoi(e)) : INT_MAX;
 }
+// member-ranked issue priority in the loops (dfx_persist_prio.h); DFX_PERSIST_PRIO=0: every wave at priority 0 (A/B runs)
+static bool persist_prio_on() {
+  const char* e = getenv("DFX_PERSIST_PRIO");
+  return !(e && e[0] == '0');
+}
 // balanced launches: `n_chunks` launches of nm / n_chunks members, the first nm % n_chunks of them one member more
 static int chunk_members(int nm, int n_chunks, int k) { return nm / n_chunks + (k < nm % n_chunks ? 1 : 0); }
 static bool persist_common_ok(dfx_handle* h, const DevCtx& c, bool any_groups = false) {
@@ -511,6 +516,7 @@ static void launch_segment_persist(dfx_handle* h, const DevCtx& c, hipStream_t s
     h->launches++;
     PersistArgs pa;
     pa.give_up = persist_give_up_word(h); pa.n_steps = n_steps; pa.nm = cnt; pa.waves_per_member = h->persist_wpm; pa.spin_limit = persist_spin_limit(h); pa.xcd_wg = xcd_wg;
+    pa.prio = persist_prio_on() ? per_cu : 0;
 #ifdef DFX_PERSIST_TIMING
     pa.dbg = ((reverse ? getenv("DFX_TIMING_REVERSE") != nullptr : getenv("DFX_TIMING_REVERSE") == nullptr) && grid <= 8192) ? persist_dbg_buffer() : nullptr;
 #endif
@@ -567,6 +573,7 @@ void launch_adaptive_persist(dfx_handle* h, const DevCtx& c, hipStream_t st, int
     h->launches++;
     PersistArgs pa;
     pa.ring = h->d_ring.p; pa.give_up = persist_give_up_word(h); pa.n_steps = max_attempts; pa.nm = cnt; pa.waves_per_member = h->persist_wpm; pa.spin_limit = persist_spin_limit(h); pa.xcd_wg = xcd_wg;
+    pa.prio = 0;       // (the controller's loop sets no priority)
 #ifdef DFX_PERSIST_TIMING
     pa.dbg = nullptr;
 #endif
@@ -604,6 +611,7 @@ void launch_adj_dense_persist(dfx_handle* h, const DevCtx& c, hipStream_t st, in
     PersistArgs pa;
     pa.ring = h->d_ring.p + (size_t)cc.m0 * h->pl.n_blocks * kPos;
     pa.give_up = persist_give_up_word(h); pa.n_steps = n_steps; pa.nm = cnt; pa.waves_per_member = h->persist_wpm; pa.spin_limit = persist_spin_limit(h); pa.xcd_wg = xcd_wg;
+    pa.prio = persist_prio_on() ? per_cu : 0;
 #ifdef DFX_PERSIST_TIMING
     pa.dbg = nullptr;
 #endif
