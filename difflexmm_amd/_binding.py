@@ -69,7 +69,8 @@ COMM_EXPORTS = ["dfx_comm_unique_id", "dfx_comm_init", "dfx_comm_destroy", "dfx_
                 "dfx_forward_tangent", "dfx_forward_tangent_dense", "dfx_dense_output_map", "dfx_forward_tangent_multi",
                 "dfx_forward_tangent_dense_multi", "dfx_rhs_jvp", "dfx_objective_value", "dfx_objective_value_and_grad",
                 "dfx_strain_objective_value", "dfx_strain_objective_value_and_grad", "dfx_signal_values", "dfx_signal_misfit_value",
-                "dfx_signal_misfit_value_and_grad"]
+                "dfx_signal_misfit_value_and_grad", "dfx_signal_projections", "dfx_signal_projection_value",
+                "dfx_signal_projection_value_and_grad"]
 EXPORTS = EXPORTS + COMM_EXPORTS
 
 
@@ -161,6 +162,12 @@ def declare(lib):
         lib.dfx_signal_misfit_value.argtypes = [H] + terms + [_dp, C.c_int32, _dp, _dp, _dp]
         lib.dfx_signal_misfit_value_and_grad.argtypes = [H] + terms + [_dp, C.c_int32, _dp, _dp, _dp, C.POINTER(dfx_grads), C.POINTER(dfx_grads),
                                                                         C.c_int32, C.POINTER(dfx_stats)]
+    if hasattr(lib, "dfx_signal_projection_value_and_grad"):
+        terms = [C.c_int32, _ip, _ip, _ip, _dp, C.c_int32]
+        lib.dfx_signal_projections.argtypes = [H] + terms + [_dp, C.c_int32, _dp]
+        lib.dfx_signal_projection_value.argtypes = [H] + terms + [_dp, C.c_int32, _dp, _dp, C.c_int32, _dp]
+        lib.dfx_signal_projection_value_and_grad.argtypes = [H] + terms + [_dp, C.c_int32, _dp, _dp, C.c_int32, _dp, C.POINTER(dfx_grads),
+                                                                            C.POINTER(dfx_grads), C.c_int32, C.POINTER(dfx_stats)]
     if hasattr(lib, "dfx_comm_init"):
         lib.dfx_comm_unique_id.argtypes = [C.c_char_p]
         lib.dfx_comm_init.argtypes = [C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(H)]
@@ -900,6 +907,79 @@ class Engine:
         self._check(self.lib.dfx_signal_misfit_value_and_grad(self._h, *args, _ptr(tg), tpm, _ptr(om), _ptr(tau), _ptr(obj), C.byref(want),
                                                               C.byref(views), int(bool(device)), C.byref(st)),
                     "dfx_signal_misfit_value_and_grad")
+        if device:
+            return obj, {n: DeviceArray(self, C.cast(getattr(views, n), C.c_void_p).value, sh[n]) for n in names}, _stats(st)
+        out = {}
+        for n in names:
+            a = np.ctypeslib.as_array(getattr(views, n), shape=sh[n])
+            a.flags.writeable = False
+            out[n] = a
+        return obj, out, _stats(st)
+
+    # -- signal projections on the device-resident history -----------------------------------------------------
+    @property
+    def has_signal_projection(self):
+        return hasattr(self.lib, "dfx_signal_projection_value_and_grad")
+
+    def _projection_args(self, n_signals, basis, row_weights=None, targets=None, weights=True):
+        """The array arguments of ``dfx_signal_projection*``: basis (n_rows, T), row weights (n_signals, n_rows), targets (n_signals, n_rows)
+        or (batch, n_signals, n_rows) or None = zeros."""
+        if not self.has_signal_projection:
+            raise NotImplementedError(f"signal projections: the library {getattr(self.lib, '_name', self.lib)!r} has no "
+                                      "dfx_signal_projection_value_and_grad (a stale libdfx.so, or the CPU port of the oracle; build the HIP engine)")
+        B, T, ns = self.batch, self.n_timepoints, int(n_signals)
+        b = _f64(basis)
+        if b.ndim != 2 or (T is not None and b.shape[1] != T):
+            raise ValueError(f"basis must be (n_rows, {T}), got {b.shape}")
+        nr = b.shape[0]
+        if not weights:
+            return b, nr, None, None, 0
+        w = _f64(row_weights)
+        if w.shape != (ns, nr):
+            raise ValueError(f"row_weights must be ({ns}, {nr}), got {w.shape}")
+        tg = None
+        if targets is not None:
+            tg = _f64(targets)
+            if tg.shape not in ((ns, nr), (B, ns, nr)):
+                raise ValueError(f"targets must be ({ns}, {nr}) or ({B}, {ns}, {nr}), got {tg.shape}")
+        return b, nr, w, tg, int(tg is not None and tg.ndim == 3)
+
+    def signal_projections(self, terms, n_signals, basis):
+        """(batch, n_signals, n_rows) projections P = B S of the signals on the rows of ``basis`` (``dfx_signal_projections``) on the
+        resident history of the last forward pass."""
+        args, keep = self._signal_terms(terms, n_signals)
+        b, nr, _, _, _ = self._projection_args(n_signals, basis, weights=False)
+        out = np.zeros((self.batch, max(int(n_signals), 1), max(nr, 1)))       # (a refused call: the library refuses before it writes)
+        self._check(self.lib.dfx_signal_projections(self._h, *args, _ptr(b), nr, _ptr(out)), "dfx_signal_projections")
+        return out
+
+    def signal_projection_value(self, terms, n_signals, basis, row_weights, targets=None):
+        """(batch,) weighted quadratic form 1/2 sum W (P - Ptarget)^2 of the projections (``dfx_signal_projection_value``)."""
+        args, keep = self._signal_terms(terms, n_signals)
+        b, nr, w, tg, tpm = self._projection_args(n_signals, basis, row_weights, targets)
+        obj = np.zeros(self.batch)
+        self._check(self.lib.dfx_signal_projection_value(self._h, *args, _ptr(b), nr, _ptr(w), _ptr(tg), tpm, _ptr(obj)), "dfx_signal_projection_value")
+        return obj
+
+    def signal_projection_value_and_grad(self, terms, n_signals, basis, row_weights, targets=None, which=ALL_GRADS, device=False):
+        """Value (batch,) and the requested gradients of the projection objective in ONE call (``dfx_signal_projection_value_and_grad``):
+        the time reduction and the cotangent on the signals are formed on the device, everything behind them is the signal misfit's.
+        Results as :meth:`signal_misfit_value_and_grad`."""
+        args, keep = self._signal_terms(terms, n_signals)
+        b, nr, w, tg, tpm = self._projection_args(n_signals, basis, row_weights, targets)
+        sh = self.shapes()
+        want, views = dfx_grads(), dfx_grads()
+        names = [n for n in which if not (n == "fn_params" and self.n_fns == 0) and not (n == "contact" and not self.contact)
+                 and not (n == "void_angle0" and self.contact != CONTACT_ANGLE)
+                 and not (n == "block_centroids" and self.contact != CONTACT_DISTANCE)]
+        flag = np.zeros(1)
+        for n in names:
+            setattr(want, n, _ptr(flag))
+        obj = np.zeros(self.batch)
+        st = dfx_stats()
+        self._check(self.lib.dfx_signal_projection_value_and_grad(self._h, *args, _ptr(b), nr, _ptr(w), _ptr(tg), tpm, _ptr(obj), C.byref(want),
+                                                                  C.byref(views), int(bool(device)), C.byref(st)),
+                    "dfx_signal_projection_value_and_grad")
         if device:
             return obj, {n: DeviceArray(self, C.cast(getattr(views, n), C.c_void_p).value, sh[n]) for n in names}, _stats(st)
         out = {}

@@ -152,6 +152,9 @@ struct dfx_handle {
   DevBuf<double> d_sig_coef, d_sig_chan, d_sig_S, d_sig_c, d_sig_w;
   struct SigJob { int n_fb = 0, n_set = 0, n_sig = 0, n_uc = 0, n_terms = 0, n_blocks = 0; bool has_target = false, has_omega = false, has_tau = false;
                   long long target_stride = 0; } sig;
+  // dfx_signal_projection* (engine_objective.hip): basis | row weights | targets of the call and the projections P; proj: their layout
+  DevBuf<double> d_proj_coef, d_proj_P;
+  struct ProjJob { int n_rows = 0; bool has_w = false, has_target = false; long long target_stride = 0; } proj;
   std::vector<double> ts;
   std::vector<int> spis;           // RK steps in each output interval (fixed grid)
   std::vector<long long> step0;    // first step ordinal of each interval

@@ -42,6 +42,16 @@
 //   k_signal_explicit   after the sweep: one lane per (member, slot of the set), output times in order: the epsilon parts of dE/d(node
 //                       vector) into g_r, of dE/dphi1 (end-0 slot) / dE/dphi2 (end-1 slot) into g_phi, and on end-0 slots of dE/d(reference
 //                       vector, stiffnesses, contact constants) into g_b when the call collects them
+//
+// The signal projections (dfx_signal_projections, dfx_signal_projection_value[_and_grad]): the same signals projected on n_rows rows of a
+// time basis B shared by the members, P_msj = sum_k B_jk S_mks, J_m = 1/2 sum_s sum_j W_sj (P_msj - Ptarget_msj)^2.  S comes from
+// k_signal_channels + k_signal_residual run without targets; from the cotangent c on, k_signal_direction / _cotangent / _explicit as above.
+//   k_signal_project           the time reduction, one wave per (member, signal, row): lane l adds B_jk S_mks for k = l, l + 64, ... in
+//                              ascending order, then obj_wave_sum over the lanes -- the order is fixed by (T, lane) alone.  Lane 0 stores
+//                              P and holds the pair's term of the value: every (s, j) is counted once; the waves of a workgroup are added
+//                              in order into its partial, k_objective_finish adds the partials
+//   k_signal_project_residual  one lane per (member, output, signal): c_mks = sum_j W_sj (P_msj - Ptarget_msj) B_jk, j ascending, into
+//                              the residual-cotangent buffer
 // No atomics anywhere: the same history gives the same bits.
 #pragma once
 #include "dfx_kernels.h"
@@ -477,6 +487,71 @@ __global__ __launch_bounds__(64) void k_signal_explicit(DevCtx c, SigArgs a) {
   c.g_r[ms * 2] += rx; c.g_r[ms * 2 + 1] += ry;
   if (CONTACT == 1 && phi != 0.0) { c.g_phi[ms] += phi; c.touch[0] = 1; }
   if (bonds) for (int i = 0; i < 8; ++i) c.g_b[ms * 8 + i] += q[i];
+}
+
+// ---- signal projections ---------------------------------------------------------------------------------------------------------------
+constexpr int kObjProject = 4;             // ObjJob::kind of a signal-projection call: a signal job behind the sweep (k_signal_explicit)
+
+struct ProjArgs {
+  const double* basis;        // n_rows * T, shared by the members
+  const double* W;            // n_sig * n_rows, or null: projections only
+  const double* target;       // (n_sig, n_rows), members target_stride apart (0: shared); null: zeros
+  double* P;                  // batch * n_sig * n_rows
+  long long target_stride;
+  int n_rows;
+};
+
+// grid (chunks of kObjWaves (signal, row) pairs, members): wave `pair` of a member holds one (s, j).  Lane l adds B_jk S_mks over
+// k = l, l + 64, ... ascending, obj_wave_sum adds the lanes; a wave past the last pair adds zeros and stores nothing (it stays for the
+// barrier).  With `partial` the value term of the pair sits on lane 0 and the workgroup's waves are added in order.
+__global__ __launch_bounds__(kObjThreads) void k_signal_project(DevCtx c, SigArgs a, ProjArgs p, double* partial) {
+  const int m = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int T = c.n_timepoints;
+  const int pair = blockIdx.x * kObjWaves + wv;
+  const bool valid = pair < a.n_sig * p.n_rows;
+  double v = 0.0, val = 0.0;
+  size_t at = 0;
+  if (valid) {
+    const int s = pair / p.n_rows, j = pair % p.n_rows;
+    const double* S = a.S + (size_t)m * T * a.n_sig + s;
+    const double* b = p.basis + (size_t)j * T;
+    for (int k = lane; k < T; k += 64) v += b[k] * S[(size_t)k * a.n_sig];
+    at = (size_t)m * a.n_sig * p.n_rows + pair;
+  }
+  v = obj_wave_sum(v);
+  if (valid && lane == 0) {
+    p.P[at] = v;
+    if (p.W) {
+      const double r = v - (p.target ? p.target[(size_t)m * p.target_stride + pair] : 0.0);
+      val = 0.5 * p.W[pair] * r * r;
+    }
+  }
+  if (!partial) return;
+  __shared__ double red[kObjWaves];
+  if (lane == 0) red[wv] = val;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = red[0];
+    for (int w = 1; w < kObjWaves; ++w) s += red[w];
+    partial[(size_t)m * gridDim.x + blockIdx.x] = s;
+  }
+}
+
+// grid (chunks of kObjThreads (output, signal) pairs, members), behind k_signal_project on the same stream: the cotangent of the value on
+// the signals, c_mks = sum_j W_sj (P_msj - Ptarget_msj) B_jk with j ascending, into cres -- where k_signal_residual puts tau omega (S - Starget)
+__global__ __launch_bounds__(kObjThreads) void k_signal_project_residual(DevCtx c, SigArgs a, ProjArgs p) {
+  const int m = blockIdx.y;
+  const int T = c.n_timepoints;
+  const long long total = (long long)T * a.n_sig;
+  const long long item = (long long)blockIdx.x * kObjThreads + threadIdx.x;
+  if (item >= total) return;
+  const int k = (int)(item / a.n_sig), s = (int)(item % a.n_sig);
+  const double* P = p.P + ((size_t)m * a.n_sig + s) * p.n_rows;
+  const double* W = p.W + (size_t)s * p.n_rows;
+  const double* tg = p.target ? p.target + (size_t)m * p.target_stride + (size_t)s * p.n_rows : nullptr;
+  double cr = 0.0;
+  for (int j = 0; j < p.n_rows; ++j) cr += W[j] * (P[j] - (tg ? tg[j] : 0.0)) * p.basis[(size_t)j * T + k];
+  a.cres[(size_t)m * total + (size_t)item] = cr;
 }
 
 }  // namespace

@@ -5,6 +5,8 @@
 // on the fields is the weighted ligament force, its explicit terms reach node vectors, void angles and the per-ligament parameters.
 // The signal misfit (dfx_signal_values, dfx_signal_misfit_value[_and_grad]) likewise: force channels, signals and residual cotangents on the
 // device, the Hessian-vector product K w of its force terms added to the cotangent, mixed second derivatives behind the sweep.
+// The signal projections (dfx_signal_projections, dfx_signal_projection_value[_and_grad]) put a time reduction between the signals and
+// their cotangent: P = B S, the value a weighted quadratic form of P, c = B^T (W (P - Ptarget)); from c on the signal misfit's launches.
 // (shared declarations in dfx_engine.h, the kernels in dfx_objective.h)
 #include "dfx_engine.h"
 #include "dfx_objective.h"
@@ -310,6 +312,20 @@ SigArgs sig_args(const dfx_handle* h) {
   return a;
 }
 
+unsigned chunks_of(long long items, int per) { return (unsigned)std::max<long long>(1, (items + per - 1) / per); }
+
+// from the residual cotangents in d_sig_c to the cotangent G of the sweep: the field rows and the direction w, then K w of the force terms
+void launch_signal_reverse(dfx_handle* h, const DevCtx& c, const SigArgs& a, double* G) {
+  const dfx_handle::SigJob& J = h->sig;
+  const size_t B = h->pl.batch;
+  const long long Tn = (long long)h->ts.size();
+  hipLaunchKernelGGL(k_signal_direction, dim3(chunks_of(Tn * J.n_uc, kObjThreads), (unsigned)B), dim3(kObjThreads), 0, h->stream, c, a, G);
+  if (J.n_set) {
+    const dim3 grid(chunks_of(Tn * J.n_set, kObjQuads), (unsigned)B);
+    with_strain_physics(h, [&](auto M, auto C) { hipLaunchKernelGGL((k_signal_cotangent<M(), C()>), grid, dim3(kObjThreads), 0, h->stream, c, a, G); });
+  }
+}
+
 // channels, signals and (with targets) residual cotangents and the value into d_obj / pinned host memory; with G the cotangent of the sweep
 int launch_signal(dfx_handle* h, double* G, double* objective_host) {
   const dfx_handle::SigJob& J = h->sig;
@@ -317,7 +333,6 @@ int launch_signal(dfx_handle* h, double* G, double* objective_host) {
   const long long Tn = (long long)h->ts.size();
   DevCtx c = make_ctx(h);
   const SigArgs a = sig_args(h);
-  auto chunks_of = [](long long items, int per) { return (unsigned)std::max<long long>(1, (items + per - 1) / per); };
   if (J.n_fb) {
     const dim3 grid(chunks_of(Tn * J.n_fb, kObjQuads), (unsigned)B);
     with_strain_physics(h, [&](auto M, auto C) { hipLaunchKernelGGL((k_signal_channels<M(), C()>), grid, dim3(kObjThreads), 0, h->stream, c, a); });
@@ -328,12 +343,74 @@ int launch_signal(dfx_handle* h, double* G, double* objective_host) {
   if (J.has_target)
     hipLaunchKernelGGL(k_objective_finish, dim3((unsigned)B), dim3(kObjThreads), 0, h->stream, (const double*)h->d_obj_part.p, (int)chunks, h->d_obj.p,
                        objective_host);
+  if (G) launch_signal_reverse(h, c, a, G);
+  return 0;
+}
+
+// ---- signal projections: the checks of the basis, the row weights and the targets (return 1 with h->err), prepare_signal without targets
+// for the terms, then basis | row weights | targets into one buffer.  want_w: the call forms a value (row weights required)
+int prepare_projection(dfx_handle* h, const char* who, const SigTerms& t, const double* basis, int32_t n_rows, const double* row_weights,
+                       const double* targets, int32_t targets_per_member, bool want_w) {
+  const size_t B = h->pl.batch;
+  const size_t Tn = h->ts.size();
+  const std::string w(who);
+  if (n_rows < 1) { h->err = w + ": n_rows must be at least 1, got " + std::to_string(n_rows); return 1; }
+  if (!basis) { h->err = w + ": basis is NULL"; return 1; }
+  if (want_w && !row_weights) { h->err = w + ": row_weights is NULL"; return 1; }
+  for (size_t i = 0; i < (size_t)n_rows * Tn; ++i)
+    if (!std::isfinite(basis[i])) { h->err = w + ": non-finite basis entry"; return 1; }
+  const size_t ns = t.n_signals > 0 ? (size_t)t.n_signals : 0, n_w = want_w ? ns * n_rows : 0;
+  const size_t n_tg = want_w && targets ? (targets_per_member ? B : 1) * ns * n_rows : 0;
+  for (size_t i = 0; i < n_w; ++i)
+    if (!std::isfinite(row_weights[i])) { h->err = w + ": non-finite row weight"; return 1; }
+  for (size_t i = 0; i < n_tg; ++i)
+    if (!std::isfinite(targets[i])) { h->err = w + ": non-finite target"; return 1; }
+  if (int rc = prepare_signal(h, who, t, nullptr, 0, nullptr, nullptr, false)) return rc;
+  dfx_handle::ProjJob& J = h->proj;
+  J.n_rows = n_rows; J.has_w = want_w; J.has_target = n_tg != 0;
+  J.target_stride = targets_per_member ? (long long)(ns * n_rows) : 0;
+  std::vector<double> dbl(basis, basis + (size_t)n_rows * Tn);
+  if (n_w) dbl.insert(dbl.end(), row_weights, row_weights + n_w);
+  if (n_tg) dbl.insert(dbl.end(), targets, targets + n_tg);
+  HIP_OK(h->d_proj_coef.ensure(dbl.size()));
+  HIP_OK(h->d_proj_P.ensure(B * ns * n_rows));
+  HIP_OK(hipMemcpyAsync(h->d_proj_coef.p, dbl.data(), sizeof(double) * dbl.size(), hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));       // the table is a local of this function
+  return 0;
+}
+
+ProjArgs proj_args(const dfx_handle* h) {
+  const dfx_handle::ProjJob& J = h->proj;
+  ProjArgs p;
+  const double* dp = h->d_proj_coef.p;
+  p.basis = dp; dp += (size_t)J.n_rows * h->ts.size();
+  p.W = J.has_w ? dp : nullptr; dp += J.has_w ? (size_t)h->sig.n_sig * J.n_rows : 0;
+  p.target = J.has_target ? dp : nullptr;
+  p.P = h->d_proj_P.p;
+  p.target_stride = J.target_stride;
+  p.n_rows = J.n_rows;
+  return p;
+}
+
+// channels and signals (launch_signal without targets), the projections and (with row weights) the value into d_obj / pinned host memory;
+// with G the cotangent c on the signals and from it the cotangent of the sweep
+int launch_projection(dfx_handle* h, double* G, double* objective_host) {
+  const dfx_handle::ProjJob& J = h->proj;
+  const size_t B = h->pl.batch;
+  if (int rc = launch_signal(h, nullptr, nullptr)) return rc;
+  DevCtx c = make_ctx(h);
+  const SigArgs a = sig_args(h);
+  const ProjArgs p = proj_args(h);
+  const unsigned chunks = chunks_of((long long)h->sig.n_sig * J.n_rows, kObjWaves);
+  if (J.has_w) HIP_OK(h->d_obj_part.ensure(B * chunks));
+  hipLaunchKernelGGL(k_signal_project, dim3(chunks, (unsigned)B), dim3(kObjThreads), 0, h->stream, c, a, p, J.has_w ? h->d_obj_part.p : nullptr);
+  if (J.has_w)
+    hipLaunchKernelGGL(k_objective_finish, dim3((unsigned)B), dim3(kObjThreads), 0, h->stream, (const double*)h->d_obj_part.p, (int)chunks, h->d_obj.p,
+                       objective_host);
   if (G) {
-    hipLaunchKernelGGL(k_signal_direction, dim3(chunks_of(Tn * J.n_uc, kObjThreads), (unsigned)B), dim3(kObjThreads), 0, h->stream, c, a, G);
-    if (J.n_set) {
-      const dim3 grid(chunks_of(Tn * J.n_set, kObjQuads), (unsigned)B);
-      with_strain_physics(h, [&](auto M, auto C) { hipLaunchKernelGGL((k_signal_cotangent<M(), C()>), grid, dim3(kObjThreads), 0, h->stream, c, a, G); });
-    }
+    hipLaunchKernelGGL(k_signal_project_residual, dim3(chunks_of((long long)h->ts.size() * h->sig.n_sig, kObjThreads), (unsigned)B), dim3(kObjThreads), 0,
+                       h->stream, c, a, p);
+    launch_signal_reverse(h, c, a, G);
   }
   return 0;
 }
@@ -343,7 +420,7 @@ int launch_signal(dfx_handle* h, double* G, double* objective_host) {
 void launch_objective_explicit(dfx_handle* h, const DevCtx& c) {
   const ObjJob& j = *h->obj_job;
   if (j.n_act == 0) return;
-  if (j.kind == kObjSignal) {
+  if (j.kind == kObjSignal || j.kind == kObjProject) {       // the same direction w, whichever residual it came from
     const SigArgs a = sig_args(h);
     const dim3 grid((unsigned)((a.n_set * 4 + 63) / 64), (unsigned)h->pl.batch);
     with_strain_physics(h, [&](auto M, auto C) { hipLaunchKernelGGL((k_signal_explicit<M(), C()>), grid, dim3(64), 0, h->stream, c, a); });
@@ -514,6 +591,68 @@ int dfx_signal_misfit_value_and_grad(dfx_handle* h, int32_t n_terms, const int32
   set_grad_wishes(h, want);
   if (zero_grad_accumulators(h, h->d_G.p, B * Tn * nb * 6, (int)h->segs.size())) return 2;
   if (int rc = launch_signal(h, h->d_G.p, objective ? reinterpret_cast<double*>(h->obj_stage.p) : nullptr)) return rc;
+  if (int rc = run_adjoint(h, want, nullptr, views, stats, false, 0, true)) return rc;
+  if (objective) memcpy(objective, h->obj_stage.p, sizeof(double) * B);
+  return 0;
+}
+
+int dfx_signal_projections(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block, const int32_t* term_component,
+                           const double* term_coef, int32_t n_signals, const double* basis, int32_t n_rows, double* values) {
+  HIP_OK(hipSetDevice(h->device));
+  if (!h->have_fields || !h->have_params) { h->err = "signal_projections: run forward first"; return 1; }
+  if (!values) { h->err = "signal_projections: values is NULL"; return 1; }
+  const SigTerms t{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
+  if (int rc = prepare_projection(h, "signal_projections", t, basis, n_rows, nullptr, nullptr, 0, false)) return rc;
+  if (int rc = launch_projection(h, nullptr, nullptr)) return rc;
+  HIP_OK(hipMemcpyAsync(values, h->d_proj_P.p, sizeof(double) * h->pl.batch * (size_t)n_signals * (size_t)n_rows, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int dfx_signal_projection_value(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block,
+                                const int32_t* term_component, const double* term_coef, int32_t n_signals, const double* basis, int32_t n_rows,
+                                const double* row_weights, const double* targets, int32_t targets_per_member, double* objective) {
+  HIP_OK(hipSetDevice(h->device));
+  if (!h->have_fields || !h->have_params) { h->err = "signal_projection_value: run forward first"; return 1; }
+  if (!objective) { h->err = "signal_projection_value: objective is NULL"; return 1; }
+  const SigTerms t{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
+  if (int rc = prepare_projection(h, "signal_projection_value", t, basis, n_rows, row_weights, targets, targets_per_member, true)) return rc;
+  if (int rc = launch_projection(h, nullptr, nullptr)) return rc;
+  HIP_OK(hipMemcpyAsync(objective, h->d_obj.p, sizeof(double) * h->pl.batch, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int dfx_signal_projection_value_and_grad(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block,
+                                         const int32_t* term_component, const double* term_coef, int32_t n_signals, const double* basis,
+                                         int32_t n_rows, const double* row_weights, const double* targets, int32_t targets_per_member,
+                                         double* objective, const dfx_grads* want, dfx_grads* views, int32_t device_views, dfx_stats* stats) {
+  HIP_OK(hipSetDevice(h->device));
+  if (!h->have_traj || !h->have_fields) { h->err = "signal_projection_value_and_grad: run forward with keep_trajectory=1 first"; return 1; }
+  if (h->ck->writer != h) { h->err = std::string("signal_projection_value_and_grad: ") + kStaleCheckpoint; return 1; }
+  const Plan& pl = h->pl;
+  const size_t B = pl.batch, nb = pl.n_blocks;
+  const int Tn = (int)h->ts.size();
+  const SigTerms t{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
+  if (int rc = prepare_projection(h, "signal_projection_value_and_grad", t, basis, n_rows, row_weights, targets, targets_per_member, true)) return rc;
+  if (ensure_adjoint_buffers(h)) return 2;
+  HIP_OK(h->d_G.ensure(B * Tn * nb * 6));
+  if (objective) HIP_OK(h->obj_stage.ensure(sizeof(double) * B));
+  // as dfx_objective_value_and_grad: what the sweep consults on the handle for this call is taken back on every way out
+  struct Scope {
+    dfx_handle* h;
+    ~Scope() { h->obj_job = nullptr; h->obj_centroids = false; h->device_views = false; }
+  } scope{h};
+  ObjJob job;
+  job.kind = kObjProject; job.n_act = h->sig.n_set; job.w_stride = job.lever_stride = 0; job.has_tau = false;
+  h->obj_centroids = false;
+  h->obj_job = &job;
+  h->device_views = device_views != 0;
+  set_grad_wishes(h, want);
+  if (zero_grad_accumulators(h, h->d_G.p, B * Tn * nb * 6, (int)h->segs.size())) return 2;
+  if (int rc = launch_projection(h, h->d_G.p, objective ? reinterpret_cast<double*>(h->obj_stage.p) : nullptr)) return rc;
   if (int rc = run_adjoint(h, want, nullptr, views, stats, false, 0, true)) return rc;
   if (objective) memcpy(objective, h->obj_stage.p, sizeof(double) * B);
   return 0;

@@ -834,6 +834,27 @@ class DynamicSolver:
         self.adjoint_stats = stats
         return obj, grads
 
+    def signal_projections(self, spec):
+        """(batch, n_signals, n_rows) projections of the signals of an ``objective.ProjectionSpec`` on the rows of its time basis, on the
+        device-resident history of the last solve (any forward pass)."""
+        return self.engine.signal_projections(spec.signal_spec.terms, spec.signal_spec.n_signals, spec.basis)
+
+    def signal_projection_value(self, spec):
+        """(batch,) weighted quadratic form of the projections of an ``objective.ProjectionSpec`` on the device-resident history."""
+        return self.engine.signal_projection_value(spec.signal_spec.terms, spec.signal_spec.n_signals, spec.basis, spec.row_weights, spec.targets)
+
+    def signal_projection_value_and_raw(self, spec, which=("centroid_node_vectors", "void_angle0", "inertia"), device=False):
+        """The projection objective (``objective.ProjectionSpec``) of the last kept solve, evaluated and differentiated on the device
+        beside :meth:`signal_misfit_value_and_raw`: the time reduction and the cotangent on the signals are formed in HBM; what follows
+        (the Hessian-vector product of force terms, their mixed second derivatives, what ``fn_params`` holds) is that method's."""
+        which = tuple(w for w in which if not (w == "void_angle0" and self.spec.contact != _b.CONTACT_ANGLE))
+        if self.spec.contact == _b.CONTACT_DISTANCE and "block_centroids" not in which:
+            which = which + ("block_centroids",)
+        obj, grads, stats = self.engine.signal_projection_value_and_grad(spec.signal_spec.terms, spec.signal_spec.n_signals, spec.basis,
+                                                                         spec.row_weights, spec.targets, which=which, device=device)
+        self.adjoint_stats = stats
+        return obj, grads
+
     @staticmethod
     def _bond_params_bar(bp, kb, refv_bar, like):
         """Gradient tree with the structure of the bond parameters that were passed in (LigamentParams /

@@ -1,7 +1,8 @@
 """Cross-correlation measures between recorded signals -- the names of ``difflexmm/objective.py`` (post-processing of space-time
 records in the notebooks; host code, SciPy where the reference uses ``jax.scipy.signal``) -- and the weighted objectives the engine
 evaluates and differentiates on the device-resident history (``ObjectiveSpec``; ``include/dfx.h``: ``dfx_objective_value_and_grad``;
-``StrainObjectiveSpec``: ``dfx_strain_objective_value_and_grad``; ``SignalSpec``: ``dfx_signal_misfit_value_and_grad``)."""
+``StrainObjectiveSpec``: ``dfx_strain_objective_value_and_grad``; ``SignalSpec``: ``dfx_signal_misfit_value_and_grad``; ``ProjectionSpec``: ``dfx_signal_projection_value_and_grad``, with ``fourier_basis``
+for its rows)."""
 from typing import Any, NamedTuple
 
 import numpy as np
@@ -306,3 +307,119 @@ def host_signal_values(spec, fields):
             raise ValueError(f"block {b} out of range [0, {f.shape[-2]})")
         out[..., s] += coef * f[..., c // 3, b, c % 3]
     return out
+
+
+# ---- signal projections on the device-resident history --------------------------------------------------------------------------------
+class ProjectionSpec:
+    """The signals of a ``SignalSpec`` projected on the rows of a time basis, and a weighted quadratic form of the coefficients
+    (``include/dfx.h``: ``dfx_signal_projections``, ``dfx_signal_projection_value[_and_grad]``):
+
+        P_msj = sum_k B_jk S_mks
+        J_m   = 1/2 sum_s sum_j W_sj (P_msj - Ptarget_msj)^2
+
+    ``signal_spec``: the terms (its own targets, omega and tau play no part; targets, when present, fix T); ``basis`` (n_rows, T), shared by
+    the members -- quadrature weights and windows are baked into the rows (``fourier_basis``); ``row_weights`` (n_signals, n_rows), any
+    sign; ``targets`` (n_signals, n_rows) shared or (batch, n_signals, n_rows), None = zeros.  Band power at f: a cos and a sin row with
+    equal weights; a matched filter: one row holding the shifted template.  Shapes and finiteness are checked here (``ValueError``);
+    T against a solve where the spec is used."""
+    __slots__ = ("signal_spec", "basis", "row_weights", "targets")
+
+    def __init__(self, signal_spec, basis, row_weights, targets=None):
+        ns = signal_spec.n_signals
+        b = np.array(basis, dtype=float)
+        if b.ndim != 2 or b.shape[0] < 1 or b.shape[1] < 1:
+            raise ValueError(f"basis must be (n_rows, T) with n_rows >= 1, got {b.shape}")
+        if signal_spec.targets is not None and signal_spec.targets.shape[-2] != b.shape[1]:
+            raise ValueError(f"basis has T = {b.shape[1]} but the targets of the signal spec have T = {signal_spec.targets.shape[-2]}")
+        if signal_spec.tau is not None and signal_spec.tau.shape[0] != b.shape[1]:
+            raise ValueError(f"basis has T = {b.shape[1]} but tau of the signal spec has T = {signal_spec.tau.shape[0]}")
+        w = np.array(row_weights, dtype=float)
+        if w.shape != (ns, b.shape[0]):
+            raise ValueError(f"row_weights must be ({ns}, {b.shape[0]}), got {w.shape}")
+        tg = None
+        if targets is not None:
+            tg = np.array(targets, dtype=float)
+            if tg.ndim not in (2, 3) or tg.shape[-2:] != (ns, b.shape[0]):
+                raise ValueError(f"targets must be ({ns}, {b.shape[0]}) or (batch, {ns}, {b.shape[0]}), got {tg.shape}")
+        for name, a in (("basis", b), ("row_weights", w), ("targets", tg)):
+            if a is not None and not np.isfinite(a).all():
+                raise ValueError(f"{name}: non-finite entry")
+        self.signal_spec, self.basis, self.row_weights, self.targets = signal_spec, b, w, tg
+
+    def __repr__(self):
+        return (f"ProjectionSpec({self.signal_spec!r}, basis={self.basis.shape}, row_weights={self.row_weights.shape}, "
+                f"targets={None if self.targets is None else self.targets.shape})")
+
+    @property
+    def n_rows(self):
+        return self.basis.shape[0]
+
+    def with_targets(self, targets):
+        """The same signals, basis and weights against other targets."""
+        return ProjectionSpec(self.signal_spec, self.basis, self.row_weights, targets)
+
+
+def fourier_basis(timepoints, frequencies, window=None, quadrature="trapezoid"):
+    """(2 * len(frequencies), T) rows of a ``ProjectionSpec`` basis: per frequency f the row q_k w_k cos(2 pi f t_k), then the row
+    q_k w_k sin(2 pi f t_k), so that P_cos - i P_sin approximates the integral of s(t) w(t) exp(-2 pi i f t) dt over the output times.
+    ``quadrature``: "trapezoid" weights of the (possibly non-uniform) grid, or "rectangle" = t_{k+1} - t_k with the last spacing repeated
+    (on a uniform grid: dt times the discrete Fourier sum).  ``window``: None, "hann" (0.5 - 0.5 cos(2 pi (t - t_0) / (t_{T-1} - t_0)))
+    or an explicit (T,) array."""
+    t = np.asarray(timepoints, dtype=float)
+    f = np.atleast_1d(np.asarray(frequencies, dtype=float))
+    if t.ndim != 1 or len(t) < 2 or not np.isfinite(t).all() or (np.diff(t) <= 0).any():
+        raise ValueError(f"timepoints must be (T,) with T >= 2, finite and increasing, got shape {t.shape}")
+    if f.ndim != 1 or len(f) == 0 or not np.isfinite(f).all():
+        raise ValueError(f"frequencies must be a non-empty sequence of finite numbers, got shape {f.shape}")
+    dt = np.diff(t)
+    if quadrature == "trapezoid":
+        q = np.zeros_like(t)
+        q[:-1] += 0.5 * dt
+        q[1:] += 0.5 * dt
+    elif quadrature == "rectangle":
+        q = np.append(dt, dt[-1])
+    else:
+        raise ValueError(f"quadrature must be 'trapezoid' or 'rectangle', got {quadrature!r}")
+    if window is None:
+        w = np.ones_like(t)
+    elif isinstance(window, str):
+        if window != "hann":
+            raise ValueError(f"window must be None, 'hann' or a (T,) array, got {window!r}")
+        w = 0.5 - 0.5 * np.cos(2.0 * np.pi * (t - t[0]) / (t[-1] - t[0]))
+    else:
+        w = np.asarray(window, dtype=float)
+        if w.shape != t.shape or not np.isfinite(w).all():
+            raise ValueError(f"window must be ({len(t)},) and finite, got shape {w.shape}")
+    phase = 2.0 * np.pi * f[:, None] * t[None, :]
+    out = np.empty((2 * len(f), len(t)))
+    out[0::2] = q * w * np.cos(phase)
+    out[1::2] = q * w * np.sin(phase)
+    return out
+
+
+def host_projection_values(spec, fields):
+    """NumPy restatement of the projections of a ``ProjectionSpec`` whose terms are field components: ``fields`` (batch, T, 2, n_blocks, 3)
+    -> (batch, n_signals, n_rows), or (T, 2, n_blocks, 3) -> (n_signals, n_rows).  Force components raise, as in ``host_signal_values``."""
+    S = host_signal_values(spec.signal_spec, fields)
+    if S.shape[-2] != spec.basis.shape[1]:
+        raise ValueError(f"basis has T = {spec.basis.shape[1]} but the fields have T = {S.shape[-2]}")
+    return np.einsum("jk,...ks->...sj", spec.basis, S)
+
+
+def host_projection_value_and_cotangent(spec, fields):
+    """(value, fields_bar) of a ``ProjectionSpec`` whose terms are field components: J = 1/2 sum W (P - Ptarget)^2 per member and its
+    cotangent on the fields (what ``vjp`` / ``dfx_adjoint`` take), coef * c_ks on the row of every term with
+    c_ks = sum_j W_sj (P_sj - Ptarget_sj) B_jk.  ``fields`` with or without the member axis; the value is (batch,) or a float."""
+    f = np.asarray(fields, dtype=float)
+    P = host_projection_values(spec, f)
+    tg = 0.0 if spec.targets is None else spec.targets
+    if f.ndim == 4 and np.ndim(tg) == 3:
+        raise ValueError("per-member targets against the fields of one member")
+    r = P - tg
+    d = spec.row_weights * r
+    value = 0.5 * np.sum(d * r, axis=(-2, -1))
+    c = np.einsum("...sj,jk->...ks", d, spec.basis)
+    fb = np.zeros_like(f)
+    for s, b, comp, coef in spec.signal_spec.terms:
+        fb[..., comp // 3, b, comp % 3] += coef * c[..., s]
+    return (float(value) if f.ndim == 4 else value), fb

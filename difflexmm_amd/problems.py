@@ -1108,6 +1108,94 @@ class TargetSignalMisfit:
         return self._device(design, True) if on_device or isinstance(design, list) else self._host(design, True)
 
 
+class TargetSignalProjection:
+    """objective(design) = 1/2 sum_s sum_j W_sj (P_sj(design) - Ptarget_sj)^2 with P_sj = sum_k B_jk S_ks for an
+    ``objective.ProjectionSpec``: the signals of a ``SignalSpec`` projected on a few rows of a time basis -- band power, transmission at the
+    drive frequency, harmonic generation, a matched filter.  Negative weights maximise.  Shaped as ``TargetSignalMisfit``: a list of
+    designs runs as one ensemble (targets (n_signals, n_rows) shared or (len(designs), n_signals, n_rows); ``run_ensemble_optimization``
+    accepts the class) on the device (``dfx_signal_projection_value_and_grad``); one design takes the host path -- field components only --
+    unless ``on_device``.  Force components have no host path."""
+
+    def __init__(self, forward, spec):
+        self.forward, self.spec = forward, spec
+        if not getattr(forward, "is_setup", False):
+            forward.setup()
+        nb = forward.geometry.n_blocks
+        if max(b for _, b, _, _ in spec.signal_spec.terms) >= nb:
+            raise ValueError(f"TargetSignalProjection: a term names a block out of range [0, {nb})")
+
+    def _chunk_spec(self, i, n):
+        """the spec of designs i .. i + n of a longer list (per-member targets are cut alike)"""
+        sp = self.spec
+        return sp if sp.targets is None or sp.targets.ndim == 2 else sp.with_targets(sp.targets[i:i + n])
+
+    def _device(self, design, grad):
+        fw, sp = self.forward, self.spec
+        many = isinstance(design, list)
+        if many and sp.targets is not None and sp.targets.ndim == 3 and len(sp.targets) != len(design):
+            raise ValueError(f"{len(design)} designs against targets for {len(sp.targets)} members")
+        if many and len(design) != fw.batch:
+            if len(design) == 0 or len(design) % fw.batch:
+                raise ValueError(f"{len(design)} designs for a forward problem built with batch={fw.batch}: pass batch designs, or a multiple of it")
+            parts = [TargetSignalProjection(fw, self._chunk_spec(i, fw.batch))._device(design[i:i + fw.batch], grad)
+                     for i in range(0, len(design), fw.batch)]
+            if not grad:
+                return np.concatenate(parts)
+            return np.concatenate([p[0] for p in parts]), [g for p in parts for g in p[1]]
+        fw.solve(design, keep_trajectory=grad, want_fields=False)
+        if not grad:
+            obj = np.asarray(fw.solve_dynamics.signal_projection_value(sp), dtype=float)
+            return obj if many else float(obj[0])
+        obj, raw = fw.solve_dynamics.signal_projection_value_and_raw(sp)
+        grads = design_gradients(fw, design if many else [design], raw)
+        obj = np.asarray(obj, dtype=float)
+        return (obj, grads) if many else (float(obj[0]), grads[0])
+
+    def _host(self, design, grad):
+        from .objective import host_projection_value_and_cotangent
+        sp, fw = self.spec, self.forward
+        if sp.signal_spec.has_force:
+            raise ValueError("TargetSignalProjection: force components are evaluated on the device only: pass on_device=True (or a list of designs)")
+        if sp.targets is not None and sp.targets.ndim == 3:
+            sp = sp.with_targets(sp.targets[0])
+        sol = fw.solve(design, keep_trajectory=grad)
+        val, fb = host_projection_value_and_cotangent(sp, sol.fields)
+        if not grad:
+            return val
+        raw = {k: np.array(v, dtype=float) for k, v in fw.solve_dynamics.vjp_raw(fb).items()}
+        return val, design_gradients(fw, [design], raw)[0]
+
+    def value(self, design, on_device=False):
+        """One design -> float, a list of designs -> (n,) array."""
+        return self._device(design, False) if on_device or isinstance(design, list) else self._host(design, False)
+
+    def value_and_grad(self, design, on_device=False):
+        """Return shapes as ``TargetKineticEnergy.value_and_grad``; only the parameter groups a design reaches are differentiated."""
+        return self._device(design, True) if on_device or isinstance(design, list) else self._host(design, True)
+
+
+def TargetBandPower(forward, block_dofs, kind, frequencies, weights, window=None):
+    """A ``TargetSignalProjection`` whose value is 1/2 sum_s sum_f weights_sf |s^_s(f)|^2: the power of the displacement or velocity
+    (``kind``, as ``SignalSpec.fields_of``) of every listed (block, dof) at every listed frequency, s^(f) the windowed Fourier integral of
+    the signal over the forward problem's own output times (``objective.fourier_basis``: trapezoid weights; ``window`` None, "hann" or a
+    (T,) array).  ``weights`` (n_frequencies,) for every signal or (n_signals, n_frequencies); negative entries maximise the power in
+    that band.  A forward problem whose members have output times of their own is refused: the basis is shared by the members."""
+    from .objective import ProjectionSpec, SignalSpec, fourier_basis
+    if not getattr(forward, "is_setup", False):
+        forward.setup()
+    tp = getattr(forward, "timepoints", None)
+    if tp is None or np.ndim(tp) != 1:
+        raise ValueError("TargetBandPower: the forward problem has no output times of its own shared by all members (per-member timepoints): "
+                         "build an objective.ProjectionSpec for one time grid")
+    sig = SignalSpec.fields_of(block_dofs, kind)
+    f = np.atleast_1d(np.asarray(frequencies, dtype=float))
+    w = np.asarray(weights, dtype=float)
+    if w.shape not in ((len(f),), (sig.n_signals, len(f))):
+        raise ValueError(f"weights must be ({len(f)},) or ({sig.n_signals}, {len(f)}), got {w.shape}")
+    w = np.repeat(np.broadcast_to(w, (sig.n_signals, len(f))), 2, axis=1)        # the cos row and the sin row of a frequency weigh alike
+    return TargetSignalProjection(forward, ProjectionSpec(sig, fourier_basis(tp, f, window), w))
+
+
 class MultiInputTargetKineticEnergy:
     """weights @ [target kinetic energy of every forward problem], all sharing one design
     (problems/quads_focusing_multi_input.py:43-86).  The forward problems differ in their boundary conditions

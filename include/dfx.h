@@ -412,6 +412,37 @@ int dfx_signal_misfit_value_and_grad(dfx_handle* h, int32_t n_terms, const int32
                                      int32_t targets_per_member, const double* signal_weights, const double* time_weights,
                                      double* objective, const dfx_grads* want, dfx_grads* views, int32_t device_views, dfx_stats* stats);
 
+/* Signal projections on the device-resident history (HIP library only): the signals S_mks of dfx_signal_values (the same term arrays, the
+ * same components 0..8) projected on n_rows rows of a time basis, and a weighted quadratic form of the coefficients -- band power (a cos
+ * and a sin row per frequency with equal weights), transmission at the drive frequency, harmonic generation, a matched filter (one row
+ * holding the shifted template).  For member m, signal s and row j
+ *   P_msj = sum_k B_jk S_mks                              k = 0 .. T-1
+ *   J_m   = 1/2 sum_s sum_j W_sj (P_msj - Ptarget_msj)^2
+ *   c_mks = sum_j W_sj (P_msj - Ptarget_msj) B_jk         the cotangent of J on the signals
+ * basis B: (n_rows, T), shared by the members; the library does no trigonometry: quadrature weights and windows are baked into the rows.
+ * row_weights W: (n_signals, n_rows), entries of any sign or zero.  targets Ptarget: (batch, n_signals, n_rows) when targets_per_member
+ * != 0, else (n_signals, n_rows); NULL = zeros.  With B the identity, W_sk = tau_k omega_s and Ptarget = Starget this is the signal misfit.
+ * basis must hold EXACTLY n_rows * T doubles, T the n_timepoints of the last forward pass, row_weights n_signals * n_rows and targets
+ * n_signals * n_rows (times batch when per member): the library cannot check a length.
+ * dfx_signal_projections writes P (batch, n_signals, n_rows) and dfx_signal_projection_value J (batch,) after any forward pass.
+ * dfx_signal_projection_value_and_grad needs the kept trajectory and equals dfx_adjoint on the fields_bar of these formulas -- c takes
+ * the place of tau omega (S - Starget) in dfx_signal_misfit_value_and_grad, all that follows it is that entry's: coef * c on the row of a
+ * field term, K(u_k) w on the position rows for force terms, PLUS the explicit terms of the force channels.  want / views / device_views /
+ * stats, the sweep forms, the checkpoint levels, the kept steps of an adaptive solve, what fn_params holds and the refusals of a missing
+ * trajectory or a stale shared checkpoint are those of dfx_signal_misfit_value_and_grad.  Every sum has a fixed order (lane l of a wave
+ * adds outputs l, l + 64, ... ascending, then the shuffle tree; rows ascending in c) and no atomics: the same history gives the same bits.
+ * Return 1 (dfx_last_error says why): n_rows < 1, a NULL or non-finite basis or row_weights, non-finite targets, and everything the
+ * signal entries refuse. */
+int dfx_signal_projections(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block, const int32_t* term_component,
+                           const double* term_coef, int32_t n_signals, const double* basis, int32_t n_rows, double* values);
+int dfx_signal_projection_value(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block,
+                                const int32_t* term_component, const double* term_coef, int32_t n_signals, const double* basis, int32_t n_rows,
+                                const double* row_weights, const double* targets, int32_t targets_per_member, double* objective);
+int dfx_signal_projection_value_and_grad(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block,
+                                         const int32_t* term_component, const double* term_coef, int32_t n_signals, const double* basis,
+                                         int32_t n_rows, const double* row_weights, const double* targets, int32_t targets_per_member,
+                                         double* objective, const dfx_grads* want, dfx_grads* views, int32_t device_views, dfx_stats* stats);
+
 /* Post-processing of the last forward solve on its device-resident history (problems/quads_focusing.py:319-372 with
  * energy.py:522-534): strain energies of every ligament 1/2 k (strain |l0|)^2 for the axial, shear and bending strain of
  * the NONLINEAR kinematics, (batch, T, n_bonds) each, and the kinetic energy of every block sum_d m_d v_d^2 / 2,
