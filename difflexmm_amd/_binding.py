@@ -70,7 +70,7 @@ COMM_EXPORTS = ["dfx_comm_unique_id", "dfx_comm_init", "dfx_comm_destroy", "dfx_
                 "dfx_forward_tangent_dense_multi", "dfx_rhs_jvp", "dfx_objective_value", "dfx_objective_value_and_grad",
                 "dfx_strain_objective_value", "dfx_strain_objective_value_and_grad", "dfx_signal_values", "dfx_signal_misfit_value",
                 "dfx_signal_misfit_value_and_grad", "dfx_signal_projections", "dfx_signal_projection_value",
-                "dfx_signal_projection_value_and_grad"]
+                "dfx_signal_projection_value_and_grad", "dfx_forward_tangent_signals_multi", "dfx_forward_tangent_signals_dense_multi"]
 EXPORTS = EXPORTS + COMM_EXPORTS
 
 
@@ -146,6 +146,12 @@ def declare(lib):
     if hasattr(lib, "dfx_forward_tangent_dense_multi"):
         lib.dfx_forward_tangent_dense_multi.argtypes = [H, _dp, _dp, C.POINTER(dfx_params), C.c_int32, _dp, C.c_int32, _dp, C.POINTER(C.c_int64),
                                                         C.c_int64, _dp, _dp, C.POINTER(dfx_stats)]
+    if hasattr(lib, "dfx_forward_tangent_signals_multi"):
+        _terms = [C.c_int32, _ip, _ip, _ip, _dp, C.c_int32]
+        lib.dfx_forward_tangent_signals_multi.argtypes = [H, _dp, _dp, C.POINTER(dfx_params), C.c_int32, _dp, C.c_int32, _ip, _dp, C.c_int32] + _terms + [
+            _dp, _dp, C.POINTER(dfx_stats)]
+        lib.dfx_forward_tangent_signals_dense_multi.argtypes = [H, _dp, _dp, C.POINTER(dfx_params), C.c_int32, _dp, C.c_int32, _dp,
+                                                                C.POINTER(C.c_int64), C.c_int64] + _terms + [_dp, _dp, C.POINTER(dfx_stats)]
     if hasattr(lib, "dfx_rhs_jvp"):
         lib.dfx_rhs_jvp.argtypes = [H, _dp, C.c_double, _dp, C.POINTER(dfx_params), C.c_int32, _dp, _dp]
     if hasattr(lib, "dfx_objective_value_and_grad"):
@@ -562,6 +568,52 @@ class Engine:
                                                              ns.ctypes.data_as(C.POINTER(C.c_int64)), st_times.shape[1], _ptr(fields),
                                                              _ptr(fields_dots), C.byref(st)), "dfx_forward_tangent_dense_multi")
         return fields, fields_dots, _stats(st)
+
+    @property
+    def has_forward_tangent_signals(self):
+        return hasattr(self.lib, "dfx_forward_tangent_signals_multi")
+
+    def forward_tangent_signals_multi(self, state0, state0_dots, params_dots, n_dirs, timepoints, steps_per_interval, terms, n_signals,
+                                      step_times=None):
+        """:meth:`forward_tangent_multi` with the history kept on the device (``dfx_forward_tangent_signals_multi``): the signals of
+        ``terms`` (sequence of (signal, block, component, coef), as :meth:`signal_values`) and their tangents along the ``n_dirs``
+        directions.  Returns (signals (batch, T, n_signals), signals_dots (batch, n_dirs, T, n_signals), stats)."""
+        self._need("dfx_forward_tangent_signals_multi")
+        K = int(n_dirs)
+        if K < 1 or (params_dots is not None and len(params_dots) != K):
+            raise ValueError(f"forward_tangent_signals_multi: need n_dirs >= 1 and one params_dot per direction (n_dirs={K})")
+        B, ns = self.batch, max(int(n_signals), 1)
+        state0, ts, T, spis, step_times, per_member = self._fixed_grid_args(state0, timepoints, steps_per_interval, step_times)
+        state0_dots = self._state0_dots(state0_dots, K)
+        p, keep = self._params_dots(params_dots, K)
+        targs, tkeep = self._signal_terms(terms, n_signals)
+        signals, signals_dots = np.zeros((B, T, ns)), np.zeros((B, K, T, ns))      # (a refusal comes before the library writes)
+        st = dfx_stats()
+        self._check(self.lib.dfx_forward_tangent_signals_multi(self._h, _ptr(state0), _ptr(state0_dots), p, K, _ptr(ts), T,
+                                                               spis.ctypes.data_as(_ip), _ptr(step_times), int(per_member), *targs,
+                                                               _ptr(signals), _ptr(signals_dots), C.byref(st)),
+                    "dfx_forward_tangent_signals_multi")
+        return signals, signals_dots, _stats(st)
+
+    def forward_tangent_signals_dense_multi(self, state0, state0_dots, params_dots, n_dirs, timepoints, step_times, n_steps, terms, n_signals):
+        """:meth:`forward_tangent_dense_multi` with the history kept on the device (``dfx_forward_tangent_signals_dense_multi``);
+        ``terms`` and the results as :meth:`forward_tangent_signals_multi`."""
+        self._need("dfx_forward_tangent_signals_dense_multi")
+        K = int(n_dirs)
+        if K < 1 or (params_dots is not None and len(params_dots) != K):
+            raise ValueError(f"forward_tangent_signals_dense_multi: need n_dirs >= 1 and one params_dot per direction (n_dirs={K})")
+        B, ns = self.batch, max(int(n_signals), 1)
+        state0, ts, T, st_times, nst = self._dense_grid_args("forward_tangent_signals_dense_multi", state0, timepoints, step_times, n_steps)
+        state0_dots = self._state0_dots(state0_dots, K)
+        p, keep = self._params_dots(params_dots, K)
+        targs, tkeep = self._signal_terms(terms, n_signals)
+        signals, signals_dots = np.zeros((B, T, ns)), np.zeros((B, K, T, ns))
+        st = dfx_stats()
+        self._check(self.lib.dfx_forward_tangent_signals_dense_multi(self._h, _ptr(state0), _ptr(state0_dots), p, K, _ptr(ts), T, _ptr(st_times),
+                                                                     nst.ctypes.data_as(C.POINTER(C.c_int64)), st_times.shape[1], *targs,
+                                                                     _ptr(signals), _ptr(signals_dots), C.byref(st)),
+                    "dfx_forward_tangent_signals_dense_multi")
+        return signals, signals_dots, _stats(st)
 
     def adaptive_step_counts(self):
         """(batch, T-1) accepted steps of the last forward_adaptive per member and output interval."""

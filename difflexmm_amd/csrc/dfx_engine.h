@@ -300,4 +300,13 @@ int run_adjoint(dfx_handle* h, const dfx_grads* want, dfx_grads* grads, dfx_grad
     bool accumulators_cleared = false);
 // engine_objective.hip: the explicit terms of the objective call in flight (h->obj_job), queued behind the sweep
 void launch_objective_explicit(dfx_handle* h, const DevCtx& c);
+// engine_objective.hip: the term list of a signal call (dfx_signal_*, dfx_forward_tangent_signals_*), checked (return 1 with h->err: a
+// signal, block or component out of range, an empty signal, a non-finite coefficient, force components with the distance-based contact or
+// with extra ligaments) and compacted: the force blocks, their index by block, the set, and the terms by signal in list order
+struct SigTerms { int32_t n; const int32_t *signal, *block, *comp; const double* coef; int32_t n_signals; };
+struct SigTables {
+  std::vector<int32_t> fblocks, fmap, set, sig_ptr, term_src;
+  std::vector<double> term_coef;
+};
+int signal_term_tables(dfx_handle* h, const char* who, const SigTerms& t, SigTables& out);
 #pragma GCC visibility pop

@@ -40,83 +40,30 @@
 // fill the chip take all their directions as slices of width 1 in one pass -- the replicated-members form, which is cheaper there
 // (profiles/r09_tangent_multi.txt); everything else takes one slice of the widest width per pass.  A single direction is KC = 1 with one
 // slice in either form: dfx_forward_tangent and dfx_forward_tangent_dense are these kernels at that width.
+//
+// The signal sink (dfx_forward_tangent_signals[_dense]_multi): instead of downloading fields / fields_dot, a pass ends in three launches on
+// its own buffers -- the history never leaves the device, what is downloaded is (B, KT, T, n_signals):
+//   k_tan_signal_channels  items (output k, force block j), the four slots of an item on one DPP quad, slices along grid.z: each lane its
+//                          own side of its ligament on DualN<KC> (dfx_tangent_signal.h) -- primal rows of fields, tangent rows of the
+//                          slice's directions of fields_dot, the slot's entry of the slice's parameter image and the contact constants
+//                          with their tangents; quad_sum of the value and of every epsilon part in direction order; lane 0 stores chan
+//                          (slice 0) and chan_dot
+//   k_tan_signal_combine   one lane per (member, direction, output, signal): the signal's terms in list order, field terms from
+//                          fields_dot, force terms from chan_dot; the pass's first direction also writes S from fields and chan
+//   k_tan_finite_flags     one flag per workgroup: a non-finite entry of fields / of the pass's fields_dot met on its stride; ordinary
+//                          stores into a buffer of the call, ORed by the host
+// Rows of prescribed DOFs: the position rows of fields_dot hold the exact tangent of c(t) (k_tan_init_multi, the stage, the dense output),
+// so force terms on or beside a driven block are complete here; the velocity rows are 0 and the caller adds dc'/dp . dp to field terms on
+// them (include/dfx.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "dfx_kernels.h"
 #include "dfx_stage.h"
+#include "dfx_tangent_signal.h"
 
 namespace dfx {
 
-// ---------------------------------------------------------------------------------------
-// first-order forward-mode number with K epsilon parts
-// ---------------------------------------------------------------------------------------
-template <int K>
-struct DualN {
-  double v, e[K];
-  DFX_HD DualN() : v(0.0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) e[k] = 0.0;
-  }
-  DFX_HD DualN(double a) : v(a) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) e[k] = 0.0;
-  }
-};
-#define DFX_DN_EACH _Pragma("unroll") for (int k = 0; k < K; ++k)
-template <int K> DFX_HD DualN<K> operator+(DualN<K> a, DualN<K> b) { DualN<K> r; r.v = a.v + b.v; DFX_DN_EACH r.e[k] = a.e[k] + b.e[k]; return r; }
-template <int K> DFX_HD DualN<K> operator-(DualN<K> a, DualN<K> b) { DualN<K> r; r.v = a.v - b.v; DFX_DN_EACH r.e[k] = a.e[k] - b.e[k]; return r; }
-template <int K> DFX_HD DualN<K> operator-(DualN<K> a) { DualN<K> r; r.v = -a.v; DFX_DN_EACH r.e[k] = -a.e[k]; return r; }
-template <int K> DFX_HD DualN<K> operator*(DualN<K> a, DualN<K> b) {
-  DualN<K> r; r.v = a.v * b.v; DFX_DN_EACH r.e[k] = a.v * b.e[k] + a.e[k] * b.v; return r;
-}
-template <int K> DFX_HD DualN<K> operator*(double a, DualN<K> b) { DualN<K> r; r.v = a * b.v; DFX_DN_EACH r.e[k] = a * b.e[k]; return r; }
-template <int K> DFX_HD DualN<K> operator*(DualN<K> a, double b) { DualN<K> r; r.v = a.v * b; DFX_DN_EACH r.e[k] = a.e[k] * b; return r; }
-template <int K> DFX_HD DualN<K> operator+(DualN<K> a, double b) { a.v = a.v + b; return a; }
-template <int K> DFX_HD DualN<K> operator+(double a, DualN<K> b) { b.v = a + b.v; return b; }
-template <int K> DFX_HD DualN<K> operator-(DualN<K> a, double b) { a.v = a.v - b; return a; }
-template <int K> DFX_HD DualN<K> operator-(double a, DualN<K> b) { DualN<K> r; r.v = a - b.v; DFX_DN_EACH r.e[k] = -b.e[k]; return r; }
-template <int K> DFX_HD DualN<K> operator/(DualN<K> a, DualN<K> b) {
-  const double r = 1.0 / b.v, q = a.v * r;
-  DualN<K> o; o.v = q; DFX_DN_EACH o.e[k] = (a.e[k] - q * b.e[k]) * r; return o;
-}
-template <int K> DFX_HD DualN<K> operator/(double a, DualN<K> b) {
-  const double r = 1.0 / b.v, q = a * r;
-  DualN<K> o; o.v = q; DFX_DN_EACH o.e[k] = -q * b.e[k] * r; return o;
-}
-
-// what the physics templates look up by argument type
-template <int K> DFX_HD double val(DualN<K> a) { return a.v; }
-template <int K> DFX_HD double eps(DualN<K> a, int k) { return a.e[k]; }
-template <int K> DFX_HD DualN<K> trcp(DualN<K> a) {
-  const double r = trcp(a.v);
-  DualN<K> o; o.v = r; DFX_DN_EACH o.e[k] = -a.e[k] * r * r; return o;
-}
-template <int K> DFX_HD DualN<K> tsqrt(DualN<K> a) {
-  const double s = sqrt(a.v);
-  DualN<K> o; o.v = s; DFX_DN_EACH o.e[k] = 0.5 * a.e[k] / s; return o;
-}
-template <int K> DFX_HD DualN<K> trsqrt(DualN<K> a) {
-  const double r = trsqrt(a.v);
-  DualN<K> o; o.v = r; DFX_DN_EACH o.e[k] = -0.5 * a.e[k] * r * r * r; return o;
-}
-template <int K> DFX_HD DualN<K> tatan2(DualN<K> y, DualN<K> x) {
-  const double w = trcp(x.v * x.v + y.v * y.v);
-  DualN<K> o; o.v = fast_atan2(y.v, x.v); DFX_DN_EACH o.e[k] = (x.v * y.e[k] - y.v * x.e[k]) * w; return o;
-}
-template <int K> DFX_HD DualN<K> twrap(DualN<K> a) { a.v = twrap(a.v); return a; }
-
-// seed_rec for K directions: the half-angle pair follows theta in every one
-template <int K>
-DFX_HD BlockRec<DualN<K>> seed_rec(const BlockRec<double>& r, const double (&wx)[K], const double (&wy)[K], const double (&wth)[K]) {
-  BlockRec<DualN<K>> d;
-  d.x.v = r.x; d.y.v = r.y; d.th.v = r.th; d.ch.v = r.ch; d.sh.v = r.sh;
-  DFX_DN_EACH {
-    d.x.e[k] = wx[k]; d.y.e[k] = wy[k]; d.th.e[k] = wth[k];
-    d.ch.e[k] = -0.5 * r.sh * wth[k];
-    d.sh.e[k] = 0.5 * r.ch * wth[k];
-  }
-  return d;
-}
 
 constexpr int kTanSlotVals = 9;                                    // the primal half of a slot (and of every tangent half)
 constexpr int kTanBlkVals = 6;                                     // likewise of a block: 1/m(3), c(3)
@@ -563,6 +510,131 @@ __global__ void __launch_bounds__(256) k_tan_dense_multi(TanCtx c, TanDenseM dm)
         dn.fields_dot[drow + nd + dof] = dov[k];
       }
     }
+  }
+}
+
+// ---- the signal sink ---------------------------------------------------------------------------------------------------------------------
+constexpr int kTanSigThreads = 256;
+constexpr int kTanSigQuads = kTanSigThreads / 4;      // items per workgroup (kObjQuads of dfx_objective.h)
+
+struct TanSigArgs {
+  const double *fields, *fields_dot;   // B * Tn * nb*6, and this pass's B * KT * Tn * nb*6
+  const int32_t* fblocks;              // n_fb force blocks
+  const int32_t* sig_ptr;              // n_sig + 1: the terms of signal s, in list order
+  const int32_t* term_src;             // >= 0: offset of a field component inside one output time of the history; < 0: -(1 + channel)
+  const double* term_coef;
+  double *chan, *chan_dot;             // B * Tn * n_fb*3, and B * KT * Tn * n_fb*3
+  double *S, *S_dot;                   // B * Tn * n_sig, and B * KT * Tn * n_sig
+  int Tn, n_fb, n_sig;
+};
+
+// grid (chunks of kTanSigQuads items, members, slices of the pass)
+template <int MODEL, int CONTACT, int KC>
+__global__ __launch_bounds__(kTanSigThreads) void k_tan_signal_channels(TanCtx c, TanSlices sl, TanSigArgs a) {
+  using D = DualN<KC>;
+  constexpr int K = KC;
+  const int m = blockIdx.y, slice = blockIdx.z;
+  const long long total = (long long)a.Tn * a.n_fb;
+  const long long item = (long long)blockIdx.x * kTanSigQuads + (threadIdx.x >> 2);
+  const int kk = threadIdx.x & 3;
+  const bool valid = item < total;
+  D f[3];
+  if (valid) {
+    const int ko = (int)(item / a.n_fb);
+    const int b = a.fblocks[(int)(item % a.n_fb)];
+    const int slot = b * kSlots + kk;
+    const int info = c.slot_info[slot];
+    if (info >= 0) {
+      const int ps = info >> 1, pb = ps >> 2;
+      const size_t nd = (size_t)c.nb * 3;
+      const double* fr = a.fields + ((size_t)m * a.Tn + ko) * 2 * nd;
+      TanSignalLigIn<KC> in;
+      in.o.x = fr[(size_t)b * 3]; in.o.y = fr[(size_t)b * 3 + 1]; in.o.th = fr[(size_t)b * 3 + 2];
+      in.p.x = fr[(size_t)pb * 3]; in.p.y = fr[(size_t)pb * 3 + 1]; in.p.th = fr[(size_t)pb * 3 + 2];
+      fast_sincos(0.5 * in.o.th, &in.o.sh, &in.o.ch);
+      fast_sincos(0.5 * in.p.th, &in.p.sh, &in.p.ch);
+      DFX_DN_EACH {
+        const double* fd = a.fields_dot + (((size_t)m * sl.kt + slice * K + k) * a.Tn + ko) * 2 * nd;
+        in.dox[k] = fd[(size_t)b * 3]; in.doy[k] = fd[(size_t)b * 3 + 1]; in.doth[k] = fd[(size_t)b * 3 + 2];
+        in.dpx[k] = fd[(size_t)pb * 3]; in.dpy[k] = fd[(size_t)pb * 3 + 1]; in.dpth[k] = fd[(size_t)pb * 3 + 2];
+      }
+      const double* tp = c.tp + (size_t)slice * sl.tp_plane + (size_t)m * c.nb * kSlots * tan_slot_n(K);
+      const double* sp = tp + (size_t)slot * tan_slot_n(K);
+      const double* pp = tp + (size_t)ps * tan_slot_n(K);
+      in.rox = tan_par_n<K>(sp, 0); in.roy = tan_par_n<K>(sp, 1); in.rpx = tan_par_n<K>(pp, 0); in.rpy = tan_par_n<K>(pp, 1);
+      in.lx = tan_par_n<K>(sp, 2); in.ly = tan_par_n<K>(sp, 3);
+      in.ks = tan_par_n<K>(sp, 4); in.ksh = tan_par_n<K>(sp, 5); in.kr = tan_par_n<K>(sp, 6);
+      if (CONTACT == 1) {
+        const double* mem = c.mem + (size_t)slice * sl.mem_plane + (size_t)m * tan_mem_n(K);
+        in.phi1 = tan_par_n<K>(sp, 7); in.phi2 = tan_par_n<K>(sp, 8);
+        in.am = tan_scalar_n<K>(mem, 0, 3, kTanMemDir); in.ac = tan_scalar_n<K>(mem, 1, 4, kTanMemDir); in.kc = tan_scalar_n<K>(mem, 2, 5, kTanMemDir);
+      }
+      in.sgn = (info & 1) ? 1.0 : -1.0;
+      tan_signal_lig<MODEL, CONTACT, KC>(in, f[0], f[1], f[2]);
+    }
+  }
+  // every lane of the quad takes part (slots without a ligament and the lanes of a padded item add zeros); direction order
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    f[i].v = quad_sum(f[i].v);
+    DFX_DN_EACH f[i].e[k] = quad_sum(f[i].e[k]);
+  }
+  if (valid && kk == 0) {
+    if (slice == 0) {
+      double* ch = a.chan + ((size_t)m * total + (size_t)item) * 3;
+      ch[0] = f[0].v; ch[1] = f[1].v; ch[2] = f[2].v;
+    }
+    DFX_DN_EACH {
+      double* cd = a.chan_dot + (((size_t)m * sl.kt + slice * K + k) * total + (size_t)item) * 3;
+      cd[0] = f[0].e[k]; cd[1] = f[1].e[k]; cd[2] = f[2].e[k];
+    }
+  }
+}
+
+// grid (chunks of kTanSigThreads (output, signal) pairs, members, directions of the pass)
+__global__ __launch_bounds__(kTanSigThreads) void k_tan_signal_combine(TanSigArgs a, int nb, int kt) {
+  const int m = blockIdx.y, d = blockIdx.z;
+  const long long total = (long long)a.Tn * a.n_sig;
+  const long long item = (long long)blockIdx.x * kTanSigThreads + threadIdx.x;
+  if (item >= total) return;
+  const int ko = (int)(item / a.n_sig), s = (int)(item % a.n_sig);
+  const size_t nd = (size_t)nb * 3, row = (size_t)m * a.Tn + ko, drow = ((size_t)m * kt + d) * a.Tn + ko;
+  const double* fd = a.fields_dot + drow * 2 * nd;
+  const double* cd = a.chan_dot + drow * ((size_t)a.n_fb * 3);
+  double Sd = 0.0;
+  for (int t = a.sig_ptr[s]; t < a.sig_ptr[s + 1]; ++t) {
+    const int src = a.term_src[t];
+    Sd += a.term_coef[t] * (src >= 0 ? fd[src] : cd[-1 - src]);
+  }
+  a.S_dot[drow * a.n_sig + s] = Sd;
+  if (d == 0) {
+    const double* f = a.fields + row * 2 * nd;
+    const double* ch = a.chan + row * ((size_t)a.n_fb * 3);
+    double S = 0.0;
+    for (int t = a.sig_ptr[s]; t < a.sig_ptr[s + 1]; ++t) {
+      const int src = a.term_src[t];
+      S += a.term_coef[t] * (src >= 0 ? f[src] : ch[-1 - src]);
+    }
+    a.S[row * a.n_sig + s] = S;
+  }
+}
+
+// flags[blockIdx.x] = 1 when a non-finite entry of x[0, nx) or y[0, ny) lies on this workgroup's stride, else 0: every workgroup stores
+// its own word, the host ORs them
+__global__ __launch_bounds__(kTanSigThreads) void k_tan_finite_flags(const double* x, size_t nx, const double* y, size_t ny, int32_t* flags) {
+  int bad = 0;
+  for (size_t i = (size_t)blockIdx.x * kTanSigThreads + threadIdx.x; i < nx + ny; i += (size_t)gridDim.x * kTanSigThreads) {
+    const double v = i < nx ? x[i] : y[i - nx];
+    bad |= !isfinite(v);
+  }
+  __shared__ int red[kTanSigThreads / 64];
+  const int any = __any(bad);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = any;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int r = 0;
+    for (int wv = 0; wv < kTanSigThreads / 64; ++wv) r |= red[wv];
+    flags[blockIdx.x] = r ? 1 : 0;
   }
 }
 

@@ -184,17 +184,17 @@ int launch_strain(dfx_handle* h, const ObjJob& j, double* G, double* objective_h
 
 // ---- signal misfit: the term list compacted into index tables.  FORCE blocks: the blocks with a force term (components 6..8); the SET: those
 // and the blocks bonded to them (every ligament with an end on a force block is evaluated from both of its ends)
-struct SigTerms { int32_t n; const int32_t *signal, *block, *comp; const double* coef; int32_t n_signals; };
+}  // namespace
 
-int prepare_signal(dfx_handle* h, const char* who, const SigTerms& t, const double* targets, int32_t targets_per_member, const double* omega,
-                   const double* tau, bool want_target) {
+// (SigTerms / SigTables: dfx_engine.h -- the forward-mode signal entries of engine_tangent.hip build the same tables)
+// The checks of a term list (return 1 with h->err) and its tables: force blocks, the set, the terms by signal in list order.
+int signal_term_tables(dfx_handle* h, const char* who, const SigTerms& t, SigTables& out) {
   const Plan& pl = h->pl;
-  const size_t B = pl.batch, nb = pl.n_blocks;
-  const int Tn = (int)h->ts.size(), ns = t.n_signals;
+  const size_t nb = pl.n_blocks;
+  const int ns = t.n_signals;
   const std::string w(who);
   if (ns <= 0) { h->err = w + ": n_signals must be positive"; return 1; }
   if (t.n <= 0 || !t.signal || !t.block || !t.comp || !t.coef) { h->err = w + ": an empty term list (a NULL term array, or n_terms <= 0)"; return 1; }
-  if (want_target && !targets) { h->err = w + ": targets is NULL"; return 1; }
   std::vector<int> count(ns, 0);
   bool force = false;
   for (int i = 0; i < t.n; ++i) {
@@ -215,15 +215,9 @@ int prepare_signal(dfx_handle* h, const char* who, const SigTerms& t, const doub
     h->err = w + ": nodes with more than one ligament (a general bond list with extra ligaments) are not supported by the force components of a signal";
     return 1;
   }
-  const size_t n_tg = want_target ? (targets_per_member ? B : 1) * (size_t)Tn * ns : 0;
-  for (size_t i = 0; i < n_tg; ++i)
-    if (!std::isfinite(targets[i])) { h->err = w + ": non-finite target"; return 1; }
-  for (int s = 0; want_target && omega && s < ns; ++s)
-    if (!std::isfinite(omega[s])) { h->err = w + ": non-finite signal weight"; return 1; }
-  for (int k = 0; want_target && tau && k < Tn; ++k)
-    if (!std::isfinite(tau[k])) { h->err = w + ": non-finite time weight"; return 1; }
   // force blocks and the set
-  std::vector<int32_t> fmap(nb, -1), fblocks, set;
+  std::vector<int32_t>&fmap = out.fmap, &fblocks = out.fblocks, &set = out.set;
+  fmap.assign(nb, -1); fblocks.clear(); set.clear();
   std::vector<char> in_f(nb, 0), in_set(nb, 0);
   for (int i = 0; i < t.n; ++i) if (t.comp[i] >= 6) in_f[t.block[i]] = 1;
   for (size_t b = 0; b < nb; ++b) {
@@ -238,8 +232,9 @@ int prepare_signal(dfx_handle* h, const char* who, const SigTerms& t, const doub
   }
   for (size_t b = 0; b < nb; ++b) if (in_set[b]) set.push_back((int32_t)b);
   // the terms by signal, list order kept
-  std::vector<int32_t> sig_ptr(ns + 1, 0), term_src(t.n);
-  std::vector<double> term_coef(t.n);
+  std::vector<int32_t>&sig_ptr = out.sig_ptr, &term_src = out.term_src;
+  std::vector<double>& term_coef = out.term_coef;
+  sig_ptr.assign(ns + 1, 0); term_src.assign(t.n, 0); term_coef.assign(t.n, 0.0);
   for (int s = 0; s < ns; ++s) sig_ptr[s + 1] = sig_ptr[s] + count[s];
   {
     std::vector<int32_t> at(sig_ptr.begin(), sig_ptr.end() - 1);
@@ -249,6 +244,32 @@ int prepare_signal(dfx_handle* h, const char* who, const SigTerms& t, const doub
       term_coef[o] = t.coef[i];
     }
   }
+  return 0;
+}
+
+namespace {
+
+int prepare_signal(dfx_handle* h, const char* who, const SigTerms& t, const double* targets, int32_t targets_per_member, const double* omega,
+                   const double* tau, bool want_target) {
+  const Plan& pl = h->pl;
+  const size_t B = pl.batch;
+  const int Tn = (int)h->ts.size(), ns = t.n_signals;
+  const std::string w(who);
+  if (ns <= 0) { h->err = w + ": n_signals must be positive"; return 1; }
+  if (t.n <= 0 || !t.signal || !t.block || !t.comp || !t.coef) { h->err = w + ": an empty term list (a NULL term array, or n_terms <= 0)"; return 1; }
+  if (want_target && !targets) { h->err = w + ": targets is NULL"; return 1; }
+  SigTables tb;
+  if (int rc = signal_term_tables(h, who, t, tb)) return rc;
+  const size_t n_tg = want_target ? (targets_per_member ? B : 1) * (size_t)Tn * ns : 0;
+  for (size_t i = 0; i < n_tg; ++i)
+    if (!std::isfinite(targets[i])) { h->err = w + ": non-finite target"; return 1; }
+  for (int s = 0; want_target && omega && s < ns; ++s)
+    if (!std::isfinite(omega[s])) { h->err = w + ": non-finite signal weight"; return 1; }
+  for (int k = 0; want_target && tau && k < Tn; ++k)
+    if (!std::isfinite(tau[k])) { h->err = w + ": non-finite time weight"; return 1; }
+  const std::vector<int32_t>&fmap = tb.fmap, &fblocks = tb.fblocks, &set = tb.set, &sig_ptr = tb.sig_ptr, &term_src = tb.term_src;
+  const std::vector<double>& term_coef = tb.term_coef;
+  const size_t nb = pl.n_blocks;
   // the terms by distinct (block, component), list order kept; all three components of a force block are listed (w is written whole)
   std::map<std::pair<int, int>, std::vector<int>> by_dof;
   for (int32_t b : fblocks) for (int c = 6; c < 9; ++c) by_dof[{b, c}];
@@ -267,7 +288,7 @@ int prepare_signal(dfx_handle* h, const char* who, const SigTerms& t, const doub
   J.target_stride = targets_per_member ? (long long)Tn * ns : 0;
   // one int table and one double table, in the order sig_args reads them
   std::vector<int32_t> tab;
-  for (const std::vector<int32_t>* v : {&fblocks, &fmap, &set, &sig_ptr, &term_src, &uc_ptr, &uc_dst, &uc_sig}) tab.insert(tab.end(), v->begin(), v->end());
+  for (const std::vector<int32_t>* v : std::initializer_list<const std::vector<int32_t>*>{&fblocks, &fmap, &set, &sig_ptr, &term_src, &uc_ptr, &uc_dst, &uc_sig}) tab.insert(tab.end(), v->begin(), v->end());
   std::vector<double> dbl(term_coef);
   dbl.insert(dbl.end(), uc_coef.begin(), uc_coef.end());
   if (J.has_omega) dbl.insert(dbl.end(), omega, omega + ns);

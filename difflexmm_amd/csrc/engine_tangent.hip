@@ -17,6 +17,11 @@
 // dfx_forward_tangent and dfx_forward_tangent_dense are the _multi entries with n_dirs = 1 -- (batch, 1, ...) is (batch, ...) -- under
 // their own names in h->err.  One direction is one pass of width 1 with one slice in BOTH forms, so DFX_TANGENT_MULTI_FORM cannot change
 // a single-direction call.
+//
+// dfx_forward_tangent_signals_multi / _dense_multi are the same two solves with another end of a pass (SignalSink): instead of the download
+// of fields / fields_dot, the force channels and their tangents, the signals and their tangents and a finiteness flag per workgroup are
+// formed on the pass's own buffers (k_tan_signal_channels, k_tan_signal_combine, k_tan_finite_flags) and (batch, KT, T, n_signals) comes
+// back -- the columns of a least-squares Jacobian without the history crossing PCIe.
 #include "dfx_engine.h"
 #include "dfx_tangent.h"
 
@@ -292,6 +297,110 @@ int multi_download_pass(dfx_handle* h, const Pass& p, int n_dirs, int Tn, MultiB
   return 0;
 }
 
+// ---- the signal sink: what a pass of dfx_forward_tangent_signals[_dense]_multi ends in instead of multi_download_pass ---------------------
+constexpr int kFlagGroups = 1024;          // workgroups of k_tan_finite_flags at the most (each strides over the rest)
+
+struct SignalSink {
+  SigTerms terms;
+  double *signals, *signals_dots;          // the caller's (batch, T, n_signals) and (batch, n_dirs, T, n_signals)
+  SigTables tb;
+  DevBuf<double> chan, chan_dot, S, S_dot, coef;
+  DevBuf<int32_t> tab, flags;
+  ~SignalSink() {
+    chan.release(); chan_dot.release(); S.release(); S_dot.release(); coef.release(); tab.release(); flags.release();
+  }
+};
+
+template <int MODEL, int CONTACT, int KC>
+void launch_sig_channels(dim3 grid, hipStream_t s, const TanCtx& c, const TanSlices& sl, const TanSigArgs& a) {
+  hipLaunchKernelGGL((k_tan_signal_channels<MODEL, CONTACT, KC>), grid, dim3(kTanSigThreads), 0, s, c, sl, a);
+}
+using SigChannelsFn = void (*)(dim3, hipStream_t, const TanCtx&, const TanSlices&, const TanSigArgs&);
+template <int KC>
+SigChannelsFn pick_sig_physics(int model, bool angle) {
+  SigChannelsFn f = nullptr;
+  with_physics<all_physics>(model, angle ? 1 : 0, [&](auto M, auto C) { if constexpr (C() != DFX_CONTACT_DISTANCE) f = launch_sig_channels<M(), C(), KC>; });
+  return f;
+}
+// the build for the handle's bond model and the pass's width; the angle contact only where the lattice has it (force terms with the
+// distance-based contact are refused, so that lattice never gets here with a force block)
+SigChannelsFn pick_sig_channels(const Plan& pl, int kc) {
+  const bool angle = pl.contact == DFX_CONTACT_ANGLE;
+  switch (kc) {
+    case 4: return pick_sig_physics<4>(pl.model, angle);
+    case 2: return pick_sig_physics<2>(pl.model, angle);
+    default: return pick_sig_physics<1>(pl.model, angle);
+  }
+}
+
+unsigned chunks_of(long long items, int per) { return (unsigned)std::max<long long>(1, (items + per - 1) / per); }
+
+// The sink's device side, sized for the widest pass and allocated with the call's other buffers, before any pass is paid for; a failure
+// releases all of it (SignalSink) and is an ordinary error return.  The term tables go up here: fblocks | sig_ptr | term_src, and term_coef.
+int sink_alloc(dfx_handle* h, SignalSink& k, const Pass& widest, int Tn) {
+  const size_t B = h->pl.batch, kt = widest.kt(), T = Tn, n_fb = k.tb.fblocks.size(), ns = k.terms.n_signals;
+  HIP_OK(k.chan.ensure(B * T * n_fb * 3)); HIP_OK(k.chan_dot.ensure(B * kt * T * n_fb * 3));
+  HIP_OK(k.S.ensure(B * T * ns)); HIP_OK(k.S_dot.ensure(B * kt * T * ns));
+  HIP_OK(k.flags.ensure(kFlagGroups));
+  std::vector<int32_t> tab;
+  for (const std::vector<int32_t>* v : {&k.tb.fblocks, &k.tb.sig_ptr, &k.tb.term_src}) tab.insert(tab.end(), v->begin(), v->end());
+  HIP_OK(k.tab.ensure(tab.size())); HIP_OK(k.coef.ensure(k.tb.term_coef.size()));
+  HIP_OK(hipMemcpyAsync(k.tab.p, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipMemcpyAsync(k.coef.p, k.tb.term_coef.data(), sizeof(double) * k.tb.term_coef.size(), hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));      // (tab is this function's own)
+  return 0;
+}
+
+// the three launches behind a pass, on its fields / fields_dot; returns how many workgroups wrote a flag
+int sink_launch(dfx_handle* h, SignalSink& k, const Pass& p, int Tn, const MultiBufs& d, const TanCtx& c, const TanSlices& sl, long long& launches) {
+  const Plan& pl = h->pl;
+  const size_t B = pl.batch, nfield = B * (size_t)Tn * pl.n_blocks * 6;
+  TanSigArgs a;
+  a.fields = d.fields.p; a.fields_dot = d.fields_dot.p;
+  a.n_fb = (int)k.tb.fblocks.size(); a.n_sig = k.terms.n_signals; a.Tn = Tn;
+  a.fblocks = k.tab.p; a.sig_ptr = k.tab.p + a.n_fb; a.term_src = a.sig_ptr + a.n_sig + 1;
+  a.term_coef = k.coef.p;
+  a.chan = k.chan.p; a.chan_dot = k.chan_dot.p; a.S = k.S.p; a.S_dot = k.S_dot.p;
+  hipStream_t st = h->stream;
+  if (a.n_fb) {
+    pick_sig_channels(pl, p.kc)(dim3(chunks_of((long long)Tn * a.n_fb, kTanSigQuads), (unsigned)B, (unsigned)p.slices), st, c, sl, a);
+    ++launches;
+  }
+  hipLaunchKernelGGL(k_tan_signal_combine, dim3(chunks_of((long long)Tn * a.n_sig, kTanSigThreads), (unsigned)B, (unsigned)p.kt()), dim3(kTanSigThreads), 0, st,
+                     a, pl.n_blocks, p.kt());
+  const size_t nx = p.k0 == 0 ? nfield : 0, ny = nfield * p.kt();       // (fields: the first pass vouches for them, later passes store the same)
+  const int groups = (int)std::min<size_t>(kFlagGroups, (nx + ny + kTanSigThreads - 1) / kTanSigThreads);
+  hipLaunchKernelGGL(k_tan_finite_flags, dim3((unsigned)groups), dim3(kTanSigThreads), 0, st, (const double*)d.fields.p, nx, (const double*)d.fields_dot.p, ny,
+                     k.flags.p);
+  launches += 2;
+  return groups;
+}
+
+// signals (first pass) and the pass's columns of signals_dots (batch, n_dirs, T, n_signals) back to the caller; 3 when a flag is set
+int sink_download(dfx_handle* h, SignalSink& k, const Pass& p, int n_dirs, int Tn, int groups, const char* who) {
+  const size_t B = h->pl.batch, nrow = (size_t)Tn * k.terms.n_signals;
+  hipStream_t st = h->stream;
+  std::vector<double> sd_host(B * p.kt() * nrow);
+  std::vector<int32_t> flags(groups);
+  HIP_OK(hipMemcpyAsync(sd_host.data(), k.S_dot.p, sizeof(double) * sd_host.size(), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(flags.data(), k.flags.p, sizeof(int32_t) * groups, hipMemcpyDeviceToHost, st));
+  if (p.k0 == 0) HIP_OK(hipMemcpyAsync(k.signals, k.S.p, sizeof(double) * B * nrow, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  for (size_t m = 0; m < B; ++m)
+    for (int j = 0; j < p.n; ++j)
+      memcpy(k.signals_dots + (m * n_dirs + p.k0 + j) * nrow, sd_host.data() + (m * p.kt() + j) * nrow, sizeof(double) * nrow);
+  int32_t bad = 0;
+  for (int32_t f : flags) bad |= f;
+  if (bad) { h->err = std::string(who) + ": non-finite state or tangent"; return 3; }
+  return 0;
+}
+
+// what a signal call checks before anything is allocated: the outputs and the term list (the refusals of dfx_signal_values)
+int sink_prepare(dfx_handle* h, const char* who, SignalSink& k) {
+  if (!k.signals || !k.signals_dots) { h->err = std::string(who) + ": signals / signals_dots is NULL"; return 1; }
+  return signal_term_tables(h, who, k.terms, k.tb);
+}
+
 TanSlices pass_slices(const dfx_handle* h, const Pass& p, int a_rows) {
   const Plan& pl = h->pl;
   const long long B = pl.batch, nb = pl.n_blocks;
@@ -436,10 +545,11 @@ void fill_stats(dfx_stats* stats, long long steps, long long evals, long long la
 
 int forward_tangent(dfx_handle* h, const char* who, const double* state0, const double* state0_dots, const dfx_params* params_dots, int n_dirs,
                     const double* timepoints, int Tn, const int32_t* steps_per_interval, const double* step_times, bool per_member_times,
-                    double* fields, double* fields_dots, dfx_stats* stats) {
+                    double* fields, double* fields_dots, dfx_stats* stats, SignalSink* sink = nullptr) {
   HIP_OK(hipSetDevice(h->device));
   if (int rc = check_handle(h, who)) return rc;
   if (n_dirs < 1) return fail(h, who, "need >= 1 direction");
+  if (sink) if (int rc = sink_prepare(h, who, *sink)) return rc;
   const Plan& pl = h->pl;
   const int B = pl.batch, nb = pl.n_blocks, S = pl.tab.s;
   std::vector<double> tgrid, t0;
@@ -449,6 +559,7 @@ int forward_tangent(dfx_handle* h, const char* who, const double* state0, const 
   MultiBufs d;
   TanCtx c;
   if (int rc = multi_alloc(h, passes[0], tgrid, t0, state0, state0_dots != nullptr, S, Tn, d, c)) return rc;
+  if (sink) if (int rc = sink_alloc(h, *sink, passes[0], Tn)) return rc;
   hipStream_t st = h->stream;
   c.grid_stride = per_member_times ? 2 * N : 0;
   c.t0_stride = per_member_times ? 1 : 0;
@@ -475,9 +586,10 @@ int forward_tangent(dfx_handle* h, const char* who, const double* state0, const 
       kn.snapshot(grid, st, B, nb, Tn, k + 1, d.Y[y].p, d.DY[y].p, sl, d.fields.p, d.fields_dot.p);
       ++launches;
     }
+    const int groups = sink ? sink_launch(h, *sink, p, Tn, d, c, sl, launches) : 0;
     HIP_OK(hipGetLastError());
     HIP_OK(hipEventRecord(h->ev1, st));
-    const int rc = multi_download_pass(h, p, n_dirs, Tn, d, fields, fields_dots, who);
+    const int rc = sink ? sink_download(h, *sink, p, n_dirs, Tn, groups, who) : multi_download_pass(h, p, n_dirs, Tn, d, fields, fields_dots, who);
     if (rc == 2) return rc;
     float ms = 0.0f;
     HIP_OK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
@@ -490,12 +602,13 @@ int forward_tangent(dfx_handle* h, const char* who, const double* state0, const 
 
 int forward_tangent_dense(dfx_handle* h, const char* who, const double* state0, const double* state0_dots, const dfx_params* params_dots,
                           int n_dirs, const double* timepoints, int Tn, const double* step_times, const int64_t* n_steps, int64_t stride,
-                          double* fields, double* fields_dots, dfx_stats* stats) {
+                          double* fields, double* fields_dots, dfx_stats* stats, SignalSink* sink = nullptr) {
   HIP_OK(hipSetDevice(h->device));
   if (int rc = check_handle(h, who)) return rc;
   const Plan& pl = h->pl;
   if (pl.tab.s != 6) return fail(h, who, "the dense output is defined for the dopri5 tableau");
   if (n_dirs < 1) return fail(h, who, "need >= 1 direction");
+  if (sink) if (int rc = sink_prepare(h, who, *sink)) return rc;
   const int B = pl.batch, nb = pl.n_blocks, S = pl.tab.s;
   DenseGrid g;
   if (int rc = dense_grid(h, who, timepoints, Tn, step_times, n_steps, stride, g)) return rc;
@@ -505,6 +618,7 @@ int forward_tangent_dense(dfx_handle* h, const char* who, const double* state0, 
   MultiBufs d;
   TanCtx c;
   if (int rc = multi_alloc(h, passes[0], g.tgrid, t0, state0, state0_dots != nullptr, 7, Tn, d, c)) return rc;
+  if (sink) if (int rc = sink_alloc(h, *sink, passes[0], Tn)) return rc;
   hipStream_t st = h->stream;
   c.grid_stride = g.gs; c.t0_stride = 0;
   c.n_steps = g.nst.p;
@@ -545,9 +659,10 @@ int forward_tangent_dense(dfx_handle* h, const char* who, const double* state0, 
       }
       y ^= 1;
     }
+    const int groups = sink ? sink_launch(h, *sink, p, Tn, d, c, sl, launches) : 0;
     HIP_OK(hipGetLastError());
     HIP_OK(hipEventRecord(h->ev1, st));
-    const int rc = multi_download_pass(h, p, n_dirs, Tn, d, fields, fields_dots, who);
+    const int rc = sink ? sink_download(h, *sink, p, n_dirs, Tn, groups, who) : multi_download_pass(h, p, n_dirs, Tn, d, fields, fields_dots, who);
     if (rc == 2) return rc;
     float ms = 0.0f;
     HIP_OK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
@@ -616,6 +731,31 @@ extern "C" int dfx_forward_tangent_dense_multi(dfx_handle* h, const double* stat
                                                const int64_t* n_steps, int64_t stride, double* fields, double* fields_dots, dfx_stats* stats) {
   return forward_tangent_dense(h, "forward_tangent_dense_multi", state0, state0_dots, params_dots, n_dirs, timepoints, n_timepoints, step_times,
                                n_steps, stride, fields, fields_dots, stats);
+}
+
+// ---- forward-mode signals: the two solves above with the signal sink at the end of every pass ----------------------------------------------
+extern "C" int dfx_forward_tangent_signals_multi(dfx_handle* h, const double* state0, const double* state0_dots, const dfx_params* params_dots,
+                                                 int32_t n_dirs, const double* timepoints, int32_t n_timepoints, const int32_t* steps_per_interval,
+                                                 const double* step_times, int32_t per_member_times, int32_t n_terms, const int32_t* term_signal,
+                                                 const int32_t* term_block, const int32_t* term_component, const double* term_coef,
+                                                 int32_t n_signals, double* signals, double* signals_dots, dfx_stats* stats) {
+  SignalSink sink;
+  sink.terms = SigTerms{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
+  sink.signals = signals; sink.signals_dots = signals_dots;
+  return forward_tangent(h, "forward_tangent_signals_multi", state0, state0_dots, params_dots, n_dirs, timepoints, n_timepoints, steps_per_interval,
+                         step_times, per_member_times != 0, nullptr, nullptr, stats, &sink);
+}
+
+extern "C" int dfx_forward_tangent_signals_dense_multi(dfx_handle* h, const double* state0, const double* state0_dots, const dfx_params* params_dots,
+                                                       int32_t n_dirs, const double* timepoints, int32_t n_timepoints, const double* step_times,
+                                                       const int64_t* n_steps, int64_t stride, int32_t n_terms, const int32_t* term_signal,
+                                                       const int32_t* term_block, const int32_t* term_component, const double* term_coef,
+                                                       int32_t n_signals, double* signals, double* signals_dots, dfx_stats* stats) {
+  SignalSink sink;
+  sink.terms = SigTerms{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
+  sink.signals = signals; sink.signals_dots = signals_dots;
+  return forward_tangent_dense(h, "forward_tangent_signals_dense_multi", state0, state0_dots, params_dots, n_dirs, timepoints, n_timepoints, step_times,
+                               n_steps, stride, nullptr, nullptr, stats, &sink);
 }
 
 // One evaluation is the tangent solve's own machinery on a step of size zero at t: k_tan_init_multi builds the records (prescribed DOFs and

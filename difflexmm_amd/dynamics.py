@@ -128,6 +128,29 @@ def unit_tangent(control_params: ControlParams, name):
     raise ValueError(f"unit_tangent: unknown leaf {name!r} (one of {', '.join(JACFWD_LEAVES)}, or a key of constraint_params / loading_params)")
 
 
+def with_leaf(control_params: ControlParams, name, value):
+    """The setter beside :func:`unit_tangent`: a copy of ``control_params`` with the scalar leaf ``name`` set to ``value`` -- the same
+    names (``JACFWD_LEAVES``, keys of ``constraint_params`` / ``loading_params``) and the same "scalar leaf" rule: a Python / 0-d scalar
+    is replaced, an array that holds one value is filled with ``value`` in its shape.  ``ValueError``: what :func:`unit_tangent` raises."""
+    shape = unit_tangent(control_params, name)          # (the checks; the tree itself tells where the leaf sits and its shape)
+    value = float(value)
+    mp = control_params.mechanical_params
+
+    def filled(ones):
+        return np.full(np.shape(ones), value) if np.ndim(ones) else value
+    if name in ("k_stretch", "k_shear", "k_rot"):
+        bp = mp.bond_params
+        return control_params._replace(mechanical_params=mp._replace(bond_params=bp._replace(
+            **{name: filled(getattr(shape.mechanical_params.bond_params, name))})))
+    if name in ("density", "damping"):
+        return control_params._replace(mechanical_params=mp._replace(**{name: filled(getattr(shape.mechanical_params, name))}))
+    if name in ("min_angle", "cutoff_angle", "k_contact"):
+        return control_params._replace(mechanical_params=mp._replace(contact_params=mp.contact_params._replace(
+            **{name: filled(getattr(shape.mechanical_params.contact_params, name))})))
+    field = "constraint_params" if name in (control_params.constraint_params or {}) else "loading_params"
+    return control_params._replace(**{field: dict(getattr(control_params, field), **{name: value})})
+
+
 class DynamicSolver:
     """Callable returned by :func:`setup_dynamic_solver`."""
 
@@ -537,18 +560,12 @@ class DynamicSolver:
             raise ValueError(f"expected {self.batch} tangents, got {len(dots)}")
         return dots
 
-    def jvp_multi(self, state0, timepoints, control_params, tangents, steps_per_interval=None, step_times=None, adaptive=False,
-                  _who="jvp_multi"):
-        """:meth:`jvp` along K directions in one pass: ``fields, fields_dot = jvp_multi(state0, timepoints, control_params, tangents)``
-        with ``tangents`` a list of K pairs ``(state0_dot, control_params_dot)`` (either element may be None: zero; ``control_params_dot``
-        follows :meth:`jvp`'s rules -- None leaves, missing keys, a list of one tree per member when batch > 1).  The stage kernel carries
-        one value and several epsilon parts (``dfx_forward_tangent_multi`` / ``dfx_forward_tangent_dense_multi``), so the primal chain --
-        records, transcendentals, branch decisions, parameter loads -- is paid once per chunk of directions instead of once per
-        direction, and a solver of batch 1 returns a whole Jacobian over a few leaves.  ``fields`` is what :meth:`jvp` returns;
-        ``fields_dot`` has a direction axis in front of T: (K, T, 2, nb, 3) for a single design, (batch, K, T, 2, nb, 3) otherwise, and
-        ``fields_dot[..., k, :, :, :, :]`` is :meth:`jvp` along ``tangents[k]`` to rounding.  Grid semantics, ``adaptive=True`` (a
-        ``ValueError`` with a grid of any kind), ``self.stats`` and "``vjp`` may follow on the kept solve" are :meth:`jvp`'s.
-        (``_who``: the public method the call came through, for the error texts.)"""
+    def _tangent_solve(self, _who, state0, timepoints, control_params, tangents, steps_per_interval, step_times, adaptive, spec=None):
+        """What :meth:`jvp_multi` and :meth:`signal_jvp_multi` share: the checks, the flattened parameters and tangents, the grid (given,
+        chosen by the adaptive controller and frozen, or the adaptive solve's own accepted steps), ``self.stats`` and the engine call.
+        ``spec=None``: (fields, fields_dot) of all members as the engine returns them (rows of prescribed DOFs not yet assembled);
+        an ``objective.SignalSpec``: (signals, signals_dot) through the signal entries.  Also returns the per-member parameters, the
+        tangent trees [direction][member] and the timepoints."""
         who = f"DynamicSolver.{_who}"
         if adaptive:
             grids = [name for name, on in (("steps_per_interval", steps_per_interval is not None), ("step_times", step_times is not None),
@@ -566,6 +583,17 @@ class DynamicSolver:
         K = len(tangents)
         dots = [self._member_tangents(cd) for _, cd in tangents]            # [direction][member]
         engine = self.engine
+        if spec is not None and not engine.has_forward_tangent_signals:
+            raise NotImplementedError(f"{who}: the library {getattr(engine.lib, '_name', engine.lib)!r} has no dfx_forward_tangent_signals_multi "
+                                      "(a stale libdfx.so, or the CPU port of the oracle; build the HIP engine)")
+        if spec is None:
+            fixed, dense = engine.forward_tangent_multi, engine.forward_tangent_dense_multi
+        else:       # the same two solves with the history kept on the device: signals and their tangents come back
+            def fixed(*a, step_times=None):
+                return engine.forward_tangent_signals_multi(*a, spec.terms, spec.n_signals, step_times=step_times)
+
+            def dense(*a):
+                return engine.forward_tangent_signals_dense_multi(*a, spec.terms, spec.n_signals)
         if not engine.has_forward_tangent_multi or (adaptive and not engine.has_forward_tangent_dense_multi):
             lib = engine.lib
             raise NotImplementedError(f"{who}: the library {getattr(lib, '_name', lib)!r} has no dfx_forward_tangent{'' if _who == 'jvp' else '_multi'} "
@@ -598,7 +626,7 @@ class DynamicSolver:
             # for: the same entry point on the initial state alone, one timepoint and no step.  Then the adaptive pass, its accepted steps
             # kept for a vjp of the same solve where the kept-steps path serves the physics, and the tangent pass over every member's own
             # step boundaries.
-            engine.forward_tangent_dense_multi(s0, None, None, 1, ts[:1], np.full((B, 1), ts[0]), np.zeros(B, dtype=np.int64))
+            dense(s0, None, None, 1, ts[:1], np.full((B, 1), ts[0]), np.zeros(B, dtype=np.int64))
             kept, primal, astats = False, None, None
             if engine.can_keep_adaptive and os.environ.get("DFX_ADAPTIVE_RECORDS", "1") != "0":
                 try:
@@ -611,7 +639,7 @@ class DynamicSolver:
                 primal, astats = engine.forward_adaptive(s0, ts, self.rtol, self.atol, max_attempts=self.max_attempts)
             self.adaptive_stats = astats
             grid, n_steps = _b.padded_step_times([engine.adaptive_step_times(m) for m in range(B)], ts[0])
-            fields, fields_dot, stats = engine.forward_tangent_dense_multi(s0, s0ds, params_dots, K, ts, grid, n_steps)
+            fields, fields_dot, stats = dense(s0, s0ds, params_dots, K, ts, grid, n_steps)
             if kept:        # as a differentiable solve leaves it: vjp reverses the adaptive pass above
                 self._last = (cps, flats, ts)
                 self._last_fields = primal
@@ -622,17 +650,80 @@ class DynamicSolver:
                 if ts.ndim == 2:
                     raise ValueError("per-member timepoints need steps_per_interval (the adaptive controller chooses one grid per call)")
                 # (the refusals before the adaptive pass that chooses the grid is paid for)
-                engine.forward_tangent_multi(s0, None, None, 1, ts[:1], 1)
+                fixed(s0, None, None, 1, ts[:1], 1)
                 spi, step_times = self.adaptive_grid(np.zeros((B, 2, nb, 3)) if s0 is None else s0, ts, flats)
                 control = "adaptive-grid"
-            fields, fields_dot, stats = engine.forward_tangent_multi(s0, s0ds, params_dots, K, ts, spi, step_times=step_times)
+            fields, fields_dot, stats = fixed(s0, s0ds, params_dots, K, ts, spi, step_times=step_times)
             self.stats = dict(stats, steps_per_interval=spi, step_times=step_times, step_control=control)
+        return fields, fields_dot, cps, dots, ts
+
+    def jvp_multi(self, state0, timepoints, control_params, tangents, steps_per_interval=None, step_times=None, adaptive=False,
+                  _who="jvp_multi"):
+        """:meth:`jvp` along K directions in one pass: ``fields, fields_dot = jvp_multi(state0, timepoints, control_params, tangents)``
+        with ``tangents`` a list of K pairs ``(state0_dot, control_params_dot)`` (either element may be None: zero; ``control_params_dot``
+        follows :meth:`jvp`'s rules -- None leaves, missing keys, a list of one tree per member when batch > 1).  The stage kernel carries
+        one value and several epsilon parts (``dfx_forward_tangent_multi`` / ``dfx_forward_tangent_dense_multi``), so the primal chain --
+        records, transcendentals, branch decisions, parameter loads -- is paid once per chunk of directions instead of once per
+        direction, and a solver of batch 1 returns a whole Jacobian over a few leaves.  ``fields`` is what :meth:`jvp` returns;
+        ``fields_dot`` has a direction axis in front of T: (K, T, 2, nb, 3) for a single design, (batch, K, T, 2, nb, 3) otherwise, and
+        ``fields_dot[..., k, :, :, :, :]`` is :meth:`jvp` along ``tangents[k]`` to rounding.  Grid semantics, ``adaptive=True`` (a
+        ``ValueError`` with a grid of any kind), ``self.stats`` and "``vjp`` may follow on the kept solve" are :meth:`jvp`'s.
+        (``_who``: the public method the call came through, for the error texts.)"""
+        fields, fields_dot, cps, dots, ts = self._tangent_solve(_who, state0, timepoints, control_params, tangents, steps_per_interval,
+                                                                step_times, adaptive)
         for m, cp in enumerate(cps):
-            for k in range(K):
+            for k in range(len(dots)):
                 self._prescribed_tangent_rows(fields_dot[m, k], cp, dots[k][m], ts[m] if ts.ndim == 2 else ts)
         if self.batch == 1 and not isinstance(control_params, list):
             return fields[0], fields_dot[0]
         return fields, fields_dot
+
+    def signal_jvp_multi(self, state0, timepoints, control_params, tangents, spec, steps_per_interval=None, step_times=None, adaptive=False):
+        """The signals of an ``objective.SignalSpec`` and their tangents along K directions, with the history kept on the device:
+        ``signals, signals_dot = signal_jvp_multi(state0, timepoints, control_params, tangents, spec)`` -- (T, ns) and (K, T, ns) for
+        one design, (batch, T, ns) and (batch, K, T, ns) otherwise.  It is :meth:`jvp_multi` followed by the signals of ``fields`` and of
+        every ``fields_dot[k]`` -- the same solve, the same kernels, the same passes -- but what crosses PCIe is (batch, K, T, ns)
+        instead of two histories, and force components (which have no host path) are differentiated where the solve ran: one dual-number
+        evaluation of the ligament gradient per listed slot and output time (``dfx_forward_tangent_signals_multi`` / ``_dense_multi``).
+        Column k is the derivative of :meth:`signal_values` along ``tangents[k]``; on the same grid it is the transpose of
+        :meth:`signal_misfit_value_and_raw`.  ``tangents``, the grid semantics, ``adaptive=True``, ``self.stats`` and "a ``vjp`` may follow
+        on the kept adaptive solve" are :meth:`jvp_multi`'s; targets and weights of ``spec`` are not read.  For a term on the VELOCITY of
+        a prescribed DOF the engine's column holds 0 and ``coef * vector * (dg'/dp . dp)`` is added here from the ``"rate"`` partials of
+        the constraint's time functions, as :meth:`jvp_multi` assembles those rows (a handful of numbers per solve)."""
+        S, Sd, cps, dots, ts = self._tangent_solve("signal_jvp_multi", state0, timepoints, control_params, tangents, steps_per_interval,
+                                                   step_times, adaptive, spec=spec)
+        if len(self.constrained_pairs) and self.con_terms:
+            n_con = len(self.constrained_pairs)
+            row = {(int(b), int(d)): i for i, (b, d) in enumerate(self.constrained_pairs)}
+            driven = [(s_, row[(b, c - 3)], coef) for s_, b, c, coef in spec.terms if 3 <= c < 6 and (b, c - 3) in row]
+            for m, cp in enumerate(cps if driven else []):
+                ts_m = ts[m] if ts.ndim == 2 else ts
+                for k in range(len(dots)):
+                    for term in self.con_terms:
+                        dp = term.resolve_jvp(cp.constraint_params, getattr(dots[k][m], "constraint_params", None))
+                        if not np.any(dp):
+                            continue
+                        p = term.resolve(cp.constraint_params)
+                        vec = _bcast(term.vector, n_con)
+                        rate = np.array([float(term.param_partials(float(t), p, "rate") @ dp) for t in ts_m])
+                        for s_, i, coef in driven:
+                            Sd[m, k, :, s_] += coef * vec[i] * rate
+        if self.batch == 1 and not isinstance(control_params, list):
+            return S[0], Sd[0]
+        return S, Sd
+
+    def signal_jacfwd(self, state0, timepoints, control_params, wrt, spec, **grid_kwargs):
+        """Columns of the Jacobian of the signals of ``spec`` with respect to scalar leaves, by :meth:`signal_jvp_multi` on one unit
+        tangent per name (:func:`unit_tangent`): ``signals, {name: d signals / d name} = signal_jacfwd(state0, timepoints,
+        control_params, wrt, spec)``; names, ``grid_kwargs`` and the batch rule are :meth:`jacfwd`'s."""
+        wrt = list(wrt)
+        if isinstance(control_params, (list, tuple)) and not isinstance(control_params, ControlParams):
+            trees = [[unit_tangent(cp, name) for cp in control_params] for name in wrt]
+        else:
+            trees = [unit_tangent(control_params, name) for name in wrt]
+        S, Sd = self.signal_jvp_multi(state0, timepoints, control_params, [(None, t) for t in trees], spec, **grid_kwargs)
+        single = Sd.ndim == 3
+        return S, {name: (Sd[k] if single else Sd[:, k]) for k, name in enumerate(wrt)}
 
     def jacfwd(self, state0, timepoints, control_params, wrt, **grid_kwargs):
         """Columns of the Jacobian of the fields with respect to scalar leaves, by :meth:`jvp_multi` on one unit tangent per name

@@ -173,13 +173,19 @@ class _HingeBase:
         rb, rd = self.reaction_block_DOF_pairs[:, 0], self.reaction_block_DOF_pairs[:, 1]
         return -(dy_dots[:, :, 1][:, :, rb, rd] * inertia[rb, rd]).sum(2).T * self.force_multiplier
 
-    def force_jacobian(self, k_values):
+    def force_jacobian(self, k_values, on_device=False):
         """(forces (T,), jac (T, 3)): the multiplied force history and its Jacobian w.r.t. (k_stretch, k_shear, k_rot) in forward mode --
         one ``solve_dynamics.jacfwd`` (on the problem's ``steps_per_interval``, or through the adaptive solve when there is none; the
-        fields come from that same pass), then :meth:`force_jvp`.  Not in the reference, which has reverse mode only."""
+        fields come from that same pass), then :meth:`force_jvp`.  Not in the reference, which has reverse mode only.
+        ``on_device=True``: one ``solve_dynamics.signal_jacfwd`` on :meth:`reaction_signal` instead -- the same solve, the force and its
+        tangents evaluated at its end on the device: no history comes down, no second handle is loaded, no ``rhs_jvp`` runs
+        (``solution_data`` is not refreshed by this path)."""
         names = ["k_stretch", "k_shear", "k_rot"]
         cp = self.control_params(k_values)
         grid = dict(steps_per_interval=self.steps_per_interval) if self.steps_per_interval is not None else dict(adaptive=True)
+        if on_device:
+            S, cols = self.solve_dynamics.signal_jacfwd(self.state0, self.timepoints, cp, names, self.reaction_signal(), **grid)
+            return S[:, 0], np.stack([cols[name][:, 0] for name in names], axis=1)
         fields, cols = self.solve_dynamics.jacfwd(self.state0, self.timepoints, cp, names, **grid)
         self.solution_data = SolutionData(self._block_centroids, self._centroid_node_vectors, self.bond_connectivity, self.timepoints, fields)
         _, forces = self.force_displacement(self.solution_data, cp)
@@ -357,28 +363,28 @@ class HingeResponseError:
             grad += np.asarray(raw["k_bond"], dtype=float)[0].sum(0)
         return value, tuple(grad)
 
-    def residuals_and_jacobian(self, k_values):
+    def residuals_and_jacobian(self, k_values, on_device=False):
         """``r`` (n_tests * T,) = reaction forces - target forces and ``J`` (n_tests * T, 3) = dr / d(k_stretch, k_shear, k_rot), tests
         in the order of ``forward_problems``; the objective is ``mean(r ** 2)`` and its gradient ``2 J^T r / r.size``.  An addition to
-        the reference (forward mode: ``_HingeBase.force_jacobian``)."""
+        the reference (forward mode: ``_HingeBase.force_jacobian``, which ``on_device`` is handed to)."""
         if not self.is_setup:
             self.setup_objective()
         r, J = [], []
         for p, target in zip(self.forward_problems, self.target_forces):
-            forces, jac = p.force_jacobian(k_values)
+            forces, jac = p.force_jacobian(k_values, on_device=on_device)
             r.append(forces - target)
             J.append(jac)
         return np.concatenate(r), np.concatenate(J)
 
-    def run_optimization_lm(self, initial_guess, n_iterations, lower_bound=None, upper_bound=None, verbose=False):
+    def run_optimization_lm(self, initial_guess, n_iterations, lower_bound=None, upper_bound=None, verbose=False, on_device=False):
         """AN ADDITION TO THE REFERENCE, which has no such loop: the fit as the nonlinear least-squares problem it is, by the bounded
         Levenberg-Marquardt of ``difflexmm_amd.optimize`` on :meth:`residuals_and_jacobian` (at most ``n_iterations`` evaluations).
         Every evaluation is recorded in ``objective_values`` / ``design_values`` as the other two loops do; ``fitted_responses`` are
-        those of the best design evaluated."""
+        those of the best design evaluated.  ``on_device=True``: every evaluation is ``residuals_and_jacobian(x, on_device=True)``."""
         from .optimize import levenberg_marquardt
 
         def fun(x):
-            r, J = self.residuals_and_jacobian(tuple(x))
+            r, J = self.residuals_and_jacobian(tuple(x), on_device=on_device)
             v = float(np.mean(r ** 2))
             self.objective_values.append(v)
             self.design_values.append(tuple(float(a) for a in x))
@@ -387,7 +393,7 @@ class HingeResponseError:
             return r, J
         history = levenberg_marquardt(fun, np.asarray(initial_guess, dtype=float), lower=lower_bound, upper=upper_bound,
                                       max_evaluations=n_iterations)
-        self.fitted_responses = self.compute_fitted_responses(tuple(float(a) for a in history["x"][-1]))
+        self.fitted_responses = self.compute_fitted_responses(tuple(float(a) for a in history["x"][-1]), on_device)
 
     def run_optimization_GD(self, initial_guess, n_iterations, step_size, lower_bound=None, upper_bound=None, verbose=False, on_device=False):
         """``on_device=True``: every evaluation is :meth:`value_and_grad_device`."""

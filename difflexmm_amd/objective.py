@@ -397,13 +397,23 @@ def fourier_basis(timepoints, frequencies, window=None, quadrature="trapezoid"):
     return out
 
 
+def project_signals(spec, S):
+    """The time reduction of a ``ProjectionSpec`` on signals that are already formed: ``S`` (..., T, n_signals) -> (..., n_signals,
+    n_rows), ``P_sj = sum_k B_jk S_ks``.  It is linear, so the same call on the tangent columns of ``DynamicSolver.signal_jvp_multi``
+    gives the tangents of the projections, ``P_dot = B S_dot``."""
+    S = np.asarray(S, dtype=float)
+    if S.ndim < 2 or S.shape[-2] != spec.basis.shape[1]:
+        raise ValueError(f"basis has T = {spec.basis.shape[1]} but the signals have shape {S.shape} (..., T, n_signals)")
+    return np.einsum("jk,...ks->...sj", spec.basis, S)
+
+
 def host_projection_values(spec, fields):
     """NumPy restatement of the projections of a ``ProjectionSpec`` whose terms are field components: ``fields`` (batch, T, 2, n_blocks, 3)
     -> (batch, n_signals, n_rows), or (T, 2, n_blocks, 3) -> (n_signals, n_rows).  Force components raise, as in ``host_signal_values``."""
     S = host_signal_values(spec.signal_spec, fields)
     if S.shape[-2] != spec.basis.shape[1]:
         raise ValueError(f"basis has T = {spec.basis.shape[1]} but the fields have T = {S.shape[-2]}")
-    return np.einsum("jk,...ks->...sj", spec.basis, S)
+    return project_signals(spec, S)
 
 
 def host_projection_value_and_cotangent(spec, fields):

@@ -1108,6 +1108,77 @@ class TargetSignalMisfit:
         return self._device(design, True) if on_device or isinstance(design, list) else self._host(design, True)
 
 
+class SignalCalibration:
+    """A calibration of a few scalars against signal histories as the nonlinear least-squares problem it is: the unknowns ``x`` are the
+    scalar leaves ``wrt`` of ``control_params`` (names as ``dynamics.unit_tangent``: stiffnesses, ``damping``, contact constants, keys of
+    ``constraint_params`` / ``loading_params`` such as a drive amplitude), the data the targets of an ``objective.SignalSpec`` --
+    tracked block motions, a measured reaction force.  One evaluation is ONE forward-mode solve: ``solve_dynamics.signal_jacfwd`` returns
+    the signals and their derivatives with the history kept on the device.  ``control_params`` a list (a solver of batch > 1): every
+    member is one specimen with parameters of its own, all share the unknowns, and the targets are per member (batch, T, n_signals)
+    or shared (T, n_signals).  ``grid_kwargs``: ``steps_per_interval``, ``step_times``, ``adaptive``.
+
+    ``residuals_and_jacobian(x)``: ``r = sqrt(tau_k omega_s) (S - Starget)`` flattened over members, outputs and signals, and ``J = dr/dx``,
+    so ``1/2 sum r^2`` is the misfit of the ``SignalSpec`` (summed over members) and ``J^T r`` its gradient.  A residual needs a square
+    root: negative weights raise ``ValueError``."""
+
+    def __init__(self, solve_dynamics, state0, timepoints, control_params, spec, wrt, **grid_kwargs):
+        if spec.targets is None:
+            raise ValueError("SignalCalibration: the SignalSpec has no targets")
+        self.wrt = list(wrt)
+        if not self.wrt:
+            raise ValueError("SignalCalibration: wrt names no leaf")
+        for name, w in (("omega", spec.omega), ("tau", spec.tau)):
+            if w is not None and np.any(np.asarray(w, dtype=float) < 0.0):
+                raise ValueError(f"SignalCalibration: negative {name}: a residual sqrt(tau omega) (S - Starget) needs non-negative weights")
+        self.solve_dynamics, self.state0, self.timepoints, self.spec, self.grid_kwargs = solve_dynamics, state0, timepoints, spec, grid_kwargs
+        self.control_params = control_params
+        self.many = isinstance(control_params, (list, tuple)) and not isinstance(control_params, ControlParams)
+        T = np.shape(timepoints)[-1]
+        tau = np.ones(T) if spec.tau is None else np.asarray(spec.tau, dtype=float)
+        om = np.ones(spec.n_signals) if spec.omega is None else np.asarray(spec.omega, dtype=float)
+        self.sqrt_w = np.sqrt(tau[:, None] * om[None, :])           # (T, n_signals)
+        if spec.targets.ndim == 3 and not self.many:
+            raise ValueError("SignalCalibration: per-member targets need a list of ControlParams, one per member")
+        if spec.targets.ndim == 3 and len(spec.targets) != len(control_params):
+            raise ValueError(f"SignalCalibration: targets for {len(spec.targets)} members against {len(control_params)} ControlParams")
+        self.objective_values, self.design_values = [], []
+
+    def params_at(self, x):
+        """``control_params`` with the leaves ``wrt`` set to ``x`` (every member's, for a list)."""
+        from .dynamics import with_leaf
+        x = np.asarray(x, dtype=float).reshape(-1)
+        if x.size != len(self.wrt):
+            raise ValueError(f"SignalCalibration: {x.size} values for the {len(self.wrt)} leaves {self.wrt}")
+
+        def one(cp):
+            for name, v in zip(self.wrt, x):
+                cp = with_leaf(cp, name, v)
+            return cp
+        return [one(cp) for cp in self.control_params] if self.many else one(self.control_params)
+
+    def residuals_and_jacobian(self, x):
+        S, cols = self.solve_dynamics.signal_jacfwd(self.state0, self.timepoints, self.params_at(x), self.wrt, self.spec, **self.grid_kwargs)
+        r = self.sqrt_w * (np.asarray(S, dtype=float) - self.spec.targets)
+        J = np.stack([(self.sqrt_w * np.asarray(cols[name], dtype=float)).reshape(-1) for name in self.wrt], axis=1)
+        return r.reshape(-1), J
+
+    def run_lm(self, x0, n_iterations=20, lower_bound=None, upper_bound=None, verbose=False):
+        """The bounded Levenberg-Marquardt of ``difflexmm_amd.optimize`` on :meth:`residuals_and_jacobian`, at most ``n_iterations``
+        evaluations.  Every evaluation is recorded in ``objective_values`` (the misfit ``1/2 sum r^2``) and ``design_values``, as the hinge
+        loop records its own; returns the iterate history of ``levenberg_marquardt`` (``x[-1]`` the best point)."""
+        from .optimize import levenberg_marquardt
+
+        def fun(x):
+            r, J = self.residuals_and_jacobian(x)
+            v = 0.5 * float(np.sum(r ** 2))
+            self.objective_values.append(v)
+            self.design_values.append(tuple(float(a) for a in x))
+            if verbose:
+                print(f"Iteration: {len(self.objective_values)}\nObjective = {v}")
+            return r, J
+        return levenberg_marquardt(fun, np.asarray(x0, dtype=float), lower=lower_bound, upper=upper_bound, max_evaluations=n_iterations)
+
+
 class TargetSignalProjection:
     """objective(design) = 1/2 sum_s sum_j W_sj (P_sj(design) - Ptarget_sj)^2 with P_sj = sum_k B_jk S_ks for an
     ``objective.ProjectionSpec``: the signals of a ``SignalSpec`` projected on a few rows of a time basis -- band power, transmission at the

@@ -8,7 +8,8 @@ of a sample with known stiffnesses; the fit starts elsewhere and must walk towar
 fit as the least-squares problem it is: Levenberg-Marquardt on the residual Jacobian, which forward mode delivers in one pass per test
 (an addition, HingeResponseError.run_optimization_lm).  --on-device (with mma) evaluates and differentiates the misfit on the kept solve
 of every test (HingeResponseError.value_and_grad_device: the signal misfit of include/dfx.h): the histories stay on the device and the
-second, reaction-force handle is not used.
+second, reaction-force handle is not used.  --on-device with lm takes the reaction force and its three tangents at the end of every
+tangent pass on the device (DynamicSolver.signal_jacfwd: the forward-mode signals of include/dfx.h): the same fit, no history downloaded.
 """
 import argparse
 import math
@@ -45,13 +46,13 @@ def main():
     ap.add_argument("--cells", type=int, default=3)
     ap.add_argument("--timepoints", type=int, default=21)
     ap.add_argument("--method", choices=("mma", "lm"), default="mma")
-    ap.add_argument("--on-device", action="store_true", help="mma: the misfit and its gradient on the kept solve of every test")
+    ap.add_argument("--on-device", action="store_true", help="mma: the misfit and its gradient on the kept solve of every test; lm: the force Jacobian at the end of the tangent pass")
     a = ap.parse_args()
     fit = build_fit(a.cells, a.timepoints)
     t0 = time.perf_counter()
     if a.method == "lm":
-        fit.run_optimization_lm(START, a.iterations, lower_bound=LOWER, upper_bound=UPPER)
-        what = "3 forward-mode solves with 3 tangents each"
+        fit.run_optimization_lm(START, a.iterations, lower_bound=LOWER, upper_bound=UPPER, on_device=a.on_device)
+        what = "3 forward-mode solves with 3 tangents each" + (", force Jacobian on the device" if a.on_device else "")
     else:
         fit.run_optimization_nlopt(START, a.iterations, lower_bound=LOWER, upper_bound=UPPER, on_device=a.on_device)
         what = "3 forward + 3 reverse solves each" + (", misfit on the device" if a.on_device else "")

@@ -286,6 +286,40 @@ int dfx_forward_tangent_dense_multi(dfx_handle* h, const double* state0, const d
                                     int32_t n_dirs, const double* timepoints, int32_t n_timepoints, const double* step_times,
                                     const int64_t* n_steps, int64_t stride, double* fields, double* fields_dots, dfx_stats* stats);
 
+/* Forward-mode SIGNALS: the two _multi solves above with the history kept on the device.  Instead of fields / fields_dots the call
+ * returns the signals of a term list (dfx_signal_values: terms (signal, block, component, coef), components 0..2 displacement, 3..5
+ * velocity, 6..8 elastic force dE/d(x, y, theta) on the block) and their tangents: signals (batch, T, n_signals), from the first pass, and
+ * signals_dots (batch, n_dirs, T, n_signals) -- the columns of the Jacobian of a least-squares fit of those signals.  At the end of every
+ * pass the force channels and their tangents K(u) du + (d grad_u E / dp) dp are evaluated on the pass's own buffers (one dual-number
+ * evaluation of the ligament gradient per listed slot and output time, with the pass's parameter tangents), the terms are added in list
+ * order, and (batch, KT, T, n_signals) is downloaded; no atomics, every sum in a fixed order, so a repeated call returns the same bits.
+ *   * column k of signals_dots is the derivative of dfx_signal_values along direction k of the same solve; on the same grid it is the
+ *     transpose of dfx_signal_misfit_value_and_grad: sum_ks c_ks Sdot_ks == <gradient, direction> with c = tau omega (S - Starget);
+ *   * prescribed DOFs: their position rows carry the exact tangent of c(t), so displacement terms on them and force terms on or beside a
+ *     driven block are complete.  Their velocity rows are 0, as in dfx_forward_tangent: for a field term on the velocity of a prescribed
+ *     DOF the column holds 0 and the caller adds coef * dc'/dp . dp;
+ *   * contracts, return codes and refusals are those of dfx_forward_tangent_multi / dfx_forward_tangent_dense_multi, plus those of
+ *     dfx_signal_values (return 1): a signal, block or component out of range, an empty signal, a non-finite coefficient, force
+ *     components with the distance-based contact or on nodes with extra ligaments; signals or signals_dots NULL.  Non-finite fields or
+ *     tangents anywhere in a member (also on blocks no term names): return 3 -- found by a pass over the history on the device, one
+ *     flag per workgroup, ORed by the host;
+ *   * the channels, signals, flags and term tables are allocated with the call's other buffers before the first pass and sized for the
+ *     widest pass: a failed allocation is return 2 with nothing left behind.  Both pass forms serve it (DFX_TANGENT_MULTI_FORM keeps its
+ *     meaning).  The trajectory checkpoint, the resident history and the signal tables of the handle are not touched: a dfx_adjoint or
+ *     a dfx_signal_* call after it still sees the last dfx_forward. */
+int dfx_forward_tangent_signals_multi(dfx_handle* h, const double* state0, const double* state0_dots, const dfx_params* params_dots,
+                                      int32_t n_dirs, const double* timepoints, int32_t n_timepoints, const int32_t* steps_per_interval,
+                                      const double* step_times, int32_t per_member_times,
+                                      int32_t n_terms, const int32_t* term_signal, const int32_t* term_block, const int32_t* term_component,
+                                      const double* term_coef, int32_t n_signals,
+                                      double* signals, double* signals_dots, dfx_stats* stats);
+int dfx_forward_tangent_signals_dense_multi(dfx_handle* h, const double* state0, const double* state0_dots, const dfx_params* params_dots,
+                                            int32_t n_dirs, const double* timepoints, int32_t n_timepoints, const double* step_times,
+                                            const int64_t* n_steps, int64_t stride,
+                                            int32_t n_terms, const int32_t* term_signal, const int32_t* term_block,
+                                            const int32_t* term_component, const double* term_coef, int32_t n_signals,
+                                            double* signals, double* signals_dots, dfx_stats* stats);
+
 /* Device-resident variants for benchmarking: the forward keeps the (T, ...) fields on the device and
  * the cotangent is the target-kinetic-energy objective  sum_t sum_{b in target} m_bd v_bd^2 / 2
  * (energy.py:494-499, problems/quads_focusing.py:447-467), evaluated on the device. */
