@@ -15,6 +15,8 @@ BOND_LINEARIZED, BOND_NONLINEAR, BOND_SIMPLE_SPRING, BOND_STRETCH_TORSION = 0, 1
 CONTACT_NONE, CONTACT_ANGLE, CONTACT_DISTANCE = 0, 1, 2
 TABLEAU = {"dopri5": 0, "rk4": 1}
 OBJ_KINETIC, OBJ_ANGULAR_MOMENTUM = 0, 1
+XCORR_NORMS = {"reference": 0, "coefficient": 1, "none": 2}          # DFX_XCORR_NORM_*
+XCORR_REDUCES = {"at": 0, "max": 1, "softmax": 2}                    # DFX_XCORR_AT / _MAX / _SOFTMAX
 FN_ZERO, FN_PULSE, FN_HARMONIC, FN_RAMP, FN_SECH2TANH, FN_CONSTANT, FN_RAMP_CAP, FN_TABLE = range(8)
 
 _dp = C.POINTER(C.c_double)
@@ -70,7 +72,8 @@ COMM_EXPORTS = ["dfx_comm_unique_id", "dfx_comm_init", "dfx_comm_destroy", "dfx_
                 "dfx_forward_tangent_dense_multi", "dfx_rhs_jvp", "dfx_objective_value", "dfx_objective_value_and_grad",
                 "dfx_strain_objective_value", "dfx_strain_objective_value_and_grad", "dfx_signal_values", "dfx_signal_misfit_value",
                 "dfx_signal_misfit_value_and_grad", "dfx_signal_projections", "dfx_signal_projection_value",
-                "dfx_signal_projection_value_and_grad", "dfx_forward_tangent_signals_multi", "dfx_forward_tangent_signals_dense_multi"]
+                "dfx_signal_projection_value_and_grad", "dfx_forward_tangent_signals_multi", "dfx_forward_tangent_signals_dense_multi",
+                "dfx_signal_xcorr", "dfx_signal_xcorr_value", "dfx_signal_xcorr_value_and_grad"]
 EXPORTS = EXPORTS + COMM_EXPORTS
 
 
@@ -174,6 +177,14 @@ def declare(lib):
         lib.dfx_signal_projection_value.argtypes = [H] + terms + [_dp, C.c_int32, _dp, _dp, C.c_int32, _dp]
         lib.dfx_signal_projection_value_and_grad.argtypes = [H] + terms + [_dp, C.c_int32, _dp, _dp, C.c_int32, _dp, C.POINTER(dfx_grads),
                                                                             C.POINTER(dfx_grads), C.c_int32, C.POINTER(dfx_stats)]
+    if hasattr(lib, "dfx_signal_xcorr_value_and_grad"):
+        terms = [C.c_int32, _ip, _ip, _ip, _dp, C.c_int32]
+        corr = [C.c_int32, _ip, _ip, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32]      # pairs, templates, max_lag, normalisation
+        value = [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, _dp, _dp, _dp]
+        lib.dfx_signal_xcorr.argtypes = [H] + terms + corr + [_dp]
+        lib.dfx_signal_xcorr_value.argtypes = [H] + terms + corr + value
+        lib.dfx_signal_xcorr_value_and_grad.argtypes = [H] + terms + corr + value + [C.POINTER(dfx_grads), C.POINTER(dfx_grads), C.c_int32,
+                                                                                      C.POINTER(dfx_stats)]
     if hasattr(lib, "dfx_comm_init"):
         lib.dfx_comm_unique_id.argtypes = [C.c_char_p]
         lib.dfx_comm_init.argtypes = [C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(H)]
@@ -1040,6 +1051,85 @@ class Engine:
             a.flags.writeable = False
             out[n] = a
         return obj, out, _stats(st)
+
+    # -- signal cross-correlation on the device-resident history ------------------------------------------------
+    @property
+    def has_signal_xcorr(self):
+        return hasattr(self.lib, "dfx_signal_xcorr_value_and_grad")
+
+    def _xcorr_args(self, n_signals, pairs, max_lag, templates, normalisation):
+        """The pair, template, lag and normalisation arguments of ``dfx_signal_xcorr*``: ``pairs`` a sequence of (a, b), b < 0 naming
+        column -1 - b of ``templates`` (T, n_templates) or (batch, T, n_templates); ``normalisation`` a name of ``XCORR_NORMS`` (or its
+        number).  Returns (the C arguments, the arrays they point into)."""
+        if not self.has_signal_xcorr:
+            raise NotImplementedError(f"signal cross-correlation: the library {getattr(self.lib, '_name', self.lib)!r} has no "
+                                      "dfx_signal_xcorr_value_and_grad (a stale libdfx.so, or the CPU port of the oracle; build the HIP engine)")
+        B, T = self.batch, self.n_timepoints
+        p = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        pa, pb = np.ascontiguousarray(p[:, 0], dtype=np.int32), np.ascontiguousarray(p[:, 1], dtype=np.int32)
+        tp, nt = None, 0
+        if templates is not None:
+            tp = _f64(templates)
+            if tp.ndim not in (2, 3) or (tp.ndim == 3 and tp.shape[0] != B) or (T is not None and tp.shape[-2] != T):
+                raise ValueError(f"templates must be ({T}, n_templates) or ({B}, {T}, n_templates), got {tp.shape}")
+            nt = tp.shape[-1]
+        norm = XCORR_NORMS[normalisation] if isinstance(normalisation, str) else int(normalisation)
+        return (len(p), pa.ctypes.data_as(_ip), pb.ctypes.data_as(_ip), _ptr(tp), nt, int(tp is not None and tp.ndim == 3), int(max_lag), norm), (pa, pb, tp)
+
+    @staticmethod
+    def _xcorr_value_args(reduce, lag, beta, w_peak, w_delay, delay_target):
+        red = XCORR_REDUCES[reduce] if isinstance(reduce, str) else int(reduce)
+        return (red, int(0 if lag is None else lag), float(1.0 if beta is None else beta), float(w_peak), float(w_delay), float(delay_target))
+
+    def signal_xcorr(self, terms, n_signals, pairs, max_lag, templates=None, normalisation="reference"):
+        """(batch, 2 max_lag + 1) normalised cross-correlation rho of the signal pairs over the lags -max_lag .. max_lag in output indices
+        (``dfx_signal_xcorr``; lag d at index d + max_lag, d > 0: side B lags side A) on the resident history of the last forward pass."""
+        xa, keep2 = self._xcorr_args(n_signals, pairs, max_lag, templates, normalisation)
+        args, keep = self._signal_terms(terms, n_signals)
+        out = np.zeros((self.batch, 2 * max(int(max_lag), 0) + 1))
+        self._check(self.lib.dfx_signal_xcorr(self._h, *args, *xa, _ptr(out)), "dfx_signal_xcorr")
+        return out
+
+    def signal_xcorr_value(self, terms, n_signals, pairs, max_lag, templates=None, normalisation="reference", reduce="max", lag=None, beta=None,
+                           w_peak=1.0, w_delay=0.0, delay_target=0.0):
+        """(J, peak, delay), (batch,) each: J = w_peak M + 1/2 w_delay (delta - delay_target)^2 of the reduction ``reduce`` ("at" the lag
+        ``lag``, "max", "softmax" with ``beta``) of the cross-correlation over the lags (``dfx_signal_xcorr_value``)."""
+        xa, keep2 = self._xcorr_args(n_signals, pairs, max_lag, templates, normalisation)
+        args, keep = self._signal_terms(terms, n_signals)
+        va = self._xcorr_value_args(reduce, lag, beta, w_peak, w_delay, delay_target)
+        obj, peak, delay = np.zeros(self.batch), np.zeros(self.batch), np.zeros(self.batch)
+        self._check(self.lib.dfx_signal_xcorr_value(self._h, *args, *xa, *va, _ptr(obj), _ptr(peak), _ptr(delay)), "dfx_signal_xcorr_value")
+        return obj, peak, delay
+
+    def signal_xcorr_value_and_grad(self, terms, n_signals, pairs, max_lag, templates=None, normalisation="reference", reduce="max", lag=None,
+                                    beta=None, w_peak=1.0, w_delay=0.0, delay_target=0.0, which=ALL_GRADS, device=False):
+        """(J, peak, delay) and the requested gradients of J in ONE call (``dfx_signal_xcorr_value_and_grad``): the correlation over the lags,
+        its reduction and the cotangent on the signals are formed on the device, everything behind them is the signal misfit's.  Returns
+        (J, peak, delay, gradients, stats), the gradients as :meth:`signal_misfit_value_and_grad`."""
+        xa, keep2 = self._xcorr_args(n_signals, pairs, max_lag, templates, normalisation)
+        args, keep = self._signal_terms(terms, n_signals)
+        va = self._xcorr_value_args(reduce, lag, beta, w_peak, w_delay, delay_target)
+        sh = self.shapes()
+        want, views = dfx_grads(), dfx_grads()
+        names = [n for n in which if not (n == "fn_params" and self.n_fns == 0) and not (n == "contact" and not self.contact)
+                 and not (n == "void_angle0" and self.contact != CONTACT_ANGLE)
+                 and not (n == "block_centroids" and self.contact != CONTACT_DISTANCE)]
+        flag = np.zeros(1)
+        for n in names:
+            setattr(want, n, _ptr(flag))
+        obj, peak, delay = np.zeros(self.batch), np.zeros(self.batch), np.zeros(self.batch)
+        st = dfx_stats()
+        self._check(self.lib.dfx_signal_xcorr_value_and_grad(self._h, *args, *xa, *va, _ptr(obj), _ptr(peak), _ptr(delay), C.byref(want),
+                                                             C.byref(views), int(bool(device)), C.byref(st)),
+                    "dfx_signal_xcorr_value_and_grad")
+        if device:
+            return obj, peak, delay, {n: DeviceArray(self, C.cast(getattr(views, n), C.c_void_p).value, sh[n]) for n in names}, _stats(st)
+        out = {}
+        for n in names:
+            a = np.ctypeslib.as_array(getattr(views, n), shape=sh[n])
+            a.flags.writeable = False
+            out[n] = a
+        return obj, peak, delay, out, _stats(st)
 
     def response_data(self, strains=True, kinetic=True):
         """Per-ligament strain energies (batch, T, n_bonds) x 3 and per-block kinetic energy (batch, T, n_blocks) of the last

@@ -155,6 +155,11 @@ struct dfx_handle {
   // dfx_signal_projection* (engine_objective.hip): basis | row weights | targets of the call and the projections P; proj: their layout
   DevBuf<double> d_proj_coef, d_proj_P;
   struct ProjJob { int n_rows = 0; bool has_w = false, has_target = false; long long target_stride = 0; } proj;
+  // dfx_signal_xcorr* (engine_objective.hip): pairs | templates of the call in one buffer (the int32 pairs in its first n_pairs doubles),
+  // R | rho | Rbar over the lags, and per member EA, EB | eA, eB | peak | delay; xc: the layout and the scalars of the call
+  DevBuf<double> d_xc_coef, d_xc_R, d_xc_s;
+  struct XcorrJob { int n_pairs = 0, n_templ = 0, D = 0, norm = 0, reduce = 0, lag0 = 0; bool has_templ = false; long long templ_stride = 0;
+                    double beta = 1.0, w_peak = 1.0, w_delay = 0.0, delay_target = 0.0; } xc;
   std::vector<double> ts;
   std::vector<int> spis;           // RK steps in each output interval (fixed grid)
   std::vector<long long> step0;    // first step ordinal of each interval

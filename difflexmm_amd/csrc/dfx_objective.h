@@ -52,6 +52,20 @@
 //                              in order into its partial, k_objective_finish adds the partials
 //   k_signal_project_residual  one lane per (member, output, signal): c_mks = sum_j W_sj (P_msj - Ptarget_msj) B_jk, j ascending, into
 //                              the residual-cotangent buffer
+//
+// The signal cross-correlation (dfx_signal_xcorr, dfx_signal_xcorr_value[_and_grad]): pairs (A_p, B_p) of those signals (B_p may be a
+// column of a fixed template array) correlated over the lags d = -D .. D in output indices, R[d] = sum_p sum_k A_p[k] B_p[k + d],
+// rho = R / N with N = EA = sum A^2 ("reference"), sqrt(EA EB) ("coefficient") or 1 ("none"); a reduction over the lags (the value at one
+// lag, the maximum, a softmax) gives a peak M and a delay delta, J = w_peak M + 1/2 w_delay (delta - delta_target)^2.  S as for the
+// projections; from the cotangent c on, k_signal_direction / _cotangent / _explicit as above.
+//   k_signal_xcorr           one wave per (member, lag) and two more per member for EA and EB: lane l adds outputs l, l + 64, ... ascending
+//                            with the pairs ascending inside, then obj_wave_sum
+//   k_signal_xcorr_reduce    one wave per member: N, rho, the reduction in a fixed lane-strided order, J, M, delta and the cotangents
+//                            Rbar = (dJ/d rho) / N on the lags and (eA, eB) on the energies.  Ties of the maximum: the lowest lag takes the
+//                            whole gradient (the subgradient np.argmax implies; JAX's max splits a tie evenly -- ties are a set of
+//                            measure zero).  A member with N == 0 gets NaN values and an all-zero cotangent
+//   k_signal_xcorr_residual  one lane per (member, output, signal): c from Rbar, eA, eB, the signals and the templates, pairs and lags
+//                            ascending, into the residual-cotangent buffer; lags whose Rbar is exactly 0 are skipped
 // No atomics anywhere: the same history gives the same bits.
 #pragma once
 #include "dfx_kernels.h"
@@ -551,6 +565,187 @@ __global__ __launch_bounds__(kObjThreads) void k_signal_project_residual(DevCtx 
   const double* tg = p.target ? p.target + (size_t)m * p.target_stride + (size_t)s * p.n_rows : nullptr;
   double cr = 0.0;
   for (int j = 0; j < p.n_rows; ++j) cr += W[j] * (P[j] - (tg ? tg[j] : 0.0)) * p.basis[(size_t)j * T + k];
+  a.cres[(size_t)m * total + (size_t)item] = cr;
+}
+
+// ---- signal cross-correlation ---------------------------------------------------------------------------------------------------------
+constexpr int kObjXcorr = 5;               // ObjJob::kind of a cross-correlation call: a signal job behind the sweep (k_signal_explicit)
+
+struct XcorrArgs {
+  const int32_t *pair_a, *pair_b;   // n_pairs: side A a signal; side B a signal (>= 0) or template column -1 - b
+  const double* templ;              // (T, n_templ), members templ_stride apart (0: shared); null: no template column is named
+  double *R, *rho, *Rbar;           // batch * (2 D + 1) each, lag d at index d + D
+  double *E, *ebar;                 // batch * 2 each: (EA, EB) and their cotangents (eA, eB)
+  double *peak, *delay;             // batch each
+  long long templ_stride;
+  int n_pairs, n_templ, D, norm, reduce, lag0;
+  double beta, w_peak, w_delay, delay_target;
+};
+
+// side B of pair p of member m at output k (S: the member's signals, (T, n_sig))
+__device__ __forceinline__ double xcorr_side_b(const XcorrArgs& x, const double* S, int n_sig, const double* G, int b, int k) {
+  return b >= 0 ? S[(size_t)k * n_sig + b] : G[(size_t)k * x.n_templ + (-1 - b)];
+}
+
+// grid (chunks of kObjWaves rows, members): wave `row` of a member holds lag d = row - D for row <= 2 D, then EA (row 2 D + 1) and EB
+// (row 2 D + 2).  Lane l adds outputs k = l, l + 64, ... ascending with the pairs ascending inside, products whose partner output k + d
+// falls outside [0, T) left out; obj_wave_sum adds the lanes.  A wave past the last row stores nothing.
+__global__ __launch_bounds__(kObjThreads) void k_signal_xcorr(DevCtx c, SigArgs a, XcorrArgs x) {
+  const int m = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int T = c.n_timepoints, nl = 2 * x.D + 1;
+  const int row = blockIdx.x * kObjWaves + wv;
+  if (row >= nl + 2) return;                    // (no barrier in this kernel: a whole wave leaves)
+  const double* S = a.S + (size_t)m * T * a.n_sig;
+  const double* G = x.templ ? x.templ + (size_t)m * x.templ_stride : nullptr;
+  double v = 0.0;
+  if (row < nl) {
+    const int d = row - x.D;
+    for (int k = lane; k < T; k += 64) {
+      const int kb = k + d;
+      if (kb < 0 || kb >= T) continue;
+      for (int p = 0; p < x.n_pairs; ++p) v += S[(size_t)k * a.n_sig + x.pair_a[p]] * xcorr_side_b(x, S, a.n_sig, G, x.pair_b[p], kb);
+    }
+  } else {
+    const bool sideA = row == nl;
+    for (int k = lane; k < T; k += 64)
+      for (int p = 0; p < x.n_pairs; ++p) {
+        const double s = sideA ? S[(size_t)k * a.n_sig + x.pair_a[p]] : xcorr_side_b(x, S, a.n_sig, G, x.pair_b[p], k);
+        v += s * s;
+      }
+  }
+  v = obj_wave_sum(v);
+  if (lane == 0) {
+    if (row < nl) x.R[(size_t)m * nl + row] = v;
+    else x.E[(size_t)m * 2 + (row - nl)] = v;
+  }
+}
+
+// the lanes' (value, index) candidates of a maximum: the larger value wins, on equal values the lower index; every lane ends with the result
+__device__ __forceinline__ void xcorr_wave_argmax(double& v, int& i) {
+  for (int off = 32; off > 0; off >>= 1) {
+    const double ov = __shfl_xor(v, off, 64);
+    const int oi = __shfl_xor(i, off, 64);
+    if (oi >= 0 && (i < 0 || ov > v || (ov == v && oi < i))) { v = ov; i = oi; }
+  }
+}
+
+// grid (members), one wave each: N and rho = R / N, then the reduction over the lags in a fixed lane-strided order (lane l holds lags
+// l, l + 64, ... ascending; the maximum first, then the exponent sums with the maximum subtracted, obj_wave_sum over the lanes), the value
+// J = w_peak M + 1/2 w_delay (delta - delta_target)^2 into objective[m] (and pinned host memory when given), M and delta per member, the
+// cotangents Rbar = g / N on the lags and (eA, eB) on the energies.  N == 0: J = M = delta = rho = NaN and every cotangent 0.
+__global__ __launch_bounds__(64) void k_signal_xcorr_reduce(XcorrArgs x, double* objective, double* host3, int batch) {
+  const int m = blockIdx.x, lane = threadIdx.x;
+  const int nl = 2 * x.D + 1;
+  const double* R = x.R + (size_t)m * nl;
+  double* rho = x.rho + (size_t)m * nl;
+  double* Rbar = x.Rbar + (size_t)m * nl;
+  const double EA = x.E[(size_t)m * 2], EB = x.E[(size_t)m * 2 + 1];
+  const double N = x.norm == DFX_XCORR_NORM_REFERENCE ? EA : x.norm == DFX_XCORR_NORM_COEFFICIENT ? sqrt(EA * EB) : 1.0;
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  if (N == 0.0) {
+    for (int i = lane; i < nl; i += 64) { rho[i] = nan; Rbar[i] = 0.0; }
+    if (lane == 0) {
+      x.ebar[(size_t)m * 2] = x.ebar[(size_t)m * 2 + 1] = 0.0;
+      x.peak[m] = x.delay[m] = nan;
+      if (objective) objective[m] = nan;
+      if (host3) { host3[m] = nan; host3[batch + m] = nan; host3[2 * batch + m] = nan; }
+    }
+    return;
+  }
+  // the maximum and the lowest lag that reaches it
+  double best = 0.0;
+  int at = -1;
+  for (int i = lane; i < nl; i += 64) {
+    const double r = R[i] / N;
+    rho[i] = r;
+    if (at < 0 || r > best) { best = r; at = i; }
+  }
+  xcorr_wave_argmax(best, at);
+  double M, delta, Z = 1.0;
+  if (x.reduce == DFX_XCORR_SOFTMAX) {
+    double z = 0.0, zd = 0.0;
+    for (int i = lane; i < nl; i += 64) {
+      const double e = exp(x.beta * (R[i] / N - best));
+      z += e; zd += (double)(i - x.D) * e;
+    }
+    z = obj_wave_sum(z); zd = obj_wave_sum(zd);
+    Z = __shfl(z, 0, 64);
+    M = best + log(Z) / x.beta;
+    delta = __shfl(zd, 0, 64) / Z;
+  } else if (x.reduce == DFX_XCORR_MAX) {
+    M = best; delta = (double)(at - x.D);
+  } else {
+    M = R[x.lag0 + x.D] / N; delta = (double)x.lag0;
+    at = x.lag0 + x.D;
+  }
+  // g = dJ / d rho on the lags, Rbar = g / N, Nbar = - sum g rho / N
+  const double dd = x.w_delay * (delta - x.delay_target);
+  double gr = 0.0;
+  for (int i = lane; i < nl; i += 64) {
+    const double r = R[i] / N;
+    double g;
+    if (x.reduce == DFX_XCORR_SOFTMAX) {
+      const double pi = exp(x.beta * (r - best)) / Z;
+      g = x.w_peak * pi + dd * x.beta * pi * ((double)(i - x.D) - delta);
+    } else {
+      g = i == at ? x.w_peak : 0.0;
+    }
+    Rbar[i] = g / N;
+    gr += g * r;
+  }
+  gr = obj_wave_sum(gr);
+  if (lane == 0) {
+    const double Nbar = -gr / N;
+    double eA = 0.0, eB = 0.0;
+    if (x.norm == DFX_XCORR_NORM_REFERENCE) eA = Nbar;
+    else if (x.norm == DFX_XCORR_NORM_COEFFICIENT) { eA = Nbar * N / (2.0 * EA); eB = Nbar * N / (2.0 * EB); }
+    x.ebar[(size_t)m * 2] = eA; x.ebar[(size_t)m * 2 + 1] = eB;
+    const double J = x.w_peak * M + 0.5 * dd * (delta - x.delay_target);
+    x.peak[m] = M; x.delay[m] = delta;
+    if (objective) objective[m] = J;
+    if (host3) { host3[m] = J; host3[batch + m] = M; host3[2 * batch + m] = delta; }     // pinned host memory, as k_objective_finish
+  }
+}
+
+// grid (chunks of kObjThreads (output, signal) items, members), behind k_signal_xcorr_reduce on the same stream: the cotangent of J on the
+// signals into cres, where k_signal_project_residual puts its own --
+//   c_ks = sum over pairs with a_p = s: ( sum_d Rbar[d] B_p[k + d] + 2 eA A_p[k] ) + sum over pairs with b_p = s: ( sum_d Rbar[d] A_p[k - d] + 2 eB B_p[k] )
+// the A-side pairs first, each group with p ascending and d ascending inside; lags whose Rbar is exactly 0 are skipped (under "at" and
+// "max" all but one), partner outputs outside [0, T) contribute nothing
+__global__ __launch_bounds__(kObjThreads) void k_signal_xcorr_residual(DevCtx c, SigArgs a, XcorrArgs x) {
+  const int m = blockIdx.y;
+  const int T = c.n_timepoints, nl = 2 * x.D + 1;
+  const long long total = (long long)T * a.n_sig;
+  const long long item = (long long)blockIdx.x * kObjThreads + threadIdx.x;
+  if (item >= total) return;
+  const int k = (int)(item / a.n_sig), s = (int)(item % a.n_sig);
+  const double* S = a.S + (size_t)m * T * a.n_sig;
+  const double* G = x.templ ? x.templ + (size_t)m * x.templ_stride : nullptr;
+  const double* Rbar = x.Rbar + (size_t)m * nl;
+  const double eA = x.ebar[(size_t)m * 2], eB = x.ebar[(size_t)m * 2 + 1];
+  double cr = 0.0;
+  for (int p = 0; p < x.n_pairs; ++p) {
+    if (x.pair_a[p] != s) continue;
+    const int b = x.pair_b[p];
+    double acc = 0.0;
+    for (int i = 0; i < nl; ++i) {
+      const int kb = k + i - x.D;
+      if (Rbar[i] == 0.0 || kb < 0 || kb >= T) continue;
+      acc += Rbar[i] * xcorr_side_b(x, S, a.n_sig, G, b, kb);
+    }
+    cr += acc + 2.0 * eA * S[(size_t)k * a.n_sig + s];
+  }
+  for (int p = 0; p < x.n_pairs; ++p) {
+    if (x.pair_b[p] != s) continue;
+    const int sa = x.pair_a[p];
+    double acc = 0.0;
+    for (int i = 0; i < nl; ++i) {
+      const int ka = k - (i - x.D);
+      if (Rbar[i] == 0.0 || ka < 0 || ka >= T) continue;
+      acc += Rbar[i] * S[(size_t)ka * a.n_sig + sa];
+    }
+    cr += acc + 2.0 * eB * S[(size_t)k * a.n_sig + s];
+  }
   a.cres[(size_t)m * total + (size_t)item] = cr;
 }
 

@@ -7,6 +7,8 @@
 // device, the Hessian-vector product K w of its force terms added to the cotangent, mixed second derivatives behind the sweep.
 // The signal projections (dfx_signal_projections, dfx_signal_projection_value[_and_grad]) put a time reduction between the signals and
 // their cotangent: P = B S, the value a weighted quadratic form of P, c = B^T (W (P - Ptarget)); from c on the signal misfit's launches.
+// The signal cross-correlation (dfx_signal_xcorr, dfx_signal_xcorr_value[_and_grad]) is a second, nonlinear occupant of that slot: R over the
+// lags and the two energies, a reduction to a peak and a delay, and the cotangent c of J = w_peak M + 1/2 w_delay (delta - delta_target)^2.
 // (shared declarations in dfx_engine.h, the kernels in dfx_objective.h)
 #include "dfx_engine.h"
 #include "dfx_objective.h"
@@ -436,12 +438,111 @@ int launch_projection(dfx_handle* h, double* G, double* objective_host) {
   return 0;
 }
 
+// ---- signal cross-correlation: the checks of the pairs, the templates, the lags and the reduction (return 1 with h->err), prepare_signal
+// without targets for the terms, then pairs | templates into one buffer.  value: the call forms J (the reduction and its weights are checked)
+struct XcorrCall {
+  int32_t n_pairs; const int32_t *pair_a, *pair_b; const double* templ; int32_t n_templ, templ_per_member, max_lag, norm;
+  bool value; int32_t reduce, lag0; double beta, w_peak, w_delay, delay_target;
+};
+
+int prepare_xcorr(dfx_handle* h, const char* who, const SigTerms& t, const XcorrCall& q) {
+  const size_t B = h->pl.batch;
+  const size_t Tn = h->ts.size();
+  const std::string w(who);
+  const int ns = t.n_signals;
+  if (q.n_pairs < 1) { h->err = w + ": n_pairs must be at least 1, got " + std::to_string(q.n_pairs); return 1; }
+  if (!q.pair_a || !q.pair_b) { h->err = w + ": pair_a or pair_b is NULL"; return 1; }
+  if (q.templ && q.n_templ < 1) { h->err = w + ": templates given with n_templates = " + std::to_string(q.n_templ); return 1; }
+  bool named = false;
+  for (int p = 0; p < q.n_pairs; ++p) {
+    const int a = q.pair_a[p], b = q.pair_b[p];
+    if (a < 0 || a >= ns) { h->err = w + ": pair " + std::to_string(p) + " names signal " + std::to_string(a) + " out of range (n_signals = " + std::to_string(ns) + ")"; return 1; }
+    if (b >= ns) { h->err = w + ": pair " + std::to_string(p) + " names signal " + std::to_string(b) + " out of range (n_signals = " + std::to_string(ns) + ")"; return 1; }
+    if (b < 0 && !q.templ) { h->err = w + ": pair " + std::to_string(p) + " names template column " + std::to_string(-1 - (long long)b) + " but templates is NULL"; return 1; }
+    if (b < 0 && -1 - (long long)b >= q.n_templ) { h->err = w + ": pair " + std::to_string(p) + " names template column " + std::to_string(-1 - (long long)b) + " out of range (n_templates = " + std::to_string(q.n_templ) + ")"; return 1; }
+    named = named || b < 0;
+  }
+  if (q.max_lag < 0 || (size_t)q.max_lag + 1 > Tn) { h->err = w + ": max_lag " + std::to_string(q.max_lag) + " outside [0, T - 1] (T = " + std::to_string(Tn) + ")"; return 1; }
+  if (q.norm != DFX_XCORR_NORM_REFERENCE && q.norm != DFX_XCORR_NORM_COEFFICIENT && q.norm != DFX_XCORR_NORM_NONE) {
+    h->err = w + ": unknown normalisation " + std::to_string(q.norm) + " (DFX_XCORR_NORM_REFERENCE = 0, _COEFFICIENT = 1, _NONE = 2)";
+    return 1;
+  }
+  if (q.value) {
+    if (q.reduce != DFX_XCORR_AT && q.reduce != DFX_XCORR_MAX && q.reduce != DFX_XCORR_SOFTMAX) {
+      h->err = w + ": unknown reduction " + std::to_string(q.reduce) + " (DFX_XCORR_AT = 0, DFX_XCORR_MAX = 1, DFX_XCORR_SOFTMAX = 2)";
+      return 1;
+    }
+    if (q.reduce == DFX_XCORR_AT && (q.lag0 < -q.max_lag || q.lag0 > q.max_lag)) {
+      h->err = w + ": lag0 " + std::to_string(q.lag0) + " outside [-max_lag, max_lag] (max_lag = " + std::to_string(q.max_lag) + ")";
+      return 1;
+    }
+    if (q.reduce == DFX_XCORR_SOFTMAX && !(std::isfinite(q.beta) && q.beta > 0.0)) { h->err = w + ": beta must be positive and finite with the softmax reduction"; return 1; }
+    if (!std::isfinite(q.w_peak) || !std::isfinite(q.w_delay)) { h->err = w + ": non-finite weight"; return 1; }
+    if (!std::isfinite(q.delay_target)) { h->err = w + ": non-finite delay_target"; return 1; }
+    if (q.w_delay != 0.0 && q.reduce != DFX_XCORR_SOFTMAX) { h->err = w + ": w_delay != 0 needs the softmax reduction (the delay of a maximum has no derivative)"; return 1; }
+  }
+  const size_t n_tp = q.templ ? (q.templ_per_member ? B : 1) * Tn * (size_t)q.n_templ : 0;
+  for (size_t i = 0; i < n_tp; ++i)
+    if (!std::isfinite(q.templ[i])) { h->err = w + ": non-finite template"; return 1; }
+  if (int rc = prepare_signal(h, who, t, nullptr, 0, nullptr, nullptr, false)) return rc;
+  dfx_handle::XcorrJob& J = h->xc;
+  J.n_pairs = q.n_pairs; J.n_templ = q.templ ? q.n_templ : 0; J.D = q.max_lag; J.norm = q.norm;
+  J.has_templ = named; J.templ_stride = q.templ_per_member ? (long long)(Tn * (size_t)q.n_templ) : 0;
+  J.reduce = q.value ? q.reduce : DFX_XCORR_AT; J.lag0 = q.value ? q.lag0 : 0; J.beta = q.value ? q.beta : 1.0;
+  J.w_peak = q.value ? q.w_peak : 1.0; J.w_delay = q.value ? q.w_delay : 0.0; J.delay_target = q.value ? q.delay_target : 0.0;
+  std::vector<double> dbl((size_t)q.n_pairs, 0.0);                 // 2 n_pairs int32: pair_a | pair_b
+  memcpy(dbl.data(), q.pair_a, sizeof(int32_t) * q.n_pairs);
+  memcpy(reinterpret_cast<char*>(dbl.data()) + sizeof(int32_t) * q.n_pairs, q.pair_b, sizeof(int32_t) * q.n_pairs);
+  if (named) dbl.insert(dbl.end(), q.templ, q.templ + n_tp);
+  const size_t nl = 2 * (size_t)q.max_lag + 1;
+  HIP_OK(h->d_xc_coef.ensure(dbl.size()));
+  HIP_OK(h->d_xc_R.ensure(B * nl * 3));
+  HIP_OK(h->d_xc_s.ensure(B * 6));
+  HIP_OK(hipMemcpyAsync(h->d_xc_coef.p, dbl.data(), sizeof(double) * dbl.size(), hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));       // the table is a local of this function
+  return 0;
+}
+
+XcorrArgs xcorr_args(const dfx_handle* h) {
+  const dfx_handle::XcorrJob& J = h->xc;
+  const size_t B = h->pl.batch, nl = 2 * (size_t)J.D + 1;
+  XcorrArgs x;
+  x.pair_a = reinterpret_cast<const int32_t*>(h->d_xc_coef.p);
+  x.pair_b = x.pair_a + J.n_pairs;
+  x.templ = J.has_templ ? h->d_xc_coef.p + J.n_pairs : nullptr;
+  x.R = h->d_xc_R.p; x.rho = x.R + B * nl; x.Rbar = x.rho + B * nl;
+  x.E = h->d_xc_s.p; x.ebar = x.E + B * 2; x.peak = x.ebar + B * 2; x.delay = x.peak + B;
+  x.templ_stride = J.templ_stride;
+  x.n_pairs = J.n_pairs; x.n_templ = J.n_templ; x.D = J.D; x.norm = J.norm; x.reduce = J.reduce; x.lag0 = J.lag0;
+  x.beta = J.beta; x.w_peak = J.w_peak; x.w_delay = J.w_delay; x.delay_target = J.delay_target;
+  return x;
+}
+
+// channels and signals (launch_signal without targets), R, EA, EB over the lags, the reduction (J into d_obj and, when given, J | M | delta
+// into pinned host memory); with G the cotangent c on the signals and from it the cotangent of the sweep
+int launch_xcorr(dfx_handle* h, double* G, double* host3) {
+  const dfx_handle::XcorrJob& J = h->xc;
+  const size_t B = h->pl.batch;
+  if (int rc = launch_signal(h, nullptr, nullptr)) return rc;
+  DevCtx c = make_ctx(h);
+  const SigArgs a = sig_args(h);
+  const XcorrArgs x = xcorr_args(h);
+  hipLaunchKernelGGL(k_signal_xcorr, dim3(chunks_of(2LL * J.D + 3, kObjWaves), (unsigned)B), dim3(kObjThreads), 0, h->stream, c, a, x);
+  hipLaunchKernelGGL(k_signal_xcorr_reduce, dim3((unsigned)B), dim3(64), 0, h->stream, x, h->d_obj.p, host3, (int)B);
+  if (G) {
+    hipLaunchKernelGGL(k_signal_xcorr_residual, dim3(chunks_of((long long)h->ts.size() * h->sig.n_sig, kObjThreads), (unsigned)B), dim3(kObjThreads), 0,
+                       h->stream, c, a, x);
+    launch_signal_reverse(h, c, a, G);
+  }
+  return 0;
+}
+
 }  // namespace
 
 void launch_objective_explicit(dfx_handle* h, const DevCtx& c) {
   const ObjJob& j = *h->obj_job;
   if (j.n_act == 0) return;
-  if (j.kind == kObjSignal || j.kind == kObjProject) {       // the same direction w, whichever residual it came from
+  if (j.kind == kObjSignal || j.kind == kObjProject || j.kind == kObjXcorr) {       // the same direction w, whichever residual it came from
     const SigArgs a = sig_args(h);
     const dim3 grid((unsigned)((a.n_set * 4 + 63) / 64), (unsigned)h->pl.batch);
     with_strain_physics(h, [&](auto M, auto C) { hipLaunchKernelGGL((k_signal_explicit<M(), C()>), grid, dim3(64), 0, h->stream, c, a); });
@@ -617,6 +718,39 @@ int dfx_signal_misfit_value_and_grad(dfx_handle* h, int32_t n_terms, const int32
   return 0;
 }
 
+namespace {
+
+// What the gradient entries of the signal projections and of the signal cross-correlation share behind their own prepare_*: the buffers of
+// the sweep, a signal job of `kind` behind it (k_signal_explicit), `launch(G, host)` for the value and the cotangent (host: n_host doubles
+// of pinned memory the launch may fill, null when n_host == 0; the caller reads h->obj_stage after a return of 0), then the sweep itself --
+// want / views / device_views / stats, every sweep form and checkpoint level, the kept steps of an adaptive solve.
+template <class Launch>
+int signal_job_sweep(dfx_handle* h, int kind, size_t n_host, Launch&& launch, const dfx_grads* want, dfx_grads* views, int32_t device_views,
+                     dfx_stats* stats) {
+  const Plan& pl = h->pl;
+  const size_t B = pl.batch, nb = pl.n_blocks;
+  const int Tn = (int)h->ts.size();
+  if (ensure_adjoint_buffers(h)) return 2;
+  HIP_OK(h->d_G.ensure(B * Tn * nb * 6));
+  if (n_host) HIP_OK(h->obj_stage.ensure(sizeof(double) * n_host));
+  // as dfx_objective_value_and_grad: what the sweep consults on the handle for this call is taken back on every way out
+  struct Scope {
+    dfx_handle* h;
+    ~Scope() { h->obj_job = nullptr; h->obj_centroids = false; h->device_views = false; }
+  } scope{h};
+  ObjJob job;
+  job.kind = kind; job.n_act = h->sig.n_set; job.w_stride = job.lever_stride = 0; job.has_tau = false;
+  h->obj_centroids = false;
+  h->obj_job = &job;
+  h->device_views = device_views != 0;
+  set_grad_wishes(h, want);
+  if (zero_grad_accumulators(h, h->d_G.p, B * Tn * nb * 6, (int)h->segs.size())) return 2;
+  if (int rc = launch(h->d_G.p, n_host ? reinterpret_cast<double*>(h->obj_stage.p) : nullptr)) return rc;
+  return run_adjoint(h, want, nullptr, views, stats, false, 0, true);
+}
+
+}  // namespace
+
 int dfx_signal_projections(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block, const int32_t* term_component,
                            const double* term_coef, int32_t n_signals, const double* basis, int32_t n_rows, double* values) {
   HIP_OK(hipSetDevice(h->device));
@@ -653,28 +787,77 @@ int dfx_signal_projection_value_and_grad(dfx_handle* h, int32_t n_terms, const i
   HIP_OK(hipSetDevice(h->device));
   if (!h->have_traj || !h->have_fields) { h->err = "signal_projection_value_and_grad: run forward with keep_trajectory=1 first"; return 1; }
   if (h->ck->writer != h) { h->err = std::string("signal_projection_value_and_grad: ") + kStaleCheckpoint; return 1; }
-  const Plan& pl = h->pl;
-  const size_t B = pl.batch, nb = pl.n_blocks;
-  const int Tn = (int)h->ts.size();
+  const size_t B = h->pl.batch;
   const SigTerms t{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
   if (int rc = prepare_projection(h, "signal_projection_value_and_grad", t, basis, n_rows, row_weights, targets, targets_per_member, true)) return rc;
-  if (ensure_adjoint_buffers(h)) return 2;
-  HIP_OK(h->d_G.ensure(B * Tn * nb * 6));
-  if (objective) HIP_OK(h->obj_stage.ensure(sizeof(double) * B));
-  // as dfx_objective_value_and_grad: what the sweep consults on the handle for this call is taken back on every way out
-  struct Scope {
-    dfx_handle* h;
-    ~Scope() { h->obj_job = nullptr; h->obj_centroids = false; h->device_views = false; }
-  } scope{h};
-  ObjJob job;
-  job.kind = kObjProject; job.n_act = h->sig.n_set; job.w_stride = job.lever_stride = 0; job.has_tau = false;
-  h->obj_centroids = false;
-  h->obj_job = &job;
-  h->device_views = device_views != 0;
-  set_grad_wishes(h, want);
-  if (zero_grad_accumulators(h, h->d_G.p, B * Tn * nb * 6, (int)h->segs.size())) return 2;
-  if (int rc = launch_projection(h, h->d_G.p, objective ? reinterpret_cast<double*>(h->obj_stage.p) : nullptr)) return rc;
-  if (int rc = run_adjoint(h, want, nullptr, views, stats, false, 0, true)) return rc;
+  if (int rc = signal_job_sweep(h, kObjProject, objective ? B : 0, [&](double* G, double* host) { return launch_projection(h, G, host); }, want, views,
+                                device_views, stats))
+    return rc;
   if (objective) memcpy(objective, h->obj_stage.p, sizeof(double) * B);
+  return 0;
+}
+
+int dfx_signal_xcorr(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block, const int32_t* term_component,
+                     const double* term_coef, int32_t n_signals, int32_t n_pairs, const int32_t* pair_a, const int32_t* pair_b,
+                     const double* templates, int32_t n_templates, int32_t templates_per_member, int32_t max_lag, int32_t normalisation,
+                     double* values) {
+  HIP_OK(hipSetDevice(h->device));
+  if (!h->have_fields || !h->have_params) { h->err = "signal_xcorr: run forward first"; return 1; }
+  if (!values) { h->err = "signal_xcorr: values is NULL"; return 1; }
+  const SigTerms t{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
+  const XcorrCall q{n_pairs, pair_a, pair_b, templates, n_templates, templates_per_member, max_lag, normalisation, false, 0, 0, 1.0, 1.0, 0.0, 0.0};
+  if (int rc = prepare_xcorr(h, "signal_xcorr", t, q)) return rc;
+  if (int rc = launch_xcorr(h, nullptr, nullptr)) return rc;
+  HIP_OK(hipMemcpyAsync(values, xcorr_args(h).rho, sizeof(double) * h->pl.batch * (2 * (size_t)max_lag + 1), hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int dfx_signal_xcorr_value(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block,
+                           const int32_t* term_component, const double* term_coef, int32_t n_signals, int32_t n_pairs, const int32_t* pair_a,
+                           const int32_t* pair_b, const double* templates, int32_t n_templates, int32_t templates_per_member, int32_t max_lag,
+                           int32_t normalisation, int32_t reduce, int32_t lag0, double beta, double w_peak, double w_delay,
+                           double delay_target, double* objective, double* peak, double* delay) {
+  HIP_OK(hipSetDevice(h->device));
+  if (!h->have_fields || !h->have_params) { h->err = "signal_xcorr_value: run forward first"; return 1; }
+  if (!objective) { h->err = "signal_xcorr_value: objective is NULL"; return 1; }
+  const SigTerms t{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
+  const XcorrCall q{n_pairs, pair_a, pair_b, templates, n_templates, templates_per_member, max_lag, normalisation, true, reduce, lag0, beta, w_peak,
+                    w_delay, delay_target};
+  if (int rc = prepare_xcorr(h, "signal_xcorr_value", t, q)) return rc;
+  if (int rc = launch_xcorr(h, nullptr, nullptr)) return rc;
+  const size_t B = h->pl.batch;
+  const XcorrArgs x = xcorr_args(h);
+  HIP_OK(hipMemcpyAsync(objective, h->d_obj.p, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
+  if (peak) HIP_OK(hipMemcpyAsync(peak, x.peak, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
+  if (delay) HIP_OK(hipMemcpyAsync(delay, x.delay, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int dfx_signal_xcorr_value_and_grad(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block,
+                                    const int32_t* term_component, const double* term_coef, int32_t n_signals, int32_t n_pairs,
+                                    const int32_t* pair_a, const int32_t* pair_b, const double* templates, int32_t n_templates,
+                                    int32_t templates_per_member, int32_t max_lag, int32_t normalisation, int32_t reduce, int32_t lag0,
+                                    double beta, double w_peak, double w_delay, double delay_target, double* objective, double* peak,
+                                    double* delay, const dfx_grads* want, dfx_grads* views, int32_t device_views, dfx_stats* stats) {
+  HIP_OK(hipSetDevice(h->device));
+  if (!h->have_traj || !h->have_fields) { h->err = "signal_xcorr_value_and_grad: run forward with keep_trajectory=1 first"; return 1; }
+  if (h->ck->writer != h) { h->err = std::string("signal_xcorr_value_and_grad: ") + kStaleCheckpoint; return 1; }
+  const size_t B = h->pl.batch;
+  const SigTerms t{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
+  const XcorrCall q{n_pairs, pair_a, pair_b, templates, n_templates, templates_per_member, max_lag, normalisation, true, reduce, lag0, beta, w_peak,
+                    w_delay, delay_target};
+  if (int rc = prepare_xcorr(h, "signal_xcorr_value_and_grad", t, q)) return rc;
+  const bool any = objective || peak || delay;
+  if (int rc = signal_job_sweep(h, kObjXcorr, any ? 3 * B : 0, [&](double* G, double* host) { return launch_xcorr(h, G, host); }, want, views,
+                                device_views, stats))
+    return rc;
+  const double* st = reinterpret_cast<const double*>(h->obj_stage.p);      // J | M | delta
+  if (objective) memcpy(objective, st, sizeof(double) * B);
+  if (peak) memcpy(peak, st + B, sizeof(double) * B);
+  if (delay) memcpy(delay, st + 2 * B, sizeof(double) * B);
   return 0;
 }

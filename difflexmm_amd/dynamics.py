@@ -947,6 +947,34 @@ class DynamicSolver:
         return obj, grads
 
     @staticmethod
+    def _xcorr_kwargs(spec):
+        return dict(templates=spec.templates, normalisation=spec.normalisation, reduce=spec.reduce, lag=spec.lag, beta=spec.beta,
+                    w_peak=spec.w_peak, w_delay=spec.w_delay, delay_target=spec.delay_target)
+
+    def signal_xcorr(self, spec):
+        """(batch, 2 max_lag + 1) normalised cross-correlation of the signal pairs of an ``objective.CorrelationSpec`` over its lags (lag d
+        at index d + max_lag), on the device-resident history of the last solve (any forward pass)."""
+        return self.engine.signal_xcorr(spec.signal_spec.terms, spec.signal_spec.n_signals, spec.pairs, spec.max_lag, spec.templates,
+                                        spec.normalisation)
+
+    def signal_xcorr_value(self, spec):
+        """(J, peak, delay), (batch,) each, of an ``objective.CorrelationSpec`` on the device-resident history."""
+        return self.engine.signal_xcorr_value(spec.signal_spec.terms, spec.signal_spec.n_signals, spec.pairs, spec.max_lag, **self._xcorr_kwargs(spec))
+
+    def signal_xcorr_value_and_raw(self, spec, which=("centroid_node_vectors", "void_angle0", "inertia"), device=False):
+        """The cross-correlation objective (``objective.CorrelationSpec``) of the last kept solve, evaluated and differentiated on the
+        device beside :meth:`signal_projection_value_and_raw`: the correlation over the lags, its reduction to a peak and a delay and the
+        cotangent on the signals are formed in HBM; what follows is :meth:`signal_misfit_value_and_raw`'s.  Returns
+        ((J, peak, delay), raw gradients)."""
+        which = tuple(w for w in which if not (w == "void_angle0" and self.spec.contact != _b.CONTACT_ANGLE))
+        if self.spec.contact == _b.CONTACT_DISTANCE and "block_centroids" not in which:
+            which = which + ("block_centroids",)
+        obj, peak, delay, grads, stats = self.engine.signal_xcorr_value_and_grad(spec.signal_spec.terms, spec.signal_spec.n_signals, spec.pairs,
+                                                                                 spec.max_lag, which=which, device=device, **self._xcorr_kwargs(spec))
+        self.adjoint_stats = stats
+        return (obj, peak, delay), grads
+
+    @staticmethod
     def _bond_params_bar(bp, kb, refv_bar, like):
         """Gradient tree with the structure of the bond parameters that were passed in (LigamentParams /
         StretchingTorsionalSpringParams / any NamedTuple with a subset of their fields)."""

@@ -2,7 +2,8 @@
 records in the notebooks; host code, SciPy where the reference uses ``jax.scipy.signal``) -- and the weighted objectives the engine
 evaluates and differentiates on the device-resident history (``ObjectiveSpec``; ``include/dfx.h``: ``dfx_objective_value_and_grad``;
 ``StrainObjectiveSpec``: ``dfx_strain_objective_value_and_grad``; ``SignalSpec``: ``dfx_signal_misfit_value_and_grad``; ``ProjectionSpec``: ``dfx_signal_projection_value_and_grad``, with ``fourier_basis``
-for its rows)."""
+for its rows; ``CorrelationSpec``: ``dfx_signal_xcorr_value_and_grad`` -- the cross-correlation measures above as an objective on the
+device, with ``xcorr_of_signals`` / ``host_xcorr_value_and_cotangent`` as its NumPy restatement)."""
 from typing import Any, NamedTuple
 
 import numpy as np
@@ -433,3 +434,197 @@ def host_projection_value_and_cotangent(spec, fields):
     for s, b, comp, coef in spec.signal_spec.terms:
         fb[..., comp // 3, b, comp % 3] += coef * c[..., s]
     return (float(value) if f.ndim == 4 else value), fb
+
+
+# ---- signal cross-correlation on the device-resident history ---------------------------------------------------------------------------
+NORMALISATIONS = ("reference", "coefficient", "none")
+REDUCTIONS = ("at", "max", "softmax")
+
+
+class CorrelationSpec:
+    """The normalised cross-correlation of pairs of signals of a ``SignalSpec`` over time lags, its peak and the delay of the peak
+    (``include/dfx.h``: ``dfx_signal_xcorr``, ``dfx_signal_xcorr_value[_and_grad]``) -- ``compute_xcorr*`` / ``compute_space_time_xcorr``
+    above as an objective, the pairs being the space rows at zero space shift:
+
+        R[d]   = sum_p sum_k A_p[k] B_p[k + d]      d = -max_lag .. max_lag in output indices; d > 0: B lags A
+        rho[d] = R[d] / N     N = sum A^2 ("reference"), sqrt(sum A^2 sum B^2) ("coefficient"), 1 ("none")
+        J      = w_peak M + 1/2 w_delay (delta - delay_target)^2
+
+    ``pairs``: a sequence of (a, b); a a signal index, b >= 0 a signal index, b < 0 column -1 - b of ``templates`` (T, n_templates) shared
+    or (batch, T, n_templates).  ``reduce``: "at" (M = rho[lag], delta = lag), "max" (the maximum and its argmax; on ties the lowest lag)
+    or "softmax" (M = log sum exp(beta rho) / beta, delta = sum d softmax(beta rho)_d; ``beta`` > 0).  A delay term (``w_delay`` != 0)
+    needs "softmax".  ``signal_spec``: the terms (its own targets, omega and tau play no part).  Shapes, finiteness and these rules are
+    checked here (``ValueError``); T against a solve where the spec is used."""
+    __slots__ = ("signal_spec", "pairs", "max_lag", "templates", "normalisation", "reduce", "lag", "beta", "w_peak", "w_delay", "delay_target")
+
+    def __init__(self, signal_spec, pairs, max_lag, templates=None, normalisation="reference", reduce="max", lag=None, beta=None, w_peak=1.0,
+                 w_delay=0.0, delay_target=0.0):
+        ns = signal_spec.n_signals
+        p = np.array(pairs, dtype=float)
+        if p.ndim != 2 or p.shape[1] != 2 or len(p) == 0:
+            raise ValueError(f"pairs must be a non-empty sequence of (a, b), got shape {p.shape}")
+        if not np.isfinite(p).all() or (p != np.round(p)).any():
+            raise ValueError("pairs: a and b must be integers")
+        p = p.astype(np.int64)
+        if (p[:, 0] < 0).any() or (p >= ns).any():
+            raise ValueError(f"pairs name a signal out of range [0, {ns})")
+        tp = None
+        if templates is not None:
+            tp = np.array(templates, dtype=float)
+            if tp.ndim not in (2, 3) or tp.shape[-1] < 1 or tp.shape[-2] < 1:
+                raise ValueError(f"templates must be (T, n_templates) or (batch, T, n_templates), got {tp.shape}")
+            if not np.isfinite(tp).all():
+                raise ValueError("templates: non-finite entry")
+        if (p[:, 1] < 0).any():
+            if tp is None:
+                raise ValueError("pairs name a template column but templates is None")
+            if (-1 - p[:, 1]).max() >= tp.shape[-1]:
+                raise ValueError(f"pairs name template column {int((-1 - p[:, 1]).max())} but templates has {tp.shape[-1]} columns")
+        if int(max_lag) != max_lag or max_lag < 0:
+            raise ValueError(f"max_lag must be a non-negative integer, got {max_lag!r}")
+        T = tp.shape[-2] if tp is not None else (signal_spec.targets.shape[-2] if signal_spec.targets is not None else None)
+        if T is not None and max_lag > T - 1:
+            raise ValueError(f"max_lag = {max_lag} outside [0, T - 1] with T = {T}")
+        if normalisation not in NORMALISATIONS:
+            raise ValueError(f"normalisation must be one of {NORMALISATIONS}, got {normalisation!r}")
+        if reduce not in REDUCTIONS:
+            raise ValueError(f"reduce must be one of {REDUCTIONS}, got {reduce!r}")
+        if reduce == "at":
+            lag = 0 if lag is None else lag
+            if int(lag) != lag or abs(lag) > max_lag:
+                raise ValueError(f"lag must be an integer in [-{max_lag}, {max_lag}], got {lag!r}")
+            lag = int(lag)
+        if reduce == "softmax" and (beta is None or not np.isfinite(beta) or beta <= 0):
+            raise ValueError(f"the softmax reduction needs a finite beta > 0, got {beta!r}")
+        for name, v in (("w_peak", w_peak), ("w_delay", w_delay), ("delay_target", delay_target)):
+            if not np.isfinite(v):
+                raise ValueError(f"{name}: non-finite")
+        if w_delay != 0 and reduce != "softmax":
+            raise ValueError("w_delay != 0 needs reduce='softmax' (the delay of a maximum has no derivative)")
+        self.signal_spec, self.pairs, self.max_lag, self.templates = signal_spec, [(int(a), int(b)) for a, b in p], int(max_lag), tp
+        self.normalisation, self.reduce, self.lag, self.beta = normalisation, reduce, lag, None if beta is None else float(beta)
+        self.w_peak, self.w_delay, self.delay_target = float(w_peak), float(w_delay), float(delay_target)
+
+    def __repr__(self):
+        return (f"CorrelationSpec({self.signal_spec!r}, {len(self.pairs)} pairs, max_lag={self.max_lag}, "
+                f"templates={None if self.templates is None else self.templates.shape}, normalisation={self.normalisation!r}, "
+                f"reduce={self.reduce!r}, lag={self.lag!r}, beta={self.beta!r}, w_peak={self.w_peak}, w_delay={self.w_delay}, "
+                f"delay_target={self.delay_target})")
+
+    @property
+    def n_lags(self):
+        return 2 * self.max_lag + 1
+
+    def with_templates(self, templates):
+        """The same signals, pairs, lags and reduction against other templates."""
+        return CorrelationSpec(self.signal_spec, self.pairs, self.max_lag, templates, self.normalisation, self.reduce, self.lag, self.beta,
+                               self.w_peak, self.w_delay, self.delay_target)
+
+
+def _xcorr_sides(spec, S):
+    """A, B (..., n_pairs, T) of the pairs of a ``CorrelationSpec`` on signals ``S`` (..., T, n_signals)."""
+    S = np.asarray(S, dtype=float)
+    if S.ndim < 2 or S.shape[-1] != spec.signal_spec.n_signals:
+        raise ValueError(f"the signals must be (..., T, {spec.signal_spec.n_signals}), got {S.shape}")
+    T = S.shape[-2]
+    if spec.max_lag > T - 1:
+        raise ValueError(f"max_lag = {spec.max_lag} outside [0, T - 1] with T = {T}")
+    tp = spec.templates
+    if tp is not None:
+        if tp.shape[-2] != T:
+            raise ValueError(f"templates have T = {tp.shape[-2]} but the signals have T = {T}")
+        if tp.ndim == 3 and (S.ndim < 3 or S.shape[-3] != tp.shape[0]):
+            raise ValueError(f"per-member templates {tp.shape} against signals of shape {S.shape}")
+        tp = np.broadcast_to(tp, S.shape[:-1] + tp.shape[-1:])
+    A = np.stack([S[..., a] for a, _ in spec.pairs], axis=-2)
+    B = np.stack([S[..., b] if b >= 0 else tp[..., -1 - b] for _, b in spec.pairs], axis=-2)
+    return A, B
+
+
+def _xcorr_norm(spec, A, B):
+    EA, EB = np.sum(A * A, axis=(-2, -1)), np.sum(B * B, axis=(-2, -1))
+    N = EA if spec.normalisation == "reference" else np.sqrt(EA * EB) if spec.normalisation == "coefficient" else np.ones_like(EA)
+    return EA, EB, N
+
+
+def xcorr_of_signals(spec, S):
+    """The cross-correlation of a ``CorrelationSpec`` on signals that are already formed: ``S`` (..., T, n_signals) -> rho
+    (..., 2 max_lag + 1), lag d at index d + max_lag.  A member whose normalisation N is 0 gets NaN."""
+    A, B = _xcorr_sides(spec, S)
+    T, D = A.shape[-1], spec.max_lag
+    R = np.stack([np.sum(A[..., max(0, -d):T - max(0, d)] * B[..., max(0, d):T - max(0, -d)], axis=(-2, -1)) for d in range(-D, D + 1)], axis=-1)
+    _, _, N = _xcorr_norm(spec, A, B)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(N[..., None] == 0, np.nan, R / N[..., None])
+
+
+def xcorr_reduce(spec, rho):
+    """(J, peak, delay, g) of the reduction of a ``CorrelationSpec`` on rho (..., 2 max_lag + 1): g = dJ / d rho."""
+    rho = np.asarray(rho, dtype=float)
+    D = spec.max_lag
+    lags = np.arange(-D, D + 1, dtype=float)
+    g = np.zeros_like(rho)
+    if spec.reduce == "softmax":
+        mx = rho.max(-1, keepdims=True)
+        e = np.exp(spec.beta * (rho - mx))
+        Z = e.sum(-1, keepdims=True)
+        pi = e / Z
+        M = (mx + np.log(Z) / spec.beta)[..., 0]
+        delta = (pi * lags).sum(-1)
+        g = spec.w_peak * pi + spec.w_delay * (delta - spec.delay_target)[..., None] * spec.beta * pi * (lags - delta[..., None])
+    else:
+        at = np.argmax(rho, axis=-1) if spec.reduce == "max" else np.full(rho.shape[:-1], spec.lag + D, dtype=np.int64)
+        M = np.take_along_axis(rho, at[..., None], -1)[..., 0]
+        delta = at.astype(float) - D
+        np.put_along_axis(g, at[..., None], spec.w_peak, -1)
+    J = spec.w_peak * M + 0.5 * spec.w_delay * (delta - spec.delay_target) ** 2
+    return J, M, delta, g
+
+
+def xcorr_value_and_signal_cotangent(spec, S):
+    """(J, peak, delay, c) of a ``CorrelationSpec`` on signals ``S`` (..., T, n_signals): the value, the peak M, the delay delta and
+    the cotangent c = dJ/dS, the formulas of ``include/dfx.h``.  A member whose N is 0 gets NaN values and c = 0."""
+    A, B = _xcorr_sides(spec, S)
+    T, D = A.shape[-1], spec.max_lag
+    EA, EB, N = _xcorr_norm(spec, A, B)
+    dead = N == 0
+    Ns = np.where(dead, 1.0, N)
+    rho = xcorr_of_signals(spec, S)
+    J, M, delta, g = xcorr_reduce(spec, np.where(dead[..., None], 0.0, rho))
+    Rbar = np.where(dead[..., None], 0.0, g / Ns[..., None])
+    Nbar = np.where(dead, 0.0, -np.sum(g * np.where(dead[..., None], 0.0, rho), -1) / Ns)
+    if spec.normalisation == "reference":
+        eA, eB = Nbar, np.zeros_like(Nbar)
+    elif spec.normalisation == "coefficient":
+        eA, eB = Nbar * Ns / (2 * np.where(dead, 1.0, EA)), Nbar * Ns / (2 * np.where(dead, 1.0, EB))
+    else:
+        eA, eB = np.zeros_like(Nbar), np.zeros_like(Nbar)
+    Abar, Bbar = 2 * eA[..., None, None] * A, 2 * eB[..., None, None] * B
+    for i, d in enumerate(range(-D, D + 1)):
+        ka, kb = slice(max(0, -d), T - max(0, d)), slice(max(0, d), T - max(0, -d))
+        Abar[..., ka] += Rbar[..., i, None, None] * B[..., kb]
+        Bbar[..., kb] += Rbar[..., i, None, None] * A[..., ka]
+    c = np.zeros(np.shape(S), dtype=float)
+    for p, (a, b) in enumerate(spec.pairs):
+        c[..., a] += Abar[..., p, :]
+        if b >= 0:
+            c[..., b] += Bbar[..., p, :]
+    nan = np.where(dead, np.nan, 0.0)
+    return J + nan, M + nan, delta + nan, c
+
+
+def host_xcorr_value_and_cotangent(spec, fields):
+    """(J, peak, delay, fields_bar) of a ``CorrelationSpec`` whose terms are field components: the value, the peak and the delay per
+    member and the cotangent of J on the fields (what ``vjp`` / ``dfx_adjoint`` take), coef * c_ks on the row of every term.  ``fields``
+    with or without the member axis; the values are (batch,) or floats.  Force components raise, as in ``host_signal_values``."""
+    f = np.asarray(fields, dtype=float)
+    S = host_signal_values(spec.signal_spec, f)
+    if f.ndim == 4 and spec.templates is not None and spec.templates.ndim == 3:
+        raise ValueError("per-member templates against the fields of one member")
+    J, M, delta, c = xcorr_value_and_signal_cotangent(spec, S)
+    fb = np.zeros_like(f)
+    for s, b, comp, coef in spec.signal_spec.terms:
+        fb[..., comp // 3, b, comp % 3] += coef * c[..., s]
+    if f.ndim == 4:
+        return float(J), float(M), float(delta), fb
+    return J, M, delta, fb

@@ -1267,6 +1267,113 @@ def TargetBandPower(forward, block_dofs, kind, frequencies, weights, window=None
     return TargetSignalProjection(forward, ProjectionSpec(sig, fourier_basis(tp, f, window), w))
 
 
+class TargetCrossCorrelation:
+    """objective(design) = w_peak M(design) + 1/2 w_delay (delta(design) - delay_target)^2 for an ``objective.CorrelationSpec``: the peak
+    M of the normalised cross-correlation of pairs of signals over time lags and the delay delta at which it occurs -- a pulse that keeps
+    its shape at any delay, a chosen arrival time, a template at an unknown shift.  A negative ``w_peak`` maximises the correlation.
+    Shaped as ``TargetSignalProjection``: a list of designs runs as one ensemble (templates (T, n_templates) shared or (len(designs), T,
+    n_templates); ``run_ensemble_optimization`` accepts the class) on the device (``dfx_signal_xcorr_value_and_grad``); one design takes
+    the host path -- field components only -- unless ``on_device``.  Force components have no host path.  ``last_peak`` / ``last_delay``:
+    M and delta of the last evaluation (floats for one design, (n,) arrays for a list)."""
+
+    def __init__(self, forward, spec):
+        self.forward, self.spec = forward, spec
+        self.last_peak = self.last_delay = None
+        if not getattr(forward, "is_setup", False):
+            forward.setup()
+        nb = forward.geometry.n_blocks
+        if max(b for _, b, _, _ in spec.signal_spec.terms) >= nb:
+            raise ValueError(f"TargetCrossCorrelation: a term names a block out of range [0, {nb})")
+
+    def _chunk_spec(self, i, n):
+        """the spec of designs i .. i + n of a longer list (per-member templates are cut alike)"""
+        sp = self.spec
+        return sp if sp.templates is None or sp.templates.ndim == 2 else sp.with_templates(sp.templates[i:i + n])
+
+    def _device(self, design, grad):
+        fw, sp = self.forward, self.spec
+        many = isinstance(design, list)
+        if many and sp.templates is not None and sp.templates.ndim == 3 and len(sp.templates) != len(design):
+            raise ValueError(f"{len(design)} designs against templates for {len(sp.templates)} members")
+        if many and len(design) != fw.batch:
+            if len(design) == 0 or len(design) % fw.batch:
+                raise ValueError(f"{len(design)} designs for a forward problem built with batch={fw.batch}: pass batch designs, or a multiple of it")
+            chunks = [TargetCrossCorrelation(fw, self._chunk_spec(i, fw.batch)) for i in range(0, len(design), fw.batch)]
+            parts = [c._device(design[i * fw.batch:(i + 1) * fw.batch], grad) for i, c in enumerate(chunks)]
+            self.last_peak, self.last_delay = np.concatenate([c.last_peak for c in chunks]), np.concatenate([c.last_delay for c in chunks])
+            if not grad:
+                return np.concatenate(parts)
+            return np.concatenate([p[0] for p in parts]), [g for p in parts for g in p[1]]
+        if not many and sp.templates is not None and sp.templates.ndim == 3:
+            sp = sp.with_templates(sp.templates[0])
+        fw.solve(design, keep_trajectory=grad, want_fields=False)
+        if grad:
+            (obj, peak, delay), raw = fw.solve_dynamics.signal_xcorr_value_and_raw(sp)
+        else:
+            obj, peak, delay = fw.solve_dynamics.signal_xcorr_value(sp)
+        obj, peak, delay = (np.array(a, dtype=float) for a in (obj, peak, delay))
+        self.last_peak, self.last_delay = (peak, delay) if many else (float(peak[0]), float(delay[0]))
+        if not grad:
+            return obj if many else float(obj[0])
+        grads = design_gradients(fw, design if many else [design], raw)
+        return (obj, grads) if many else (float(obj[0]), grads[0])
+
+    def _host(self, design, grad):
+        from .objective import host_xcorr_value_and_cotangent
+        sp, fw = self.spec, self.forward
+        if sp.signal_spec.has_force:
+            raise ValueError("TargetCrossCorrelation: force components are evaluated on the device only: pass on_device=True (or a list of designs)")
+        if sp.templates is not None and sp.templates.ndim == 3:
+            sp = sp.with_templates(sp.templates[0])
+        sol = fw.solve(design, keep_trajectory=grad)
+        val, self.last_peak, self.last_delay, fb = host_xcorr_value_and_cotangent(sp, sol.fields)
+        if not grad:
+            return val
+        raw = {k: np.array(v, dtype=float) for k, v in fw.solve_dynamics.vjp_raw(fb).items()}
+        return val, design_gradients(fw, [design], raw)[0]
+
+    def value(self, design, on_device=False):
+        """One design -> float, a list of designs -> (n,) array."""
+        return self._device(design, False) if on_device or isinstance(design, list) else self._host(design, False)
+
+    def value_and_grad(self, design, on_device=False):
+        """Return shapes as ``TargetKineticEnergy.value_and_grad``; only the parameter groups a design reaches are differentiated."""
+        return self._device(design, True) if on_device or isinstance(design, list) else self._host(design, True)
+
+
+def TargetWaveDelay(forward, source_block_dofs, target_block_dofs, kind, max_lag, beta, delay_target_seconds=None, w_peak=-1.0, w_delay=0.0,
+                    normalisation="coefficient"):
+    """A ``TargetCrossCorrelation`` between the displacement or velocity (``kind``, as ``SignalSpec.fields_of``) of source (block, dof)
+    number i and target (block, dof) number i: the softmax peak of their correlation over the lags -max_lag .. max_lag (in outputs) with
+    the sharpness ``beta``, and -- with ``w_delay`` != 0 -- the squared distance of the soft delay from ``delay_target_seconds``, which is
+    turned into outputs with the spacing of the forward problem's own output times: tune the arrival time of a pulse, i.e. the wave speed.
+    The defaults maximise the correlation coefficient.  Lags are output indices, so a forward problem whose members have output times of
+    their own, or whose output times are not uniformly spaced (to a relative 1e-9), is refused."""
+    from .objective import CorrelationSpec, SignalSpec
+    if not getattr(forward, "is_setup", False):
+        forward.setup()
+    tp = getattr(forward, "timepoints", None)
+    if tp is None or np.ndim(tp) != 1:
+        raise ValueError("TargetWaveDelay: the forward problem has no output times of its own shared by all members (per-member timepoints): "
+                         "lags are output indices of one time grid")
+    tp = np.asarray(tp, dtype=float)
+    dt = np.diff(tp)
+    if len(dt) < 1 or not np.isfinite(dt).all() or (dt <= 0).any() or np.abs(dt - dt.mean()).max() > 1e-9 * abs(dt.mean()):
+        raise ValueError("TargetWaveDelay: the output times are not uniformly spaced (relative 1e-9): lags are output indices")
+    src, tgt = np.array(source_block_dofs, dtype=np.int64).reshape(-1, 2), np.array(target_block_dofs, dtype=np.int64).reshape(-1, 2)
+    if len(src) == 0 or len(src) != len(tgt):
+        raise ValueError(f"TargetWaveDelay: {len(src)} source (block, dof) pairs against {len(tgt)} target pairs")
+    sig = SignalSpec.fields_of(np.concatenate([src, tgt]), kind)
+    n = len(src)
+    target = 0.0 if delay_target_seconds is None else float(delay_target_seconds) / float(dt.mean())
+    if delay_target_seconds is None and w_delay != 0:
+        raise ValueError("TargetWaveDelay: w_delay != 0 needs delay_target_seconds")
+    spec = CorrelationSpec(sig, [(i, n + i) for i in range(n)], max_lag, None, normalisation, "softmax", None, beta, w_peak, w_delay, target)
+    if spec.max_lag > len(tp) - 1:
+        raise ValueError(f"TargetWaveDelay: max_lag = {max_lag} outside [0, T - 1] with T = {len(tp)}")
+    return TargetCrossCorrelation(forward, spec)
+
+
 class MultiInputTargetKineticEnergy:
     """weights @ [target kinetic energy of every forward problem], all sharing one design
     (problems/quads_focusing_multi_input.py:43-86).  The forward problems differ in their boundary conditions

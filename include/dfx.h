@@ -477,6 +477,67 @@ int dfx_signal_projection_value_and_grad(dfx_handle* h, int32_t n_terms, const i
                                          int32_t n_rows, const double* row_weights, const double* targets, int32_t targets_per_member,
                                          double* objective, const dfx_grads* want, dfx_grads* views, int32_t device_views, dfx_stats* stats);
 
+/* Signal cross-correlation on the device-resident history (HIP library only): the normalised cross-correlation of pairs of the signals
+ * S_mks of dfx_signal_values (the same term arrays, the same components 0..8) over time lags, its peak and the delay of the peak -- the
+ * measures of difflexmm/objective.py (compute_xcorr*, compute_space_time_xcorr: pairs are the space rows at zero space shift) as an
+ * objective: a pulse that keeps its shape at any delay, a chosen arrival time, a template at an unknown shift.
+ * Pairs: n_pairs entries (pair_a[p], pair_b[p]); pair_a is a signal index; pair_b >= 0 a signal index, pair_b < 0 names column
+ * -1 - pair_b of the fixed template array `templates`, (T, n_templates) shared by the members or (batch, T, n_templates) when
+ * templates_per_member != 0 (EXACTLY that many doubles, T the n_timepoints of the last forward pass; NULL when no pair names a column).
+ * A signal may stand on both sides of a pair and in several pairs.  With A_p[k], B_p[k] the two sides at output k, lags in OUTPUT
+ * INDICES d = -max_lag .. max_lag, 0 <= max_lag <= T - 1, per member, all fp64:
+ *   R[d]   = sum_p sum_{k : 0 <= k < T, 0 <= k + d < T} A_p[k] B_p[k + d]          d > 0: B lags A (the reference's `delay`)
+ *   EA     = sum_p sum_k A_p[k]^2,   EB = sum_p sum_k B_p[k]^2
+ *   rho[d] = R[d] / N     N = EA (DFX_XCORR_NORM_REFERENCE: the peak of A's auto-correlation, what compute_xcorr* divide by),
+ *                         sqrt(EA EB) (DFX_XCORR_NORM_COEFFICIENT) or 1 (DFX_XCORR_NORM_NONE)
+ * and a reduction over the lags to a peak M and a delay delta:
+ *   DFX_XCORR_AT       M = rho[lag0], delta = lag0
+ *   DFX_XCORR_MAX      M = max_d rho[d], delta its argmax; on ties the lowest d wins and takes the whole gradient (the subgradient
+ *                      np.argmax implies; JAX's max splits a tie evenly -- ties are a set of measure zero)
+ *   DFX_XCORR_SOFTMAX  M = (1 / beta) log sum_d exp(beta rho[d]) (the maximum subtracted first), pi = softmax(beta rho),
+ *                      delta = sum_d d pi_d;  beta > 0
+ *   J = w_peak M + 1/2 w_delay (delta - delay_target)^2          (w_peak < 0 maximises the correlation)
+ * The cotangent of J: g_d = dJ/d rho[d] = w_peak at lag0 / at the argmax and zero elsewhere, or
+ * w_peak pi_d + w_delay (delta - delay_target) beta pi_d (d - delta);  Rbar[d] = g_d / N, Nbar = - sum_d g_d rho[d] / N; on the energies
+ * (eA, eB) = (Nbar, 0), (Nbar N / (2 EA), Nbar N / (2 EB)) or (0, 0) for the three normalisations; on the signals
+ *   c[k, s] = sum_{p : a_p = s} ( sum_d Rbar[d] B_p[k + d] + 2 eA A_p[k] ) + sum_{p : b_p = s} ( sum_d Rbar[d] A_p[k - d] + 2 eB B_p[k] )
+ * (outputs outside [0, T) contribute nothing; template columns receive nothing).  A member whose N is exactly 0 (a signal on a clamped
+ * DOF) gets J = M = delta = rho = NaN and an all-zero cotangent: no division by zero reaches the sweep, the other members are unaffected.
+ * dfx_signal_xcorr writes rho (batch, 2 max_lag + 1), lag d at index d + max_lag, and dfx_signal_xcorr_value J (batch,), M into `peak` and
+ * delta into `delay` ((batch,) each, may be NULL) after any forward pass.  dfx_signal_xcorr_value_and_grad needs the kept trajectory and
+ * equals dfx_adjoint on the fields_bar of these formulas -- c takes the place of tau omega (S - Starget) in
+ * dfx_signal_misfit_value_and_grad, all that follows is that entry's, as for dfx_signal_projection_value_and_grad: want / views /
+ * device_views / stats, the sweep forms, the checkpoint levels, the kept steps of an adaptive solve, what fn_params holds and the
+ * refusals of a missing trajectory or a stale shared checkpoint.  Every sum has a fixed order and no atomics -- R, EA, EB: lane l of a
+ * wave adds outputs l, l + 64, ... ascending with the pairs ascending inside, then the shuffle tree; the reduction: lane l holds lags
+ * l, l + 64, ..., the maximum first, then the exponent sums; c: the A-side pairs then the B-side pairs, pairs and lags ascending -- so
+ * the same history gives the same bits.
+ * Return 1 (dfx_last_error says why): n_pairs < 1, a NULL pair array, a pair index or template column out of range, a template column
+ * named with templates == NULL, max_lag outside [0, T - 1], an unknown normalisation or reduction, lag0 outside [-max_lag, max_lag]
+ * (DFX_XCORR_AT), beta <= 0 or non-finite (DFX_XCORR_SOFTMAX), w_delay != 0 without DFX_XCORR_SOFTMAX, a non-finite template, weight or
+ * delay_target, and everything the signal entries refuse. */
+#define DFX_XCORR_NORM_REFERENCE 0
+#define DFX_XCORR_NORM_COEFFICIENT 1
+#define DFX_XCORR_NORM_NONE 2
+#define DFX_XCORR_AT 0
+#define DFX_XCORR_MAX 1
+#define DFX_XCORR_SOFTMAX 2
+int dfx_signal_xcorr(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block, const int32_t* term_component,
+                     const double* term_coef, int32_t n_signals, int32_t n_pairs, const int32_t* pair_a, const int32_t* pair_b,
+                     const double* templates, int32_t n_templates, int32_t templates_per_member, int32_t max_lag, int32_t normalisation,
+                     double* values);
+int dfx_signal_xcorr_value(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block,
+                           const int32_t* term_component, const double* term_coef, int32_t n_signals, int32_t n_pairs, const int32_t* pair_a,
+                           const int32_t* pair_b, const double* templates, int32_t n_templates, int32_t templates_per_member, int32_t max_lag,
+                           int32_t normalisation, int32_t reduce, int32_t lag0, double beta, double w_peak, double w_delay,
+                           double delay_target, double* objective, double* peak, double* delay);
+int dfx_signal_xcorr_value_and_grad(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block,
+                                    const int32_t* term_component, const double* term_coef, int32_t n_signals, int32_t n_pairs,
+                                    const int32_t* pair_a, const int32_t* pair_b, const double* templates, int32_t n_templates,
+                                    int32_t templates_per_member, int32_t max_lag, int32_t normalisation, int32_t reduce, int32_t lag0,
+                                    double beta, double w_peak, double w_delay, double delay_target, double* objective, double* peak,
+                                    double* delay, const dfx_grads* want, dfx_grads* views, int32_t device_views, dfx_stats* stats);
+
 /* Post-processing of the last forward solve on its device-resident history (problems/quads_focusing.py:319-372 with
  * energy.py:522-534): strain energies of every ligament 1/2 k (strain |l0|)^2 for the axial, shear and bending strain of
  * the NONLINEAR kinematics, (batch, T, n_bonds) each, and the kinetic energy of every block sum_d m_d v_d^2 / 2,
