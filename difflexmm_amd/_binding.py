@@ -17,6 +17,7 @@ TABLEAU = {"dopri5": 0, "rk4": 1}
 OBJ_KINETIC, OBJ_ANGULAR_MOMENTUM = 0, 1
 XCORR_NORMS = {"reference": 0, "coefficient": 1, "none": 2}          # DFX_XCORR_NORM_*
 XCORR_REDUCES = {"at": 0, "max": 1, "softmax": 2}                    # DFX_XCORR_AT / _MAX / _SOFTMAX
+PEAK_KS, PEAK_PNORM = 0, 1                                           # DFX_PEAK_*
 FN_ZERO, FN_PULSE, FN_HARMONIC, FN_RAMP, FN_SECH2TANH, FN_CONSTANT, FN_RAMP_CAP, FN_TABLE = range(8)
 
 _dp = C.POINTER(C.c_double)
@@ -73,7 +74,8 @@ COMM_EXPORTS = ["dfx_comm_unique_id", "dfx_comm_init", "dfx_comm_destroy", "dfx_
                 "dfx_strain_objective_value", "dfx_strain_objective_value_and_grad", "dfx_signal_values", "dfx_signal_misfit_value",
                 "dfx_signal_misfit_value_and_grad", "dfx_signal_projections", "dfx_signal_projection_value",
                 "dfx_signal_projection_value_and_grad", "dfx_forward_tangent_signals_multi", "dfx_forward_tangent_signals_dense_multi",
-                "dfx_signal_xcorr", "dfx_signal_xcorr_value", "dfx_signal_xcorr_value_and_grad"]
+                "dfx_signal_xcorr", "dfx_signal_xcorr_value", "dfx_signal_xcorr_value_and_grad", "dfx_strain_peak_value",
+                "dfx_strain_peak_value_and_grad"]
 EXPORTS = EXPORTS + COMM_EXPORTS
 
 
@@ -185,6 +187,10 @@ def declare(lib):
         lib.dfx_signal_xcorr_value.argtypes = [H] + terms + corr + value
         lib.dfx_signal_xcorr_value_and_grad.argtypes = [H] + terms + corr + value + [C.POINTER(dfx_grads), C.POINTER(dfx_grads), C.c_int32,
                                                                                       C.POINTER(dfx_stats)]
+    if hasattr(lib, "dfx_strain_peak_value_and_grad"):
+        peak = [_dp, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, C.c_double, _dp, _dp, _ip]      # coef, weights, tau, aggregate, sharpness, outputs
+        lib.dfx_strain_peak_value.argtypes = [H] + peak
+        lib.dfx_strain_peak_value_and_grad.argtypes = [H] + peak + [C.POINTER(dfx_grads), C.POINTER(dfx_grads), C.c_int32, C.POINTER(dfx_stats)]
     if hasattr(lib, "dfx_comm_init"):
         lib.dfx_comm_unique_id.argtypes = [C.c_char_p]
         lib.dfx_comm_init.argtypes = [C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(H)]
@@ -903,6 +909,71 @@ class Engine:
             a.flags.writeable = False
             out[n] = a
         return obj, out, _stats(st)
+
+    # -- peak ligament strain on the device-resident history --------------------------------------------------
+    @property
+    def has_strain_peak(self):
+        return hasattr(self.lib, "dfx_strain_peak_value_and_grad")
+
+    def _strain_peak_args(self, bond_coef, bond_weights, time_weights, aggregate, sharpness):
+        """The arguments of ``dfx_strain_peak_value[_and_grad]``: coefficients (n_bonds, 3) or (batch, n_bonds, 3), bond weights
+        (n_bonds,), (batch, n_bonds) or None = ones, time weights (T,) or None, the aggregate ("ks" / "pnorm" or DFX_PEAK_*), beta or p."""
+        if not self.has_strain_peak:
+            raise NotImplementedError(f"peak-strain objective: the library {getattr(self.lib, '_name', self.lib)!r} has no "
+                                      "dfx_strain_peak_value_and_grad (a stale libdfx.so, or the CPU port of the oracle; build the HIP engine)")
+        B, nbd = self.batch, self.n_bonds
+        c = _f64(bond_coef)
+        if c.shape not in ((nbd, 3), (B, nbd, 3)):
+            raise ValueError(f"bond_coef must be ({nbd}, 3) or ({B}, {nbd}, 3), got {c.shape}")
+        w = None
+        if bond_weights is not None:
+            w = _f64(bond_weights)
+            if w.shape not in ((nbd,), (B, nbd)):
+                raise ValueError(f"bond_weights must be ({nbd},) or ({B}, {nbd}), got {w.shape}")
+        tau = None
+        if time_weights is not None:
+            tau = _f64(time_weights)
+            if self.n_timepoints is not None and tau.shape != (self.n_timepoints,):
+                raise ValueError(f"time_weights must be ({self.n_timepoints},), got {tau.shape}")
+        agg = {"ks": PEAK_KS, "pnorm": PEAK_PNORM}.get(aggregate, aggregate)
+        return c, int(c.ndim == 3), w, int(w is not None and w.ndim == 2), tau, int(agg), float(sharpness)
+
+    def strain_peak_value(self, bond_coef, bond_weights=None, time_weights=None, aggregate="ks", sharpness=1.0):
+        """(J, peak, peak_at): the smooth maximum (batch,), the hard maximum (batch,) and its (output, bond) (batch, 2) of the ligament strain
+        measure (``dfx_strain_peak_value``) on the resident history of the last forward pass."""
+        c, cpm, w, wpm, tau, agg, sharp = self._strain_peak_args(bond_coef, bond_weights, time_weights, aggregate, sharpness)
+        obj, peak, at = np.zeros(self.batch), np.zeros(self.batch), np.zeros((self.batch, 2), dtype=np.int32)
+        self._check(self.lib.dfx_strain_peak_value(self._h, _ptr(c), cpm, _ptr(w), wpm, _ptr(tau), agg, sharp, _ptr(obj), _ptr(peak),
+                                                   at.ctypes.data_as(_ip)), "dfx_strain_peak_value")
+        return obj, peak, at
+
+    def strain_peak_value_and_grad(self, bond_coef, bond_weights=None, time_weights=None, aggregate="ks", sharpness=1.0, which=ALL_GRADS,
+                                   device=False):
+        """(J, peak, peak_at) and the requested gradients of J in ONE call (``dfx_strain_peak_value_and_grad``): maximum, softmax sum and
+        the softmax-weighted ligament forces are formed on the device as the cotangent of the reverse sweep, the explicit node-vector /
+        reference-vector terms are added behind it.  Results as :meth:`objective_value_and_grad`."""
+        c, cpm, w, wpm, tau, agg, sharp = self._strain_peak_args(bond_coef, bond_weights, time_weights, aggregate, sharpness)
+        sh = self.shapes()
+        want, views = dfx_grads(), dfx_grads()
+        names = [n for n in which if not (n == "fn_params" and self.n_fns == 0) and not (n == "contact" and not self.contact)
+                 and not (n == "void_angle0" and self.contact != CONTACT_ANGLE)
+                 and not (n == "block_centroids" and self.contact != CONTACT_DISTANCE)]
+        flag = np.zeros(1)
+        for n in names:
+            setattr(want, n, _ptr(flag))
+        obj, peak, at = np.zeros(self.batch), np.zeros(self.batch), np.zeros((self.batch, 2), dtype=np.int32)
+        st = dfx_stats()
+        self._check(self.lib.dfx_strain_peak_value_and_grad(self._h, _ptr(c), cpm, _ptr(w), wpm, _ptr(tau), agg, sharp, _ptr(obj), _ptr(peak),
+                                                            at.ctypes.data_as(_ip), C.byref(want), C.byref(views), int(bool(device)),
+                                                            C.byref(st)), "dfx_strain_peak_value_and_grad")
+        if device:
+            return (obj, peak, at), {n: DeviceArray(self, C.cast(getattr(views, n), C.c_void_p).value, sh[n]) for n in names}, _stats(st)
+        out = {}
+        for n in names:
+            a = np.ctypeslib.as_array(getattr(views, n), shape=sh[n])
+            a.flags.writeable = False
+            out[n] = a
+        return (obj, peak, at), out, _stats(st)
 
     # -- signal misfit on the device-resident history ---------------------------------------------------------
     @property

@@ -160,6 +160,12 @@ struct dfx_handle {
   DevBuf<double> d_xc_coef, d_xc_R, d_xc_s;
   struct XcorrJob { int n_pairs = 0, n_templ = 0, D = 0, norm = 0, reduce = 0, lag0 = 0; bool has_templ = false; long long templ_stride = 0;
                     double beta = 1.0, w_peak = 1.0, w_delay = 0.0, delay_target = 0.0; } xc;
+  // dfx_strain_peak_* (engine_objective.hip): slot coefficients, the q image, per-workgroup maxima and keys, per member q_hat | S | J and
+  // (k_hat, b_hat); pk: the scalars of the call (the explicit terms behind the sweep read them)
+  DevBuf<double> d_pk_coef, d_pk_q, d_pk_max, d_pk_res;
+  DevBuf<long long> d_pk_key;
+  DevBuf<int32_t> d_pk_at;
+  struct PeakJob { int aggregate = 0; double sharp = 1.0; long long coef_stride = 0; } pk;
   std::vector<double> ts;
   std::vector<int> spis;           // RK steps in each output interval (fixed grid)
   std::vector<long long> step0;    // first step ordinal of each interval

@@ -66,6 +66,18 @@
 //                            measure zero).  A member with N == 0 gets NaN values and an all-zero cotangent
 //   k_signal_xcorr_residual  one lane per (member, output, signal): c from Rbar, eA, eB, the signals and the templates, pairs and lags
 //                            ascending, into the residual-cotangent buffer; lags whose Rbar is exactly 0 are skipped
+//
+// The peak ligament strain (dfx_strain_peak_value[_and_grad]): NOT a sum but a smooth maximum over (output time, ligament) pairs of
+//   q_mkb = a_mb (l0 eps)^2 + s_mb (l0 gamma)^2 + r_mb kappa^2 = 2 E_bond with the coefficient triple in place of the stiffnesses,
+// weighted W = tau_k omega_mb >= 0: KS  J = q_hat + log(sum W exp(beta (q - q_hat))) / beta, or PNORM  J = q_hat (sum W (q / q_hat)^p)^(1/p).
+// Items and quads as for the strain energy.  The softmax weights pi need the global maximum and sum first, hence four passes:
+//   k_strain_peak_measure    q of every counted pair (end-0 lane) into a scratch image by (member, output, bond), per-workgroup (maximum, key k * n_bonds + bond);
+//                            k_strain_peak_finish reduces them to q_hat, k_hat, b_hat per member (ties: the lowest key)
+//   k_strain_peak_sum        the terms from the stored q: wave sum, waves in order, one partial per workgroup; k_strain_peak_value adds the
+//                            partials as k_objective_finish does and forms J (J, q_hat, k_hat, b_hat into pinned host memory)
+//   k_strain_peak_cotangent  the ligament gradient again (nothing but q is stored; both ends of a ligament read the same q, hence the same
+//                            pi), times 2 pi, quad-summed into rows 0..2 of G
+//   k_strain_peak_explicit   after the sweep: 2 pi dE/d(node vector) into g_r and, on end-0 slots, 2 pi dE/d(reference vector) into g_b[0..1]
 // No atomics anywhere: the same history gives the same bits.
 #pragma once
 #include "dfx_kernels.h"
@@ -747,6 +759,253 @@ __global__ __launch_bounds__(kObjThreads) void k_signal_xcorr_residual(DevCtx c,
     cr += acc + 2.0 * eB * S[(size_t)k * a.n_sig + s];
   }
   a.cres[(size_t)m * total + (size_t)item] = cr;
+}
+
+// ---- peak ligament strain ------------------------------------------------------------------------------------------------------------
+constexpr int kObjPeak = 6;                // ObjJob::kind of a peak-strain call
+
+// ObjArgs of a peak call: blocks = listed blocks, w = SLOT weights omega (as a strain call), tau, lever unused.  Beside it:
+struct PeakArgs {
+  const double* coef;          // coef_members * n_slots * 3: (a, s, r) of the slot's ligament (both end slots carry them)
+  const int32_t* slot_bond;    // n_slots: bond id of the slot's ligament
+  double* Q;                   // batch * T * n_bonds: q of every counted (output, ligament) pair; other entries are never read
+  double* pmax;                // batch * chunks: the maximum of each workgroup ...
+  long long* pkey;             // ... and its key k * n_bonds + bond (the lowest key among equal maxima)
+  double* res;                 // batch * 4: q_hat, S (the sum of pass 2), J
+  int32_t* at;                 // batch * 2: k_hat, b_hat
+  long long coef_stride;       // 0 when one array serves all members
+  int n_bonds, aggregate;
+  double sharp;                // beta (KS) or p (PNORM)
+};
+
+constexpr long long kPeakNoKey = 0x7fffffffffffffffLL;
+
+__device__ __forceinline__ double peak_neg_inf() { return -__longlong_as_double(0x7ff0000000000000LL); }
+
+// (value, key) candidates of a maximum: the larger value wins, on equal values the lower key; the identity is (-inf, kPeakNoKey)
+__device__ __forceinline__ void peak_take(double& v, long long& key, double ov, long long okey) {
+  if (ov > v || (ov == v && okey < key)) { v = ov; key = okey; }
+}
+__device__ __forceinline__ void peak_wave_argmax(double& v, long long& key) {
+  for (int off = 32; off > 0; off >>= 1) {
+    const double ov = __shfl_xor(v, off, 64);
+    const long long okey = __shfl_xor(key, off, 64);
+    peak_take(v, key, ov, okey);
+  }
+}
+
+// one side of the ligament on `slot` with the coefficient triple in place of the stiffnesses: g.e = q / 2 and every first derivative of it
+// (the loads of strain_eval, repeated here because no existing kernel may change: a change to how slots, the reference-vector dictionary
+// or the fields are laid out has to be made in both; the stiffness image is not read)
+template <int MODEL>
+__device__ __forceinline__ void peak_eval(const DevCtx& c, const MemberBases& B, const double* f, int slot, int info, const double* coef,
+                                          BondGrad<double>& g) {
+  const int b = slot >> 2, ps = info >> 1, pb = ps >> 2;
+  BlockRec<double> o, p;
+  o.x = f[(size_t)b * 3]; o.y = f[(size_t)b * 3 + 1]; o.th = f[(size_t)b * 3 + 2];
+  p.x = f[(size_t)pb * 3]; p.y = f[(size_t)pb * 3 + 1]; p.th = f[(size_t)pb * 3 + 2];
+  fast_sincos(0.5 * o.th, &o.sh, &o.ch);
+  fast_sincos(0.5 * p.th, &p.sh, &p.ch);
+  const double2 ro = ldg<double2>(B.p_r, (u32)slot * 16), rp = ldg<double2>(B.p_r, (u32)ps * 16);
+  double lx, ly, l0, il0;
+  if (c.l_dict_on) {
+    const int li = B.p_lidx[slot];
+    lx = B.l_dict[li * 4]; ly = B.l_dict[li * 4 + 1]; l0 = B.l_dict[li * 4 + 2]; il0 = B.l_dict[li * 4 + 3];
+  } else {
+    lx = B.p_l[(size_t)slot * 2]; ly = B.p_l[(size_t)slot * 2 + 1]; l0 = sqrt(lx * lx + ly * ly); il0 = 1.0 / l0;
+  }
+  const double* cf = coef + (size_t)slot * 3;
+  bond_grad<MODEL, double>(o, p, ro.x, ro.y, rp.x, rp.y, lx, ly, l0, il0, cf[0], cf[1], cf[2], (info & 1) ? 1.0 : -1.0, g);
+}
+
+// the weight W = tau_k omega of the pair on this lane; 0: the lane contributes the identity
+__device__ __forceinline__ double peak_weight(const DevCtx& c, const ObjArgs& a, int m, int k, int slot, int& info) {
+  info = c.slot_info[slot];
+  if (info < 0) return 0.0;
+  return (a.tau ? a.tau[k] : 1.0) * a.w[(size_t)m * a.w_stride + slot];
+}
+
+// pass 1, grid (chunks of kObjQuads items, members): q of every counted pair (a ligament is counted on its end-0 lane) into Q and the
+// workgroup's maximum with its key into pmax / pkey
+template <int MODEL>
+__global__ __launch_bounds__(kObjThreads) void k_strain_peak_measure(DevCtx c, ObjArgs a, PeakArgs p) {
+  const int m = blockIdx.y;
+  const long long total = (long long)c.n_timepoints * a.n_act;
+  const long long item = (long long)blockIdx.x * kObjQuads + (threadIdx.x >> 2);
+  const int kk = threadIdx.x & 3;
+  double best = peak_neg_inf();
+  long long key = kPeakNoKey;
+  if (item < total) {
+    const int k = (int)(item / a.n_act);
+    const int slot = a.blocks[(int)(item % a.n_act)] * 4 + kk;
+    int info;
+    const double W = peak_weight(c, a, m, k, slot, info);
+    if (W != 0.0 && !(info & 1)) {
+      BondGrad<double> g;
+      peak_eval<MODEL>(c, member_bases(c, m), a.fields + ((size_t)m * c.n_timepoints + k) * ((size_t)c.n_blocks * 6), slot, info,
+                       p.coef + (size_t)m * p.coef_stride, g);
+      const int bond = p.slot_bond[slot];
+      best = 2.0 * g.e;
+      key = (long long)k * p.n_bonds + bond;
+      p.Q[((size_t)m * c.n_timepoints + k) * p.n_bonds + bond] = best;
+    }
+  }
+  __shared__ double red[kObjWaves];
+  __shared__ long long redk[kObjWaves];
+  peak_wave_argmax(best, key);
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = best; redk[threadIdx.x >> 6] = key; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int wv = 1; wv < kObjWaves; ++wv) peak_take(best, key, red[wv], redk[wv]);
+    p.pmax[(size_t)m * gridDim.x + blockIdx.x] = best;
+    p.pkey[(size_t)m * gridDim.x + blockIdx.x] = key;
+  }
+}
+
+// grid (members): the member's workgroup maxima, strided over the lanes, to q_hat, k_hat, b_hat (a maximum with the lowest-key tie rule does
+// not depend on the order it is taken in)
+__global__ __launch_bounds__(kObjThreads) void k_strain_peak_finish(PeakArgs p, int n_partial) {
+  const int m = blockIdx.x;
+  double best = peak_neg_inf();
+  long long key = kPeakNoKey;
+  for (int i = threadIdx.x; i < n_partial; i += kObjThreads) peak_take(best, key, p.pmax[(size_t)m * n_partial + i], p.pkey[(size_t)m * n_partial + i]);
+  __shared__ double red[kObjWaves];
+  __shared__ long long redk[kObjWaves];
+  peak_wave_argmax(best, key);
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = best; redk[threadIdx.x >> 6] = key; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int wv = 1; wv < kObjWaves; ++wv) peak_take(best, key, red[wv], redk[wv]);
+    p.res[(size_t)m * 4] = best;
+    // no candidate won (every q of the member is NaN: a non-finite history): peak = -inf, J = NaN and peak_at = (-1, -1)
+    p.at[(size_t)m * 2] = key == kPeakNoKey ? -1 : (int32_t)(key / p.n_bonds);
+    p.at[(size_t)m * 2 + 1] = key == kPeakNoKey ? -1 : (int32_t)(key % p.n_bonds);
+  }
+}
+
+// the term of a counted pair in the sum of pass 2: W exp(beta (q - q_hat)) or W (q / q_hat)^p (q_hat == 0: every q is 0 and so is the term)
+__device__ __forceinline__ double peak_term(const PeakArgs& p, double W, double q, double qhat) {
+  if (p.aggregate == DFX_PEAK_KS) return W * exp(p.sharp * (q - qhat));
+  return qhat > 0.0 ? W * pow(q / qhat, p.sharp) : 0.0;
+}
+
+// pi of a pair from the member's q_hat and S: KS  W exp(beta (q - q_hat)) / S  (= W exp(beta (q - J)));
+// PNORM  W (q / q_hat)^(p - 1) S^((1 - p) / p)  (= W q^(p-1) J^(1-p)), 0 when q_hat == 0
+__device__ __forceinline__ double peak_pi(const PeakArgs& p, double W, double q, double qhat, double S) {
+  if (p.aggregate == DFX_PEAK_KS) return W * exp(p.sharp * (q - qhat)) / S;
+  return qhat > 0.0 ? W * pow(q / qhat, p.sharp - 1.0) * pow(S, (1.0 - p.sharp) / p.sharp) : 0.0;
+}
+
+// pass 2, grid as pass 1: the terms from the stored q, wave sum, the waves of a workgroup in order into its partial
+__global__ __launch_bounds__(kObjThreads) void k_strain_peak_sum(DevCtx c, ObjArgs a, PeakArgs p, double* partial) {
+  const int m = blockIdx.y;
+  const long long total = (long long)c.n_timepoints * a.n_act;
+  const long long item = (long long)blockIdx.x * kObjQuads + (threadIdx.x >> 2);
+  const int kk = threadIdx.x & 3;
+  double val = 0.0;
+  if (item < total) {
+    const int k = (int)(item / a.n_act);
+    const int slot = a.blocks[(int)(item % a.n_act)] * 4 + kk;
+    int info;
+    const double W = peak_weight(c, a, m, k, slot, info);
+    if (W != 0.0 && !(info & 1)) val = peak_term(p, W, p.Q[((size_t)m * c.n_timepoints + k) * p.n_bonds + p.slot_bond[slot]], p.res[(size_t)m * 4]);
+  }
+  __shared__ double red[kObjWaves];
+  val = obj_wave_sum(val);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = val;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = red[0];
+    for (int wv = 1; wv < kObjWaves; ++wv) s += red[wv];
+    partial[(size_t)m * gridDim.x + blockIdx.x] = s;
+  }
+}
+
+// grid (members): the second level of k_objective_finish on the partials of pass 2, then J; S and J beside q_hat in res, J into objective[m],
+// and J | q_hat (doubles) and (k_hat, b_hat) (int32) into pinned host memory when given
+__global__ __launch_bounds__(kObjThreads) void k_strain_peak_value(PeakArgs p, const double* partial, int n_partial, double* objective,
+                                                                    double* host2, int32_t* host_at, int batch) {
+  const int m = blockIdx.x;
+  double v = 0.0;
+  for (int i = threadIdx.x; i < n_partial; i += kObjThreads) v += partial[(size_t)m * n_partial + i];
+  __shared__ double red[kObjWaves];
+  v = obj_wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double S = red[0];
+    for (int wv = 1; wv < kObjWaves; ++wv) S += red[wv];
+    const double qhat = p.res[(size_t)m * 4];
+    const double J = p.aggregate == DFX_PEAK_KS ? qhat + log(S) / p.sharp : (qhat > 0.0 ? qhat * pow(S, 1.0 / p.sharp) : 0.0);
+    p.res[(size_t)m * 4 + 1] = S; p.res[(size_t)m * 4 + 2] = J;
+    if (objective) objective[m] = J;
+    if (host2) { host2[m] = J; host2[batch + m] = qhat; }          // pinned host memory, as k_objective_finish
+    if (host_at) { host_at[m * 2] = p.at[(size_t)m * 2]; host_at[m * 2 + 1] = p.at[(size_t)m * 2 + 1]; }
+  }
+}
+
+// pass 3, grid as pass 1: every lane whose slot carries a weighted ligament evaluates its own side again, pi dq/d(x, y, theta) = 2 pi dE/d(..)
+// is added over the quad and lane 0 stores rows 0..2 of G[(k, m, b)], as k_strain_objective does
+template <int MODEL>
+__global__ __launch_bounds__(kObjThreads) void k_strain_peak_cotangent(DevCtx c, ObjArgs a, PeakArgs p, double* G) {
+  const int m = blockIdx.y;
+  const long long total = (long long)c.n_timepoints * a.n_act;
+  const long long item = (long long)blockIdx.x * kObjQuads + (threadIdx.x >> 2);
+  const int kk = threadIdx.x & 3;
+  const bool valid = item < total;
+  double fx = 0.0, fy = 0.0, fth = 0.0;
+  int k = 0, b = 0;
+  if (valid) {
+    k = (int)(item / a.n_act);
+    b = a.blocks[(int)(item % a.n_act)];
+    const int slot = b * 4 + kk;
+    int info;
+    const double W = peak_weight(c, a, m, k, slot, info);
+    if (W != 0.0) {
+      BondGrad<double> g;
+      peak_eval<MODEL>(c, member_bases(c, m), a.fields + ((size_t)m * c.n_timepoints + k) * ((size_t)c.n_blocks * 6), slot, info,
+                       p.coef + (size_t)m * p.coef_stride, g);
+      const double q = p.Q[((size_t)m * c.n_timepoints + k) * p.n_bonds + p.slot_bond[slot]];      // both ends of a ligament: the same pi
+      const double s = 2.0 * peak_pi(p, W, q, p.res[(size_t)m * 4], p.res[(size_t)m * 4 + 1]);
+      fx = s * g.fx; fy = s * g.fy; fth = s * g.fth;
+    }
+  }
+  fx = quad_sum(fx); fy = quad_sum(fy); fth = quad_sum(fth);
+  if (valid && kk == 0) {
+    double* g = G + ((size_t)k * c.batch + m) * ((size_t)c.n_blocks * 6) + (size_t)b * 6;
+    g[0] = fx; g[1] = fy; g[2] = fth;
+  }
+}
+
+// pass 4, after the sweep, grid (chunks of 64 listed slots, members): pi dq/d(own node vector) into g_r and, on end-0 slots when the call
+// collects them, pi dq/d(reference vector) into g_b[0..1] (the coefficients are constants of the call: nothing reaches the stiffnesses, the
+// contact constants or the void angles); output times in order, every accumulator entry touched belongs to one lane
+template <int MODEL>
+__global__ __launch_bounds__(64) void k_strain_peak_explicit(DevCtx c, ObjArgs a, PeakArgs p) {
+  const int m = blockIdx.y;
+  const int idx = blockIdx.x * 64 + threadIdx.x;
+  if (idx >= a.n_act * 4) return;
+  const int slot = a.blocks[idx >> 2] * 4 + (idx & 3);
+  const int info = c.slot_info[slot];
+  const double w = a.w[(size_t)m * a.w_stride + slot];
+  if (info < 0 || w == 0.0) return;
+  const MemberBases B = member_bases(c, m);
+  const bool bonds = c.g_b && !(info & 1);
+  const int bond = p.slot_bond[slot];
+  const double qhat = p.res[(size_t)m * 4], S = p.res[(size_t)m * 4 + 1];
+  double rx = 0.0, ry = 0.0, lx = 0.0, ly = 0.0;
+  for (int k = 0; k < c.n_timepoints; ++k) {
+    const double W = (a.tau ? a.tau[k] : 1.0) * w;
+    if (W == 0.0) continue;
+    BondGrad<double> g;
+    peak_eval<MODEL>(c, B, a.fields + ((size_t)m * c.n_timepoints + k) * ((size_t)c.n_blocks * 6), slot, info, p.coef + (size_t)m * p.coef_stride, g);
+    const double s = 2.0 * peak_pi(p, W, p.Q[((size_t)m * c.n_timepoints + k) * p.n_bonds + bond], qhat, S);
+    rx += s * g.rx; ry += s * g.ry;
+    if (bonds) { lx += s * g.lx; ly += s * g.ly; }
+  }
+  const size_t ms = (size_t)m * c.n_slots + slot;
+  c.g_r[ms * 2] += rx; c.g_r[ms * 2 + 1] += ry;
+  if (bonds) { c.g_b[ms * 8] += lx; c.g_b[ms * 8 + 1] += ly; }
 }
 
 }  // namespace

@@ -172,6 +172,7 @@ int dfx_destroy(dfx_handle* h) {
   h->d_obj_blocks.release(); h->d_obj_w.release(); h->d_obj_tau.release(); h->d_obj_lever.release(); h->d_obj_part.release();
   h->d_sig_tab.release(); h->d_sig_coef.release(); h->d_sig_chan.release(); h->d_sig_S.release(); h->d_sig_c.release(); h->d_sig_w.release();
   h->d_xc_coef.release(); h->d_xc_R.release(); h->d_xc_s.release();
+  h->d_pk_coef.release(); h->d_pk_q.release(); h->d_pk_max.release(); h->d_pk_res.release(); h->d_pk_key.release(); h->d_pk_at.release();
   for (auto& gr : h->groups) {
     for (auto e : gr.ev_a) (void)hipEventDestroy(e);
     for (auto e : gr.ev_b) (void)hipEventDestroy(e);

@@ -9,6 +9,8 @@
 // their cotangent: P = B S, the value a weighted quadratic form of P, c = B^T (W (P - Ptarget)); from c on the signal misfit's launches.
 // The signal cross-correlation (dfx_signal_xcorr, dfx_signal_xcorr_value[_and_grad]) is a second, nonlinear occupant of that slot: R over the
 // lags and the two energies, a reduction to a peak and a delay, and the cotangent c of J = w_peak M + 1/2 w_delay (delta - delta_target)^2.
+// The peak ligament strain (dfx_strain_peak_value[_and_grad]) is a smooth maximum, not a sum: its cotangent is the ligament force weighted
+// by a softmax over all (output, ligament) pairs, so a maximum and a sum are reduced before the first cotangent is written.
 // (shared declarations in dfx_engine.h, the kernels in dfx_objective.h)
 #include "dfx_engine.h"
 #include "dfx_objective.h"
@@ -181,6 +183,122 @@ int launch_strain(dfx_handle* h, const ObjJob& j, double* G, double* objective_h
   with_strain_physics(h, [&](auto M, auto C) { hipLaunchKernelGGL((k_strain_objective<M(), C()>), grid, dim3(kObjThreads), 0, h->stream, c, a, G, h->d_obj_part.p); });
   hipLaunchKernelGGL(k_objective_finish, dim3((unsigned)B), dim3(kObjThreads), 0, h->stream, (const double*)h->d_obj_part.p, (int)chunks, h->d_obj.p,
                      objective_host);
+  return 0;
+}
+
+// ---- peak ligament strain: the checks of a call (return 1 with h->err), then bond weights -> slot weights and bond coefficients -> slot
+// coefficients (both end slots of a ligament carry them), listed blocks = the blocks that own a weighted end
+int prepare_peak(dfx_handle* h, const char* who, const double* coef, int32_t coef_per_member, const double* bw, int32_t w_per_member,
+                 const double* tau, int32_t aggregate, double sharp, ObjHost& out) {
+  const Plan& pl = h->pl;
+  const size_t B = pl.batch, nb = pl.n_blocks, NS = pl.n_slots, nbd = pl.n_bonds;
+  const int Tn = (int)h->ts.size();
+  const std::string w(who);
+  if (!coef) { h->err = w + ": bond_coef is NULL"; return 1; }
+  if (pl.n_ovf) {
+    h->err = w + ": nodes with more than one ligament (a general bond list with extra ligaments) are not supported by the peak-strain objective";
+    return 1;
+  }
+  if (aggregate != DFX_PEAK_KS && aggregate != DFX_PEAK_PNORM) {
+    h->err = w + ": unknown aggregate " + std::to_string(aggregate) + " (DFX_PEAK_KS = 0, DFX_PEAK_PNORM = 1)";
+    return 1;
+  }
+  if (!std::isfinite(sharp)) { h->err = w + ": sharpness is not finite"; return 1; }
+  if (aggregate == DFX_PEAK_KS && !(sharp > 0.0)) { h->err = w + ": sharpness beta must be positive with the KS aggregate"; return 1; }
+  if (aggregate == DFX_PEAK_PNORM && !(sharp >= 1.0)) { h->err = w + ": sharpness p must be at least 1 with the p-norm aggregate"; return 1; }
+  const size_t cm = coef_per_member ? B : 1, wm = bw && w_per_member ? B : 1;
+  for (size_t i = 0; i < cm * nbd * 3; ++i)
+    if (!std::isfinite(coef[i]) || coef[i] < 0.0) { h->err = w + ": non-finite or negative bond coefficient"; return 1; }
+  for (size_t i = 0; bw && i < wm * nbd; ++i)
+    if (!std::isfinite(bw[i]) || bw[i] < 0.0) { h->err = w + ": non-finite or negative bond weight"; return 1; }
+  bool any_tau = !tau;
+  for (int k = 0; tau && k < Tn; ++k) {
+    if (!std::isfinite(tau[k]) || tau[k] < 0.0) { h->err = w + ": non-finite or negative time weight"; return 1; }
+    any_tau = any_tau || tau[k] > 0.0;
+  }
+  std::vector<double> sw(wm * NS, 0.0), sc(cm * NS * 3, 0.0);
+  std::vector<char> listed(nb, 0), member_any(wm, 0);
+  for (size_t sl = 0; sl < NS; ++sl) {
+    if (pl.slot_info[sl] < 0) continue;
+    const size_t bond = (size_t)pl.slot_bond[sl];
+    for (size_t m = 0; m < wm; ++m) {
+      const double v = bw ? bw[m * nbd + bond] : 1.0;
+      sw[m * NS + sl] = v;
+      if (v != 0.0) { listed[sl >> 2] = 1; member_any[m] = 1; }
+    }
+    for (size_t m = 0; m < cm; ++m)
+      for (int i = 0; i < 3; ++i) sc[(m * NS + sl) * 3 + i] = coef[(m * nbd + bond) * 3 + i];
+  }
+  for (size_t m = 0; m < wm; ++m)
+    if (!member_any[m] || !any_tau) {
+      h->err = w + ": all weights are zero for member " + std::to_string(m) + " (a peak needs one (output, ligament) pair with tau * omega > 0)";
+      return 1;
+    }
+  out.blocks.clear();
+  for (size_t b = 0; b < nb; ++b) if (listed[b]) out.blocks.push_back((int32_t)b);
+  out.job.kind = kObjPeak;
+  out.job.n_act = (int)out.blocks.size();
+  out.job.w_stride = wm > 1 || (bw && w_per_member) ? (int)NS : 0;
+  out.job.lever_stride = 0;
+  out.job.has_tau = tau != nullptr;
+  h->pk.aggregate = aggregate; h->pk.sharp = sharp; h->pk.coef_stride = coef_per_member ? (long long)(NS * 3) : 0;
+  HIP_OK(h->d_obj_blocks.ensure(std::max<size_t>(1, out.blocks.size())));
+  HIP_OK(h->d_obj_w.ensure(sw.size()));
+  HIP_OK(h->d_pk_coef.ensure(sc.size()));
+  HIP_OK(h->d_pk_res.ensure(B * 4));
+  HIP_OK(h->d_pk_at.ensure(B * 2));
+  HIP_OK(h->d_obj.ensure(B));
+  HIP_OK(hipMemcpyAsync(h->d_obj_blocks.p, out.blocks.data(), sizeof(int32_t) * out.blocks.size(), hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipMemcpyAsync(h->d_obj_w.p, sw.data(), sizeof(double) * sw.size(), hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipMemcpyAsync(h->d_pk_coef.p, sc.data(), sizeof(double) * sc.size(), hipMemcpyHostToDevice, h->stream));
+  if (tau) {
+    HIP_OK(h->d_obj_tau.ensure(Tn));
+    HIP_OK(hipMemcpyAsync(h->d_obj_tau.p, tau, sizeof(double) * Tn, hipMemcpyHostToDevice, h->stream));
+  }
+  HIP_OK(hipStreamSynchronize(h->stream));       // the slot arrays are locals of this function
+  return 0;
+}
+
+unsigned peak_chunks(const dfx_handle* h, const ObjJob& j) {
+  const long long items = (long long)h->ts.size() * j.n_act;
+  return (unsigned)std::max<long long>(1, (items + kObjQuads - 1) / kObjQuads);
+}
+
+PeakArgs peak_args(const dfx_handle* h) {
+  PeakArgs p;
+  p.coef = h->d_pk_coef.p; p.slot_bond = h->d_slot_bond.p;
+  p.Q = h->d_pk_q.p; p.pmax = h->d_pk_max.p; p.pkey = h->d_pk_key.p; p.res = h->d_pk_res.p; p.at = h->d_pk_at.p;
+  p.coef_stride = h->pk.coef_stride;
+  p.n_bonds = (int)h->pl.n_bonds; p.aggregate = h->pk.aggregate; p.sharp = h->pk.sharp;
+  return p;
+}
+
+// the peak kernels are built per bond model only (no contact part in q)
+template <class F> void with_peak_physics(const dfx_handle* h, F&& f) {
+  with_physics<all_physics>(h->pl.model, 0, [&](auto M, auto C) { if constexpr (C() == 0) f(M); });
+}
+
+// the four reductions of the value (J into d_obj; J | q_hat as doubles and (k_hat, b_hat) as int32 behind them into pinned host memory when
+// given), then -- with G -- the cotangent of the sweep
+int launch_peak(dfx_handle* h, const ObjJob& j, double* G, char* host) {
+  const size_t B = h->pl.batch;
+  const unsigned chunks = peak_chunks(h, j);
+  HIP_OK(h->d_pk_q.ensure(B * h->ts.size() * (size_t)h->pl.n_bonds));
+  HIP_OK(h->d_pk_max.ensure(B * chunks));
+  HIP_OK(h->d_pk_key.ensure(B * chunks));
+  HIP_OK(h->d_obj_part.ensure(B * chunks));
+  DevCtx c = make_ctx(h);
+  const ObjArgs a = strain_args(h, j);
+  const PeakArgs p = peak_args(h);
+  const dim3 grid(chunks, (unsigned)B);
+  double* host2 = reinterpret_cast<double*>(host);
+  int32_t* host_at = host ? reinterpret_cast<int32_t*>(host + sizeof(double) * 2 * B) : nullptr;
+  with_peak_physics(h, [&](auto M) { hipLaunchKernelGGL((k_strain_peak_measure<M()>), grid, dim3(kObjThreads), 0, h->stream, c, a, p); });
+  hipLaunchKernelGGL(k_strain_peak_finish, dim3((unsigned)B), dim3(kObjThreads), 0, h->stream, p, (int)chunks);
+  hipLaunchKernelGGL(k_strain_peak_sum, grid, dim3(kObjThreads), 0, h->stream, c, a, p, h->d_obj_part.p);
+  hipLaunchKernelGGL(k_strain_peak_value, dim3((unsigned)B), dim3(kObjThreads), 0, h->stream, p, (const double*)h->d_obj_part.p, (int)chunks, h->d_obj.p,
+                     host2, host_at, (int)B);
+  if (G) with_peak_physics(h, [&](auto M) { hipLaunchKernelGGL((k_strain_peak_cotangent<M()>), grid, dim3(kObjThreads), 0, h->stream, c, a, p, G); });
   return 0;
 }
 
@@ -548,6 +666,13 @@ void launch_objective_explicit(dfx_handle* h, const DevCtx& c) {
     with_strain_physics(h, [&](auto M, auto C) { hipLaunchKernelGGL((k_signal_explicit<M(), C()>), grid, dim3(64), 0, h->stream, c, a); });
     return;
   }
+  if (j.kind == kObjPeak) {
+    const ObjArgs a = strain_args(h, j);
+    const PeakArgs p = peak_args(h);
+    const dim3 grid((unsigned)((j.n_act * 4 + 63) / 64), (unsigned)h->pl.batch);
+    with_peak_physics(h, [&](auto M) { hipLaunchKernelGGL((k_strain_peak_explicit<M()>), grid, dim3(64), 0, h->stream, c, a, p); });
+    return;
+  }
   if (j.kind == kObjStrain) {
     const ObjArgs a = strain_args(h, j);
     const dim3 grid((unsigned)((j.n_act * 4 + 63) / 64), (unsigned)h->pl.batch);
@@ -653,6 +778,66 @@ int dfx_strain_objective_value_and_grad(dfx_handle* h, const double* bond_weight
   if (int rc = launch_strain(h, oh.job, h->d_G.p, objective ? reinterpret_cast<double*>(h->obj_stage.p) : nullptr)) return rc;
   if (int rc = run_adjoint(h, want, nullptr, views, stats, false, 0, true)) return rc;
   if (objective) memcpy(objective, h->obj_stage.p, sizeof(double) * B);
+  return 0;
+}
+
+int dfx_strain_peak_value(dfx_handle* h, const double* bond_coef, int32_t coef_per_member, const double* bond_weights,
+                          int32_t weights_per_member, const double* time_weights, int32_t aggregate, double sharpness, double* objective,
+                          double* peak, int32_t* peak_at) {
+  HIP_OK(hipSetDevice(h->device));
+  if (!h->have_fields || !h->have_params) { h->err = "strain_peak_value: run forward first"; return 1; }
+  if (!objective) { h->err = "strain_peak_value: objective is NULL"; return 1; }
+  ObjHost oh;
+  if (int rc = prepare_peak(h, "strain_peak_value", bond_coef, coef_per_member, bond_weights, weights_per_member, time_weights, aggregate, sharpness, oh))
+    return rc;
+  if (int rc = launch_peak(h, oh.job, nullptr, nullptr)) return rc;
+  const size_t B = h->pl.batch;
+  std::vector<double> res(B * 4);
+  HIP_OK(hipMemcpyAsync(res.data(), h->d_pk_res.p, sizeof(double) * B * 4, hipMemcpyDeviceToHost, h->stream));
+  if (peak_at) HIP_OK(hipMemcpyAsync(peak_at, h->d_pk_at.p, sizeof(int32_t) * B * 2, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  HIP_OK(hipGetLastError());
+  for (size_t m = 0; m < B; ++m) {
+    objective[m] = res[m * 4 + 2];
+    if (peak) peak[m] = res[m * 4];
+  }
+  return 0;
+}
+
+int dfx_strain_peak_value_and_grad(dfx_handle* h, const double* bond_coef, int32_t coef_per_member, const double* bond_weights,
+                                   int32_t weights_per_member, const double* time_weights, int32_t aggregate, double sharpness,
+                                   double* objective, double* peak, int32_t* peak_at, const dfx_grads* want, dfx_grads* views,
+                                   int32_t device_views, dfx_stats* stats) {
+  HIP_OK(hipSetDevice(h->device));
+  if (!h->have_traj || !h->have_fields) { h->err = "strain_peak_value_and_grad: run forward with keep_trajectory=1 first"; return 1; }
+  if (h->ck->writer != h) { h->err = std::string("strain_peak_value_and_grad: ") + kStaleCheckpoint; return 1; }
+  const Plan& pl = h->pl;
+  const size_t B = pl.batch, nb = pl.n_blocks;
+  const int Tn = (int)h->ts.size();
+  ObjHost oh;
+  if (int rc = prepare_peak(h, "strain_peak_value_and_grad", bond_coef, coef_per_member, bond_weights, weights_per_member, time_weights, aggregate,
+                            sharpness, oh))
+    return rc;
+  if (ensure_adjoint_buffers(h)) return 2;
+  HIP_OK(h->d_G.ensure(B * Tn * nb * 6));
+  const bool any = objective || peak || peak_at;
+  if (any) HIP_OK(h->obj_stage.ensure((sizeof(double) + sizeof(int32_t)) * 2 * B));
+  // as dfx_objective_value_and_grad: what the sweep consults on the handle for this call is taken back on every way out
+  struct Scope {
+    dfx_handle* h;
+    ~Scope() { h->obj_job = nullptr; h->obj_centroids = false; h->device_views = false; }
+  } scope{h};
+  h->obj_centroids = false;
+  h->obj_job = &oh.job;
+  h->device_views = device_views != 0;
+  set_grad_wishes(h, want);
+  if (zero_grad_accumulators(h, h->d_G.p, B * Tn * nb * 6, (int)h->segs.size())) return 2;
+  if (int rc = launch_peak(h, oh.job, h->d_G.p, any ? h->obj_stage.p : nullptr)) return rc;
+  if (int rc = run_adjoint(h, want, nullptr, views, stats, false, 0, true)) return rc;
+  const double* st = reinterpret_cast<const double*>(h->obj_stage.p);      // J | q_hat | (k_hat, b_hat) as int32
+  if (objective) memcpy(objective, st, sizeof(double) * B);
+  if (peak) memcpy(peak, st + B, sizeof(double) * B);
+  if (peak_at) memcpy(peak_at, st + 2 * B, sizeof(int32_t) * 2 * B);
   return 0;
 }
 

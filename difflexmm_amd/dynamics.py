@@ -901,6 +901,27 @@ class DynamicSolver:
         self.adjoint_stats = stats
         return obj, grads
 
+    def peak_strain_value(self, spec):
+        """(J, peak, peak_at) of a peak ligament-strain measure (``objective.PeakStrainSpec``) on the device-resident history of the last
+        solve (any forward pass: no kept trajectory needed): the smooth maximum (batch,), the hard maximum (batch,) and its (output, bond)
+        (batch, 2)."""
+        return self.engine.strain_peak_value(spec.bond_coef, spec.bond_weights, spec.time_weights, spec.aggregate, spec.sharpness)
+
+    def peak_strain_value_and_raw(self, spec, which=("centroid_node_vectors", "void_angle0", "inertia"), device=False):
+        """The peak ligament strain (``objective.PeakStrainSpec``) of the last kept solve, evaluated and differentiated on the device beside
+        :meth:`strain_objective_value_and_raw`: ((J, peak, peak_at), raw gradients of J).  The softmax-weighted ligament forces are formed on
+        the device as the cotangent of the reverse sweep; the explicit node-vector and (when ``which`` names ``reference_vector``) reference-
+        vector terms are already in the raw gradients returned.  The coefficients of the spec are constants: the ``reference_vector``
+        gradient does not see how ``objective.strain_limit_coefficients`` derived them from l0.  As with :meth:`vjp_raw`, ``fn_params``
+        holds what the sweep accumulates: the direct dependence of a prescribed output DOF on its drive is not in it."""
+        which = tuple(w for w in which if not (w == "void_angle0" and self.spec.contact != _b.CONTACT_ANGLE))
+        if self.spec.contact == _b.CONTACT_DISTANCE and "block_centroids" not in which:
+            which = which + ("block_centroids",)
+        out, grads, stats = self.engine.strain_peak_value_and_grad(spec.bond_coef, spec.bond_weights, spec.time_weights, spec.aggregate,
+                                                                   spec.sharpness, which=which, device=device)
+        self.adjoint_stats = stats
+        return out, grads
+
     def signal_values(self, spec):
         """(batch, T, n_signals) signals of an ``objective.SignalSpec`` on the device-resident history of the last solve (any forward
         pass): field components are read from the history, force components are the elastic force dE/d(x, y, theta) on the block,

@@ -3,7 +3,9 @@ records in the notebooks; host code, SciPy where the reference uses ``jax.scipy.
 evaluates and differentiates on the device-resident history (``ObjectiveSpec``; ``include/dfx.h``: ``dfx_objective_value_and_grad``;
 ``StrainObjectiveSpec``: ``dfx_strain_objective_value_and_grad``; ``SignalSpec``: ``dfx_signal_misfit_value_and_grad``; ``ProjectionSpec``: ``dfx_signal_projection_value_and_grad``, with ``fourier_basis``
 for its rows; ``CorrelationSpec``: ``dfx_signal_xcorr_value_and_grad`` -- the cross-correlation measures above as an objective on the
-device, with ``xcorr_of_signals`` / ``host_xcorr_value_and_cotangent`` as its NumPy restatement)."""
+device, with ``xcorr_of_signals`` / ``host_xcorr_value_and_cotangent`` as its NumPy restatement; ``PeakStrainSpec``:
+``dfx_strain_peak_value_and_grad`` -- a smooth maximum over output times and ligaments of a squared strain measure, with
+``strain_limit_coefficients`` for its coefficients and ``host_peak_strain_value`` as its NumPy restatement)."""
 from typing import Any, NamedTuple
 
 import numpy as np
@@ -208,6 +210,154 @@ def host_strain_value(spec, fields, centroid_node_vectors, bond_connectivity, re
         e = c[0] * 0.5 * k_stretch * (axial * l0) ** 2 + c[1] * 0.5 * k_shear * (shear * l0) ** 2 + c[2] * 0.5 * k_rot * bending ** 2
         out[m] = tau @ (e @ w[m])
     return float(out[0]) if single else out
+
+
+# ---- peak ligament strain on the device-resident history ------------------------------------------------------------------------------
+PEAK_AGGREGATES = ("ks", "pnorm")          # DFX_PEAK_KS, DFX_PEAK_PNORM
+
+
+class PeakStrainSpec:
+    """A smooth maximum over output times and ligaments of a squared strain measure (``include/dfx.h``:
+    ``dfx_strain_peak_value[_and_grad]``):
+
+        q_mkb = a_mb (l0 eps)^2 + s_mb (l0 gamma)^2 + r_mb kappa^2        W_mkb = tau_k omega_mb
+        "ks"     J_m = q_hat_m + log( sum W exp(beta (q - q_hat_m)) ) / beta        (sharpness = beta > 0)
+        "pnorm"  J_m = q_hat_m ( sum W (q / q_hat_m)^p )^(1/p)                      (sharpness = p >= 1)
+
+    with q_hat the hard maximum over the pairs with W > 0.  ``bond_coef`` (n_bonds, 3) or (batch, n_bonds, 3): (a, s, r) per ligament, in
+    the order of the problem's bond list (``strain_limit_coefficients`` turns strain limits into them: q is then the squared utilisation
+    and J <= 1 a strain limit); ``bond_weights`` omega (n_bonds,), (batch, n_bonds) or None = ones; ``time_weights`` tau (T,) or None = ones.
+    Coefficients and weights are non-negative and finite; a zero weight excludes the pair.  The coefficients are CONSTANTS of the spec: the
+    ``reference_vector`` gradient of J does not see how a helper derived them from l0.  Shapes, signs and finiteness are checked here
+    (``ValueError``); lengths against a solve are checked where the spec is used."""
+    __slots__ = ("bond_coef", "bond_weights", "time_weights", "aggregate", "sharpness")
+
+    def __init__(self, bond_coef, bond_weights=None, time_weights=None, aggregate="ks", sharpness=20.0):
+        c = np.array(bond_coef, dtype=float)
+        if c.ndim not in (2, 3) or c.shape[-1] != 3 or c.shape[-2] == 0:
+            raise ValueError(f"bond_coef must be (n_bonds, 3) or (batch, n_bonds, 3), got {c.shape}")
+        if not np.isfinite(c).all() or (c < 0).any():
+            raise ValueError("bond_coef must be finite and non-negative")
+        w = None
+        if bond_weights is not None:
+            w = np.array(bond_weights, dtype=float)
+            if w.ndim not in (1, 2) or w.shape[-1] != c.shape[-2]:
+                raise ValueError(f"bond_weights must be ({c.shape[-2]},) or (batch, {c.shape[-2]}), got {w.shape}")
+            if not np.isfinite(w).all() or (w < 0).any():
+                raise ValueError("bond_weights must be finite and non-negative")
+            if not (w > 0).any(-1).all():
+                raise ValueError("bond_weights: all weights are zero for some member")
+        tau = None
+        if time_weights is not None:
+            tau = np.array(time_weights, dtype=float)
+            if tau.ndim != 1:
+                raise ValueError(f"time_weights must be (T,), got {tau.shape}")
+            if not np.isfinite(tau).all() or (tau < 0).any():
+                raise ValueError("time_weights must be finite and non-negative")
+            if not (tau > 0).any():
+                raise ValueError("time_weights: all weights are zero")
+        if aggregate not in PEAK_AGGREGATES:
+            raise ValueError(f"aggregate must be one of {PEAK_AGGREGATES}, got {aggregate!r}")
+        s = float(sharpness)
+        if not np.isfinite(s) or (aggregate == "ks" and not s > 0.0) or (aggregate == "pnorm" and not s >= 1.0):
+            raise ValueError(f"sharpness must be finite, beta > 0 for 'ks' and p >= 1 for 'pnorm', got {sharpness!r}")
+        self.bond_coef, self.bond_weights, self.time_weights, self.aggregate, self.sharpness = c, w, tau, aggregate, s
+
+    def __repr__(self):
+        return (f"PeakStrainSpec(bond_coef={self.bond_coef.shape}, bond_weights={None if self.bond_weights is None else self.bond_weights.shape}, "
+                f"time_weights={self.time_weights!r}, aggregate={self.aggregate!r}, sharpness={self.sharpness})")
+
+
+def strain_limit_coefficients(reference_bond_vectors, eps_lim=None, gamma_lim=None, kappa_lim=None):
+    """(n_bonds, 3) coefficients (a, s, r) = (1 / (l0 eps_lim)^2, 1 / (l0 gamma_lim)^2, 1 / kappa_lim^2) of a ``PeakStrainSpec`` from strain
+    limits: q is then the squared utilisation of a ligament.  ``reference_bond_vectors`` (n_bonds, 2), l0 its row norms; every limit a
+    positive scalar or (n_bonds,); a limit of None or inf gives coefficient 0 (that part is not limited)."""
+    refv = np.asarray(reference_bond_vectors, dtype=float)
+    if refv.ndim != 2 or refv.shape[1] != 2:
+        raise ValueError(f"reference_bond_vectors must be (n_bonds, 2), got {refv.shape}")
+    l0 = np.linalg.norm(refv, axis=-1)
+    out = np.zeros((len(refv), 3))
+    for i, (lim, scale) in enumerate(((eps_lim, l0), (gamma_lim, l0), (kappa_lim, np.ones_like(l0)))):
+        if lim is None:
+            continue
+        lim = np.broadcast_to(np.asarray(lim, dtype=float), l0.shape)
+        if np.isnan(lim).any() or (lim <= 0).any():
+            raise ValueError("strain limits must be positive (None or inf: no limit)")
+        out[:, i] = np.where(np.isinf(lim), 0.0, 1.0 / (scale * np.where(np.isinf(lim), 1.0, lim)) ** 2)
+    return out
+
+
+def host_strain_measure(bond_coef, fields, centroid_node_vectors, bond_connectivity, reference_bond_vectors, model="nonlinear"):
+    """NumPy restatement of the squared strain measure q of a ``PeakStrainSpec`` for the ligament models (``model`` = "nonlinear" or
+    "linearized"), from the strains of ``energy.ligament_strains[_linearized]``:  q = a (eps l0)^2 + s (gamma l0)^2 + r kappa^2.  ``fields``
+    (batch, T, 2, n_blocks, 3) -> (batch, T, n_bonds), or (T, 2, n_blocks, 3) -> (T, n_bonds); ``bond_coef`` and ``centroid_node_vectors``
+    with or without the member axis."""
+    from .energy import block_to_node_kinematics, ligament_strains, ligament_strains_linearized
+    strains = {"nonlinear": ligament_strains, "linearized": ligament_strains_linearized}.get(model)
+    if strains is None:
+        raise ValueError(f"host_strain_measure: model must be 'nonlinear' or 'linearized', got {model!r}")
+    f = np.asarray(fields, dtype=float)
+    single = f.ndim == 4
+    if single:
+        f = f[None]
+    B, T = f.shape[:2]
+    bonds = np.asarray(bond_connectivity)
+    nbd = len(bonds)
+    coef = np.asarray(bond_coef, dtype=float)
+    if coef.shape not in ((nbd, 3), (B, nbd, 3)):
+        raise ValueError(f"bond_coef must be ({nbd}, 3) or ({B}, {nbd}, 3), got {coef.shape}")
+    coef = np.broadcast_to(coef, (B, nbd, 3))
+    cnv = np.asarray(centroid_node_vectors, dtype=float)
+    cnv = np.broadcast_to(cnv, (B,) + cnv.shape[-3:])
+    refv = np.broadcast_to(np.asarray(reference_bond_vectors, dtype=float), (nbd, 2))
+    l0 = np.linalg.norm(refv, axis=-1)
+    q = np.zeros((B, T, nbd))
+    for m in range(B):
+        for k in range(T):
+            nd = block_to_node_kinematics(f[m, k, 0], cnv[m]).reshape(-1, 3)
+            axial, shear, bend = strains(nd[bonds[:, 0]], nd[bonds[:, 1]], reference_vector=refv)
+            q[m, k] = coef[m, :, 0] * (axial * l0) ** 2 + coef[m, :, 1] * (shear * l0) ** 2 + coef[m, :, 2] * bend ** 2
+    return q[0] if single else q
+
+
+def peak_of_measure(spec, q):
+    """(J, peak, peak_at) of a ``PeakStrainSpec`` from the measure ``q`` (batch, T, n_bonds): the formulas of the class in NumPy.  peak_at =
+    (output, bond) of the hard maximum over the pairs with W > 0; on ties the lowest output, then the lowest bond."""
+    q = np.asarray(q, dtype=float)
+    B, T, nbd = q.shape
+    w = np.ones(nbd) if spec.bond_weights is None else np.asarray(spec.bond_weights, dtype=float)
+    if w.shape not in ((nbd,), (B, nbd)):
+        raise ValueError(f"bond_weights must be ({nbd},) or ({B}, {nbd}), got {w.shape}")
+    w = np.broadcast_to(w, (B, nbd))
+    tau = np.ones(T) if spec.time_weights is None else np.asarray(spec.time_weights, dtype=float)
+    if tau.shape != (T,):
+        raise ValueError(f"time_weights must be ({T},), got {tau.shape}")
+    J, peak, at = np.zeros(B), np.zeros(B), np.zeros((B, 2), dtype=np.int32)
+    for m in range(B):
+        W = tau[:, None] * w[m][None, :]
+        on = W > 0
+        if not on.any():
+            raise ValueError(f"all weights are zero for member {m}")
+        flat = int(np.argmax(np.where(on, q[m], -np.inf)))          # row-major: the lowest output, then the lowest bond
+        qh = q[m].reshape(-1)[flat]
+        peak[m], at[m] = qh, (flat // nbd, flat % nbd)
+        if spec.aggregate == "ks":
+            J[m] = qh + np.log(np.sum(W[on] * np.exp(spec.sharpness * (q[m][on] - qh)))) / spec.sharpness
+        else:
+            J[m] = qh * np.sum(W[on] * (q[m][on] / qh) ** spec.sharpness) ** (1.0 / spec.sharpness) if qh > 0 else 0.0
+    return J, peak, at
+
+
+def host_peak_strain_value(spec, fields, centroid_node_vectors, bond_connectivity, reference_bond_vectors, model="nonlinear"):
+    """NumPy restatement of a ``PeakStrainSpec`` beside ``host_strain_value``, for the ligament models (``model`` = "nonlinear" or
+    "linearized"): (J, peak, peak_at) with the member axis of ``fields`` ((batch, T, 2, n_blocks, 3) -> (batch,), (batch,), (batch, 2); (T, 2,
+    n_blocks, 3) -> float, float, (2,)).  ``host_strain_measure`` gives q, ``peak_of_measure`` the reduction."""
+    single = np.asarray(fields).ndim == 4
+    q = host_strain_measure(spec.bond_coef, fields, centroid_node_vectors, bond_connectivity, reference_bond_vectors, model)
+    J, peak, at = peak_of_measure(spec, q[None] if single else q)
+    if single:
+        return float(J[0]), float(peak[0]), at[0]
+    return J, peak, at
 
 
 # ---- signal misfit on the device-resident history -------------------------------------------------------------------------------------

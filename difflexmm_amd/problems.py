@@ -1034,6 +1034,77 @@ class TargetStrainEnergy:
         return (obj, grads) if many else (float(obj[0]), grads[0])
 
 
+class PeakLigamentStrain:
+    """constraint(design) = J - 1 with J a smooth maximum, over all output times and the watched ligaments, of the squared strain
+    utilisation  q = (eps / eps_lim)^2 + (gamma / gamma_lim)^2 + (kappa / kappa_lim)^2  (``objective.PeakStrainSpec`` with the coefficients
+    of ``objective.strain_limit_coefficients``): feasible when <= 0 -- "no ligament exceeds its allowable strain at any instant" with a
+    gradient, the sign convention of the inequality constraints ``OptimizationProblem.run_optimization_nlopt`` hands to the method of
+    moving asymptotes (``state_constraints``).  ``limits`` = (eps_lim, gamma_lim, kappa_lim), each a positive number, an (n_bonds,) array, or
+    None / inf for "not limited"; ``beta`` is beta of the KS aggregate or p of the p-norm.  With target regions only their ligaments are
+    watched (a ligament belongs to a region when any / both of its end blocks do, ``ends``); without, every ligament.
+    Device only, as ``TargetStrainEnergy``: value and gradient are ``dfx_strain_peak_value[_and_grad]``.  A list of designs runs as one
+    ensemble (``run_ensemble_optimization`` accepts the class).  ``last_peak`` / ``last_peak_at`` keep the hard maximum of q and its
+    (output, bond) of the last evaluation (per design)."""
+
+    def __init__(self, forward, limits, beta=20.0, aggregate="ks", target_sizes=None, target_shifts=None, ends="any"):
+        from .objective import PeakStrainSpec, bond_weights_from_blocks, strain_limit_coefficients
+        self.forward = forward
+        if not getattr(forward, "is_setup", False):
+            forward.setup()
+        if len(limits) != 3:
+            raise ValueError("limits must be (eps_lim, gamma_lim, kappa_lim)")
+        self.limits = tuple(limits)
+        coef = strain_limit_coefficients(forward.reference_bond_vectors, *self.limits)
+        if not coef.any():
+            raise ValueError("PeakLigamentStrain: no strain is limited (every limit is None or inf)")
+        if (target_sizes is None) != (target_shifts is None):
+            raise ValueError("target_sizes and target_shifts go together")
+        self.bond_weights, self.target_blocks_list = None, None
+        if target_sizes is not None:
+            pick = kagome_target_blocks if isinstance(forward.geometry, KagomeGeometry) else quads_target_blocks
+            self.target_sizes, self.target_shifts = tuple(map(tuple, target_sizes)), tuple(map(tuple, target_shifts))
+            if len(self.target_sizes) != len(self.target_shifts):
+                raise ValueError("target_sizes and target_shifts must have the same length")
+            self.target_blocks_list = [pick(forward.geometry, ts, sh) for ts, sh in zip(self.target_sizes, self.target_shifts)]
+            w = bond_weights_from_blocks(forward.bond_connectivity, forward.geometry.n_npb, self.target_blocks_list,
+                                         np.ones(len(self.target_blocks_list)), ends=ends)
+            self.bond_weights = (w > 0).astype(float)           # watched or not: overlapping regions do not weigh a ligament twice
+        self.ends = ends
+        self.spec = PeakStrainSpec(coef, self.bond_weights, None, aggregate, beta)
+        self.last_peak = self.last_peak_at = None
+
+    def _keep(self, out, many):
+        obj, peak, at = (np.array(a) for a in out)
+        self.last_peak, self.last_peak_at = (peak, at) if many else (float(peak[0]), at[0])
+        return obj - 1.0
+
+    def value(self, design):
+        """One design -> float, a list of ``forward.batch`` designs (or a multiple of it) -> (n,) array; no trajectory is kept."""
+        fw = self.forward
+        parts = _in_batches(fw, design, lambda d: (self.value(d), self.last_peak, self.last_peak_at))
+        if parts is not None:
+            self.last_peak, self.last_peak_at = np.concatenate([p[1] for p in parts]), np.concatenate([p[2] for p in parts])
+            return np.concatenate([p[0] for p in parts])
+        many = isinstance(design, list)
+        fw.solve(design, keep_trajectory=False, want_fields=False)
+        c = self._keep(fw.solve_dynamics.peak_strain_value(self.spec), many)
+        return c if many else float(c[0])
+
+    def value_and_grad(self, design):
+        """Return shapes as ``TargetStrainEnergy.value_and_grad``; only the parameter groups a design reaches are differentiated."""
+        fw = self.forward
+        parts = _in_batches(fw, design, lambda d: self.value_and_grad(d) + (self.last_peak, self.last_peak_at))
+        if parts is not None:
+            self.last_peak, self.last_peak_at = np.concatenate([p[2] for p in parts]), np.concatenate([p[3] for p in parts])
+            return np.concatenate([p[0] for p in parts]), [g for p in parts for g in p[1]]
+        many = isinstance(design, list)
+        fw.solve(design, keep_trajectory=True, want_fields=False)
+        out, raw = fw.solve_dynamics.peak_strain_value_and_raw(self.spec)
+        grads = design_gradients(fw, design if many else [design], raw)
+        c = self._keep(out, many)
+        return (c, grads) if many else (float(c[0]), grads[0])
+
+
 class TargetSignalMisfit:
     """objective(design) = 1/2 sum_k tau_k sum_s omega_s (S_ks(design) - Starget_ks)^2 for an ``objective.SignalSpec``: signals that are
     linear combinations of displacement, velocity and elastic-force components of blocks against target histories -- waveform shaping, a
@@ -1772,10 +1843,16 @@ class OptimizationProblem:
 
     def run_optimization_nlopt(self, initial_guess, n_iterations, max_time=None, lower_bound=None, upper_bound=None,
                                min_void_angle=None, min_block_angle=None, min_edge_length=None, boundary_angle_constraint=False,
-                               verbose=True):
+                               verbose=True, state_constraints=None):
         """The reference's loop (problems/quads_focusing.py:546-652) with the same arguments and bookkeeping: maximise the
         objective with the method of moving asymptotes (``difflexmm_amd.optimize``, standing in for ``nlopt.LD_MMA``)
-        under the angle and edge-length inequality constraints, ``n_iterations`` objective evaluations at most."""
+        under the angle and edge-length inequality constraints, ``n_iterations`` objective evaluations at most.
+        ``state_constraints``: a list of objects with ``value_and_grad(design) -> (c, grad)``, feasible when c <= 0 (``PeakLigamentStrain``:
+        peak strain utilisation - 1); each becomes one more inequality constraint of the method of moving asymptotes.  It is evaluated
+        once per optimisation point (value and gradient together, cached on the bytes of the optimisation vector);
+        ``constraints_violation["state"]`` receives one entry per point, the largest value over the state constraints (as "angles" and
+        "edge_lengths" hold one maximum per point).  A state constraint runs a forward solve of its own per point, beside the
+        objective's: the price of keeping the two classes independent.  With None the loop does exactly what it did without the keyword."""
         import time
         from .optimize import mma_maximize
         g = self.objective.forward.geometry
@@ -1827,6 +1904,25 @@ class OptimizationProblem:
                 self.constraints_violation["edge_lengths"].append(float(r.max()))
                 return r
             constraints.append((ce, lambda x: restrict(edge_length_constraints_jac(g, designs_of(x)[1]))))
+        if state_constraints:
+            self.constraints_violation.setdefault("state", [])
+            cache = {}
+
+            def states_at(x):
+                # every state constraint at x, value and gradient together, once per point: the cache holds the last point only
+                key = np.ascontiguousarray(x, dtype=float).tobytes()
+                if cache.get("key") != key:
+                    design = designs_of(x)[1]
+                    vals, jac = [], []
+                    for sc in state_constraints:
+                        v, grad = sc.value_and_grad(design)
+                        gflat = _flatten_design(grad)
+                        vals.append(float(v))
+                        jac.append(gflat if cols is None else gflat[cols])
+                    cache.update(key=key, vals=np.array(vals), jac=np.stack(jac))
+                    self.constraints_violation["state"].append(float(max(vals)))      # one maximum per point, as "angles" / "edge_lengths"
+                return cache
+            constraints.append((lambda x: states_at(x)["vals"], lambda x: states_at(x)["jac"]))
         try:
             res = mma_maximize(fun, _flatten_design(initial_guess), lower=lower_bound, upper=upper_bound,
                                constraints=constraints, maxeval=n_iterations,

@@ -409,6 +409,43 @@ int dfx_strain_objective_value_and_grad(dfx_handle* h, const double* bond_weight
                                         const double* parts4, double* objective, const dfx_grads* want, dfx_grads* views,
                                         int32_t device_views, dfx_stats* stats);
 
+/* The peak ligament strain as an objective or constraint on the device-resident history (HIP library only): a smooth maximum over output
+ * times and ligaments instead of a weighted sum.  For member m, output time k and every ligament b with a non-zero weight
+ *   q_mkb = a_mb (l0 eps)^2 + s_mb (l0 gamma)^2 + r_mb kappa^2
+ *         = 2 E_bond(b; u_mk) of the handle's bond model with (a_mb, s_mb, r_mb) = bond_coef in place of (k_stretch, k_shear, k_rot)
+ *   W_mkb = tau_k omega_mb                       (tau = time_weights, omega = bond_weights, both >= 0; a zero weight excludes the pair)
+ *   peak  q_hat_m = max over W > 0 of q_mkb at (k_hat, b_hat); on ties the lowest k, then the lowest bond
+ *   DFX_PEAK_KS     J_m = q_hat_m + log( sum W exp(beta (q - q_hat_m)) ) / beta      pi = W exp(beta (q - J))          (sum pi = 1)
+ *   DFX_PEAK_PNORM  J_m = q_hat_m ( sum W (q / q_hat_m)^p )^(1/p)                    pi = W q^(p-1) J^(1-p)            (J = 0: pi = 0)
+ *   dJ_m = sum pi_mkb dq_mkb
+ * (l0 eps, l0 gamma, kappa: the stretch elongation, the shear displacement and the bend angle of the ligament models; a part a model does
+ * not have contributes nothing).  With a = 1 / (l0 eps_lim)^2, s = 1 / (l0 gamma_lim)^2, r = 1 / kappa_lim^2, q is the squared utilisation
+ * of the ligament and J <= 1 a strain limit.  The coefficients are CONSTANTS of the call: the reference_vector gradient is that of q at
+ * fixed (a, s, r) and does not see how a caller derived them from l0.
+ * bond_coef: (batch, n_bonds, 3) when coef_per_member != 0, else (n_bonds, 3); bond_weights: (batch, n_bonds) when weights_per_member != 0,
+ * else (n_bonds,), NULL = all ones; time_weights: NULL = all ones, else EXACTLY T doubles; sharpness: beta > 0 (KS) or p >= 1 (PNORM).
+ * objective: (batch,), may be NULL in the gradient call; peak: (batch,) q_hat or NULL; peak_at: (batch, 2) int32 (output, bond) or NULL.
+ * dfx_strain_peak_value works after any forward pass; dfx_strain_peak_value_and_grad needs the kept trajectory and equals dfx_adjoint on
+ * the fields_bar of these formulas (sum_b pi dq/du on the position rows; velocity rows zero) PLUS the explicit terms d J /
+ * d centroid_node_vectors and -- when want asks for it -- d J / d reference_vector.  q does not depend on the stiffnesses, the contact
+ * constants or the void angles: k_bond, contact and void_angle0 receive what the sweep accumulates and nothing explicit.  The direct
+ * dependence of a PRESCRIBED output DOF on its time function is not part of fn_params, as for the other device objectives.  want / views /
+ * device_views / stats, the sweep forms and checkpoint levels, the kept steps of an adaptive solve and the refusals of a missing trajectory
+ * or a stale shared checkpoint are those of dfx_strain_objective_value_and_grad.  Maximum and sum are fixed-order two-level reductions
+ * without atomics: two calls on the same history return the same bits for J, peak, peak_at and every gradient.
+ * A member whose history is not finite (every q NaN) gets peak = -inf, J = NaN and peak_at = (-1, -1).
+ * Return 1 (dfx_last_error says why): no forward pass, a NULL bond_coef (/ objective in the value call), a non-finite or negative
+ * coefficient or weight, all weights zero for some member, an unknown aggregate, sharpness not finite, beta <= 0 or p < 1, nodes with more
+ * than one ligament. */
+enum { DFX_PEAK_KS = 0, DFX_PEAK_PNORM = 1 };
+int dfx_strain_peak_value(dfx_handle* h, const double* bond_coef, int32_t coef_per_member, const double* bond_weights,
+                          int32_t weights_per_member, const double* time_weights, int32_t aggregate, double sharpness, double* objective,
+                          double* peak, int32_t* peak_at);
+int dfx_strain_peak_value_and_grad(dfx_handle* h, const double* bond_coef, int32_t coef_per_member, const double* bond_weights,
+                                   int32_t weights_per_member, const double* time_weights, int32_t aggregate, double sharpness,
+                                   double* objective, double* peak, int32_t* peak_at, const dfx_grads* want, dfx_grads* views,
+                                   int32_t device_views, dfx_stats* stats);
+
 /* Signal misfit on the device-resident history (HIP library only): a least-squares misfit between target histories and signals that are
  * linear combinations of displacement, velocity and elastic-force components of chosen blocks -- the objective of the hinge
  * characterisation (problems/hinge_characterization.py: the reaction force on the driven DOFs against a measured one), of a calibration
