@@ -319,6 +319,9 @@ def _ptr(a):
     return a.ctypes.data_as(_dp) if a is not None else None
 
 
+_WANTED = np.zeros(1)        # what a non-null field of a ``want`` points at (the library tests the pointer only)
+
+
 class Engine:
     """One ``dfx_handle``: a lattice + boundary-condition pattern, ``batch`` members wide."""
 
@@ -438,10 +441,11 @@ class Engine:
         return fields, _stats(st)
 
     # -- forward mode: the single-direction entries are the K-direction ones at K = 1, and share their marshalling -------------------
-    def _need(self, entry):
+    def _need(self, entry, family="forward mode", why="the CPU port of the oracle is reverse mode only"):
         if not hasattr(self.lib, entry):
-            raise NotImplementedError(f"forward mode: the library {getattr(self.lib, '_name', self.lib)!r} has no {entry} "
-                                      "(the CPU port of the oracle is reverse mode only; build the HIP engine)")
+            raise NotImplementedError(f"{family}: the library {getattr(self.lib, '_name', self.lib)!r} has no {entry} ({why}; build the HIP engine)")
+
+    _STALE = "a stale libdfx.so, or the CPU port of the oracle"          # why a library lacks an entry of the later objective families
 
     def _params_dots(self, params_dots, K):
         """K ``dfx_params`` (one per direction) from a list of dicts of arrays by field name (None / a missing name: zero tangent)."""
@@ -681,19 +685,48 @@ class Engine:
     def can_keep_adaptive(self):
         return hasattr(self.lib, "dfx_forward_adaptive_keep")
 
+    def _grad_names(self, which, centroids=False):
+        """The names of ``which`` that exist on this lattice (``centroids``: block_centroids on every lattice -- the angular kind)."""
+        return [n for n in which if not (n == "fn_params" and self.n_fns == 0) and not (n == "contact" and not self.contact)
+                and not (n == "void_angle0" and self.contact != CONTACT_ANGLE)
+                and not (n == "block_centroids" and self.contact != CONTACT_DISTANCE and not centroids)]
+
     def _grads(self, which):
         sh = self.shapes()
         g = dfx_grads()
-        out = {}
-        for name in which:
-            if name == "fn_params" and self.n_fns == 0:
-                continue
-            if (name == "contact" and not self.contact) or (name == "void_angle0" and self.contact != CONTACT_ANGLE) or \
-                    (name == "block_centroids" and self.contact != CONTACT_DISTANCE):
-                continue
-            out[name] = np.zeros(sh[name])
-            setattr(g, name, _ptr(out[name]))
+        out = {n: np.zeros(sh[n]) for n in self._grad_names(which)}
+        for name, a in out.items():
+            setattr(g, name, _ptr(a))
         return g, out
+
+    def _grad_request(self, which, centroids=False):
+        """What a ``*_value_and_grad`` entry takes besides its own arguments: ``want`` (a non-null field per requested gradient), the
+        ``views`` the library fills, the requested names and the stats."""
+        want, views = dfx_grads(), dfx_grads()
+        names = self._grad_names(which, centroids)
+        for n in names:
+            setattr(want, n, _ptr(_WANTED))
+        return want, views, names, dfx_stats()
+
+    def _grad_views(self, views, names, device):
+        """The gradients the library left behind ``views``: ``DeviceArray`` handles, or read-only views of its pinned memory."""
+        sh = self.shapes()
+        if device:
+            return {n: DeviceArray(self, C.cast(getattr(views, n), C.c_void_p).value, sh[n]) for n in names}
+        out = {}
+        for n in names:
+            a = np.ctypeslib.as_array(getattr(views, n), shape=sh[n])
+            a.flags.writeable = False
+            out[n] = a
+        return out
+
+    def _time_weights(self, time_weights):
+        if time_weights is None:
+            return None
+        tau = _f64(time_weights)
+        if self.n_timepoints is not None and tau.shape != (self.n_timepoints,):
+            raise ValueError(f"time_weights must be ({self.n_timepoints},), got {tau.shape}")
+        return tau
 
     ALL_GRADS = tuple(_PARAM_FIELDS + ["state0", "block_centroids"])
 
@@ -727,30 +760,13 @@ class Engine:
         memory (valid until the next call on this engine: copy what must outlive it).  ``device=True`` leaves the gradients in HBM
         (HIP library only): the values are ``DeviceArray`` handles, ``.to_host()`` downloads one."""
         tb = np.ascontiguousarray(target_blocks, dtype=np.int32)
-        sh = self.shapes()
-        want, views = dfx_grads(), dfx_grads()
-        names = [n for n in which if not (n == "fn_params" and self.n_fns == 0) and not (n == "contact" and not self.contact)
-                 and not (n == "void_angle0" and self.contact != CONTACT_ANGLE)
-                 and not (n == "block_centroids" and self.contact != CONTACT_DISTANCE)]
-        flag = np.zeros(1)
-        for n in names:
-            setattr(want, n, _ptr(flag))
+        want, views, names, st = self._grad_request(which)
         obj = np.zeros(self.batch)
-        st = dfx_stats()
-        if device:
-            if not hasattr(self.lib, "dfx_kinetic_value_and_grad_device"):
-                raise RuntimeError("device-resident gradients need the HIP library")
-            self._check(self.lib.dfx_kinetic_value_and_grad_device(self._h, tb.ctypes.data_as(_ip), len(tb), _ptr(obj), C.byref(want),
-                                                                   C.byref(views), C.byref(st)), "dfx_kinetic_value_and_grad_device")
-            return obj, {n: DeviceArray(self, C.cast(getattr(views, n), C.c_void_p).value, sh[n]) for n in names}, _stats(st)
-        self._check(self.lib.dfx_kinetic_value_and_grad(self._h, tb.ctypes.data_as(_ip), len(tb), _ptr(obj), C.byref(want),
-                                                        C.byref(views), C.byref(st)), "dfx_kinetic_value_and_grad")
-        out = {}
-        for n in names:
-            a = np.ctypeslib.as_array(getattr(views, n), shape=sh[n])
-            a.flags.writeable = False
-            out[n] = a
-        return obj, out, _stats(st)
+        entry = "dfx_kinetic_value_and_grad_device" if device else "dfx_kinetic_value_and_grad"
+        if device and not hasattr(self.lib, entry):
+            raise RuntimeError("device-resident gradients need the HIP library")
+        self._check(getattr(self.lib, entry)(self._h, tb.ctypes.data_as(_ip), len(tb), _ptr(obj), C.byref(want), C.byref(views), C.byref(st)), entry)
+        return obj, self._grad_views(views, names, device), _stats(st)
 
     def forward_kinetic_value_and_grad(self, state0, timepoints, steps_per_interval, target_blocks, which=ALL_GRADS, device=False):
         """``forward(keep_trajectory=True, want_fields=False)`` + ``kinetic_value_and_grad`` as ONE library call (HIP library only): the host
@@ -765,29 +781,14 @@ class Engine:
         T = len(ts)
         spis = np.ascontiguousarray(np.broadcast_to(steps_per_interval, (max(T - 1, 0),)), dtype=np.int32)
         tb = np.ascontiguousarray(target_blocks, dtype=np.int32)
-        sh = self.shapes()
-        want, views = dfx_grads(), dfx_grads()
-        names = [n for n in which if not (n == "fn_params" and self.n_fns == 0) and not (n == "contact" and not self.contact)
-                 and not (n == "void_angle0" and self.contact != CONTACT_ANGLE)
-                 and not (n == "block_centroids" and self.contact != CONTACT_DISTANCE)]
-        flag = np.zeros(1)
-        for n in names:
-            setattr(want, n, _ptr(flag))
+        want, views, names, st_a = self._grad_request(which)
         obj = np.zeros(B)
-        st_f, st_a = dfx_stats(), dfx_stats()
+        st_f = dfx_stats()
         self._check(self.lib.dfx_forward_kinetic_value_and_grad(self._h, _ptr(state0), _ptr(ts), T, spis.ctypes.data_as(_ip), tb.ctypes.data_as(_ip),
                                                                 len(tb), _ptr(obj), C.byref(want), C.byref(views), int(bool(device)),
                                                                 C.byref(st_f), C.byref(st_a)), "dfx_forward_kinetic_value_and_grad")
         self.n_timepoints = T
-        if device:
-            out = {n: DeviceArray(self, C.cast(getattr(views, n), C.c_void_p).value, sh[n]) for n in names}
-        else:
-            out = {}
-            for n in names:
-                a = np.ctypeslib.as_array(getattr(views, n), shape=sh[n])
-                a.flags.writeable = False
-                out[n] = a
-        return obj, out, _stats(st_f), _stats(st_a)
+        return obj, self._grad_views(views, names, device), _stats(st_f), _stats(st_a)
 
     # -- weighted objectives on the device-resident history ----------------------------------------------
     @property
@@ -797,18 +798,12 @@ class Engine:
     def _objective_args(self, kind, block_weights, time_weights, lever0):
         """The array arguments of ``dfx_objective_value[_and_grad]``: weights (n_blocks,) or (batch, n_blocks), time weights (T,) or
         None, lever0 (n_blocks, 2) or (batch, n_blocks, 2) or None."""
-        if not self.has_objective:
-            raise NotImplementedError(f"device objectives: the library {getattr(self.lib, '_name', self.lib)!r} has no dfx_objective_value_and_grad "
-                                      "(the CPU port of the oracle has the kinetic entries only; build the HIP engine)")
+        self._need("dfx_objective_value_and_grad", "device objectives", "the CPU port of the oracle has the kinetic entries only")
         B, nb = self.batch, self.n_blocks
         w = _f64(block_weights)
         if w.shape not in ((nb,), (B, nb)):
             raise ValueError(f"block_weights must be ({nb},) or ({B}, {nb}), got {w.shape}")
-        tau = None
-        if time_weights is not None:
-            tau = _f64(time_weights)
-            if self.n_timepoints is not None and tau.shape != (self.n_timepoints,):
-                raise ValueError(f"time_weights must be ({self.n_timepoints},), got {tau.shape}")
+        tau = self._time_weights(time_weights)
         lev = None
         if lever0 is not None:
             lev = _f64(lever0)
@@ -830,26 +825,11 @@ class Engine:
         behind it.  Results as :meth:`kinetic_value_and_grad`: read-only views of pinned memory, or ``DeviceArray`` handles with
         ``device=True``; ``block_centroids`` is available on every lattice for the angular kind."""
         w, wpm, tau, lev, lpm = self._objective_args(kind, block_weights, time_weights, lever0)
-        sh = self.shapes()
-        want, views = dfx_grads(), dfx_grads()
-        names = [n for n in which if not (n == "fn_params" and self.n_fns == 0) and not (n == "contact" and not self.contact)
-                 and not (n == "void_angle0" and self.contact != CONTACT_ANGLE)
-                 and not (n == "block_centroids" and self.contact != CONTACT_DISTANCE and int(kind) != OBJ_ANGULAR_MOMENTUM)]
-        flag = np.zeros(1)
-        for n in names:
-            setattr(want, n, _ptr(flag))
+        want, views, names, st = self._grad_request(which, int(kind) == OBJ_ANGULAR_MOMENTUM)
         obj = np.zeros(self.batch)
-        st = dfx_stats()
         self._check(self.lib.dfx_objective_value_and_grad(self._h, int(kind), _ptr(w), wpm, _ptr(tau), _ptr(lev), lpm, _ptr(obj), C.byref(want),
                                                           C.byref(views), int(bool(device)), C.byref(st)), "dfx_objective_value_and_grad")
-        if device:
-            return obj, {n: DeviceArray(self, C.cast(getattr(views, n), C.c_void_p).value, sh[n]) for n in names}, _stats(st)
-        out = {}
-        for n in names:
-            a = np.ctypeslib.as_array(getattr(views, n), shape=sh[n])
-            a.flags.writeable = False
-            out[n] = a
-        return obj, out, _stats(st)
+        return obj, self._grad_views(views, names, device), _stats(st)
 
     # -- ligament strain-energy objective on the device-resident history ----------------------------------
     @property
@@ -859,18 +839,12 @@ class Engine:
     def _strain_objective_args(self, bond_weights, time_weights, parts):
         """The array arguments of ``dfx_strain_objective_value[_and_grad]``: bond weights (n_bonds,) or (batch, n_bonds), time weights (T,)
         or None, the four part coefficients (c_stretch, c_shear, c_bend, c_contact)."""
-        if not self.has_strain_objective:
-            raise NotImplementedError(f"strain-energy objective: the library {getattr(self.lib, '_name', self.lib)!r} has no "
-                                      "dfx_strain_objective_value_and_grad (a stale libdfx.so, or the CPU port of the oracle; build the HIP engine)")
+        self._need("dfx_strain_objective_value_and_grad", "strain-energy objective", self._STALE)
         B, nbd = self.batch, self.n_bonds
         w = _f64(bond_weights)
         if w.shape not in ((nbd,), (B, nbd)):
             raise ValueError(f"bond_weights must be ({nbd},) or ({B}, {nbd}), got {w.shape}")
-        tau = None
-        if time_weights is not None:
-            tau = _f64(time_weights)
-            if self.n_timepoints is not None and tau.shape != (self.n_timepoints,):
-                raise ValueError(f"time_weights must be ({self.n_timepoints},), got {tau.shape}")
+        tau = self._time_weights(time_weights)
         c = _f64(parts)
         if c.shape != (4,):
             raise ValueError(f"parts must be (c_stretch, c_shear, c_bend, c_contact), got shape {c.shape}")
@@ -888,27 +862,12 @@ class Engine:
         (``dfx_strain_objective_value_and_grad``): the ligament forces are formed on the device as the cotangent of the reverse sweep, the
         explicit node-vector / void-angle / per-ligament terms are added behind it.  Results as :meth:`objective_value_and_grad`."""
         w, wpm, tau, c = self._strain_objective_args(bond_weights, time_weights, parts)
-        sh = self.shapes()
-        want, views = dfx_grads(), dfx_grads()
-        names = [n for n in which if not (n == "fn_params" and self.n_fns == 0) and not (n == "contact" and not self.contact)
-                 and not (n == "void_angle0" and self.contact != CONTACT_ANGLE)
-                 and not (n == "block_centroids" and self.contact != CONTACT_DISTANCE)]
-        flag = np.zeros(1)
-        for n in names:
-            setattr(want, n, _ptr(flag))
+        want, views, names, st = self._grad_request(which)
         obj = np.zeros(self.batch)
-        st = dfx_stats()
         self._check(self.lib.dfx_strain_objective_value_and_grad(self._h, _ptr(w), wpm, _ptr(tau), _ptr(c), _ptr(obj), C.byref(want),
                                                                  C.byref(views), int(bool(device)), C.byref(st)),
                     "dfx_strain_objective_value_and_grad")
-        if device:
-            return obj, {n: DeviceArray(self, C.cast(getattr(views, n), C.c_void_p).value, sh[n]) for n in names}, _stats(st)
-        out = {}
-        for n in names:
-            a = np.ctypeslib.as_array(getattr(views, n), shape=sh[n])
-            a.flags.writeable = False
-            out[n] = a
-        return obj, out, _stats(st)
+        return obj, self._grad_views(views, names, device), _stats(st)
 
     # -- peak ligament strain on the device-resident history --------------------------------------------------
     @property
@@ -918,9 +877,7 @@ class Engine:
     def _strain_peak_args(self, bond_coef, bond_weights, time_weights, aggregate, sharpness):
         """The arguments of ``dfx_strain_peak_value[_and_grad]``: coefficients (n_bonds, 3) or (batch, n_bonds, 3), bond weights
         (n_bonds,), (batch, n_bonds) or None = ones, time weights (T,) or None, the aggregate ("ks" / "pnorm" or DFX_PEAK_*), beta or p."""
-        if not self.has_strain_peak:
-            raise NotImplementedError(f"peak-strain objective: the library {getattr(self.lib, '_name', self.lib)!r} has no "
-                                      "dfx_strain_peak_value_and_grad (a stale libdfx.so, or the CPU port of the oracle; build the HIP engine)")
+        self._need("dfx_strain_peak_value_and_grad", "peak-strain objective", self._STALE)
         B, nbd = self.batch, self.n_bonds
         c = _f64(bond_coef)
         if c.shape not in ((nbd, 3), (B, nbd, 3)):
@@ -930,11 +887,7 @@ class Engine:
             w = _f64(bond_weights)
             if w.shape not in ((nbd,), (B, nbd)):
                 raise ValueError(f"bond_weights must be ({nbd},) or ({B}, {nbd}), got {w.shape}")
-        tau = None
-        if time_weights is not None:
-            tau = _f64(time_weights)
-            if self.n_timepoints is not None and tau.shape != (self.n_timepoints,):
-                raise ValueError(f"time_weights must be ({self.n_timepoints},), got {tau.shape}")
+        tau = self._time_weights(time_weights)
         agg = {"ks": PEAK_KS, "pnorm": PEAK_PNORM}.get(aggregate, aggregate)
         return c, int(c.ndim == 3), w, int(w is not None and w.ndim == 2), tau, int(agg), float(sharpness)
 
@@ -953,27 +906,12 @@ class Engine:
         the softmax-weighted ligament forces are formed on the device as the cotangent of the reverse sweep, the explicit node-vector /
         reference-vector terms are added behind it.  Results as :meth:`objective_value_and_grad`."""
         c, cpm, w, wpm, tau, agg, sharp = self._strain_peak_args(bond_coef, bond_weights, time_weights, aggregate, sharpness)
-        sh = self.shapes()
-        want, views = dfx_grads(), dfx_grads()
-        names = [n for n in which if not (n == "fn_params" and self.n_fns == 0) and not (n == "contact" and not self.contact)
-                 and not (n == "void_angle0" and self.contact != CONTACT_ANGLE)
-                 and not (n == "block_centroids" and self.contact != CONTACT_DISTANCE)]
-        flag = np.zeros(1)
-        for n in names:
-            setattr(want, n, _ptr(flag))
+        want, views, names, st = self._grad_request(which)
         obj, peak, at = np.zeros(self.batch), np.zeros(self.batch), np.zeros((self.batch, 2), dtype=np.int32)
-        st = dfx_stats()
         self._check(self.lib.dfx_strain_peak_value_and_grad(self._h, _ptr(c), cpm, _ptr(w), wpm, _ptr(tau), agg, sharp, _ptr(obj), _ptr(peak),
                                                             at.ctypes.data_as(_ip), C.byref(want), C.byref(views), int(bool(device)),
                                                             C.byref(st)), "dfx_strain_peak_value_and_grad")
-        if device:
-            return (obj, peak, at), {n: DeviceArray(self, C.cast(getattr(views, n), C.c_void_p).value, sh[n]) for n in names}, _stats(st)
-        out = {}
-        for n in names:
-            a = np.ctypeslib.as_array(getattr(views, n), shape=sh[n])
-            a.flags.writeable = False
-            out[n] = a
-        return (obj, peak, at), out, _stats(st)
+        return (obj, peak, at), self._grad_views(views, names, device), _stats(st)
 
     # -- signal misfit on the device-resident history ---------------------------------------------------------
     @property
@@ -982,9 +920,7 @@ class Engine:
 
     def _signal_terms(self, terms, n_signals):
         """The term arrays of ``dfx_signal_*``: ``terms`` is a sequence of (signal, block, component, coef)."""
-        if not self.has_signal_misfit:
-            raise NotImplementedError(f"signal misfit: the library {getattr(self.lib, '_name', self.lib)!r} has no "
-                                      "dfx_signal_misfit_value_and_grad (a stale libdfx.so, or the CPU port of the oracle; build the HIP engine)")
+        self._need("dfx_signal_misfit_value_and_grad", "signal misfit", self._STALE)
         t = np.asarray(terms, dtype=float).reshape(-1, 4)
         idx = [np.ascontiguousarray(t[:, i], dtype=np.int32) for i in range(3)]
         coef = np.ascontiguousarray(t[:, 3], dtype=np.float64)
@@ -995,16 +931,12 @@ class Engine:
         tg = _f64(targets)
         if tg.ndim not in (2, 3) or tg.shape[-1] != ns or (tg.ndim == 3 and tg.shape[0] != B) or (T is not None and tg.shape[-2] != T):
             raise ValueError(f"targets must be ({T}, {ns}) or ({B}, {T}, {ns}), got {tg.shape}")
-        om = tau = None
+        om = None
         if signal_weights is not None:
             om = _f64(signal_weights)
             if om.shape != (ns,):
                 raise ValueError(f"signal_weights must be ({ns},), got {om.shape}")
-        if time_weights is not None:
-            tau = _f64(time_weights)
-            if T is not None and tau.shape != (T,):
-                raise ValueError(f"time_weights must be ({T},), got {tau.shape}")
-        return tg, int(tg.ndim == 3), om, tau
+        return tg, int(tg.ndim == 3), om, self._time_weights(time_weights)
 
     def signal_values(self, terms, n_signals):
         """(batch, T, n_signals) signals (``dfx_signal_values``) on the resident history of the last forward pass: linear combinations of
@@ -1028,27 +960,12 @@ class Engine:
         reverse sweep and their mixed second derivatives behind it.  Results as :meth:`objective_value_and_grad`."""
         args, keep = self._signal_terms(terms, n_signals)
         tg, tpm, om, tau = self._signal_targets(n_signals, targets, signal_weights, time_weights)
-        sh = self.shapes()
-        want, views = dfx_grads(), dfx_grads()
-        names = [n for n in which if not (n == "fn_params" and self.n_fns == 0) and not (n == "contact" and not self.contact)
-                 and not (n == "void_angle0" and self.contact != CONTACT_ANGLE)
-                 and not (n == "block_centroids" and self.contact != CONTACT_DISTANCE)]
-        flag = np.zeros(1)
-        for n in names:
-            setattr(want, n, _ptr(flag))
+        want, views, names, st = self._grad_request(which)
         obj = np.zeros(self.batch)
-        st = dfx_stats()
         self._check(self.lib.dfx_signal_misfit_value_and_grad(self._h, *args, _ptr(tg), tpm, _ptr(om), _ptr(tau), _ptr(obj), C.byref(want),
                                                               C.byref(views), int(bool(device)), C.byref(st)),
                     "dfx_signal_misfit_value_and_grad")
-        if device:
-            return obj, {n: DeviceArray(self, C.cast(getattr(views, n), C.c_void_p).value, sh[n]) for n in names}, _stats(st)
-        out = {}
-        for n in names:
-            a = np.ctypeslib.as_array(getattr(views, n), shape=sh[n])
-            a.flags.writeable = False
-            out[n] = a
-        return obj, out, _stats(st)
+        return obj, self._grad_views(views, names, device), _stats(st)
 
     # -- signal projections on the device-resident history -----------------------------------------------------
     @property
@@ -1058,9 +975,7 @@ class Engine:
     def _projection_args(self, n_signals, basis, row_weights=None, targets=None, weights=True):
         """The array arguments of ``dfx_signal_projection*``: basis (n_rows, T), row weights (n_signals, n_rows), targets (n_signals, n_rows)
         or (batch, n_signals, n_rows) or None = zeros."""
-        if not self.has_signal_projection:
-            raise NotImplementedError(f"signal projections: the library {getattr(self.lib, '_name', self.lib)!r} has no "
-                                      "dfx_signal_projection_value_and_grad (a stale libdfx.so, or the CPU port of the oracle; build the HIP engine)")
+        self._need("dfx_signal_projection_value_and_grad", "signal projections", self._STALE)
         B, T, ns = self.batch, self.n_timepoints, int(n_signals)
         b = _f64(basis)
         if b.ndim != 2 or (T is not None and b.shape[1] != T):
@@ -1101,27 +1016,12 @@ class Engine:
         Results as :meth:`signal_misfit_value_and_grad`."""
         args, keep = self._signal_terms(terms, n_signals)
         b, nr, w, tg, tpm = self._projection_args(n_signals, basis, row_weights, targets)
-        sh = self.shapes()
-        want, views = dfx_grads(), dfx_grads()
-        names = [n for n in which if not (n == "fn_params" and self.n_fns == 0) and not (n == "contact" and not self.contact)
-                 and not (n == "void_angle0" and self.contact != CONTACT_ANGLE)
-                 and not (n == "block_centroids" and self.contact != CONTACT_DISTANCE)]
-        flag = np.zeros(1)
-        for n in names:
-            setattr(want, n, _ptr(flag))
+        want, views, names, st = self._grad_request(which)
         obj = np.zeros(self.batch)
-        st = dfx_stats()
         self._check(self.lib.dfx_signal_projection_value_and_grad(self._h, *args, _ptr(b), nr, _ptr(w), _ptr(tg), tpm, _ptr(obj), C.byref(want),
                                                                   C.byref(views), int(bool(device)), C.byref(st)),
                     "dfx_signal_projection_value_and_grad")
-        if device:
-            return obj, {n: DeviceArray(self, C.cast(getattr(views, n), C.c_void_p).value, sh[n]) for n in names}, _stats(st)
-        out = {}
-        for n in names:
-            a = np.ctypeslib.as_array(getattr(views, n), shape=sh[n])
-            a.flags.writeable = False
-            out[n] = a
-        return obj, out, _stats(st)
+        return obj, self._grad_views(views, names, device), _stats(st)
 
     # -- signal cross-correlation on the device-resident history ------------------------------------------------
     @property
@@ -1132,9 +1032,7 @@ class Engine:
         """The pair, template, lag and normalisation arguments of ``dfx_signal_xcorr*``: ``pairs`` a sequence of (a, b), b < 0 naming
         column -1 - b of ``templates`` (T, n_templates) or (batch, T, n_templates); ``normalisation`` a name of ``XCORR_NORMS`` (or its
         number).  Returns (the C arguments, the arrays they point into)."""
-        if not self.has_signal_xcorr:
-            raise NotImplementedError(f"signal cross-correlation: the library {getattr(self.lib, '_name', self.lib)!r} has no "
-                                      "dfx_signal_xcorr_value_and_grad (a stale libdfx.so, or the CPU port of the oracle; build the HIP engine)")
+        self._need("dfx_signal_xcorr_value_and_grad", "signal cross-correlation", self._STALE)
         B, T = self.batch, self.n_timepoints
         p = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
         pa, pb = np.ascontiguousarray(p[:, 0], dtype=np.int32), np.ascontiguousarray(p[:, 1], dtype=np.int32)
@@ -1180,27 +1078,12 @@ class Engine:
         xa, keep2 = self._xcorr_args(n_signals, pairs, max_lag, templates, normalisation)
         args, keep = self._signal_terms(terms, n_signals)
         va = self._xcorr_value_args(reduce, lag, beta, w_peak, w_delay, delay_target)
-        sh = self.shapes()
-        want, views = dfx_grads(), dfx_grads()
-        names = [n for n in which if not (n == "fn_params" and self.n_fns == 0) and not (n == "contact" and not self.contact)
-                 and not (n == "void_angle0" and self.contact != CONTACT_ANGLE)
-                 and not (n == "block_centroids" and self.contact != CONTACT_DISTANCE)]
-        flag = np.zeros(1)
-        for n in names:
-            setattr(want, n, _ptr(flag))
+        want, views, names, st = self._grad_request(which)
         obj, peak, delay = np.zeros(self.batch), np.zeros(self.batch), np.zeros(self.batch)
-        st = dfx_stats()
         self._check(self.lib.dfx_signal_xcorr_value_and_grad(self._h, *args, *xa, *va, _ptr(obj), _ptr(peak), _ptr(delay), C.byref(want),
                                                              C.byref(views), int(bool(device)), C.byref(st)),
                     "dfx_signal_xcorr_value_and_grad")
-        if device:
-            return obj, peak, delay, {n: DeviceArray(self, C.cast(getattr(views, n), C.c_void_p).value, sh[n]) for n in names}, _stats(st)
-        out = {}
-        for n in names:
-            a = np.ctypeslib.as_array(getattr(views, n), shape=sh[n])
-            a.flags.writeable = False
-            out[n] = a
-        return obj, peak, delay, out, _stats(st)
+        return obj, peak, delay, self._grad_views(views, names, device), _stats(st)
 
     def response_data(self, strains=True, kinetic=True):
         """Per-ligament strain energies (batch, T, n_bonds) x 3 and per-block kinetic energy (batch, T, n_blocks) of the last

@@ -4,7 +4,8 @@
 //   engine_adaptive.hip  the reference's adaptive odeint semantics
 //   engine_reverse.hip   reverse sweep, gradient collection, objectives
 //   engine_dense.hip     reverse sweep of an adaptive solve that kept its accepted steps (dense-output discrete adjoint)
-//   engine_objective.hip weighted objectives on the device-resident history (kernels: dfx_objective.h)
+//   engine_objective.hip objectives on the device-resident history (kernels: dfx_objective.h): a prepare_* and a launch_* per family, one
+//                        sweep driver (objective_sweep) behind every gradient entry
 //   engine_abi.hip       create / destroy / set_params / reserve, test hooks, post-processing, downloads
 // The kernels live in dfx_kernels.h (stage kernels: instantiated by engine_launch.hip, the reverse per-stage builds by stage_builds_adj.hip)
 // and dfx_persist.hip.

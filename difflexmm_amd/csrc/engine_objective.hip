@@ -11,6 +11,9 @@
 // lags and the two energies, a reduction to a peak and a delay, and the cotangent c of J = w_peak M + 1/2 w_delay (delta - delta_target)^2.
 // The peak ligament strain (dfx_strain_peak_value[_and_grad]) is a smooth maximum, not a sum: its cotangent is the ligament force weighted
 // by a softmax over all (output, ligament) pairs, so a maximum and a sum are reduced before the first cotangent is written.
+// Every family is a prepare_* (the checks of the call, return 1 with h->err; then its uploads) and a launch_* (the value and, with G, the
+// cotangent).  A value entry runs them between need_fields and download; a gradient entry between need_trajectory and objective_sweep, the
+// one place that sets what the sweep consults on the handle for the call in flight and takes it back on every way out.
 // (shared declarations in dfx_engine.h, the kernels in dfx_objective.h)
 #include "dfx_engine.h"
 #include "dfx_objective.h"
@@ -24,12 +27,60 @@ struct ObjHost {               // the validated arguments of a call, compacted
   std::vector<int32_t> blocks; // blocks whose weight is non-zero in any member
 };
 
+unsigned chunks_of(long long items, int per) { return (unsigned)std::max<long long>(1, (items + per - 1) / per); }
+
+// v[0..n) (null: nothing to check) is finite and, with nonneg, not negative -- or h->err says that `what` is not
+bool all_finite(dfx_handle* h, const char* who, const char* what, const double* v, size_t n, bool nonneg = false) {
+  for (size_t i = 0; v && i < n; ++i)
+    if (!std::isfinite(v[i]) || (nonneg && v[i] < 0.0)) {
+      h->err = std::string(who) + (nonneg ? ": non-finite or negative " : ": non-finite ") + what;
+      return false;
+    }
+  return true;
+}
+
+// what the weighted jobs share: the job of the listed blocks, then the uploads of listed blocks, weights (nw of them, w_stride apart per
+// member) and output-time weights; the value buffer
+int upload_job(dfx_handle* h, int kind, const double* w, size_t nw, int w_stride, const double* tau, ObjHost& out) {
+  const int Tn = (int)h->ts.size();
+  out.job = ObjJob{kind, (int)out.blocks.size(), w_stride, 0, tau != nullptr};
+  HIP_OK(h->d_obj_blocks.ensure(std::max<size_t>(1, out.blocks.size())));
+  HIP_OK(h->d_obj_w.ensure(nw));
+  HIP_OK(h->d_obj.ensure(h->pl.batch));
+  if (!out.blocks.empty())
+    HIP_OK(hipMemcpyAsync(h->d_obj_blocks.p, out.blocks.data(), sizeof(int32_t) * out.blocks.size(), hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipMemcpyAsync(h->d_obj_w.p, w, sizeof(double) * nw, hipMemcpyHostToDevice, h->stream));
+  if (tau) {
+    HIP_OK(h->d_obj_tau.ensure(Tn));
+    HIP_OK(hipMemcpyAsync(h->d_obj_tau.p, tau, sizeof(double) * Tn, hipMemcpyHostToDevice, h->stream));
+  }
+  return 0;
+}
+
+// bond weights (null: ones) of wm members -> slot weights (both end slots of a ligament carry its weight); listed blocks = the blocks that
+// own a weighted end; member_any, when given: which members have a non-zero weight at all
+void slot_weights(const Plan& pl, const double* bw, size_t wm, std::vector<double>& sw, std::vector<int32_t>& blocks, std::vector<char>* member_any) {
+  const size_t nb = pl.n_blocks, NS = pl.n_slots, nbd = pl.n_bonds;
+  sw.assign(wm * NS, 0.0);
+  std::vector<char> listed(nb, 0);
+  for (size_t sl = 0; sl < NS; ++sl) {
+    if (pl.slot_info[sl] < 0) continue;
+    const size_t bond = (size_t)pl.slot_bond[sl];
+    for (size_t m = 0; m < wm; ++m) {
+      const double v = bw ? bw[m * nbd + bond] : 1.0;
+      sw[m * NS + sl] = v;
+      if (v != 0.0) { listed[sl >> 2] = 1; if (member_any) (*member_any)[m] = 1; }
+    }
+  }
+  blocks.clear();
+  for (size_t b = 0; b < nb; ++b) if (listed[b]) blocks.push_back((int32_t)b);
+}
+
 // argument checks shared by the two entries (return 1 with h->err), then the uploads: listed blocks, weights, output-time weights, levers
 int prepare_objective(dfx_handle* h, const char* who, int32_t kind, const double* w, int32_t w_per_member, const double* tau, const double* lever,
                       int32_t lever_per_member, ObjHost& out) {
   const Plan& pl = h->pl;
   const size_t B = pl.batch, nb = pl.n_blocks;
-  const int Tn = (int)h->ts.size();
   if (kind != DFX_OBJ_KINETIC && kind != DFX_OBJ_ANGULAR_MOMENTUM) {
     h->err = std::string(who) + ": unknown objective kind " + std::to_string(kind) + " (DFX_OBJ_KINETIC = 0, DFX_OBJ_ANGULAR_MOMENTUM = 1)";
     return 1;
@@ -40,33 +91,15 @@ int prepare_objective(dfx_handle* h, const char* who, int32_t kind, const double
     return 1;
   }
   const size_t nw = (w_per_member ? B : 1) * nb, nl = kind == DFX_OBJ_ANGULAR_MOMENTUM ? (lever_per_member ? B : 1) * nb * 2 : 0;
-  for (size_t i = 0; i < nw; ++i)
-    if (!std::isfinite(w[i])) { h->err = std::string(who) + ": non-finite block weight"; return 1; }
-  for (int k = 0; tau && k < Tn; ++k)
-    if (!std::isfinite(tau[k])) { h->err = std::string(who) + ": non-finite time weight"; return 1; }
-  for (size_t i = 0; i < nl; ++i)
-    if (!std::isfinite(lever[i])) { h->err = std::string(who) + ": non-finite lever0"; return 1; }
+  if (!all_finite(h, who, "block weight", w, nw) || !all_finite(h, who, "time weight", tau, h->ts.size()) || !all_finite(h, who, "lever0", lever, nl)) return 1;
   out.blocks.clear();
   for (size_t b = 0; b < nb; ++b) {
     bool any = false;
     for (size_t m = 0; m < (w_per_member ? B : 1) && !any; ++m) any = w[m * nb + b] != 0.0;
     if (any) out.blocks.push_back((int32_t)b);
   }
-  out.job.kind = kind;
-  out.job.n_act = (int)out.blocks.size();
-  out.job.w_stride = w_per_member ? (int)nb : 0;
+  if (int rc = upload_job(h, kind, w, nw, w_per_member ? (int)nb : 0, tau, out)) return rc;
   out.job.lever_stride = lever_per_member ? (int)nb * 2 : 0;
-  out.job.has_tau = tau != nullptr;
-  HIP_OK(h->d_obj_blocks.ensure(std::max<size_t>(1, out.blocks.size())));
-  HIP_OK(h->d_obj_w.ensure(nw));
-  HIP_OK(h->d_obj.ensure(B));
-  if (!out.blocks.empty())
-    HIP_OK(hipMemcpyAsync(h->d_obj_blocks.p, out.blocks.data(), sizeof(int32_t) * out.blocks.size(), hipMemcpyHostToDevice, h->stream));
-  HIP_OK(hipMemcpyAsync(h->d_obj_w.p, w, sizeof(double) * nw, hipMemcpyHostToDevice, h->stream));
-  if (tau) {
-    HIP_OK(h->d_obj_tau.ensure(Tn));
-    HIP_OK(hipMemcpyAsync(h->d_obj_tau.p, tau, sizeof(double) * Tn, hipMemcpyHostToDevice, h->stream));
-  }
   if (nl) {
     HIP_OK(h->d_obj_lever.ensure(nl));
     HIP_OK(hipMemcpyAsync(h->d_obj_lever.p, lever, sizeof(double) * nl, hipMemcpyHostToDevice, h->stream));
@@ -74,11 +107,12 @@ int prepare_objective(dfx_handle* h, const char* who, int32_t kind, const double
   return 0;
 }
 
+// the kernel arguments of a weighted job; the lever buffer carries the levers (angular kind) or the part coefficients (strain)
 ObjArgs obj_args(const dfx_handle* h, const ObjJob& j) {
   ObjArgs a;
   a.fields = h->d_fields.p; a.blocks = h->d_obj_blocks.p; a.w = h->d_obj_w.p;
   a.tau = j.has_tau ? h->d_obj_tau.p : nullptr;
-  a.lever = j.kind == DFX_OBJ_ANGULAR_MOMENTUM ? h->d_obj_lever.p : nullptr;
+  a.lever = j.kind == DFX_OBJ_KINETIC ? nullptr : h->d_obj_lever.p;
   a.n_act = j.n_act; a.w_stride = j.w_stride; a.lever_stride = j.lever_stride;
   return a;
 }
@@ -86,8 +120,7 @@ ObjArgs obj_args(const dfx_handle* h, const ObjJob& j) {
 // cotangents into G (may be null: value only), the value into d_obj and, when given, into pinned host memory
 int launch_objective(dfx_handle* h, const ObjJob& j, double* G, double* objective_host) {
   const size_t B = h->pl.batch;
-  const long long items = (long long)h->ts.size() * j.n_act;
-  const unsigned chunks = (unsigned)std::max<long long>(1, (items + kObjThreads - 1) / kObjThreads);
+  const unsigned chunks = chunks_of((long long)h->ts.size() * j.n_act, kObjThreads);
   HIP_OK(h->d_obj_part.ensure(B * chunks));
   DevCtx c = make_ctx(h);
   const ObjArgs a = obj_args(h, j);
@@ -99,70 +132,30 @@ int launch_objective(dfx_handle* h, const ObjJob& j, double* G, double* objectiv
   return 0;
 }
 
-// ---- ligament strain energy: bond weights -> slot weights (both end slots of a ligament carry its weight), listed blocks = the blocks that
-// own a weighted end; the part coefficients travel in the lever buffer
+// ---- ligament strain energy: slot weights and listed blocks of the bond weights; the part coefficients travel in the lever buffer
 int prepare_strain(dfx_handle* h, const char* who, const double* bw, int32_t w_per_member, const double* tau, const double* parts, ObjHost& out) {
   const Plan& pl = h->pl;
-  const size_t B = pl.batch, nb = pl.n_blocks, NS = pl.n_slots, nbd = pl.n_bonds;
-  const int Tn = (int)h->ts.size();
   if (!bw) { h->err = std::string(who) + ": bond_weights is NULL"; return 1; }
   if (!parts) { h->err = std::string(who) + ": parts4 is NULL"; return 1; }
   if (pl.n_ovf) {
     h->err = std::string(who) + ": nodes with more than one ligament (a general bond list with extra ligaments) are not supported by the strain-energy objective";
     return 1;
   }
-  const size_t wm = w_per_member ? B : 1;
-  for (size_t i = 0; i < wm * nbd; ++i)
-    if (!std::isfinite(bw[i])) { h->err = std::string(who) + ": non-finite bond weight"; return 1; }
-  for (int k = 0; tau && k < Tn; ++k)
-    if (!std::isfinite(tau[k])) { h->err = std::string(who) + ": non-finite time weight"; return 1; }
-  for (int i = 0; i < 4; ++i)
-    if (!std::isfinite(parts[i])) { h->err = std::string(who) + ": non-finite part coefficient"; return 1; }
+  const size_t wm = w_per_member ? pl.batch : 1;
+  if (!all_finite(h, who, "bond weight", bw, wm * pl.n_bonds) || !all_finite(h, who, "time weight", tau, h->ts.size()) ||
+      !all_finite(h, who, "part coefficient", parts, 4))
+    return 1;
   if (parts[3] != 0.0 && pl.contact != DFX_CONTACT_ANGLE) {
     h->err = std::string(who) + ": c_contact != 0 needs a lattice with the angle contact (the distance-based contact energy is not part of this objective)";
     return 1;
   }
-  std::vector<double> sw(wm * NS, 0.0);
-  std::vector<char> listed(nb, 0);
-  for (size_t sl = 0; sl < NS; ++sl) {
-    if (pl.slot_info[sl] < 0) continue;
-    const size_t bond = (size_t)pl.slot_bond[sl];
-    for (size_t m = 0; m < wm; ++m) {
-      const double v = bw[m * nbd + bond];
-      sw[m * NS + sl] = v;
-      if (v != 0.0) listed[sl >> 2] = 1;
-    }
-  }
-  out.blocks.clear();
-  for (size_t b = 0; b < nb; ++b) if (listed[b]) out.blocks.push_back((int32_t)b);
-  out.job.kind = kObjStrain;
-  out.job.n_act = (int)out.blocks.size();
-  out.job.w_stride = w_per_member ? (int)NS : 0;
-  out.job.lever_stride = 0;
-  out.job.has_tau = tau != nullptr;
-  HIP_OK(h->d_obj_blocks.ensure(std::max<size_t>(1, out.blocks.size())));
-  HIP_OK(h->d_obj_w.ensure(sw.size()));
+  std::vector<double> sw;
+  slot_weights(pl, bw, wm, sw, out.blocks, nullptr);
+  if (int rc = upload_job(h, kObjStrain, sw.data(), sw.size(), w_per_member ? (int)pl.n_slots : 0, tau, out)) return rc;
   HIP_OK(h->d_obj_lever.ensure(4));
-  HIP_OK(h->d_obj.ensure(B));
-  if (!out.blocks.empty())
-    HIP_OK(hipMemcpyAsync(h->d_obj_blocks.p, out.blocks.data(), sizeof(int32_t) * out.blocks.size(), hipMemcpyHostToDevice, h->stream));
-  HIP_OK(hipMemcpyAsync(h->d_obj_w.p, sw.data(), sizeof(double) * sw.size(), hipMemcpyHostToDevice, h->stream));
   HIP_OK(hipMemcpyAsync(h->d_obj_lever.p, parts, sizeof(double) * 4, hipMemcpyHostToDevice, h->stream));
-  if (tau) {
-    HIP_OK(h->d_obj_tau.ensure(Tn));
-    HIP_OK(hipMemcpyAsync(h->d_obj_tau.p, tau, sizeof(double) * Tn, hipMemcpyHostToDevice, h->stream));
-  }
   HIP_OK(hipStreamSynchronize(h->stream));       // the slot weights are a local of this function
   return 0;
-}
-
-ObjArgs strain_args(const dfx_handle* h, const ObjJob& j) {
-  ObjArgs a;
-  a.fields = h->d_fields.p; a.blocks = h->d_obj_blocks.p; a.w = h->d_obj_w.p;
-  a.tau = j.has_tau ? h->d_obj_tau.p : nullptr;
-  a.lever = h->d_obj_lever.p;
-  a.n_act = j.n_act; a.w_stride = j.w_stride; a.lever_stride = 0;
-  return a;
 }
 
 // the build of a strain kernel for the handle's bond model; the angle contact only where the lattice has it (c_contact != 0 is refused
@@ -174,11 +167,10 @@ template <class F> void with_strain_physics(const dfx_handle* h, F&& f) {
 // ligament forces into G (may be null: value only), the value into d_obj and, when given, into pinned host memory
 int launch_strain(dfx_handle* h, const ObjJob& j, double* G, double* objective_host) {
   const size_t B = h->pl.batch;
-  const long long items = (long long)h->ts.size() * j.n_act;
-  const unsigned chunks = (unsigned)std::max<long long>(1, (items + kObjQuads - 1) / kObjQuads);
+  const unsigned chunks = chunks_of((long long)h->ts.size() * j.n_act, kObjQuads);
   HIP_OK(h->d_obj_part.ensure(B * chunks));
   DevCtx c = make_ctx(h);
-  const ObjArgs a = strain_args(h, j);
+  const ObjArgs a = obj_args(h, j);
   const dim3 grid(chunks, (unsigned)B);
   with_strain_physics(h, [&](auto M, auto C) { hipLaunchKernelGGL((k_strain_objective<M(), C()>), grid, dim3(kObjThreads), 0, h->stream, c, a, G, h->d_obj_part.p); });
   hipLaunchKernelGGL(k_objective_finish, dim3((unsigned)B), dim3(kObjThreads), 0, h->stream, (const double*)h->d_obj_part.p, (int)chunks, h->d_obj.p,
@@ -186,13 +178,12 @@ int launch_strain(dfx_handle* h, const ObjJob& j, double* G, double* objective_h
   return 0;
 }
 
-// ---- peak ligament strain: the checks of a call (return 1 with h->err), then bond weights -> slot weights and bond coefficients -> slot
-// coefficients (both end slots of a ligament carry them), listed blocks = the blocks that own a weighted end
+// ---- peak ligament strain: the checks of a call (return 1 with h->err), then slot weights and listed blocks of the bond weights and bond
+// coefficients -> slot coefficients (both end slots of a ligament carry them)
 int prepare_peak(dfx_handle* h, const char* who, const double* coef, int32_t coef_per_member, const double* bw, int32_t w_per_member,
                  const double* tau, int32_t aggregate, double sharp, ObjHost& out) {
   const Plan& pl = h->pl;
-  const size_t B = pl.batch, nb = pl.n_blocks, NS = pl.n_slots, nbd = pl.n_bonds;
-  const int Tn = (int)h->ts.size();
+  const size_t B = pl.batch, NS = pl.n_slots, nbd = pl.n_bonds, Tn = h->ts.size();
   const std::string w(who);
   if (!coef) { h->err = w + ": bond_coef is NULL"; return 1; }
   if (pl.n_ovf) {
@@ -207,25 +198,16 @@ int prepare_peak(dfx_handle* h, const char* who, const double* coef, int32_t coe
   if (aggregate == DFX_PEAK_KS && !(sharp > 0.0)) { h->err = w + ": sharpness beta must be positive with the KS aggregate"; return 1; }
   if (aggregate == DFX_PEAK_PNORM && !(sharp >= 1.0)) { h->err = w + ": sharpness p must be at least 1 with the p-norm aggregate"; return 1; }
   const size_t cm = coef_per_member ? B : 1, wm = bw && w_per_member ? B : 1;
-  for (size_t i = 0; i < cm * nbd * 3; ++i)
-    if (!std::isfinite(coef[i]) || coef[i] < 0.0) { h->err = w + ": non-finite or negative bond coefficient"; return 1; }
-  for (size_t i = 0; bw && i < wm * nbd; ++i)
-    if (!std::isfinite(bw[i]) || bw[i] < 0.0) { h->err = w + ": non-finite or negative bond weight"; return 1; }
-  bool any_tau = !tau;
-  for (int k = 0; tau && k < Tn; ++k) {
-    if (!std::isfinite(tau[k]) || tau[k] < 0.0) { h->err = w + ": non-finite or negative time weight"; return 1; }
-    any_tau = any_tau || tau[k] > 0.0;
-  }
-  std::vector<double> sw(wm * NS, 0.0), sc(cm * NS * 3, 0.0);
-  std::vector<char> listed(nb, 0), member_any(wm, 0);
+  if (!all_finite(h, who, "bond coefficient", coef, cm * nbd * 3, true) || !all_finite(h, who, "bond weight", bw, wm * nbd, true) ||
+      !all_finite(h, who, "time weight", tau, Tn, true))
+    return 1;
+  const bool any_tau = !tau || std::any_of(tau, tau + Tn, [](double t) { return t > 0.0; });
+  std::vector<double> sw, sc(cm * NS * 3, 0.0);
+  std::vector<char> member_any(wm, 0);
+  slot_weights(pl, bw, wm, sw, out.blocks, &member_any);
   for (size_t sl = 0; sl < NS; ++sl) {
     if (pl.slot_info[sl] < 0) continue;
     const size_t bond = (size_t)pl.slot_bond[sl];
-    for (size_t m = 0; m < wm; ++m) {
-      const double v = bw ? bw[m * nbd + bond] : 1.0;
-      sw[m * NS + sl] = v;
-      if (v != 0.0) { listed[sl >> 2] = 1; member_any[m] = 1; }
-    }
     for (size_t m = 0; m < cm; ++m)
       for (int i = 0; i < 3; ++i) sc[(m * NS + sl) * 3 + i] = coef[(m * nbd + bond) * 3 + i];
   }
@@ -234,34 +216,14 @@ int prepare_peak(dfx_handle* h, const char* who, const double* coef, int32_t coe
       h->err = w + ": all weights are zero for member " + std::to_string(m) + " (a peak needs one (output, ligament) pair with tau * omega > 0)";
       return 1;
     }
-  out.blocks.clear();
-  for (size_t b = 0; b < nb; ++b) if (listed[b]) out.blocks.push_back((int32_t)b);
-  out.job.kind = kObjPeak;
-  out.job.n_act = (int)out.blocks.size();
-  out.job.w_stride = wm > 1 || (bw && w_per_member) ? (int)NS : 0;
-  out.job.lever_stride = 0;
-  out.job.has_tau = tau != nullptr;
   h->pk.aggregate = aggregate; h->pk.sharp = sharp; h->pk.coef_stride = coef_per_member ? (long long)(NS * 3) : 0;
-  HIP_OK(h->d_obj_blocks.ensure(std::max<size_t>(1, out.blocks.size())));
-  HIP_OK(h->d_obj_w.ensure(sw.size()));
+  if (int rc = upload_job(h, kObjPeak, sw.data(), sw.size(), wm > 1 || (bw && w_per_member) ? (int)NS : 0, tau, out)) return rc;
   HIP_OK(h->d_pk_coef.ensure(sc.size()));
   HIP_OK(h->d_pk_res.ensure(B * 4));
   HIP_OK(h->d_pk_at.ensure(B * 2));
-  HIP_OK(h->d_obj.ensure(B));
-  HIP_OK(hipMemcpyAsync(h->d_obj_blocks.p, out.blocks.data(), sizeof(int32_t) * out.blocks.size(), hipMemcpyHostToDevice, h->stream));
-  HIP_OK(hipMemcpyAsync(h->d_obj_w.p, sw.data(), sizeof(double) * sw.size(), hipMemcpyHostToDevice, h->stream));
   HIP_OK(hipMemcpyAsync(h->d_pk_coef.p, sc.data(), sizeof(double) * sc.size(), hipMemcpyHostToDevice, h->stream));
-  if (tau) {
-    HIP_OK(h->d_obj_tau.ensure(Tn));
-    HIP_OK(hipMemcpyAsync(h->d_obj_tau.p, tau, sizeof(double) * Tn, hipMemcpyHostToDevice, h->stream));
-  }
   HIP_OK(hipStreamSynchronize(h->stream));       // the slot arrays are locals of this function
   return 0;
-}
-
-unsigned peak_chunks(const dfx_handle* h, const ObjJob& j) {
-  const long long items = (long long)h->ts.size() * j.n_act;
-  return (unsigned)std::max<long long>(1, (items + kObjQuads - 1) / kObjQuads);
 }
 
 PeakArgs peak_args(const dfx_handle* h) {
@@ -280,24 +242,23 @@ template <class F> void with_peak_physics(const dfx_handle* h, F&& f) {
 
 // the four reductions of the value (J into d_obj; J | q_hat as doubles and (k_hat, b_hat) as int32 behind them into pinned host memory when
 // given), then -- with G -- the cotangent of the sweep
-int launch_peak(dfx_handle* h, const ObjJob& j, double* G, char* host) {
+int launch_peak(dfx_handle* h, const ObjJob& j, double* G, double* host) {
   const size_t B = h->pl.batch;
-  const unsigned chunks = peak_chunks(h, j);
+  const unsigned chunks = chunks_of((long long)h->ts.size() * j.n_act, kObjQuads);
   HIP_OK(h->d_pk_q.ensure(B * h->ts.size() * (size_t)h->pl.n_bonds));
   HIP_OK(h->d_pk_max.ensure(B * chunks));
   HIP_OK(h->d_pk_key.ensure(B * chunks));
   HIP_OK(h->d_obj_part.ensure(B * chunks));
   DevCtx c = make_ctx(h);
-  const ObjArgs a = strain_args(h, j);
+  const ObjArgs a = obj_args(h, j);
   const PeakArgs p = peak_args(h);
   const dim3 grid(chunks, (unsigned)B);
-  double* host2 = reinterpret_cast<double*>(host);
-  int32_t* host_at = host ? reinterpret_cast<int32_t*>(host + sizeof(double) * 2 * B) : nullptr;
+  int32_t* host_at = host ? reinterpret_cast<int32_t*>(host + 2 * B) : nullptr;
   with_peak_physics(h, [&](auto M) { hipLaunchKernelGGL((k_strain_peak_measure<M()>), grid, dim3(kObjThreads), 0, h->stream, c, a, p); });
   hipLaunchKernelGGL(k_strain_peak_finish, dim3((unsigned)B), dim3(kObjThreads), 0, h->stream, p, (int)chunks);
   hipLaunchKernelGGL(k_strain_peak_sum, grid, dim3(kObjThreads), 0, h->stream, c, a, p, h->d_obj_part.p);
   hipLaunchKernelGGL(k_strain_peak_value, dim3((unsigned)B), dim3(kObjThreads), 0, h->stream, p, (const double*)h->d_obj_part.p, (int)chunks, h->d_obj.p,
-                     host2, host_at, (int)B);
+                     host, host_at, (int)B);
   if (G) with_peak_physics(h, [&](auto M) { hipLaunchKernelGGL((k_strain_peak_cotangent<M()>), grid, dim3(kObjThreads), 0, h->stream, c, a, p, G); });
   return 0;
 }
@@ -375,18 +336,16 @@ int prepare_signal(dfx_handle* h, const char* who, const SigTerms& t, const doub
   const size_t B = pl.batch;
   const int Tn = (int)h->ts.size(), ns = t.n_signals;
   const std::string w(who);
+  // (signal_term_tables makes these two checks again: here they come before the check of the targets, there before the checks of the terms,
+  // and a call that is wrong in both ways reports the same error as ever)
   if (ns <= 0) { h->err = w + ": n_signals must be positive"; return 1; }
   if (t.n <= 0 || !t.signal || !t.block || !t.comp || !t.coef) { h->err = w + ": an empty term list (a NULL term array, or n_terms <= 0)"; return 1; }
   if (want_target && !targets) { h->err = w + ": targets is NULL"; return 1; }
   SigTables tb;
   if (int rc = signal_term_tables(h, who, t, tb)) return rc;
   const size_t n_tg = want_target ? (targets_per_member ? B : 1) * (size_t)Tn * ns : 0;
-  for (size_t i = 0; i < n_tg; ++i)
-    if (!std::isfinite(targets[i])) { h->err = w + ": non-finite target"; return 1; }
-  for (int s = 0; want_target && omega && s < ns; ++s)
-    if (!std::isfinite(omega[s])) { h->err = w + ": non-finite signal weight"; return 1; }
-  for (int k = 0; want_target && tau && k < Tn; ++k)
-    if (!std::isfinite(tau[k])) { h->err = w + ": non-finite time weight"; return 1; }
+  if (!all_finite(h, who, "target", targets, n_tg)) return 1;
+  if (want_target && (!all_finite(h, who, "signal weight", omega, ns) || !all_finite(h, who, "time weight", tau, Tn))) return 1;
   const std::vector<int32_t>&fmap = tb.fmap, &fblocks = tb.fblocks, &set = tb.set, &sig_ptr = tb.sig_ptr, &term_src = tb.term_src;
   const std::vector<double>& term_coef = tb.term_coef;
   const size_t nb = pl.n_blocks;
@@ -453,8 +412,6 @@ SigArgs sig_args(const dfx_handle* h) {
   return a;
 }
 
-unsigned chunks_of(long long items, int per) { return (unsigned)std::max<long long>(1, (items + per - 1) / per); }
-
 // from the residual cotangents in d_sig_c to the cotangent G of the sweep: the field rows and the direction w, then K w of the force terms
 void launch_signal_reverse(dfx_handle* h, const DevCtx& c, const SigArgs& a, double* G) {
   const dfx_handle::SigJob& J = h->sig;
@@ -498,14 +455,11 @@ int prepare_projection(dfx_handle* h, const char* who, const SigTerms& t, const 
   if (n_rows < 1) { h->err = w + ": n_rows must be at least 1, got " + std::to_string(n_rows); return 1; }
   if (!basis) { h->err = w + ": basis is NULL"; return 1; }
   if (want_w && !row_weights) { h->err = w + ": row_weights is NULL"; return 1; }
-  for (size_t i = 0; i < (size_t)n_rows * Tn; ++i)
-    if (!std::isfinite(basis[i])) { h->err = w + ": non-finite basis entry"; return 1; }
   const size_t ns = t.n_signals > 0 ? (size_t)t.n_signals : 0, n_w = want_w ? ns * n_rows : 0;
   const size_t n_tg = want_w && targets ? (targets_per_member ? B : 1) * ns * n_rows : 0;
-  for (size_t i = 0; i < n_w; ++i)
-    if (!std::isfinite(row_weights[i])) { h->err = w + ": non-finite row weight"; return 1; }
-  for (size_t i = 0; i < n_tg; ++i)
-    if (!std::isfinite(targets[i])) { h->err = w + ": non-finite target"; return 1; }
+  if (!all_finite(h, who, "basis entry", basis, (size_t)n_rows * Tn) || !all_finite(h, who, "row weight", row_weights, n_w) ||
+      !all_finite(h, who, "target", targets, n_tg))
+    return 1;
   if (int rc = prepare_signal(h, who, t, nullptr, 0, nullptr, nullptr, false)) return rc;
   dfx_handle::ProjJob& J = h->proj;
   J.n_rows = n_rows; J.has_w = want_w; J.has_target = n_tg != 0;
@@ -600,8 +554,7 @@ int prepare_xcorr(dfx_handle* h, const char* who, const SigTerms& t, const Xcorr
     if (q.w_delay != 0.0 && q.reduce != DFX_XCORR_SOFTMAX) { h->err = w + ": w_delay != 0 needs the softmax reduction (the delay of a maximum has no derivative)"; return 1; }
   }
   const size_t n_tp = q.templ ? (q.templ_per_member ? B : 1) * Tn * (size_t)q.n_templ : 0;
-  for (size_t i = 0; i < n_tp; ++i)
-    if (!std::isfinite(q.templ[i])) { h->err = w + ": non-finite template"; return 1; }
+  if (!all_finite(h, who, "template", q.templ, n_tp)) return 1;
   if (int rc = prepare_signal(h, who, t, nullptr, 0, nullptr, nullptr, false)) return rc;
   dfx_handle::XcorrJob& J = h->xc;
   J.n_pairs = q.n_pairs; J.n_templ = q.templ ? q.n_templ : 0; J.D = q.max_lag; J.norm = q.norm;
@@ -655,6 +608,65 @@ int launch_xcorr(dfx_handle* h, double* G, double* host3) {
   return 0;
 }
 
+// ---- what the entries share
+// A value entry needs the fields of a forward pass (and, all but dfx_objective_value, its parameters) and somewhere to put its result
+int need_fields(dfx_handle* h, const char* who, const void* out, const char* out_name, bool params = true) {
+  if (!h->have_fields || (params && !h->have_params)) { h->err = std::string(who) + ": run forward first"; return 1; }
+  if (!out) { h->err = std::string(who) + ": " + out_name + " is NULL"; return 1; }
+  return 0;
+}
+
+// A gradient entry needs the kept trajectory of a forward pass whose checkpoint is still this handle's
+int need_trajectory(dfx_handle* h, const char* who) {
+  if (!h->have_traj || !h->have_fields) { h->err = std::string(who) + ": run forward with keep_trajectory=1 first"; return 1; }
+  if (h->ck->writer != h) { h->err = std::string(who) + ": " + kStaleCheckpoint; return 1; }
+  return 0;
+}
+
+// The end of a value entry: the results (dst null: not asked for) down, then the one wait of the call
+struct Download { void* dst; const void* src; size_t bytes; };
+int download(dfx_handle* h, std::initializer_list<Download> list) {
+  for (const Download& d : list)
+    if (d.dst) HIP_OK(hipMemcpyAsync(d.dst, d.src, d.bytes, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// How every gradient entry runs behind its own prepare_*: the buffers of the sweep, `job` behind it (launch_objective_explicit; centroids: the
+// block-centroid accumulator exists for this call on every lattice), `launch(G, host)` for the value and the cotangent (host: stage_bytes of
+// pinned memory the launch may fill, null when stage_bytes == 0; the caller reads h->obj_stage after a return of 0), then the sweep itself --
+// want / views / device_views / stats, every sweep form and checkpoint level, the kept steps of an adaptive solve.
+template <class Launch>
+int objective_sweep(dfx_handle* h, const ObjJob& job, bool centroids, size_t stage_bytes, Launch&& launch, const dfx_grads* want, dfx_grads* views,
+                    int32_t device_views, dfx_stats* stats) {
+  const Plan& pl = h->pl;
+  const size_t B = pl.batch, nb = pl.n_blocks, n_G = B * h->ts.size() * nb * 6;
+  if (ensure_adjoint_buffers(h)) return 2;
+  HIP_OK(h->d_G.ensure(n_G));
+  // (on a lattice without distance contact the buffer stays on the handle afterwards: the stage kernels touch g_c with distance contact only,
+  // and the other entries neither zero nor collect it)
+  if (centroids) HIP_OK(h->d_g_c.ensure(B * nb * 2));
+  if (stage_bytes) HIP_OK(h->obj_stage.ensure(stage_bytes));
+  // what the sweep consults on the handle for this call (explicit terms behind it, the centroid accumulator, device views) is taken back on
+  // EVERY way out of this function, a failed launch or allocation included: the next call on the handle must not inherit it
+  struct Scope {
+    dfx_handle* h;
+    ~Scope() { h->obj_job = nullptr; h->obj_centroids = false; h->device_views = false; }
+  } scope{h};
+  h->obj_centroids = centroids;
+  h->obj_job = &job;
+  h->device_views = device_views != 0;
+  set_grad_wishes(h, want);
+  // one launch: accumulators and cotangents cleared, cursors at the last segment (as the kinetic entries)
+  if (zero_grad_accumulators(h, h->d_G.p, n_G, (int)h->segs.size())) return 2;
+  if (int rc = launch(h->d_G.p, stage_bytes ? reinterpret_cast<double*>(h->obj_stage.p) : nullptr)) return rc;
+  return run_adjoint(h, want, nullptr, views, stats, false, 0, true);
+}
+
+// the job of a signal family behind the sweep (k_signal_explicit): the set of the term list in flight
+ObjJob signal_job(const dfx_handle* h, int kind, bool has_tau) { return ObjJob{kind, h->sig.n_set, 0, 0, has_tau}; }
+
 }  // namespace
 
 void launch_objective_explicit(dfx_handle* h, const DevCtx& c) {
@@ -667,14 +679,14 @@ void launch_objective_explicit(dfx_handle* h, const DevCtx& c) {
     return;
   }
   if (j.kind == kObjPeak) {
-    const ObjArgs a = strain_args(h, j);
+    const ObjArgs a = obj_args(h, j);
     const PeakArgs p = peak_args(h);
     const dim3 grid((unsigned)((j.n_act * 4 + 63) / 64), (unsigned)h->pl.batch);
     with_peak_physics(h, [&](auto M) { hipLaunchKernelGGL((k_strain_peak_explicit<M()>), grid, dim3(64), 0, h->stream, c, a, p); });
     return;
   }
   if (j.kind == kObjStrain) {
-    const ObjArgs a = strain_args(h, j);
+    const ObjArgs a = obj_args(h, j);
     const dim3 grid((unsigned)((j.n_act * 4 + 63) / 64), (unsigned)h->pl.batch);
     with_strain_physics(h, [&](auto M, auto C) { hipLaunchKernelGGL((k_strain_objective_explicit<M(), C()>), grid, dim3(64), 0, h->stream, c, a); });
     return;
@@ -687,96 +699,55 @@ void launch_objective_explicit(dfx_handle* h, const DevCtx& c) {
 
 int dfx_objective_value(dfx_handle* h, int32_t kind, const double* block_weights, int32_t weights_per_member, const double* time_weights,
                         const double* lever0, int32_t lever_per_member, double* objective) {
+  const char* who = "objective_value";
   HIP_OK(hipSetDevice(h->device));
-  if (!h->have_fields) { h->err = "objective_value: run forward first"; return 1; }
-  if (!objective) { h->err = "objective_value: objective is NULL"; return 1; }
+  if (int rc = need_fields(h, who, objective, "objective", false)) return rc;
   ObjHost oh;
-  if (int rc = prepare_objective(h, "objective_value", kind, block_weights, weights_per_member, time_weights, lever0, lever_per_member, oh)) return rc;
+  if (int rc = prepare_objective(h, who, kind, block_weights, weights_per_member, time_weights, lever0, lever_per_member, oh)) return rc;
   if (int rc = launch_objective(h, oh.job, nullptr, nullptr)) return rc;
-  HIP_OK(hipMemcpyAsync(objective, h->d_obj.p, sizeof(double) * h->pl.batch, hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipStreamSynchronize(h->stream));
-  HIP_OK(hipGetLastError());
-  return 0;
+  return download(h, {{objective, h->d_obj.p, sizeof(double) * h->pl.batch}});
 }
 
 int dfx_objective_value_and_grad(dfx_handle* h, int32_t kind, const double* block_weights, int32_t weights_per_member,
                                  const double* time_weights, const double* lever0, int32_t lever_per_member, double* objective,
                                  const dfx_grads* want, dfx_grads* views, int32_t device_views, dfx_stats* stats) {
+  const char* who = "objective_value_and_grad";
   HIP_OK(hipSetDevice(h->device));
-  if (!h->have_traj || !h->have_fields) { h->err = "objective_value_and_grad: run forward with keep_trajectory=1 first"; return 1; }
-  if (h->ck->writer != h) { h->err = std::string("objective_value_and_grad: ") + kStaleCheckpoint; return 1; }
-  const Plan& pl = h->pl;
-  const size_t B = pl.batch, nb = pl.n_blocks;
-  const int Tn = (int)h->ts.size();
+  if (int rc = need_trajectory(h, who)) return rc;
+  const size_t B = h->pl.batch;
   ObjHost oh;
-  if (int rc = prepare_objective(h, "objective_value_and_grad", kind, block_weights, weights_per_member, time_weights, lever0, lever_per_member, oh))
+  if (int rc = prepare_objective(h, who, kind, block_weights, weights_per_member, time_weights, lever0, lever_per_member, oh)) return rc;
+  // the angular kind depends on the block centroids through its levers
+  if (int rc = objective_sweep(h, oh.job, kind == DFX_OBJ_ANGULAR_MOMENTUM, objective ? sizeof(double) * B : 0,
+                               [&](double* G, double* host) { return launch_objective(h, oh.job, G, host); }, want, views, device_views, stats))
     return rc;
-  if (ensure_adjoint_buffers(h)) return 2;
-  HIP_OK(h->d_G.ensure(B * Tn * nb * 6));
-  // the angular kind depends on the block centroids through its levers: that accumulator exists for this call on every lattice
-  const bool centroids = kind == DFX_OBJ_ANGULAR_MOMENTUM;
-  // (on a lattice without distance contact the buffer stays on the handle afterwards: the stage kernels touch g_c with distance contact only,
-  // and the other entries neither zero nor collect it)
-  if (centroids) HIP_OK(h->d_g_c.ensure(B * nb * 2));
-  if (objective) HIP_OK(h->obj_stage.ensure(sizeof(double) * B));
-  // what the sweep consults on the handle for this call (explicit terms behind it, the centroid accumulator, device views) is taken back on
-  // EVERY way out of this function, a failed launch or allocation included: the next call on the handle must not inherit it
-  struct Scope {
-    dfx_handle* h;
-    ~Scope() { h->obj_job = nullptr; h->obj_centroids = false; h->device_views = false; }
-  } scope{h};
-  h->obj_centroids = centroids;
-  h->obj_job = &oh.job;
-  h->device_views = device_views != 0;
-  set_grad_wishes(h, want);
-  // one launch: accumulators and cotangents cleared, cursors at the last segment (as the kinetic entries)
-  if (zero_grad_accumulators(h, h->d_G.p, B * Tn * nb * 6, (int)h->segs.size())) return 2;
-  if (int rc = launch_objective(h, oh.job, h->d_G.p, objective ? reinterpret_cast<double*>(h->obj_stage.p) : nullptr)) return rc;
-  if (int rc = run_adjoint(h, want, nullptr, views, stats, false, 0, true)) return rc;
   if (objective) memcpy(objective, h->obj_stage.p, sizeof(double) * B);
   return 0;
 }
 
 int dfx_strain_objective_value(dfx_handle* h, const double* bond_weights, int32_t weights_per_member, const double* time_weights,
                                const double* parts4, double* objective) {
+  const char* who = "strain_objective_value";
   HIP_OK(hipSetDevice(h->device));
-  if (!h->have_fields || !h->have_params) { h->err = "strain_objective_value: run forward first"; return 1; }
-  if (!objective) { h->err = "strain_objective_value: objective is NULL"; return 1; }
+  if (int rc = need_fields(h, who, objective, "objective")) return rc;
   ObjHost oh;
-  if (int rc = prepare_strain(h, "strain_objective_value", bond_weights, weights_per_member, time_weights, parts4, oh)) return rc;
+  if (int rc = prepare_strain(h, who, bond_weights, weights_per_member, time_weights, parts4, oh)) return rc;
   if (int rc = launch_strain(h, oh.job, nullptr, nullptr)) return rc;
-  HIP_OK(hipMemcpyAsync(objective, h->d_obj.p, sizeof(double) * h->pl.batch, hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipStreamSynchronize(h->stream));
-  HIP_OK(hipGetLastError());
-  return 0;
+  return download(h, {{objective, h->d_obj.p, sizeof(double) * h->pl.batch}});
 }
 
 int dfx_strain_objective_value_and_grad(dfx_handle* h, const double* bond_weights, int32_t weights_per_member, const double* time_weights,
                                         const double* parts4, double* objective, const dfx_grads* want, dfx_grads* views, int32_t device_views,
                                         dfx_stats* stats) {
+  const char* who = "strain_objective_value_and_grad";
   HIP_OK(hipSetDevice(h->device));
-  if (!h->have_traj || !h->have_fields) { h->err = "strain_objective_value_and_grad: run forward with keep_trajectory=1 first"; return 1; }
-  if (h->ck->writer != h) { h->err = std::string("strain_objective_value_and_grad: ") + kStaleCheckpoint; return 1; }
-  const Plan& pl = h->pl;
-  const size_t B = pl.batch, nb = pl.n_blocks;
-  const int Tn = (int)h->ts.size();
+  if (int rc = need_trajectory(h, who)) return rc;
+  const size_t B = h->pl.batch;
   ObjHost oh;
-  if (int rc = prepare_strain(h, "strain_objective_value_and_grad", bond_weights, weights_per_member, time_weights, parts4, oh)) return rc;
-  if (ensure_adjoint_buffers(h)) return 2;
-  HIP_OK(h->d_G.ensure(B * Tn * nb * 6));
-  if (objective) HIP_OK(h->obj_stage.ensure(sizeof(double) * B));
-  // as dfx_objective_value_and_grad: what the sweep consults on the handle for this call is taken back on every way out
-  struct Scope {
-    dfx_handle* h;
-    ~Scope() { h->obj_job = nullptr; h->obj_centroids = false; h->device_views = false; }
-  } scope{h};
-  h->obj_centroids = false;
-  h->obj_job = &oh.job;
-  h->device_views = device_views != 0;
-  set_grad_wishes(h, want);
-  if (zero_grad_accumulators(h, h->d_G.p, B * Tn * nb * 6, (int)h->segs.size())) return 2;
-  if (int rc = launch_strain(h, oh.job, h->d_G.p, objective ? reinterpret_cast<double*>(h->obj_stage.p) : nullptr)) return rc;
-  if (int rc = run_adjoint(h, want, nullptr, views, stats, false, 0, true)) return rc;
+  if (int rc = prepare_strain(h, who, bond_weights, weights_per_member, time_weights, parts4, oh)) return rc;
+  if (int rc = objective_sweep(h, oh.job, false, objective ? sizeof(double) * B : 0,
+                               [&](double* G, double* host) { return launch_strain(h, oh.job, G, host); }, want, views, device_views, stats))
+    return rc;
   if (objective) memcpy(objective, h->obj_stage.p, sizeof(double) * B);
   return 0;
 }
@@ -784,19 +755,15 @@ int dfx_strain_objective_value_and_grad(dfx_handle* h, const double* bond_weight
 int dfx_strain_peak_value(dfx_handle* h, const double* bond_coef, int32_t coef_per_member, const double* bond_weights,
                           int32_t weights_per_member, const double* time_weights, int32_t aggregate, double sharpness, double* objective,
                           double* peak, int32_t* peak_at) {
+  const char* who = "strain_peak_value";
   HIP_OK(hipSetDevice(h->device));
-  if (!h->have_fields || !h->have_params) { h->err = "strain_peak_value: run forward first"; return 1; }
-  if (!objective) { h->err = "strain_peak_value: objective is NULL"; return 1; }
+  if (int rc = need_fields(h, who, objective, "objective")) return rc;
   ObjHost oh;
-  if (int rc = prepare_peak(h, "strain_peak_value", bond_coef, coef_per_member, bond_weights, weights_per_member, time_weights, aggregate, sharpness, oh))
-    return rc;
+  if (int rc = prepare_peak(h, who, bond_coef, coef_per_member, bond_weights, weights_per_member, time_weights, aggregate, sharpness, oh)) return rc;
   if (int rc = launch_peak(h, oh.job, nullptr, nullptr)) return rc;
   const size_t B = h->pl.batch;
   std::vector<double> res(B * 4);
-  HIP_OK(hipMemcpyAsync(res.data(), h->d_pk_res.p, sizeof(double) * B * 4, hipMemcpyDeviceToHost, h->stream));
-  if (peak_at) HIP_OK(hipMemcpyAsync(peak_at, h->d_pk_at.p, sizeof(int32_t) * B * 2, hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipStreamSynchronize(h->stream));
-  HIP_OK(hipGetLastError());
+  if (int rc = download(h, {{res.data(), h->d_pk_res.p, sizeof(double) * B * 4}, {peak_at, h->d_pk_at.p, sizeof(int32_t) * B * 2}})) return rc;
   for (size_t m = 0; m < B; ++m) {
     objective[m] = res[m * 4 + 2];
     if (peak) peak[m] = res[m * 4];
@@ -808,32 +775,16 @@ int dfx_strain_peak_value_and_grad(dfx_handle* h, const double* bond_coef, int32
                                    int32_t weights_per_member, const double* time_weights, int32_t aggregate, double sharpness,
                                    double* objective, double* peak, int32_t* peak_at, const dfx_grads* want, dfx_grads* views,
                                    int32_t device_views, dfx_stats* stats) {
+  const char* who = "strain_peak_value_and_grad";
   HIP_OK(hipSetDevice(h->device));
-  if (!h->have_traj || !h->have_fields) { h->err = "strain_peak_value_and_grad: run forward with keep_trajectory=1 first"; return 1; }
-  if (h->ck->writer != h) { h->err = std::string("strain_peak_value_and_grad: ") + kStaleCheckpoint; return 1; }
-  const Plan& pl = h->pl;
-  const size_t B = pl.batch, nb = pl.n_blocks;
-  const int Tn = (int)h->ts.size();
+  if (int rc = need_trajectory(h, who)) return rc;
+  const size_t B = h->pl.batch;
   ObjHost oh;
-  if (int rc = prepare_peak(h, "strain_peak_value_and_grad", bond_coef, coef_per_member, bond_weights, weights_per_member, time_weights, aggregate,
-                            sharpness, oh))
-    return rc;
-  if (ensure_adjoint_buffers(h)) return 2;
-  HIP_OK(h->d_G.ensure(B * Tn * nb * 6));
+  if (int rc = prepare_peak(h, who, bond_coef, coef_per_member, bond_weights, weights_per_member, time_weights, aggregate, sharpness, oh)) return rc;
   const bool any = objective || peak || peak_at;
-  if (any) HIP_OK(h->obj_stage.ensure((sizeof(double) + sizeof(int32_t)) * 2 * B));
-  // as dfx_objective_value_and_grad: what the sweep consults on the handle for this call is taken back on every way out
-  struct Scope {
-    dfx_handle* h;
-    ~Scope() { h->obj_job = nullptr; h->obj_centroids = false; h->device_views = false; }
-  } scope{h};
-  h->obj_centroids = false;
-  h->obj_job = &oh.job;
-  h->device_views = device_views != 0;
-  set_grad_wishes(h, want);
-  if (zero_grad_accumulators(h, h->d_G.p, B * Tn * nb * 6, (int)h->segs.size())) return 2;
-  if (int rc = launch_peak(h, oh.job, h->d_G.p, any ? h->obj_stage.p : nullptr)) return rc;
-  if (int rc = run_adjoint(h, want, nullptr, views, stats, false, 0, true)) return rc;
+  if (int rc = objective_sweep(h, oh.job, false, any ? (sizeof(double) + sizeof(int32_t)) * 2 * B : 0,
+                               [&](double* G, double* host) { return launch_peak(h, oh.job, G, host); }, want, views, device_views, stats))
+    return rc;
   const double* st = reinterpret_cast<const double*>(h->obj_stage.p);      // J | q_hat | (k_hat, b_hat) as int32
   if (objective) memcpy(objective, st, sizeof(double) * B);
   if (peak) memcpy(peak, st + B, sizeof(double) * B);
@@ -843,140 +794,79 @@ int dfx_strain_peak_value_and_grad(dfx_handle* h, const double* bond_coef, int32
 
 int dfx_signal_values(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block, const int32_t* term_component,
                       const double* term_coef, int32_t n_signals, double* values) {
+  const char* who = "signal_values";
   HIP_OK(hipSetDevice(h->device));
-  if (!h->have_fields || !h->have_params) { h->err = "signal_values: run forward first"; return 1; }
-  if (!values) { h->err = "signal_values: values is NULL"; return 1; }
+  if (int rc = need_fields(h, who, values, "values")) return rc;
   const SigTerms t{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
-  if (int rc = prepare_signal(h, "signal_values", t, nullptr, 0, nullptr, nullptr, false)) return rc;
+  if (int rc = prepare_signal(h, who, t, nullptr, 0, nullptr, nullptr, false)) return rc;
   if (int rc = launch_signal(h, nullptr, nullptr)) return rc;
-  HIP_OK(hipMemcpyAsync(values, h->d_sig_S.p, sizeof(double) * h->pl.batch * h->ts.size() * (size_t)n_signals, hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipStreamSynchronize(h->stream));
-  HIP_OK(hipGetLastError());
-  return 0;
+  return download(h, {{values, h->d_sig_S.p, sizeof(double) * h->pl.batch * h->ts.size() * (size_t)n_signals}});
 }
 
 int dfx_signal_misfit_value(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block, const int32_t* term_component,
                             const double* term_coef, int32_t n_signals, const double* targets, int32_t targets_per_member,
                             const double* signal_weights, const double* time_weights, double* objective) {
+  const char* who = "signal_misfit_value";
   HIP_OK(hipSetDevice(h->device));
-  if (!h->have_fields || !h->have_params) { h->err = "signal_misfit_value: run forward first"; return 1; }
-  if (!objective) { h->err = "signal_misfit_value: objective is NULL"; return 1; }
+  if (int rc = need_fields(h, who, objective, "objective")) return rc;
   const SigTerms t{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
-  if (int rc = prepare_signal(h, "signal_misfit_value", t, targets, targets_per_member, signal_weights, time_weights, true)) return rc;
+  if (int rc = prepare_signal(h, who, t, targets, targets_per_member, signal_weights, time_weights, true)) return rc;
   if (int rc = launch_signal(h, nullptr, nullptr)) return rc;
-  HIP_OK(hipMemcpyAsync(objective, h->d_obj.p, sizeof(double) * h->pl.batch, hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipStreamSynchronize(h->stream));
-  HIP_OK(hipGetLastError());
-  return 0;
+  return download(h, {{objective, h->d_obj.p, sizeof(double) * h->pl.batch}});
 }
 
 int dfx_signal_misfit_value_and_grad(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block,
                                      const int32_t* term_component, const double* term_coef, int32_t n_signals, const double* targets,
                                      int32_t targets_per_member, const double* signal_weights, const double* time_weights, double* objective,
                                      const dfx_grads* want, dfx_grads* views, int32_t device_views, dfx_stats* stats) {
+  const char* who = "signal_misfit_value_and_grad";
   HIP_OK(hipSetDevice(h->device));
-  if (!h->have_traj || !h->have_fields) { h->err = "signal_misfit_value_and_grad: run forward with keep_trajectory=1 first"; return 1; }
-  if (h->ck->writer != h) { h->err = std::string("signal_misfit_value_and_grad: ") + kStaleCheckpoint; return 1; }
-  const Plan& pl = h->pl;
-  const size_t B = pl.batch, nb = pl.n_blocks;
-  const int Tn = (int)h->ts.size();
+  if (int rc = need_trajectory(h, who)) return rc;
+  const size_t B = h->pl.batch;
   const SigTerms t{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
-  if (int rc = prepare_signal(h, "signal_misfit_value_and_grad", t, targets, targets_per_member, signal_weights, time_weights, true)) return rc;
-  if (ensure_adjoint_buffers(h)) return 2;
-  HIP_OK(h->d_G.ensure(B * Tn * nb * 6));
-  if (objective) HIP_OK(h->obj_stage.ensure(sizeof(double) * B));
-  // as dfx_objective_value_and_grad: what the sweep consults on the handle for this call is taken back on every way out
-  struct Scope {
-    dfx_handle* h;
-    ~Scope() { h->obj_job = nullptr; h->obj_centroids = false; h->device_views = false; }
-  } scope{h};
-  ObjJob job;
-  job.kind = kObjSignal; job.n_act = h->sig.n_set; job.w_stride = job.lever_stride = 0; job.has_tau = h->sig.has_tau;
-  h->obj_centroids = false;
-  h->obj_job = &job;
-  h->device_views = device_views != 0;
-  set_grad_wishes(h, want);
-  if (zero_grad_accumulators(h, h->d_G.p, B * Tn * nb * 6, (int)h->segs.size())) return 2;
-  if (int rc = launch_signal(h, h->d_G.p, objective ? reinterpret_cast<double*>(h->obj_stage.p) : nullptr)) return rc;
-  if (int rc = run_adjoint(h, want, nullptr, views, stats, false, 0, true)) return rc;
+  if (int rc = prepare_signal(h, who, t, targets, targets_per_member, signal_weights, time_weights, true)) return rc;
+  if (int rc = objective_sweep(h, signal_job(h, kObjSignal, h->sig.has_tau), false, objective ? sizeof(double) * B : 0,
+                               [&](double* G, double* host) { return launch_signal(h, G, host); }, want, views, device_views, stats))
+    return rc;
   if (objective) memcpy(objective, h->obj_stage.p, sizeof(double) * B);
   return 0;
 }
 
-namespace {
-
-// What the gradient entries of the signal projections and of the signal cross-correlation share behind their own prepare_*: the buffers of
-// the sweep, a signal job of `kind` behind it (k_signal_explicit), `launch(G, host)` for the value and the cotangent (host: n_host doubles
-// of pinned memory the launch may fill, null when n_host == 0; the caller reads h->obj_stage after a return of 0), then the sweep itself --
-// want / views / device_views / stats, every sweep form and checkpoint level, the kept steps of an adaptive solve.
-template <class Launch>
-int signal_job_sweep(dfx_handle* h, int kind, size_t n_host, Launch&& launch, const dfx_grads* want, dfx_grads* views, int32_t device_views,
-                     dfx_stats* stats) {
-  const Plan& pl = h->pl;
-  const size_t B = pl.batch, nb = pl.n_blocks;
-  const int Tn = (int)h->ts.size();
-  if (ensure_adjoint_buffers(h)) return 2;
-  HIP_OK(h->d_G.ensure(B * Tn * nb * 6));
-  if (n_host) HIP_OK(h->obj_stage.ensure(sizeof(double) * n_host));
-  // as dfx_objective_value_and_grad: what the sweep consults on the handle for this call is taken back on every way out
-  struct Scope {
-    dfx_handle* h;
-    ~Scope() { h->obj_job = nullptr; h->obj_centroids = false; h->device_views = false; }
-  } scope{h};
-  ObjJob job;
-  job.kind = kind; job.n_act = h->sig.n_set; job.w_stride = job.lever_stride = 0; job.has_tau = false;
-  h->obj_centroids = false;
-  h->obj_job = &job;
-  h->device_views = device_views != 0;
-  set_grad_wishes(h, want);
-  if (zero_grad_accumulators(h, h->d_G.p, B * Tn * nb * 6, (int)h->segs.size())) return 2;
-  if (int rc = launch(h->d_G.p, n_host ? reinterpret_cast<double*>(h->obj_stage.p) : nullptr)) return rc;
-  return run_adjoint(h, want, nullptr, views, stats, false, 0, true);
-}
-
-}  // namespace
-
 int dfx_signal_projections(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block, const int32_t* term_component,
                            const double* term_coef, int32_t n_signals, const double* basis, int32_t n_rows, double* values) {
+  const char* who = "signal_projections";
   HIP_OK(hipSetDevice(h->device));
-  if (!h->have_fields || !h->have_params) { h->err = "signal_projections: run forward first"; return 1; }
-  if (!values) { h->err = "signal_projections: values is NULL"; return 1; }
+  if (int rc = need_fields(h, who, values, "values")) return rc;
   const SigTerms t{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
-  if (int rc = prepare_projection(h, "signal_projections", t, basis, n_rows, nullptr, nullptr, 0, false)) return rc;
+  if (int rc = prepare_projection(h, who, t, basis, n_rows, nullptr, nullptr, 0, false)) return rc;
   if (int rc = launch_projection(h, nullptr, nullptr)) return rc;
-  HIP_OK(hipMemcpyAsync(values, h->d_proj_P.p, sizeof(double) * h->pl.batch * (size_t)n_signals * (size_t)n_rows, hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipStreamSynchronize(h->stream));
-  HIP_OK(hipGetLastError());
-  return 0;
+  return download(h, {{values, h->d_proj_P.p, sizeof(double) * h->pl.batch * (size_t)n_signals * (size_t)n_rows}});
 }
 
 int dfx_signal_projection_value(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block,
                                 const int32_t* term_component, const double* term_coef, int32_t n_signals, const double* basis, int32_t n_rows,
                                 const double* row_weights, const double* targets, int32_t targets_per_member, double* objective) {
+  const char* who = "signal_projection_value";
   HIP_OK(hipSetDevice(h->device));
-  if (!h->have_fields || !h->have_params) { h->err = "signal_projection_value: run forward first"; return 1; }
-  if (!objective) { h->err = "signal_projection_value: objective is NULL"; return 1; }
+  if (int rc = need_fields(h, who, objective, "objective")) return rc;
   const SigTerms t{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
-  if (int rc = prepare_projection(h, "signal_projection_value", t, basis, n_rows, row_weights, targets, targets_per_member, true)) return rc;
+  if (int rc = prepare_projection(h, who, t, basis, n_rows, row_weights, targets, targets_per_member, true)) return rc;
   if (int rc = launch_projection(h, nullptr, nullptr)) return rc;
-  HIP_OK(hipMemcpyAsync(objective, h->d_obj.p, sizeof(double) * h->pl.batch, hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipStreamSynchronize(h->stream));
-  HIP_OK(hipGetLastError());
-  return 0;
+  return download(h, {{objective, h->d_obj.p, sizeof(double) * h->pl.batch}});
 }
 
 int dfx_signal_projection_value_and_grad(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block,
                                          const int32_t* term_component, const double* term_coef, int32_t n_signals, const double* basis,
                                          int32_t n_rows, const double* row_weights, const double* targets, int32_t targets_per_member,
                                          double* objective, const dfx_grads* want, dfx_grads* views, int32_t device_views, dfx_stats* stats) {
+  const char* who = "signal_projection_value_and_grad";
   HIP_OK(hipSetDevice(h->device));
-  if (!h->have_traj || !h->have_fields) { h->err = "signal_projection_value_and_grad: run forward with keep_trajectory=1 first"; return 1; }
-  if (h->ck->writer != h) { h->err = std::string("signal_projection_value_and_grad: ") + kStaleCheckpoint; return 1; }
+  if (int rc = need_trajectory(h, who)) return rc;
   const size_t B = h->pl.batch;
   const SigTerms t{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
-  if (int rc = prepare_projection(h, "signal_projection_value_and_grad", t, basis, n_rows, row_weights, targets, targets_per_member, true)) return rc;
-  if (int rc = signal_job_sweep(h, kObjProject, objective ? B : 0, [&](double* G, double* host) { return launch_projection(h, G, host); }, want, views,
-                                device_views, stats))
+  if (int rc = prepare_projection(h, who, t, basis, n_rows, row_weights, targets, targets_per_member, true)) return rc;
+  if (int rc = objective_sweep(h, signal_job(h, kObjProject, false), false, objective ? sizeof(double) * B : 0,
+                               [&](double* G, double* host) { return launch_projection(h, G, host); }, want, views, device_views, stats))
     return rc;
   if (objective) memcpy(objective, h->obj_stage.p, sizeof(double) * B);
   return 0;
@@ -986,17 +876,14 @@ int dfx_signal_xcorr(dfx_handle* h, int32_t n_terms, const int32_t* term_signal,
                      const double* term_coef, int32_t n_signals, int32_t n_pairs, const int32_t* pair_a, const int32_t* pair_b,
                      const double* templates, int32_t n_templates, int32_t templates_per_member, int32_t max_lag, int32_t normalisation,
                      double* values) {
+  const char* who = "signal_xcorr";
   HIP_OK(hipSetDevice(h->device));
-  if (!h->have_fields || !h->have_params) { h->err = "signal_xcorr: run forward first"; return 1; }
-  if (!values) { h->err = "signal_xcorr: values is NULL"; return 1; }
+  if (int rc = need_fields(h, who, values, "values")) return rc;
   const SigTerms t{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
   const XcorrCall q{n_pairs, pair_a, pair_b, templates, n_templates, templates_per_member, max_lag, normalisation, false, 0, 0, 1.0, 1.0, 0.0, 0.0};
-  if (int rc = prepare_xcorr(h, "signal_xcorr", t, q)) return rc;
+  if (int rc = prepare_xcorr(h, who, t, q)) return rc;
   if (int rc = launch_xcorr(h, nullptr, nullptr)) return rc;
-  HIP_OK(hipMemcpyAsync(values, xcorr_args(h).rho, sizeof(double) * h->pl.batch * (2 * (size_t)max_lag + 1), hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipStreamSynchronize(h->stream));
-  HIP_OK(hipGetLastError());
-  return 0;
+  return download(h, {{values, xcorr_args(h).rho, sizeof(double) * h->pl.batch * (2 * (size_t)max_lag + 1)}});
 }
 
 int dfx_signal_xcorr_value(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block,
@@ -1004,22 +891,17 @@ int dfx_signal_xcorr_value(dfx_handle* h, int32_t n_terms, const int32_t* term_s
                            const int32_t* pair_b, const double* templates, int32_t n_templates, int32_t templates_per_member, int32_t max_lag,
                            int32_t normalisation, int32_t reduce, int32_t lag0, double beta, double w_peak, double w_delay,
                            double delay_target, double* objective, double* peak, double* delay) {
+  const char* who = "signal_xcorr_value";
   HIP_OK(hipSetDevice(h->device));
-  if (!h->have_fields || !h->have_params) { h->err = "signal_xcorr_value: run forward first"; return 1; }
-  if (!objective) { h->err = "signal_xcorr_value: objective is NULL"; return 1; }
+  if (int rc = need_fields(h, who, objective, "objective")) return rc;
   const SigTerms t{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
   const XcorrCall q{n_pairs, pair_a, pair_b, templates, n_templates, templates_per_member, max_lag, normalisation, true, reduce, lag0, beta, w_peak,
                     w_delay, delay_target};
-  if (int rc = prepare_xcorr(h, "signal_xcorr_value", t, q)) return rc;
+  if (int rc = prepare_xcorr(h, who, t, q)) return rc;
   if (int rc = launch_xcorr(h, nullptr, nullptr)) return rc;
-  const size_t B = h->pl.batch;
+  const size_t bytes = sizeof(double) * h->pl.batch;
   const XcorrArgs x = xcorr_args(h);
-  HIP_OK(hipMemcpyAsync(objective, h->d_obj.p, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
-  if (peak) HIP_OK(hipMemcpyAsync(peak, x.peak, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
-  if (delay) HIP_OK(hipMemcpyAsync(delay, x.delay, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipStreamSynchronize(h->stream));
-  HIP_OK(hipGetLastError());
-  return 0;
+  return download(h, {{objective, h->d_obj.p, bytes}, {peak, x.peak, bytes}, {delay, x.delay, bytes}});
 }
 
 int dfx_signal_xcorr_value_and_grad(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block,
@@ -1028,17 +910,17 @@ int dfx_signal_xcorr_value_and_grad(dfx_handle* h, int32_t n_terms, const int32_
                                     int32_t templates_per_member, int32_t max_lag, int32_t normalisation, int32_t reduce, int32_t lag0,
                                     double beta, double w_peak, double w_delay, double delay_target, double* objective, double* peak,
                                     double* delay, const dfx_grads* want, dfx_grads* views, int32_t device_views, dfx_stats* stats) {
+  const char* who = "signal_xcorr_value_and_grad";
   HIP_OK(hipSetDevice(h->device));
-  if (!h->have_traj || !h->have_fields) { h->err = "signal_xcorr_value_and_grad: run forward with keep_trajectory=1 first"; return 1; }
-  if (h->ck->writer != h) { h->err = std::string("signal_xcorr_value_and_grad: ") + kStaleCheckpoint; return 1; }
+  if (int rc = need_trajectory(h, who)) return rc;
   const size_t B = h->pl.batch;
   const SigTerms t{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
   const XcorrCall q{n_pairs, pair_a, pair_b, templates, n_templates, templates_per_member, max_lag, normalisation, true, reduce, lag0, beta, w_peak,
                     w_delay, delay_target};
-  if (int rc = prepare_xcorr(h, "signal_xcorr_value_and_grad", t, q)) return rc;
+  if (int rc = prepare_xcorr(h, who, t, q)) return rc;
   const bool any = objective || peak || delay;
-  if (int rc = signal_job_sweep(h, kObjXcorr, any ? 3 * B : 0, [&](double* G, double* host) { return launch_xcorr(h, G, host); }, want, views,
-                                device_views, stats))
+  if (int rc = objective_sweep(h, signal_job(h, kObjXcorr, false), false, any ? sizeof(double) * 3 * B : 0,
+                               [&](double* G, double* host) { return launch_xcorr(h, G, host); }, want, views, device_views, stats))
     return rc;
   const double* st = reinterpret_cast<const double*>(h->obj_stage.p);      // J | M | delta
   if (objective) memcpy(objective, st, sizeof(double) * B);

@@ -828,6 +828,19 @@ class DynamicSolver:
                         out[m, i] = float(np.vdot(g, rate))
         return out[0] if (B == 1 and ts.ndim == 1) else out
 
+    def _raw_which(self, which, centroids=False):
+        """The parameter groups a raw-gradient call asks the engine for: no ``void_angle0`` without the angle contact, ``block_centroids``
+        added with the distance contact (``centroids``: on every lattice -- the angular-momentum objective)."""
+        which = tuple(w for w in which if not (w == "void_angle0" and self.spec.contact != _b.CONTACT_ANGLE))
+        if (self.spec.contact == _b.CONTACT_DISTANCE or centroids) and "block_centroids" not in which:
+            which = which + ("block_centroids",)
+        return which
+
+    def _take_stats(self, result):
+        """An engine result that ends with the stats of its reverse sweep: those kept as ``adjoint_stats``, the rest returned."""
+        self.adjoint_stats = result[-1]
+        return result[:-1]
+
     def vjp_raw(self, fields_bar, which=("centroid_node_vectors", "void_angle0", "inertia")):
         """Reverse sweep for a cotangent of the fields, returning the engine's raw gradient arrays (batch-leading) of the requested
         parameter groups only -- by default what a design reaches.  Asking for every ControlParams leaf (``vjp``) runs the reverse
@@ -837,18 +850,13 @@ class DynamicSolver:
         fb = np.asarray(fields_bar, dtype=float)
         if fb.ndim == 4:
             fb = fb[None]
-        which = tuple(w for w in which if not (w == "void_angle0" and self.spec.contact != _b.CONTACT_ANGLE))
-        if self.spec.contact == _b.CONTACT_DISTANCE and "block_centroids" not in which:
-            which = which + ("block_centroids",)
-        grads, stats = self.engine.adjoint(fb, which=which)
-        self.adjoint_stats = stats
-        return grads
+        which = self._raw_which(which)
+        return self._take_stats(self.engine.adjoint(fb, which=which))[0]
 
     def kinetic_energy_value_and_vjp(self, target_blocks):
         """objective = sum_t sum_{b in target} m v^2/2 (energy.py:494-499 over problems/quads_focusing.py:461-467),
         evaluated and differentiated on the device (one engine call: the objective rides along with the reverse sweep)."""
-        obj, grads, stats = self.engine.kinetic_value_and_grad(target_blocks)
-        self.adjoint_stats = stats
+        obj, grads = self._take_stats(self.engine.kinetic_value_and_grad(target_blocks))
         grads = {k: np.array(v) for k, v in grads.items()}      # the gradient tree outlives the engine's result area
         trees, s0 = self._unflatten_grads(grads, None)
         return (obj[0] if self.batch == 1 else obj), trees, s0
@@ -858,12 +866,8 @@ class DynamicSolver:
         read-only views of the engine's pinned result area, valid until the next call on this solver.
         The maps from these to a design (void-angle and inertia chain rules, lattice map) are linear in the cotangent, so a
         caller that sums several solves of ONE design (multi-input problems) applies them once to the sum."""
-        which = tuple(w for w in which if not (w == "void_angle0" and self.spec.contact != _b.CONTACT_ANGLE))
-        if self.spec.contact == _b.CONTACT_DISTANCE and "block_centroids" not in which:
-            which = which + ("block_centroids",)
-        obj, grads, stats = self.engine.kinetic_value_and_grad(target_blocks, which=which)
-        self.adjoint_stats = stats
-        return obj, grads
+        which = self._raw_which(which)
+        return self._take_stats(self.engine.kinetic_value_and_grad(target_blocks, which=which))
 
     def objective_value(self, spec):
         """(batch,) value of a weighted objective (``objective.ObjectiveSpec``) on the device-resident history of the last solve."""
@@ -875,13 +879,9 @@ class DynamicSolver:
         and the explicit inertia / block-centroid terms are already in the raw gradients returned (``block_centroids`` is added to
         ``which`` for the angular kind: its levers contain the centroids)."""
         from .objective import ANGULAR_MOMENTUM
-        which = tuple(w for w in which if not (w == "void_angle0" and self.spec.contact != _b.CONTACT_ANGLE))
-        if (self.spec.contact == _b.CONTACT_DISTANCE or spec.kind == ANGULAR_MOMENTUM) and "block_centroids" not in which:
-            which = which + ("block_centroids",)
-        obj, grads, stats = self.engine.objective_value_and_grad(spec.kind, spec.block_weights, spec.time_weights, spec.lever0, which=which,
-                                                                 device=device)
-        self.adjoint_stats = stats
-        return obj, grads
+        which = self._raw_which(which, centroids=spec.kind == ANGULAR_MOMENTUM)
+        return self._take_stats(self.engine.objective_value_and_grad(spec.kind, spec.block_weights, spec.time_weights, spec.lever0, which=which,
+                                                                     device=device))
 
     def strain_objective_value(self, spec):
         """(batch,) value of a weighted ligament strain-energy objective (``objective.StrainObjectiveSpec``) on the device-resident history
@@ -894,12 +894,9 @@ class DynamicSolver:
         of the reverse sweep, and the explicit node-vector, void-angle and (when ``which`` names ``reference_vector`` / ``k_bond`` /
         ``contact``) per-ligament terms are already in the raw gradients returned.  As with :meth:`vjp_raw`, ``fn_params`` holds what the
         sweep accumulates: the direct dependence of a prescribed output DOF on its drive is not in it."""
-        which = tuple(w for w in which if not (w == "void_angle0" and self.spec.contact != _b.CONTACT_ANGLE))
-        if self.spec.contact == _b.CONTACT_DISTANCE and "block_centroids" not in which:
-            which = which + ("block_centroids",)
-        obj, grads, stats = self.engine.strain_objective_value_and_grad(spec.bond_weights, spec.time_weights, spec.parts, which=which, device=device)
-        self.adjoint_stats = stats
-        return obj, grads
+        which = self._raw_which(which)
+        return self._take_stats(self.engine.strain_objective_value_and_grad(spec.bond_weights, spec.time_weights, spec.parts, which=which,
+                                                                            device=device))
 
     def peak_strain_value(self, spec):
         """(J, peak, peak_at) of a peak ligament-strain measure (``objective.PeakStrainSpec``) on the device-resident history of the last
@@ -914,13 +911,9 @@ class DynamicSolver:
         vector terms are already in the raw gradients returned.  The coefficients of the spec are constants: the ``reference_vector``
         gradient does not see how ``objective.strain_limit_coefficients`` derived them from l0.  As with :meth:`vjp_raw`, ``fn_params``
         holds what the sweep accumulates: the direct dependence of a prescribed output DOF on its drive is not in it."""
-        which = tuple(w for w in which if not (w == "void_angle0" and self.spec.contact != _b.CONTACT_ANGLE))
-        if self.spec.contact == _b.CONTACT_DISTANCE and "block_centroids" not in which:
-            which = which + ("block_centroids",)
-        out, grads, stats = self.engine.strain_peak_value_and_grad(spec.bond_coef, spec.bond_weights, spec.time_weights, spec.aggregate,
-                                                                   spec.sharpness, which=which, device=device)
-        self.adjoint_stats = stats
-        return out, grads
+        which = self._raw_which(which)
+        return self._take_stats(self.engine.strain_peak_value_and_grad(spec.bond_coef, spec.bond_weights, spec.time_weights, spec.aggregate,
+                                                                       spec.sharpness, which=which, device=device))
 
     def signal_values(self, spec):
         """(batch, T, n_signals) signals of an ``objective.SignalSpec`` on the device-resident history of the last solve (any forward
@@ -938,13 +931,9 @@ class DynamicSolver:
         onto the fields are formed in HBM; the mixed second derivatives of the force terms (node vectors, void angles and, when ``which``
         names them, ``reference_vector`` / ``k_bond`` / ``contact``) are already in the raw gradients returned.  As with :meth:`vjp_raw`,
         ``fn_params`` holds what the sweep accumulates: the direct dependence of a prescribed output DOF on its drive is not in it."""
-        which = tuple(w for w in which if not (w == "void_angle0" and self.spec.contact != _b.CONTACT_ANGLE))
-        if self.spec.contact == _b.CONTACT_DISTANCE and "block_centroids" not in which:
-            which = which + ("block_centroids",)
-        obj, grads, stats = self.engine.signal_misfit_value_and_grad(spec.terms, spec.n_signals, spec.targets, spec.omega, spec.tau, which=which,
-                                                                     device=device)
-        self.adjoint_stats = stats
-        return obj, grads
+        which = self._raw_which(which)
+        return self._take_stats(self.engine.signal_misfit_value_and_grad(spec.terms, spec.n_signals, spec.targets, spec.omega, spec.tau,
+                                                                         which=which, device=device))
 
     def signal_projections(self, spec):
         """(batch, n_signals, n_rows) projections of the signals of an ``objective.ProjectionSpec`` on the rows of its time basis, on the
@@ -959,13 +948,9 @@ class DynamicSolver:
         """The projection objective (``objective.ProjectionSpec``) of the last kept solve, evaluated and differentiated on the device
         beside :meth:`signal_misfit_value_and_raw`: the time reduction and the cotangent on the signals are formed in HBM; what follows
         (the Hessian-vector product of force terms, their mixed second derivatives, what ``fn_params`` holds) is that method's."""
-        which = tuple(w for w in which if not (w == "void_angle0" and self.spec.contact != _b.CONTACT_ANGLE))
-        if self.spec.contact == _b.CONTACT_DISTANCE and "block_centroids" not in which:
-            which = which + ("block_centroids",)
-        obj, grads, stats = self.engine.signal_projection_value_and_grad(spec.signal_spec.terms, spec.signal_spec.n_signals, spec.basis,
-                                                                         spec.row_weights, spec.targets, which=which, device=device)
-        self.adjoint_stats = stats
-        return obj, grads
+        which = self._raw_which(which)
+        return self._take_stats(self.engine.signal_projection_value_and_grad(spec.signal_spec.terms, spec.signal_spec.n_signals, spec.basis,
+                                                                             spec.row_weights, spec.targets, which=which, device=device))
 
     @staticmethod
     def _xcorr_kwargs(spec):
@@ -987,13 +972,10 @@ class DynamicSolver:
         device beside :meth:`signal_projection_value_and_raw`: the correlation over the lags, its reduction to a peak and a delay and the
         cotangent on the signals are formed in HBM; what follows is :meth:`signal_misfit_value_and_raw`'s.  Returns
         ((J, peak, delay), raw gradients)."""
-        which = tuple(w for w in which if not (w == "void_angle0" and self.spec.contact != _b.CONTACT_ANGLE))
-        if self.spec.contact == _b.CONTACT_DISTANCE and "block_centroids" not in which:
-            which = which + ("block_centroids",)
-        obj, peak, delay, grads, stats = self.engine.signal_xcorr_value_and_grad(spec.signal_spec.terms, spec.signal_spec.n_signals, spec.pairs,
-                                                                                 spec.max_lag, which=which, device=device, **self._xcorr_kwargs(spec))
-        self.adjoint_stats = stats
-        return (obj, peak, delay), grads
+        which = self._raw_which(which)
+        *out, grads = self._take_stats(self.engine.signal_xcorr_value_and_grad(spec.signal_spec.terms, spec.signal_spec.n_signals, spec.pairs,
+                                                                               spec.max_lag, which=which, device=device, **self._xcorr_kwargs(spec)))
+        return tuple(out), grads
 
     @staticmethod
     def _bond_params_bar(bp, kb, refv_bar, like):

@@ -1105,68 +1105,61 @@ class PeakLigamentStrain:
         return (c, grads) if many else (float(c[0]), grads[0])
 
 
-class TargetSignalMisfit:
-    """objective(design) = 1/2 sum_k tau_k sum_s omega_s (S_ks(design) - Starget_ks)^2 for an ``objective.SignalSpec``: signals that are
-    linear combinations of displacement, velocity and elastic-force components of blocks against target histories -- waveform shaping, a
-    calibration against tracked block motions, a reaction force against a measured one.  A list of designs runs as one ensemble (targets
-    (T, n_signals) shared or (len(designs), T, n_signals); ``run_ensemble_optimization`` accepts the class) on the device
-    (``dfx_signal_misfit_value_and_grad``); one design takes the host path -- signals of field components only: the history is downloaded
-    and the cotangent built in NumPy -- unless ``on_device``.  Force components have no host path."""
+class _SignalTarget:
+    """What ``TargetSignalMisfit``, ``TargetSignalProjection`` and ``TargetCrossCorrelation`` share: the range check of the terms, a list
+    of designs as ensembles of ``forward.batch`` on the device, one design on the host, the return shapes.  Per class: ``_per_member``
+    (the spec's array that may carry one entry per design), ``_chunk_spec``, ``_first`` (the spec cut to the first member's entry, for one
+    design), ``_device_value`` -> (values, raw gradients or None) and ``_host_value`` -> (value, cotangent of the fields)."""
+    _cut_on_device = False
 
     def __init__(self, forward, spec):
         self.forward, self.spec = forward, spec
-        if spec.targets is None:
-            raise ValueError("TargetSignalMisfit: the SignalSpec has no targets")
         if not getattr(forward, "is_setup", False):
             forward.setup()
         nb = forward.geometry.n_blocks
-        if max(b for _, b, _, _ in spec.terms) >= nb:
-            raise ValueError(f"TargetSignalMisfit: a term names a block out of range [0, {nb})")
+        if max(b for _, b, _, _ in getattr(spec, "signal_spec", spec).terms) >= nb:
+            raise ValueError(f"{type(self).__name__}: a term names a block out of range [0, {nb})")
 
-    def _chunk_spec(self, i, n):
-        """the spec of designs i .. i + n of a longer list (per-member targets are cut alike)"""
-        sp = self.spec
-        return sp if sp.targets.ndim == 2 else sp.with_targets(sp.targets[i:i + n], sp.omega, sp.tau)
+    def _first(self, sp):
+        return sp
+
+    def _gather(self, chunks):
+        pass
 
     def _device(self, design, grad):
-        fw = self.forward
+        fw, sp = self.forward, self.spec
         many = isinstance(design, list)
-        if many and self.spec.targets.ndim == 3 and len(self.spec.targets) != len(design):
-            raise ValueError(f"{len(design)} designs against targets for {len(self.spec.targets)} members")
+        per = getattr(sp, self._per_member)
+        if many and per is not None and per.ndim == 3 and len(per) != len(design):
+            raise ValueError(f"{len(design)} designs against {self._per_member} for {len(per)} members")
         if many and len(design) != fw.batch:
             if len(design) == 0 or len(design) % fw.batch:
                 raise ValueError(f"{len(design)} designs for a forward problem built with batch={fw.batch}: pass batch designs, or a multiple of it")
-            parts = [TargetSignalMisfit(fw, self._chunk_spec(i, fw.batch))._device(design[i:i + fw.batch], grad) for i in range(0, len(design), fw.batch)]
+            chunks = [type(self)(fw, self._chunk_spec(i, fw.batch)) for i in range(0, len(design), fw.batch)]
+            parts = [c._device(design[i * fw.batch:(i + 1) * fw.batch], grad) for i, c in enumerate(chunks)]
+            self._gather(chunks)
             if not grad:
                 return np.concatenate(parts)
             return np.concatenate([p[0] for p in parts]), [g for p in parts for g in p[1]]
+        if not many and self._cut_on_device:
+            sp = self._first(sp)
         fw.solve(design, keep_trajectory=grad, want_fields=False)
-        if not grad:
-            obj = np.asarray(fw.solve_dynamics.signal_misfit_value(self.spec), dtype=float)
-            return obj if many else float(obj[0])
-        obj, raw = fw.solve_dynamics.signal_misfit_value_and_raw(self.spec)
-        grads = design_gradients(fw, design if many else [design], raw)
+        obj, raw = self._device_value(sp, many, grad)
         obj = np.asarray(obj, dtype=float)
+        if not grad:
+            return obj if many else float(obj[0])
+        grads = design_gradients(fw, design if many else [design], raw)
         return (obj, grads) if many else (float(obj[0]), grads[0])
 
     def _host(self, design, grad):
-        from .objective import host_signal_values
-        sp, fw = self.spec, self.forward
-        if sp.has_force:
-            raise ValueError("TargetSignalMisfit: force components are evaluated on the device only: pass on_device=True (or a list of designs)")
+        fw = self.forward
+        if getattr(self.spec, "signal_spec", self.spec).has_force:
+            raise ValueError(f"{type(self).__name__}: force components are evaluated on the device only: pass on_device=True (or a list of designs)")
+        sp = self._first(self.spec)
         sol = fw.solve(design, keep_trajectory=grad)
-        S = host_signal_values(sp, sol.fields)
-        T = S.shape[0]
-        tg = sp.targets if sp.targets.ndim == 2 else sp.targets[0]
-        tau = np.ones(T) if sp.tau is None else sp.tau
-        om = np.ones(sp.n_signals) if sp.omega is None else sp.omega
-        c = tau[:, None] * om[None, :] * (S - tg)
-        val = float(0.5 * np.sum(c * (S - tg)))
+        val, fb = self._host_value(sp, sol.fields, grad)
         if not grad:
             return val
-        fb = np.zeros_like(sol.fields)
-        for s, b, comp, coef in sp.terms:
-            fb[:, comp // 3, b, comp % 3] += coef * c[:, s]
         raw = {k: np.array(v, dtype=float) for k, v in fw.solve_dynamics.vjp_raw(fb).items()}
         return val, design_gradients(fw, [design], raw)[0]
 
@@ -1177,6 +1170,47 @@ class TargetSignalMisfit:
     def value_and_grad(self, design, on_device=False):
         """Return shapes as ``TargetKineticEnergy.value_and_grad``; only the parameter groups a design reaches are differentiated."""
         return self._device(design, True) if on_device or isinstance(design, list) else self._host(design, True)
+
+
+class TargetSignalMisfit(_SignalTarget):
+    """objective(design) = 1/2 sum_k tau_k sum_s omega_s (S_ks(design) - Starget_ks)^2 for an ``objective.SignalSpec``: signals that are
+    linear combinations of displacement, velocity and elastic-force components of blocks against target histories -- waveform shaping, a
+    calibration against tracked block motions, a reaction force against a measured one.  A list of designs runs as one ensemble (targets
+    (T, n_signals) shared or (len(designs), T, n_signals); ``run_ensemble_optimization`` accepts the class) on the device
+    (``dfx_signal_misfit_value_and_grad``); one design takes the host path -- signals of field components only: the history is downloaded
+    and the cotangent built in NumPy -- unless ``on_device``.  Force components have no host path."""
+
+    _per_member = "targets"
+
+    def __init__(self, forward, spec):
+        if spec.targets is None:
+            raise ValueError("TargetSignalMisfit: the SignalSpec has no targets")
+        super().__init__(forward, spec)
+
+    def _chunk_spec(self, i, n):
+        """the spec of designs i .. i + n of a longer list (per-member targets are cut alike)"""
+        sp = self.spec
+        return sp if sp.targets.ndim == 2 else sp.with_targets(sp.targets[i:i + n], sp.omega, sp.tau)
+
+    def _device_value(self, sp, many, grad):
+        sd = self.forward.solve_dynamics
+        return sd.signal_misfit_value_and_raw(sp) if grad else (sd.signal_misfit_value(sp), None)
+
+    def _host_value(self, sp, fields, grad):
+        from .objective import host_signal_values
+        S = host_signal_values(sp, fields)
+        T = S.shape[0]
+        tg = sp.targets if sp.targets.ndim == 2 else sp.targets[0]
+        tau = np.ones(T) if sp.tau is None else sp.tau
+        om = np.ones(sp.n_signals) if sp.omega is None else sp.omega
+        c = tau[:, None] * om[None, :] * (S - tg)
+        val = float(0.5 * np.sum(c * (S - tg)))
+        if not grad:
+            return val, None
+        fb = np.zeros_like(fields)
+        for s, b, comp, coef in sp.terms:
+            fb[:, comp // 3, b, comp % 3] += coef * c[:, s]
+        return val, fb
 
 
 class SignalCalibration:
@@ -1250,7 +1284,7 @@ class SignalCalibration:
         return levenberg_marquardt(fun, np.asarray(x0, dtype=float), lower=lower_bound, upper=upper_bound, max_evaluations=n_iterations)
 
 
-class TargetSignalProjection:
+class TargetSignalProjection(_SignalTarget):
     """objective(design) = 1/2 sum_s sum_j W_sj (P_sj(design) - Ptarget_sj)^2 with P_sj = sum_k B_jk S_ks for an
     ``objective.ProjectionSpec``: the signals of a ``SignalSpec`` projected on a few rows of a time basis -- band power, transmission at the
     drive frequency, harmonic generation, a matched filter.  Negative weights maximise.  Shaped as ``TargetSignalMisfit``: a list of
@@ -1258,62 +1292,23 @@ class TargetSignalProjection:
     accepts the class) on the device (``dfx_signal_projection_value_and_grad``); one design takes the host path -- field components only --
     unless ``on_device``.  Force components have no host path."""
 
-    def __init__(self, forward, spec):
-        self.forward, self.spec = forward, spec
-        if not getattr(forward, "is_setup", False):
-            forward.setup()
-        nb = forward.geometry.n_blocks
-        if max(b for _, b, _, _ in spec.signal_spec.terms) >= nb:
-            raise ValueError(f"TargetSignalProjection: a term names a block out of range [0, {nb})")
+    _per_member = "targets"
 
     def _chunk_spec(self, i, n):
         """the spec of designs i .. i + n of a longer list (per-member targets are cut alike)"""
         sp = self.spec
         return sp if sp.targets is None or sp.targets.ndim == 2 else sp.with_targets(sp.targets[i:i + n])
 
-    def _device(self, design, grad):
-        fw, sp = self.forward, self.spec
-        many = isinstance(design, list)
-        if many and sp.targets is not None and sp.targets.ndim == 3 and len(sp.targets) != len(design):
-            raise ValueError(f"{len(design)} designs against targets for {len(sp.targets)} members")
-        if many and len(design) != fw.batch:
-            if len(design) == 0 or len(design) % fw.batch:
-                raise ValueError(f"{len(design)} designs for a forward problem built with batch={fw.batch}: pass batch designs, or a multiple of it")
-            parts = [TargetSignalProjection(fw, self._chunk_spec(i, fw.batch))._device(design[i:i + fw.batch], grad)
-                     for i in range(0, len(design), fw.batch)]
-            if not grad:
-                return np.concatenate(parts)
-            return np.concatenate([p[0] for p in parts]), [g for p in parts for g in p[1]]
-        fw.solve(design, keep_trajectory=grad, want_fields=False)
-        if not grad:
-            obj = np.asarray(fw.solve_dynamics.signal_projection_value(sp), dtype=float)
-            return obj if many else float(obj[0])
-        obj, raw = fw.solve_dynamics.signal_projection_value_and_raw(sp)
-        grads = design_gradients(fw, design if many else [design], raw)
-        obj = np.asarray(obj, dtype=float)
-        return (obj, grads) if many else (float(obj[0]), grads[0])
+    def _first(self, sp):
+        return sp.with_targets(sp.targets[0]) if sp.targets is not None and sp.targets.ndim == 3 else sp
 
-    def _host(self, design, grad):
+    def _device_value(self, sp, many, grad):
+        sd = self.forward.solve_dynamics
+        return sd.signal_projection_value_and_raw(sp) if grad else (sd.signal_projection_value(sp), None)
+
+    def _host_value(self, sp, fields, grad):
         from .objective import host_projection_value_and_cotangent
-        sp, fw = self.spec, self.forward
-        if sp.signal_spec.has_force:
-            raise ValueError("TargetSignalProjection: force components are evaluated on the device only: pass on_device=True (or a list of designs)")
-        if sp.targets is not None and sp.targets.ndim == 3:
-            sp = sp.with_targets(sp.targets[0])
-        sol = fw.solve(design, keep_trajectory=grad)
-        val, fb = host_projection_value_and_cotangent(sp, sol.fields)
-        if not grad:
-            return val
-        raw = {k: np.array(v, dtype=float) for k, v in fw.solve_dynamics.vjp_raw(fb).items()}
-        return val, design_gradients(fw, [design], raw)[0]
-
-    def value(self, design, on_device=False):
-        """One design -> float, a list of designs -> (n,) array."""
-        return self._device(design, False) if on_device or isinstance(design, list) else self._host(design, False)
-
-    def value_and_grad(self, design, on_device=False):
-        """Return shapes as ``TargetKineticEnergy.value_and_grad``; only the parameter groups a design reaches are differentiated."""
-        return self._device(design, True) if on_device or isinstance(design, list) else self._host(design, True)
+        return host_projection_value_and_cotangent(sp, fields)
 
 
 def TargetBandPower(forward, block_dofs, kind, frequencies, weights, window=None):
@@ -1338,7 +1333,7 @@ def TargetBandPower(forward, block_dofs, kind, frequencies, weights, window=None
     return TargetSignalProjection(forward, ProjectionSpec(sig, fourier_basis(tp, f, window), w))
 
 
-class TargetCrossCorrelation:
+class TargetCrossCorrelation(_SignalTarget):
     """objective(design) = w_peak M(design) + 1/2 w_delay (delta(design) - delay_target)^2 for an ``objective.CorrelationSpec``: the peak
     M of the normalised cross-correlation of pairs of signals over time lags and the delay delta at which it occurs -- a pulse that keeps
     its shape at any delay, a chosen arrival time, a template at an unknown shift.  A negative ``w_peak`` maximises the correlation.
@@ -1347,69 +1342,35 @@ class TargetCrossCorrelation:
     the host path -- field components only -- unless ``on_device``.  Force components have no host path.  ``last_peak`` / ``last_delay``:
     M and delta of the last evaluation (floats for one design, (n,) arrays for a list)."""
 
+    _per_member = "templates"
+    _cut_on_device = True
+
     def __init__(self, forward, spec):
-        self.forward, self.spec = forward, spec
         self.last_peak = self.last_delay = None
-        if not getattr(forward, "is_setup", False):
-            forward.setup()
-        nb = forward.geometry.n_blocks
-        if max(b for _, b, _, _ in spec.signal_spec.terms) >= nb:
-            raise ValueError(f"TargetCrossCorrelation: a term names a block out of range [0, {nb})")
+        super().__init__(forward, spec)
 
     def _chunk_spec(self, i, n):
         """the spec of designs i .. i + n of a longer list (per-member templates are cut alike)"""
         sp = self.spec
         return sp if sp.templates is None or sp.templates.ndim == 2 else sp.with_templates(sp.templates[i:i + n])
 
-    def _device(self, design, grad):
-        fw, sp = self.forward, self.spec
-        many = isinstance(design, list)
-        if many and sp.templates is not None and sp.templates.ndim == 3 and len(sp.templates) != len(design):
-            raise ValueError(f"{len(design)} designs against templates for {len(sp.templates)} members")
-        if many and len(design) != fw.batch:
-            if len(design) == 0 or len(design) % fw.batch:
-                raise ValueError(f"{len(design)} designs for a forward problem built with batch={fw.batch}: pass batch designs, or a multiple of it")
-            chunks = [TargetCrossCorrelation(fw, self._chunk_spec(i, fw.batch)) for i in range(0, len(design), fw.batch)]
-            parts = [c._device(design[i * fw.batch:(i + 1) * fw.batch], grad) for i, c in enumerate(chunks)]
-            self.last_peak, self.last_delay = np.concatenate([c.last_peak for c in chunks]), np.concatenate([c.last_delay for c in chunks])
-            if not grad:
-                return np.concatenate(parts)
-            return np.concatenate([p[0] for p in parts]), [g for p in parts for g in p[1]]
-        if not many and sp.templates is not None and sp.templates.ndim == 3:
-            sp = sp.with_templates(sp.templates[0])
-        fw.solve(design, keep_trajectory=grad, want_fields=False)
-        if grad:
-            (obj, peak, delay), raw = fw.solve_dynamics.signal_xcorr_value_and_raw(sp)
-        else:
-            obj, peak, delay = fw.solve_dynamics.signal_xcorr_value(sp)
-        obj, peak, delay = (np.array(a, dtype=float) for a in (obj, peak, delay))
+    def _first(self, sp):
+        return sp.with_templates(sp.templates[0]) if sp.templates is not None and sp.templates.ndim == 3 else sp
+
+    def _gather(self, chunks):
+        self.last_peak, self.last_delay = np.concatenate([c.last_peak for c in chunks]), np.concatenate([c.last_delay for c in chunks])
+
+    def _device_value(self, sp, many, grad):
+        sd = self.forward.solve_dynamics
+        (obj, peak, delay), raw = sd.signal_xcorr_value_and_raw(sp) if grad else (sd.signal_xcorr_value(sp), None)
+        peak, delay = np.array(peak, dtype=float), np.array(delay, dtype=float)
         self.last_peak, self.last_delay = (peak, delay) if many else (float(peak[0]), float(delay[0]))
-        if not grad:
-            return obj if many else float(obj[0])
-        grads = design_gradients(fw, design if many else [design], raw)
-        return (obj, grads) if many else (float(obj[0]), grads[0])
+        return obj, raw
 
-    def _host(self, design, grad):
+    def _host_value(self, sp, fields, grad):
         from .objective import host_xcorr_value_and_cotangent
-        sp, fw = self.spec, self.forward
-        if sp.signal_spec.has_force:
-            raise ValueError("TargetCrossCorrelation: force components are evaluated on the device only: pass on_device=True (or a list of designs)")
-        if sp.templates is not None and sp.templates.ndim == 3:
-            sp = sp.with_templates(sp.templates[0])
-        sol = fw.solve(design, keep_trajectory=grad)
-        val, self.last_peak, self.last_delay, fb = host_xcorr_value_and_cotangent(sp, sol.fields)
-        if not grad:
-            return val
-        raw = {k: np.array(v, dtype=float) for k, v in fw.solve_dynamics.vjp_raw(fb).items()}
-        return val, design_gradients(fw, [design], raw)[0]
-
-    def value(self, design, on_device=False):
-        """One design -> float, a list of designs -> (n,) array."""
-        return self._device(design, False) if on_device or isinstance(design, list) else self._host(design, False)
-
-    def value_and_grad(self, design, on_device=False):
-        """Return shapes as ``TargetKineticEnergy.value_and_grad``; only the parameter groups a design reaches are differentiated."""
-        return self._device(design, True) if on_device or isinstance(design, list) else self._host(design, True)
+        val, self.last_peak, self.last_delay, fb = host_xcorr_value_and_cotangent(sp, fields)
+        return val, fb
 
 
 def TargetWaveDelay(forward, source_block_dofs, target_block_dofs, kind, max_lag, beta, delay_target_seconds=None, w_peak=-1.0, w_delay=0.0,
