@@ -71,7 +71,7 @@ COMM_EXPORTS = ["dfx_comm_unique_id", "dfx_comm_init", "dfx_comm_destroy", "dfx_
                 "dfx_mem_info", "dfx_device_synchronize", "dfx_kinetic_value_and_grad_device", "dfx_download", "dfx_forward_kinetic_value_and_grad",
                 "dfx_forward_tangent", "dfx_forward_tangent_dense", "dfx_dense_output_map", "dfx_forward_tangent_multi",
                 "dfx_forward_tangent_dense_multi", "dfx_rhs_jvp", "dfx_objective_value", "dfx_objective_value_and_grad",
-                "dfx_strain_objective_value", "dfx_strain_objective_value_and_grad", "dfx_signal_values", "dfx_signal_misfit_value",
+                "dfx_strain_objective_value", "dfx_strain_objective_value_and_grad", "dfx_signal_values", "dfx_signal_hinge_channels", "dfx_signal_misfit_value",
                 "dfx_signal_misfit_value_and_grad", "dfx_signal_projections", "dfx_signal_projection_value",
                 "dfx_signal_projection_value_and_grad", "dfx_forward_tangent_signals_multi", "dfx_forward_tangent_signals_dense_multi",
                 "dfx_signal_xcorr", "dfx_signal_xcorr_value", "dfx_signal_xcorr_value_and_grad", "dfx_strain_peak_value",
@@ -170,6 +170,8 @@ def declare(lib):
     if hasattr(lib, "dfx_signal_misfit_value_and_grad"):
         terms = [C.c_int32, _ip, _ip, _ip, _dp, C.c_int32]
         lib.dfx_signal_values.argtypes = [H] + terms + [_dp]
+    if hasattr(lib, "dfx_signal_hinge_channels"):
+        lib.dfx_signal_hinge_channels.argtypes = [H, C.c_int32]
         lib.dfx_signal_misfit_value.argtypes = [H] + terms + [_dp, C.c_int32, _dp, _dp, _dp]
         lib.dfx_signal_misfit_value_and_grad.argtypes = [H] + terms + [_dp, C.c_int32, _dp, _dp, _dp, C.POINTER(dfx_grads), C.POINTER(dfx_grads),
                                                                         C.c_int32, C.POINTER(dfx_stats)]
@@ -918,9 +920,17 @@ class Engine:
     def has_signal_misfit(self):
         return hasattr(self.lib, "dfx_signal_misfit_value_and_grad")
 
+    # ``hinge_channels = True`` opens the hinge components 9 + 3 node + dof to every entry that takes signal terms
+    # (``dfx_signal_hinge_channels``); off, the default, they are refused as out of range, as before the hinge channels existed
+    hinge_channels = False
+
     def _signal_terms(self, terms, n_signals):
         """The term arrays of ``dfx_signal_*``: ``terms`` is a sequence of (signal, block, component, coef)."""
         self._need("dfx_signal_misfit_value_and_grad", "signal misfit", self._STALE)
+        if self.hinge_channels:
+            self._need("dfx_signal_hinge_channels", "hinge-force signal channels", self._STALE)
+        if hasattr(self.lib, "dfx_signal_hinge_channels"):
+            self.lib.dfx_signal_hinge_channels(self._h, int(bool(self.hinge_channels)))
         t = np.asarray(terms, dtype=float).reshape(-1, 4)
         idx = [np.ascontiguousarray(t[:, i], dtype=np.int32) for i in range(3)]
         coef = np.ascontiguousarray(t[:, 3], dtype=np.float64)
@@ -940,7 +950,7 @@ class Engine:
 
     def signal_values(self, terms, n_signals):
         """(batch, T, n_signals) signals (``dfx_signal_values``) on the resident history of the last forward pass: linear combinations of
-        displacement (components 0..2), velocity (3..5) and elastic-force (6..8) components of blocks."""
+        displacement (components 0..2), velocity (3..5), elastic-force (6..8) and, with ``hinge_channels`` set, hinge-force (9 + 3 node + dof) components of blocks."""
         args, keep = self._signal_terms(terms, n_signals)
         out = np.zeros((self.batch, self.n_timepoints or 1, max(int(n_signals), 1)))       # (no forward pass yet: the library refuses before it writes)
         self._check(self.lib.dfx_signal_values(self._h, *args, _ptr(out)), "dfx_signal_values")

@@ -150,8 +150,9 @@ struct dfx_handle {
   // channels, the signals, their residual cotangents and the direction w of the call; sig: how many of each (the explicit terms behind the
   // sweep read it)
   DevBuf<int32_t> d_sig_tab;
+  bool sig_hinges = false;     // dfx_signal_hinge_channels: the term lists may hold hinge components (9 + 3 node + dof)
   DevBuf<double> d_sig_coef, d_sig_chan, d_sig_S, d_sig_c, d_sig_w;
-  struct SigJob { int n_fb = 0, n_set = 0, n_sig = 0, n_uc = 0, n_terms = 0, n_blocks = 0; bool has_target = false, has_omega = false, has_tau = false;
+  struct SigJob { int n_fb = 0, n_set = 0, n_sig = 0, n_uc = 0, n_terms = 0, n_blocks = 0, n_hg = 0; bool has_target = false, has_omega = false, has_tau = false;
                   long long target_stride = 0; } sig;
   // dfx_signal_projection* (engine_objective.hip): basis | row weights | targets of the call and the projections P; proj: their layout
   DevBuf<double> d_proj_coef, d_proj_P;
@@ -314,10 +315,12 @@ int run_adjoint(dfx_handle* h, const dfx_grads* want, dfx_grads* grads, dfx_grad
 void launch_objective_explicit(dfx_handle* h, const DevCtx& c);
 // engine_objective.hip: the term list of a signal call (dfx_signal_*, dfx_forward_tangent_signals_*), checked (return 1 with h->err: a
 // signal, block or component out of range, an empty signal, a non-finite coefficient, force components with the distance-based contact or
-// with extra ligaments) and compacted: the force blocks, their index by block, the set, and the terms by signal in list order
+// with extra ligaments; a hinge component 9 + 3 n + d whose node n the lattice does not have or whose slot carries no ligament) and
+// compacted: the force blocks, their index by block, the listed hinges (slots, ascending) and their index by slot (empty without hinge
+// terms), the set, and the terms by signal in list order.  Channels: block j of fblocks holds 3 j + d, hinge i of hslots 3 (n_fb + i) + d
 struct SigTerms { int32_t n; const int32_t *signal, *block, *comp; const double* coef; int32_t n_signals; };
 struct SigTables {
-  std::vector<int32_t> fblocks, fmap, set, sig_ptr, term_src;
+  std::vector<int32_t> fblocks, fmap, hslots, hmap, set, sig_ptr, term_src;
   std::vector<double> term_coef;
 };
 int signal_term_tables(dfx_handle* h, const char* who, const SigTerms& t, SigTables& out);

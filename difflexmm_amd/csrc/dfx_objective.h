@@ -42,6 +42,14 @@
 //   k_signal_explicit   after the sweep: one lane per (member, slot of the set), output times in order: the epsilon parts of dE/d(node
 //                       vector) into g_r, of dE/dphi1 (end-0 slot) / dE/dphi2 (end-1 slot) into g_phi, and on end-0 slots of dE/d(reference
 //                       vector, stiffnesses, contact constants) into g_b when the call collects them
+// HINGE channels (components 9 + 3 n + d): dE_h/d(x, y, theta)_b of ONE ligament, the one on node n of block b -- the summand that
+// k_signal_channels adds over a block's four slots.  The listed hinges extend the channel space behind the block channels: a (member, output)
+// row of chan and of w holds n_fb * 3 block entries, then n_hg * 3 hinge entries.  The set also holds the two end blocks of every listed hinge.
+//   k_signal_hinge_channels  one lane per (output k, listed hinge): the own side of that ligament, nothing summed across lanes
+//   the cotangent of a hinge direction w_h is Hess(E_h) w_h on both end blocks: in k_signal_cotangent / k_signal_explicit the lane on the
+//   hinge's own slot adds w_h to its own-block seed and the lane on the partner slot adds it to its partner-block seed (signal_seed_hinge;
+//   the seeds are linear) -- still one evaluation per lane, the quad sum and lane 0's store as before, so two hinges of a block never
+//   meet in a row of G from two lanes.  A call without hinge terms takes none of these branches: the arithmetic of the parent, bit for bit.
 //
 // The signal projections (dfx_signal_projections, dfx_signal_projection_value[_and_grad]): the same signals projected on n_rows rows of a
 // time basis B shared by the members, P_msj = sum_k B_jk S_mks, J_m = 1/2 sum_s sum_j W_sj (P_msj - Ptarget_msj)^2.  S comes from
@@ -323,7 +331,9 @@ struct SigArgs {
   const double* fields;       // batch * T * n_blocks*6
   const int32_t* fblocks;     // n_fb force blocks
   const int32_t* fmap;        // n_blocks: index of the block in fblocks, or -1
-  const int32_t* set;         // n_set blocks: force blocks and the blocks bonded to them
+  const int32_t* set;         // n_set blocks: force blocks and the blocks bonded to them, and both end blocks of every listed hinge
+  const int32_t* hslots;      // n_hg listed hinges: the slot block * 4 + node of each (null when n_hg == 0)
+  const int32_t* hmap;        // n_slots: index of the slot in hslots, or -1 (null when n_hg == 0)
   const int32_t* sig_ptr;     // n_sig + 1: the terms of signal s, in list order
   const int32_t* term_src;    // >= 0: offset of a field component inside one output time of the history; < 0: -(1 + channel)
   const double* term_coef;
@@ -334,9 +344,10 @@ struct SigArgs {
   const double* target;       // (T, n_sig), members target_stride apart (0: shared); null: signal values only
   const double* omega;        // n_sig or null
   const double* tau;          // T or null
-  double *chan, *S, *cres, *w;  // batch * T * (n_fb*3 | n_sig | n_sig | n_fb*3)
+  double *chan, *S, *cres, *w;  // batch * T * (n_ch | n_sig | n_sig | n_ch)
   long long target_stride;
   int n_fb, n_set, n_sig, n_uc;
+  int n_hg, n_ch;             // listed hinges; channels of one (member, output): (n_fb + n_hg) * 3
 };
 
 // what one side of the ligament on `slot` reads at one output time (f: the member's history at that time), as strain_eval
@@ -386,9 +397,32 @@ __global__ __launch_bounds__(kObjThreads) void k_signal_channels(DevCtx c, SigAr
   // every lane of the quad takes part (slots without a ligament and the lanes of a padded item add zeros)
   fx = quad_sum(fx); fy = quad_sum(fy); fth = quad_sum(fth);
   if (valid && kk == 0) {
-    double* ch = a.chan + ((size_t)m * total + (size_t)item) * 3;
+    double* ch = a.chan + ((size_t)m * c.n_timepoints + (size_t)(item / a.n_fb)) * (size_t)a.n_ch + (size_t)(item % a.n_fb) * 3;
     ch[0] = fx; ch[1] = fy; ch[2] = fth;
   }
+}
+
+constexpr int kHingeThreads = 64;          // items per workgroup of k_signal_hinge_channels: one lane each
+
+// grid (chunks of kHingeThreads (output, listed hinge) items, members): the own side of the hinge's ligament -- the summand of
+// k_signal_channels, stored behind the block channels of its (member, output) row.  Every listed slot carries a ligament (the host refuses
+// the others), so a lane needs no neighbour and nothing is summed.
+template <int MODEL, int CONTACT>
+__global__ __launch_bounds__(kHingeThreads) void k_signal_hinge_channels(DevCtx c, SigArgs a) {
+  const int m = blockIdx.y;
+  const long long total = (long long)c.n_timepoints * a.n_hg;
+  const long long item = (long long)blockIdx.x * kHingeThreads + threadIdx.x;
+  if (item >= total) return;
+  const int k = (int)(item / a.n_hg), i = (int)(item % a.n_hg);
+  const int slot = a.hslots[i];
+  const int info = c.slot_info[slot];
+  if (info < 0) return;
+  SignalLigIn in;
+  double fx, fy, fth;
+  signal_load(c, member_bases(c, m), a.fields + ((size_t)m * c.n_timepoints + k) * ((size_t)c.n_blocks * 6), slot, info, CONTACT, in);
+  signal_lig_force<MODEL, CONTACT>(in, fx, fy, fth);
+  double* ch = a.chan + ((size_t)m * c.n_timepoints + k) * (size_t)a.n_ch + (size_t)(a.n_fb + i) * 3;
+  ch[0] = fx; ch[1] = fy; ch[2] = fth;
 }
 
 // grid (chunks of kObjThreads (output, signal) pairs, members)
@@ -400,7 +434,7 @@ __global__ __launch_bounds__(kObjThreads) void k_signal_residual(DevCtx c, SigAr
   if (item < total) {
     const int k = (int)(item / a.n_sig), s = (int)(item % a.n_sig);
     const double* f = a.fields + ((size_t)m * c.n_timepoints + k) * ((size_t)c.n_blocks * 6);
-    const double* ch = a.chan + ((size_t)m * c.n_timepoints + k) * ((size_t)a.n_fb * 3);
+    const double* ch = a.chan + ((size_t)m * c.n_timepoints + k) * (size_t)a.n_ch;
     double S = 0.0;
     for (int t = a.sig_ptr[s]; t < a.sig_ptr[s + 1]; ++t) {
       const int src = a.term_src[t];
@@ -439,13 +473,24 @@ __global__ __launch_bounds__(kObjThreads) void k_signal_direction(DevCtx c, SigA
   for (int t = a.uc_ptr[i]; t < a.uc_ptr[i + 1]; ++t) v += a.uc_coef[t] * cr[a.uc_sig[t]];
   const int dst = a.uc_dst[i];
   if (dst >= 0) G[((size_t)k * c.batch + m) * ((size_t)c.n_blocks * 6) + dst] = v;
-  else a.w[((size_t)m * c.n_timepoints + k) * ((size_t)a.n_fb * 3) + (-1 - dst)] = v;
+  else a.w[((size_t)m * c.n_timepoints + k) * (size_t)a.n_ch + (-1 - dst)] = v;
 }
 
 // the direction on block b at one (member, output): w of a force block, zero elsewhere
 __device__ __forceinline__ bool signal_seed(const SigArgs& a, const double* wk, int b, double* w3) {
   const int j = a.fmap[b];
   w3[0] = j >= 0 ? wk[j * 3] : 0.0; w3[1] = j >= 0 ? wk[j * 3 + 1] : 0.0; w3[2] = j >= 0 ? wk[j * 3 + 2] : 0.0;
+  return w3[0] != 0.0 || w3[1] != 0.0 || w3[2] != 0.0;
+}
+
+// the direction of the listed hinge on `slot` (if any) added to w3 (the own-block seed of the lane on that slot, the partner-block seed of
+// the lane on its partner slot); only called when the call lists hinges.  Returns whether w3 is non-zero now.
+__device__ __forceinline__ bool signal_seed_hinge(const SigArgs& a, const double* wk, int slot, double* w3) {
+  const int i = a.hmap[slot];
+  if (i >= 0) {
+    const double* wh = wk + (size_t)(a.n_fb + i) * 3;
+    w3[0] += wh[0]; w3[1] += wh[1]; w3[2] += wh[2];
+  }
   return w3[0] != 0.0 || w3[1] != 0.0 || w3[2] != 0.0;
 }
 
@@ -465,9 +510,10 @@ __global__ __launch_bounds__(kObjThreads) void k_signal_cotangent(DevCtx c, SigA
     const int slot = b * 4 + kk;
     const int info = c.slot_info[slot];
     if (info >= 0) {
-      const double* wk = a.w + ((size_t)m * c.n_timepoints + k) * ((size_t)a.n_fb * 3);
+      const double* wk = a.w + ((size_t)m * c.n_timepoints + k) * (size_t)a.n_ch;
       double wo[3], wp[3];
-      const bool so = signal_seed(a, wk, b, wo), sp = signal_seed(a, wk, info >> 3, wp);
+      bool so = signal_seed(a, wk, b, wo), sp = signal_seed(a, wk, info >> 3, wp);
+      if (a.n_hg) { so = signal_seed_hinge(a, wk, slot, wo); sp = signal_seed_hinge(a, wk, info >> 1, wp); }
       if (so || sp) {
         SignalLigIn in;
         SignalLigOut out;
@@ -497,9 +543,10 @@ __global__ __launch_bounds__(64) void k_signal_explicit(DevCtx c, SigArgs a) {
   const bool end0 = !(info & 1), bonds = c.g_b && end0;
   double rx = 0.0, ry = 0.0, phi = 0.0, q[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   for (int k = 0; k < c.n_timepoints; ++k) {
-    const double* wk = a.w + ((size_t)m * c.n_timepoints + k) * ((size_t)a.n_fb * 3);
+    const double* wk = a.w + ((size_t)m * c.n_timepoints + k) * (size_t)a.n_ch;
     double wo[3], wp[3];
-    const bool so = signal_seed(a, wk, b, wo), sp = signal_seed(a, wk, info >> 3, wp);
+    bool so = signal_seed(a, wk, b, wo), sp = signal_seed(a, wk, info >> 3, wp);
+    if (a.n_hg) { so = signal_seed_hinge(a, wk, slot, wo); sp = signal_seed_hinge(a, wk, info >> 1, wp); }
     if (!so && !sp) continue;
     SignalLigIn in;
     SignalLigOut out;

@@ -48,6 +48,8 @@
 //                          slice's directions of fields_dot, the slot's entry of the slice's parameter image and the contact constants
 //                          with their tangents; quad_sum of the value and of every epsilon part in direction order; lane 0 stores chan
 //                          (slice 0) and chan_dot
+//   k_tan_hinge_channels   items (output k, listed hinge), one lane each: the same evaluation of ONE ligament (a hinge channel, component
+//                          9 + 3 node + dof, is the summand of a force channel), stored behind the block channels
 //   k_tan_signal_combine   one lane per (member, direction, output, signal): the signal's terms in list order, field terms from
 //                          fields_dot, force terms from chan_dot; the pass's first direction also writes S from fields and chan
 //   k_tan_finite_flags     one flag per workgroup: a non-finite entry of fields / of the pass's fields_dot met on its stride; ordinary
@@ -520,13 +522,50 @@ constexpr int kTanSigQuads = kTanSigThreads / 4;      // items per workgroup (kO
 struct TanSigArgs {
   const double *fields, *fields_dot;   // B * Tn * nb*6, and this pass's B * KT * Tn * nb*6
   const int32_t* fblocks;              // n_fb force blocks
+  const int32_t* hslots;               // n_hg listed hinges: the slot block * 4 + node of each
   const int32_t* sig_ptr;              // n_sig + 1: the terms of signal s, in list order
   const int32_t* term_src;             // >= 0: offset of a field component inside one output time of the history; < 0: -(1 + channel)
   const double* term_coef;
-  double *chan, *chan_dot;             // B * Tn * n_fb*3, and B * KT * Tn * n_fb*3
+  double *chan, *chan_dot;             // B * Tn * n_ch, and B * KT * Tn * n_ch
   double *S, *S_dot;                   // B * Tn * n_sig, and B * KT * Tn * n_sig
   int Tn, n_fb, n_sig;
+  int n_hg, n_ch;                      // listed hinges; channels of one (member, output): (n_fb + n_hg) * 3, the hinges behind the blocks
 };
+
+// the own side of the ligament on `slot` (info = its slot_info, >= 0) of member m at output ko, for the directions of `slice`: the value and
+// the KC epsilon parts of dE/d(x, y, theta) on the slot's block into f[0..2]
+template <int MODEL, int CONTACT, int KC>
+__device__ __forceinline__ void tan_signal_side(const TanCtx& c, const TanSlices& sl, const TanSigArgs& a, int m, int slice, int ko, int slot, int info,
+                                                DualN<KC>* f) {
+  constexpr int K = KC;
+  const int b = slot >> 2;
+  const int ps = info >> 1, pb = ps >> 2;
+  const size_t nd = (size_t)c.nb * 3;
+  const double* fr = a.fields + ((size_t)m * a.Tn + ko) * 2 * nd;
+  TanSignalLigIn<KC> in;
+  in.o.x = fr[(size_t)b * 3]; in.o.y = fr[(size_t)b * 3 + 1]; in.o.th = fr[(size_t)b * 3 + 2];
+  in.p.x = fr[(size_t)pb * 3]; in.p.y = fr[(size_t)pb * 3 + 1]; in.p.th = fr[(size_t)pb * 3 + 2];
+  fast_sincos(0.5 * in.o.th, &in.o.sh, &in.o.ch);
+  fast_sincos(0.5 * in.p.th, &in.p.sh, &in.p.ch);
+  DFX_DN_EACH {
+    const double* fd = a.fields_dot + (((size_t)m * sl.kt + slice * K + k) * a.Tn + ko) * 2 * nd;
+    in.dox[k] = fd[(size_t)b * 3]; in.doy[k] = fd[(size_t)b * 3 + 1]; in.doth[k] = fd[(size_t)b * 3 + 2];
+    in.dpx[k] = fd[(size_t)pb * 3]; in.dpy[k] = fd[(size_t)pb * 3 + 1]; in.dpth[k] = fd[(size_t)pb * 3 + 2];
+  }
+  const double* tp = c.tp + (size_t)slice * sl.tp_plane + (size_t)m * c.nb * kSlots * tan_slot_n(K);
+  const double* sp = tp + (size_t)slot * tan_slot_n(K);
+  const double* pp = tp + (size_t)ps * tan_slot_n(K);
+  in.rox = tan_par_n<K>(sp, 0); in.roy = tan_par_n<K>(sp, 1); in.rpx = tan_par_n<K>(pp, 0); in.rpy = tan_par_n<K>(pp, 1);
+  in.lx = tan_par_n<K>(sp, 2); in.ly = tan_par_n<K>(sp, 3);
+  in.ks = tan_par_n<K>(sp, 4); in.ksh = tan_par_n<K>(sp, 5); in.kr = tan_par_n<K>(sp, 6);
+  if (CONTACT == 1) {
+    const double* mem = c.mem + (size_t)slice * sl.mem_plane + (size_t)m * tan_mem_n(K);
+    in.phi1 = tan_par_n<K>(sp, 7); in.phi2 = tan_par_n<K>(sp, 8);
+    in.am = tan_scalar_n<K>(mem, 0, 3, kTanMemDir); in.ac = tan_scalar_n<K>(mem, 1, 4, kTanMemDir); in.kc = tan_scalar_n<K>(mem, 2, 5, kTanMemDir);
+  }
+  in.sgn = (info & 1) ? 1.0 : -1.0;
+  tan_signal_lig<MODEL, CONTACT, KC>(in, f[0], f[1], f[2]);
+}
 
 // grid (chunks of kTanSigQuads items, members, slices of the pass)
 template <int MODEL, int CONTACT, int KC>
@@ -541,37 +580,9 @@ __global__ __launch_bounds__(kTanSigThreads) void k_tan_signal_channels(TanCtx c
   D f[3];
   if (valid) {
     const int ko = (int)(item / a.n_fb);
-    const int b = a.fblocks[(int)(item % a.n_fb)];
-    const int slot = b * kSlots + kk;
+    const int slot = a.fblocks[(int)(item % a.n_fb)] * kSlots + kk;
     const int info = c.slot_info[slot];
-    if (info >= 0) {
-      const int ps = info >> 1, pb = ps >> 2;
-      const size_t nd = (size_t)c.nb * 3;
-      const double* fr = a.fields + ((size_t)m * a.Tn + ko) * 2 * nd;
-      TanSignalLigIn<KC> in;
-      in.o.x = fr[(size_t)b * 3]; in.o.y = fr[(size_t)b * 3 + 1]; in.o.th = fr[(size_t)b * 3 + 2];
-      in.p.x = fr[(size_t)pb * 3]; in.p.y = fr[(size_t)pb * 3 + 1]; in.p.th = fr[(size_t)pb * 3 + 2];
-      fast_sincos(0.5 * in.o.th, &in.o.sh, &in.o.ch);
-      fast_sincos(0.5 * in.p.th, &in.p.sh, &in.p.ch);
-      DFX_DN_EACH {
-        const double* fd = a.fields_dot + (((size_t)m * sl.kt + slice * K + k) * a.Tn + ko) * 2 * nd;
-        in.dox[k] = fd[(size_t)b * 3]; in.doy[k] = fd[(size_t)b * 3 + 1]; in.doth[k] = fd[(size_t)b * 3 + 2];
-        in.dpx[k] = fd[(size_t)pb * 3]; in.dpy[k] = fd[(size_t)pb * 3 + 1]; in.dpth[k] = fd[(size_t)pb * 3 + 2];
-      }
-      const double* tp = c.tp + (size_t)slice * sl.tp_plane + (size_t)m * c.nb * kSlots * tan_slot_n(K);
-      const double* sp = tp + (size_t)slot * tan_slot_n(K);
-      const double* pp = tp + (size_t)ps * tan_slot_n(K);
-      in.rox = tan_par_n<K>(sp, 0); in.roy = tan_par_n<K>(sp, 1); in.rpx = tan_par_n<K>(pp, 0); in.rpy = tan_par_n<K>(pp, 1);
-      in.lx = tan_par_n<K>(sp, 2); in.ly = tan_par_n<K>(sp, 3);
-      in.ks = tan_par_n<K>(sp, 4); in.ksh = tan_par_n<K>(sp, 5); in.kr = tan_par_n<K>(sp, 6);
-      if (CONTACT == 1) {
-        const double* mem = c.mem + (size_t)slice * sl.mem_plane + (size_t)m * tan_mem_n(K);
-        in.phi1 = tan_par_n<K>(sp, 7); in.phi2 = tan_par_n<K>(sp, 8);
-        in.am = tan_scalar_n<K>(mem, 0, 3, kTanMemDir); in.ac = tan_scalar_n<K>(mem, 1, 4, kTanMemDir); in.kc = tan_scalar_n<K>(mem, 2, 5, kTanMemDir);
-      }
-      in.sgn = (info & 1) ? 1.0 : -1.0;
-      tan_signal_lig<MODEL, CONTACT, KC>(in, f[0], f[1], f[2]);
-    }
+    if (info >= 0) tan_signal_side<MODEL, CONTACT, KC>(c, sl, a, m, slice, ko, slot, info, f);
   }
   // every lane of the quad takes part (slots without a ligament and the lanes of a padded item add zeros); direction order
 #pragma unroll
@@ -581,13 +592,43 @@ __global__ __launch_bounds__(kTanSigThreads) void k_tan_signal_channels(TanCtx c
   }
   if (valid && kk == 0) {
     if (slice == 0) {
-      double* ch = a.chan + ((size_t)m * total + (size_t)item) * 3;
+      double* ch = a.chan + ((size_t)m * a.Tn + (size_t)(item / a.n_fb)) * (size_t)a.n_ch + (size_t)(item % a.n_fb) * 3;
       ch[0] = f[0].v; ch[1] = f[1].v; ch[2] = f[2].v;
     }
     DFX_DN_EACH {
-      double* cd = a.chan_dot + (((size_t)m * sl.kt + slice * K + k) * total + (size_t)item) * 3;
+      double* cd = a.chan_dot + (((size_t)m * sl.kt + slice * K + k) * a.Tn + (size_t)(item / a.n_fb)) * (size_t)a.n_ch + (size_t)(item % a.n_fb) * 3;
       cd[0] = f[0].e[k]; cd[1] = f[1].e[k]; cd[2] = f[2].e[k];
     }
+  }
+}
+
+constexpr int kTanHingeThreads = 64;       // items per workgroup of k_tan_hinge_channels: one lane each
+
+// grid (chunks of kTanHingeThreads (output, listed hinge) items, members, slices of the pass): the own side of ONE ligament, as a lane of
+// k_tan_signal_channels evaluates it, with nothing summed: value (slice 0) and KC epsilon parts into the hinge's three channels, which sit
+// behind the block channels of the (member, output) row.  Every listed slot carries a ligament (the host refuses the others).
+template <int MODEL, int CONTACT, int KC>
+__global__ __launch_bounds__(kTanHingeThreads) void k_tan_hinge_channels(TanCtx c, TanSlices sl, TanSigArgs a) {
+  using D = DualN<KC>;
+  constexpr int K = KC;
+  const int m = blockIdx.y, slice = blockIdx.z;
+  const long long total = (long long)a.Tn * a.n_hg;
+  const long long item = (long long)blockIdx.x * kTanHingeThreads + threadIdx.x;
+  if (item >= total) return;
+  const int ko = (int)(item / a.n_hg), ih = (int)(item % a.n_hg);
+  const int slot = a.hslots[ih];
+  const int info = c.slot_info[slot];
+  if (info < 0) return;
+  D f[3];
+  tan_signal_side<MODEL, CONTACT, KC>(c, sl, a, m, slice, ko, slot, info, f);
+  const size_t at = (size_t)(a.n_fb + ih) * 3;
+  if (slice == 0) {
+    double* ch = a.chan + ((size_t)m * a.Tn + ko) * (size_t)a.n_ch + at;
+    ch[0] = f[0].v; ch[1] = f[1].v; ch[2] = f[2].v;
+  }
+  DFX_DN_EACH {
+    double* cd = a.chan_dot + (((size_t)m * sl.kt + slice * K + k) * a.Tn + ko) * (size_t)a.n_ch + at;
+    cd[0] = f[0].e[k]; cd[1] = f[1].e[k]; cd[2] = f[2].e[k];
   }
 }
 
@@ -600,7 +641,7 @@ __global__ __launch_bounds__(kTanSigThreads) void k_tan_signal_combine(TanSigArg
   const int ko = (int)(item / a.n_sig), s = (int)(item % a.n_sig);
   const size_t nd = (size_t)nb * 3, row = (size_t)m * a.Tn + ko, drow = ((size_t)m * kt + d) * a.Tn + ko;
   const double* fd = a.fields_dot + drow * 2 * nd;
-  const double* cd = a.chan_dot + drow * ((size_t)a.n_fb * 3);
+  const double* cd = a.chan_dot + drow * (size_t)a.n_ch;
   double Sd = 0.0;
   for (int t = a.sig_ptr[s]; t < a.sig_ptr[s + 1]; ++t) {
     const int src = a.term_src[t];
@@ -609,7 +650,7 @@ __global__ __launch_bounds__(kTanSigThreads) void k_tan_signal_combine(TanSigArg
   a.S_dot[drow * a.n_sig + s] = Sd;
   if (d == 0) {
     const double* f = a.fields + row * 2 * nd;
-    const double* ch = a.chan + row * ((size_t)a.n_fb * 3);
+    const double* ch = a.chan + row * (size_t)a.n_ch;
     double S = 0.0;
     for (int t = a.sig_ptr[s]; t < a.sig_ptr[s + 1]; ++t) {
       const int src = a.term_src[t];

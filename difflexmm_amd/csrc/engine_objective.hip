@@ -264,7 +264,8 @@ int launch_peak(dfx_handle* h, const ObjJob& j, double* G, double* host) {
 }
 
 // ---- signal misfit: the term list compacted into index tables.  FORCE blocks: the blocks with a force term (components 6..8); the SET: those
-// and the blocks bonded to them (every ligament with an end on a force block is evaluated from both of its ends)
+// and the blocks bonded to them (every ligament with an end on a force block is evaluated from both of its ends).  HINGES: the (block, node)
+// slots with a hinge term (components 9 + 3 node + dof), their channels behind the block channels; both end blocks of each join the set
 }  // namespace
 
 // (SigTerms / SigTables: dfx_engine.h -- the forward-mode signal entries of engine_tangent.hip build the same tables)
@@ -281,7 +282,16 @@ int signal_term_tables(dfx_handle* h, const char* who, const SigTerms& t, SigTab
   for (int i = 0; i < t.n; ++i) {
     if (t.signal[i] < 0 || t.signal[i] >= ns) { h->err = w + ": term " + std::to_string(i) + " names signal " + std::to_string(t.signal[i]) + " out of range (n_signals = " + std::to_string(ns) + ")"; return 1; }
     if (t.block[i] < 0 || (size_t)t.block[i] >= nb) { h->err = w + ": term " + std::to_string(i) + " names block " + std::to_string(t.block[i]) + " out of range (n_blocks = " + std::to_string(nb) + ")"; return 1; }
-    if (t.comp[i] < 0 || t.comp[i] > 8) { h->err = w + ": term " + std::to_string(i) + " names component " + std::to_string(t.comp[i]) + " out of range (0..2 displacement, 3..5 velocity, 6..8 elastic force)"; return 1; }
+    if (t.comp[i] < 0 || t.comp[i] > (h->sig_hinges ? 20 : 8)) {
+      h->err = w + ": term " + std::to_string(i) + " names component " + std::to_string(t.comp[i]) + " out of range (0..2 displacement, 3..5 velocity, 6..8 elastic force" +
+               (h->sig_hinges ? ", 9 + 3 node + dof hinge force)" : "; the hinge forces 9 + 3 node + dof are off: dfx_signal_hinge_channels)");
+      return 1;
+    }
+    if (t.comp[i] >= 9) {
+      const int node = (t.comp[i] - 9) / 3;
+      if (node >= pl.n_npb) { h->err = w + ": term " + std::to_string(i) + " names the hinge on node " + std::to_string(node) + " but a block of this lattice has " + std::to_string(pl.n_npb) + " nodes"; return 1; }
+      if (pl.slot_info[(size_t)t.block[i] * 4 + node] < 0) { h->err = w + ": term " + std::to_string(i) + " names the hinge on node " + std::to_string(node) + " of block " + std::to_string(t.block[i]) + ", which carries no ligament"; return 1; }
+    }
     if (!std::isfinite(t.coef[i])) { h->err = w + ": non-finite coefficient"; return 1; }
     ++count[t.signal[i]];
     force = force || t.comp[i] >= 6;
@@ -296,11 +306,22 @@ int signal_term_tables(dfx_handle* h, const char* who, const SigTerms& t, SigTab
     h->err = w + ": nodes with more than one ligament (a general bond list with extra ligaments) are not supported by the force components of a signal";
     return 1;
   }
-  // force blocks and the set
-  std::vector<int32_t>&fmap = out.fmap, &fblocks = out.fblocks, &set = out.set;
-  fmap.assign(nb, -1); fblocks.clear(); set.clear();
+  // force blocks, listed hinges and the set
+  std::vector<int32_t>&fmap = out.fmap, &fblocks = out.fblocks, &set = out.set, &hslots = out.hslots, &hmap = out.hmap;
+  fmap.assign(nb, -1); fblocks.clear(); set.clear(); hslots.clear(); hmap.clear();
   std::vector<char> in_f(nb, 0), in_set(nb, 0);
-  for (int i = 0; i < t.n; ++i) if (t.comp[i] >= 6) in_f[t.block[i]] = 1;
+  for (int i = 0; i < t.n; ++i) if (t.comp[i] >= 6 && t.comp[i] < 9) in_f[t.block[i]] = 1;
+  if (std::any_of(t.comp, t.comp + t.n, [](int32_t c) { return c >= 9; })) {
+    hmap.assign(pl.n_slots, -1);
+    for (int i = 0; i < t.n; ++i) if (t.comp[i] >= 9) hmap[(size_t)t.block[i] * 4 + (t.comp[i] - 9) / 3] = 0;
+    for (size_t sl = 0; sl < (size_t)pl.n_slots; ++sl) {
+      if (hmap[sl] < 0) continue;
+      hmap[sl] = (int32_t)hslots.size();
+      hslots.push_back((int32_t)sl);
+      in_set[sl >> 2] = 1;
+      in_set[pl.slot_info[sl] >> 3] = 1;
+    }
+  }
   for (size_t b = 0; b < nb; ++b) {
     if (!in_f[b]) continue;
     fmap[b] = (int32_t)fblocks.size();
@@ -321,7 +342,8 @@ int signal_term_tables(dfx_handle* h, const char* who, const SigTerms& t, SigTab
     std::vector<int32_t> at(sig_ptr.begin(), sig_ptr.end() - 1);
     for (int i = 0; i < t.n; ++i) {
       const int c = t.comp[i], b = t.block[i], o = at[t.signal[i]]++;
-      term_src[o] = c < 3 ? b * 3 + c : c < 6 ? (int)nb * 3 + b * 3 + (c - 3) : -1 - (fmap[b] * 3 + (c - 6));
+      term_src[o] = c < 3 ? b * 3 + c : c < 6 ? (int)nb * 3 + b * 3 + (c - 3) : c < 9 ? -1 - (fmap[b] * 3 + (c - 6))
+                                                                              : -1 - (((int)fblocks.size() + hmap[(size_t)b * 4 + (c - 9) / 3]) * 3 + (c - 9) % 3);
       term_coef[o] = t.coef[i];
     }
   }
@@ -346,28 +368,33 @@ int prepare_signal(dfx_handle* h, const char* who, const SigTerms& t, const doub
   const size_t n_tg = want_target ? (targets_per_member ? B : 1) * (size_t)Tn * ns : 0;
   if (!all_finite(h, who, "target", targets, n_tg)) return 1;
   if (want_target && (!all_finite(h, who, "signal weight", omega, ns) || !all_finite(h, who, "time weight", tau, Tn))) return 1;
-  const std::vector<int32_t>&fmap = tb.fmap, &fblocks = tb.fblocks, &set = tb.set, &sig_ptr = tb.sig_ptr, &term_src = tb.term_src;
+  const std::vector<int32_t>&fmap = tb.fmap, &fblocks = tb.fblocks, &set = tb.set, &sig_ptr = tb.sig_ptr, &term_src = tb.term_src, &hslots = tb.hslots, &hmap = tb.hmap;
   const std::vector<double>& term_coef = tb.term_coef;
   const size_t nb = pl.n_blocks;
-  // the terms by distinct (block, component), list order kept; all three components of a force block are listed (w is written whole)
+  // the terms by distinct (block, component), list order kept; all three components of a force block and of a listed hinge are listed
+  // (w is written whole)
+  const int n_fb = (int)fblocks.size();
   std::map<std::pair<int, int>, std::vector<int>> by_dof;
   for (int32_t b : fblocks) for (int c = 6; c < 9; ++c) by_dof[{b, c}];
+  for (int32_t sl : hslots) for (int d = 0; d < 3; ++d) by_dof[{sl >> 2, 9 + 3 * (sl & 3) + d}];
   for (int i = 0; i < t.n; ++i) by_dof[{t.block[i], t.comp[i]}].push_back(i);
   std::vector<int32_t> uc_ptr(1, 0), uc_dst, uc_sig;
   std::vector<double> uc_coef;
   for (const auto& e : by_dof) {
     const int b = e.first.first, c = e.first.second;
-    uc_dst.push_back(c < 6 ? b * 6 + c : -1 - (fmap[b] * 3 + (c - 6)));
+    uc_dst.push_back(c < 6 ? b * 6 + c : c < 9 ? -1 - (fmap[b] * 3 + (c - 6)) : -1 - ((n_fb + hmap[(size_t)b * 4 + (c - 9) / 3]) * 3 + (c - 9) % 3));
     for (int i : e.second) { uc_sig.push_back(t.signal[i]); uc_coef.push_back(t.coef[i]); }
     uc_ptr.push_back((int32_t)uc_sig.size());
   }
   dfx_handle::SigJob& J = h->sig;
-  J.n_fb = (int)fblocks.size(); J.n_set = (int)set.size(); J.n_sig = ns; J.n_uc = (int)uc_dst.size(); J.n_terms = t.n; J.n_blocks = (int)nb;
+  J.n_fb = n_fb; J.n_set = (int)set.size(); J.n_sig = ns; J.n_uc = (int)uc_dst.size(); J.n_terms = t.n; J.n_blocks = (int)nb;
+  J.n_hg = (int)hslots.size();
+  const size_t n_ch = (size_t)(J.n_fb + J.n_hg) * 3;
   J.has_target = want_target; J.has_omega = want_target && omega; J.has_tau = want_target && tau;
   J.target_stride = targets_per_member ? (long long)Tn * ns : 0;
   // one int table and one double table, in the order sig_args reads them
   std::vector<int32_t> tab;
-  for (const std::vector<int32_t>* v : std::initializer_list<const std::vector<int32_t>*>{&fblocks, &fmap, &set, &sig_ptr, &term_src, &uc_ptr, &uc_dst, &uc_sig}) tab.insert(tab.end(), v->begin(), v->end());
+  for (const std::vector<int32_t>* v : std::initializer_list<const std::vector<int32_t>*>{&fblocks, &fmap, &set, &sig_ptr, &term_src, &uc_ptr, &uc_dst, &uc_sig, &hslots, &hmap}) tab.insert(tab.end(), v->begin(), v->end());
   std::vector<double> dbl(term_coef);
   dbl.insert(dbl.end(), uc_coef.begin(), uc_coef.end());
   if (J.has_omega) dbl.insert(dbl.end(), omega, omega + ns);
@@ -375,8 +402,8 @@ int prepare_signal(dfx_handle* h, const char* who, const SigTerms& t, const doub
   if (want_target) dbl.insert(dbl.end(), targets, targets + n_tg);
   HIP_OK(h->d_sig_tab.ensure(tab.size()));
   HIP_OK(h->d_sig_coef.ensure(dbl.size()));
-  HIP_OK(h->d_sig_chan.ensure(B * Tn * (size_t)J.n_fb * 3));
-  HIP_OK(h->d_sig_w.ensure(B * Tn * (size_t)J.n_fb * 3));
+  HIP_OK(h->d_sig_chan.ensure(B * Tn * n_ch));
+  HIP_OK(h->d_sig_w.ensure(B * Tn * n_ch));
   HIP_OK(h->d_sig_S.ensure(B * Tn * (size_t)ns));
   HIP_OK(h->d_sig_c.ensure(B * Tn * (size_t)ns));
   HIP_OK(h->d_obj.ensure(B));
@@ -399,7 +426,9 @@ SigArgs sig_args(const dfx_handle* h) {
   a.term_src = ip; ip += J.n_terms;
   a.uc_ptr = ip; ip += J.n_uc + 1;
   a.uc_dst = ip; ip += J.n_uc;
-  a.uc_sig = ip;
+  a.uc_sig = ip; ip += J.n_terms;
+  a.hslots = J.n_hg ? ip : nullptr; ip += J.n_hg;
+  a.hmap = J.n_hg ? ip : nullptr;
   const double* dp = h->d_sig_coef.p;
   a.term_coef = dp; dp += J.n_terms;
   a.uc_coef = dp; dp += J.n_terms;
@@ -409,6 +438,7 @@ SigArgs sig_args(const dfx_handle* h) {
   a.chan = h->d_sig_chan.p; a.S = h->d_sig_S.p; a.cres = h->d_sig_c.p; a.w = h->d_sig_w.p;
   a.target_stride = J.target_stride;
   a.n_fb = J.n_fb; a.n_set = J.n_set; a.n_sig = J.n_sig; a.n_uc = J.n_uc;
+  a.n_hg = J.n_hg; a.n_ch = (J.n_fb + J.n_hg) * 3;
   return a;
 }
 
@@ -434,6 +464,10 @@ int launch_signal(dfx_handle* h, double* G, double* objective_host) {
   if (J.n_fb) {
     const dim3 grid(chunks_of(Tn * J.n_fb, kObjQuads), (unsigned)B);
     with_strain_physics(h, [&](auto M, auto C) { hipLaunchKernelGGL((k_signal_channels<M(), C()>), grid, dim3(kObjThreads), 0, h->stream, c, a); });
+  }
+  if (J.n_hg) {
+    const dim3 grid(chunks_of(Tn * J.n_hg, kHingeThreads), (unsigned)B);
+    with_strain_physics(h, [&](auto M, auto C) { hipLaunchKernelGGL((k_signal_hinge_channels<M(), C()>), grid, dim3(kHingeThreads), 0, h->stream, c, a); });
   }
   const unsigned chunks = chunks_of(Tn * J.n_sig, kObjThreads);
   if (J.has_target) HIP_OK(h->d_obj_part.ensure(B * chunks));
@@ -789,6 +823,11 @@ int dfx_strain_peak_value_and_grad(dfx_handle* h, const double* bond_coef, int32
   if (objective) memcpy(objective, st, sizeof(double) * B);
   if (peak) memcpy(peak, st + B, sizeof(double) * B);
   if (peak_at) memcpy(peak_at, st + 2 * B, sizeof(int32_t) * 2 * B);
+  return 0;
+}
+
+int dfx_signal_hinge_channels(dfx_handle* h, int32_t enable) {
+  h->sig_hinges = enable != 0;
   return 0;
 }
 

@@ -311,11 +311,20 @@ struct SignalSink {
   }
 };
 
+unsigned chunks_of(long long items, int per) { return (unsigned)std::max<long long>(1, (items + per - 1) / per); }
+
+// the channel launches of one pass: the force blocks on quads, then the listed hinges one lane each (either may be absent); returns how many
 template <int MODEL, int CONTACT, int KC>
-void launch_sig_channels(dim3 grid, hipStream_t s, const TanCtx& c, const TanSlices& sl, const TanSigArgs& a) {
-  hipLaunchKernelGGL((k_tan_signal_channels<MODEL, CONTACT, KC>), grid, dim3(kTanSigThreads), 0, s, c, sl, a);
+int launch_sig_channels(unsigned members, unsigned slices, hipStream_t s, const TanCtx& c, const TanSlices& sl, const TanSigArgs& a) {
+  if (a.n_fb)
+    hipLaunchKernelGGL((k_tan_signal_channels<MODEL, CONTACT, KC>), dim3(chunks_of((long long)a.Tn * a.n_fb, kTanSigQuads), members, slices), dim3(kTanSigThreads),
+                       0, s, c, sl, a);
+  if (a.n_hg)
+    hipLaunchKernelGGL((k_tan_hinge_channels<MODEL, CONTACT, KC>), dim3(chunks_of((long long)a.Tn * a.n_hg, kTanHingeThreads), members, slices),
+                       dim3(kTanHingeThreads), 0, s, c, sl, a);
+  return (a.n_fb != 0) + (a.n_hg != 0);
 }
-using SigChannelsFn = void (*)(dim3, hipStream_t, const TanCtx&, const TanSlices&, const TanSigArgs&);
+using SigChannelsFn = int (*)(unsigned, unsigned, hipStream_t, const TanCtx&, const TanSlices&, const TanSigArgs&);
 template <int KC>
 SigChannelsFn pick_sig_physics(int model, bool angle) {
   SigChannelsFn f = nullptr;
@@ -333,17 +342,15 @@ SigChannelsFn pick_sig_channels(const Plan& pl, int kc) {
   }
 }
 
-unsigned chunks_of(long long items, int per) { return (unsigned)std::max<long long>(1, (items + per - 1) / per); }
-
 // The sink's device side, sized for the widest pass and allocated with the call's other buffers, before any pass is paid for; a failure
-// releases all of it (SignalSink) and is an ordinary error return.  The term tables go up here: fblocks | sig_ptr | term_src, and term_coef.
+// releases all of it (SignalSink) and is an ordinary error return.  The term tables go up here: fblocks | sig_ptr | term_src | hslots, and term_coef.
 int sink_alloc(dfx_handle* h, SignalSink& k, const Pass& widest, int Tn) {
-  const size_t B = h->pl.batch, kt = widest.kt(), T = Tn, n_fb = k.tb.fblocks.size(), ns = k.terms.n_signals;
-  HIP_OK(k.chan.ensure(B * T * n_fb * 3)); HIP_OK(k.chan_dot.ensure(B * kt * T * n_fb * 3));
+  const size_t B = h->pl.batch, kt = widest.kt(), T = Tn, n_ch = (k.tb.fblocks.size() + k.tb.hslots.size()) * 3, ns = k.terms.n_signals;
+  HIP_OK(k.chan.ensure(B * T * n_ch)); HIP_OK(k.chan_dot.ensure(B * kt * T * n_ch));
   HIP_OK(k.S.ensure(B * T * ns)); HIP_OK(k.S_dot.ensure(B * kt * T * ns));
   HIP_OK(k.flags.ensure(kFlagGroups));
   std::vector<int32_t> tab;
-  for (const std::vector<int32_t>* v : {&k.tb.fblocks, &k.tb.sig_ptr, &k.tb.term_src}) tab.insert(tab.end(), v->begin(), v->end());
+  for (const std::vector<int32_t>* v : {&k.tb.fblocks, &k.tb.sig_ptr, &k.tb.term_src, &k.tb.hslots}) tab.insert(tab.end(), v->begin(), v->end());
   HIP_OK(k.tab.ensure(tab.size())); HIP_OK(k.coef.ensure(k.tb.term_coef.size()));
   HIP_OK(hipMemcpyAsync(k.tab.p, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice, h->stream));
   HIP_OK(hipMemcpyAsync(k.coef.p, k.tb.term_coef.data(), sizeof(double) * k.tb.term_coef.size(), hipMemcpyHostToDevice, h->stream));
@@ -358,14 +365,12 @@ int sink_launch(dfx_handle* h, SignalSink& k, const Pass& p, int Tn, const Multi
   TanSigArgs a;
   a.fields = d.fields.p; a.fields_dot = d.fields_dot.p;
   a.n_fb = (int)k.tb.fblocks.size(); a.n_sig = k.terms.n_signals; a.Tn = Tn;
-  a.fblocks = k.tab.p; a.sig_ptr = k.tab.p + a.n_fb; a.term_src = a.sig_ptr + a.n_sig + 1;
+  a.n_hg = (int)k.tb.hslots.size(); a.n_ch = (a.n_fb + a.n_hg) * 3;
+  a.fblocks = k.tab.p; a.sig_ptr = k.tab.p + a.n_fb; a.term_src = a.sig_ptr + a.n_sig + 1; a.hslots = a.term_src + k.terms.n;
   a.term_coef = k.coef.p;
   a.chan = k.chan.p; a.chan_dot = k.chan_dot.p; a.S = k.S.p; a.S_dot = k.S_dot.p;
   hipStream_t st = h->stream;
-  if (a.n_fb) {
-    pick_sig_channels(pl, p.kc)(dim3(chunks_of((long long)Tn * a.n_fb, kTanSigQuads), (unsigned)B, (unsigned)p.slices), st, c, sl, a);
-    ++launches;
-  }
+  if (a.n_ch) launches += pick_sig_channels(pl, p.kc)((unsigned)B, (unsigned)p.slices, st, c, sl, a);
   hipLaunchKernelGGL(k_tan_signal_combine, dim3(chunks_of((long long)Tn * a.n_sig, kTanSigThreads), (unsigned)B, (unsigned)p.kt()), dim3(kTanSigThreads), 0, st,
                      a, pl.n_blocks, p.kt());
   const size_t nx = p.k0 == 0 ? nfield : 0, ny = nfield * p.kt();       // (fields: the first pass vouches for them, later passes store the same)

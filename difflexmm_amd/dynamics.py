@@ -590,10 +590,10 @@ class DynamicSolver:
             fixed, dense = engine.forward_tangent_multi, engine.forward_tangent_dense_multi
         else:       # the same two solves with the history kept on the device: signals and their tangents come back
             def fixed(*a, step_times=None):
-                return engine.forward_tangent_signals_multi(*a, spec.terms, spec.n_signals, step_times=step_times)
+                return engine.forward_tangent_signals_multi(*a, *self._terms(spec), step_times=step_times)
 
             def dense(*a):
-                return engine.forward_tangent_signals_dense_multi(*a, spec.terms, spec.n_signals)
+                return engine.forward_tangent_signals_dense_multi(*a, *self._terms(spec))
         if not engine.has_forward_tangent_multi or (adaptive and not engine.has_forward_tangent_dense_multi):
             lib = engine.lib
             raise NotImplementedError(f"{who}: the library {getattr(lib, '_name', lib)!r} has no dfx_forward_tangent{'' if _who == 'jvp' else '_multi'} "
@@ -915,15 +915,21 @@ class DynamicSolver:
         return self._take_stats(self.engine.strain_peak_value_and_grad(spec.bond_coef, spec.bond_weights, spec.time_weights, spec.aggregate,
                                                                        spec.sharpness, which=which, device=device))
 
+    def _terms(self, spec):
+        """(terms, n_signals) of an ``objective.SignalSpec`` for the engine, whose hinge components are switched on or off as the spec says
+        (``dfx_signal_hinge_channels``: off, component 9 and above are refused as out of range)"""
+        self.engine.hinge_channels = spec.hinge_channels
+        return spec.terms, spec.n_signals
+
     def signal_values(self, spec):
         """(batch, T, n_signals) signals of an ``objective.SignalSpec`` on the device-resident history of the last solve (any forward
-        pass): field components are read from the history, force components are the elastic force dE/d(x, y, theta) on the block,
-        evaluated there -- no second handle, no upload of states."""
-        return self.engine.signal_values(spec.terms, spec.n_signals)
+        pass): field components are read from the history, force components are the elastic force dE/d(x, y, theta) on the block
+        and hinge components the part of it that one ligament carries, evaluated there -- no second handle, no upload of states."""
+        return self.engine.signal_values(*self._terms(spec))
 
     def signal_misfit_value(self, spec):
         """(batch,) least-squares misfit of an ``objective.SignalSpec`` against its targets on the device-resident history."""
-        return self.engine.signal_misfit_value(spec.terms, spec.n_signals, spec.targets, spec.omega, spec.tau)
+        return self.engine.signal_misfit_value(*self._terms(spec), spec.targets, spec.omega, spec.tau)
 
     def signal_misfit_value_and_raw(self, spec, which=("centroid_node_vectors", "void_angle0", "inertia"), device=False):
         """The signal misfit (``objective.SignalSpec``) of the last kept solve, evaluated and differentiated on the device beside
@@ -932,24 +938,24 @@ class DynamicSolver:
         names them, ``reference_vector`` / ``k_bond`` / ``contact``) are already in the raw gradients returned.  As with :meth:`vjp_raw`,
         ``fn_params`` holds what the sweep accumulates: the direct dependence of a prescribed output DOF on its drive is not in it."""
         which = self._raw_which(which)
-        return self._take_stats(self.engine.signal_misfit_value_and_grad(spec.terms, spec.n_signals, spec.targets, spec.omega, spec.tau,
+        return self._take_stats(self.engine.signal_misfit_value_and_grad(*self._terms(spec), spec.targets, spec.omega, spec.tau,
                                                                          which=which, device=device))
 
     def signal_projections(self, spec):
         """(batch, n_signals, n_rows) projections of the signals of an ``objective.ProjectionSpec`` on the rows of its time basis, on the
         device-resident history of the last solve (any forward pass)."""
-        return self.engine.signal_projections(spec.signal_spec.terms, spec.signal_spec.n_signals, spec.basis)
+        return self.engine.signal_projections(*self._terms(spec.signal_spec), spec.basis)
 
     def signal_projection_value(self, spec):
         """(batch,) weighted quadratic form of the projections of an ``objective.ProjectionSpec`` on the device-resident history."""
-        return self.engine.signal_projection_value(spec.signal_spec.terms, spec.signal_spec.n_signals, spec.basis, spec.row_weights, spec.targets)
+        return self.engine.signal_projection_value(*self._terms(spec.signal_spec), spec.basis, spec.row_weights, spec.targets)
 
     def signal_projection_value_and_raw(self, spec, which=("centroid_node_vectors", "void_angle0", "inertia"), device=False):
         """The projection objective (``objective.ProjectionSpec``) of the last kept solve, evaluated and differentiated on the device
         beside :meth:`signal_misfit_value_and_raw`: the time reduction and the cotangent on the signals are formed in HBM; what follows
         (the Hessian-vector product of force terms, their mixed second derivatives, what ``fn_params`` holds) is that method's."""
         which = self._raw_which(which)
-        return self._take_stats(self.engine.signal_projection_value_and_grad(spec.signal_spec.terms, spec.signal_spec.n_signals, spec.basis,
+        return self._take_stats(self.engine.signal_projection_value_and_grad(*self._terms(spec.signal_spec), spec.basis,
                                                                              spec.row_weights, spec.targets, which=which, device=device))
 
     @staticmethod
@@ -960,12 +966,12 @@ class DynamicSolver:
     def signal_xcorr(self, spec):
         """(batch, 2 max_lag + 1) normalised cross-correlation of the signal pairs of an ``objective.CorrelationSpec`` over its lags (lag d
         at index d + max_lag), on the device-resident history of the last solve (any forward pass)."""
-        return self.engine.signal_xcorr(spec.signal_spec.terms, spec.signal_spec.n_signals, spec.pairs, spec.max_lag, spec.templates,
+        return self.engine.signal_xcorr(*self._terms(spec.signal_spec), spec.pairs, spec.max_lag, spec.templates,
                                         spec.normalisation)
 
     def signal_xcorr_value(self, spec):
         """(J, peak, delay), (batch,) each, of an ``objective.CorrelationSpec`` on the device-resident history."""
-        return self.engine.signal_xcorr_value(spec.signal_spec.terms, spec.signal_spec.n_signals, spec.pairs, spec.max_lag, **self._xcorr_kwargs(spec))
+        return self.engine.signal_xcorr_value(*self._terms(spec.signal_spec), spec.pairs, spec.max_lag, **self._xcorr_kwargs(spec))
 
     def signal_xcorr_value_and_raw(self, spec, which=("centroid_node_vectors", "void_angle0", "inertia"), device=False):
         """The cross-correlation objective (``objective.CorrelationSpec``) of the last kept solve, evaluated and differentiated on the
@@ -973,7 +979,7 @@ class DynamicSolver:
         cotangent on the signals are formed in HBM; what follows is :meth:`signal_misfit_value_and_raw`'s.  Returns
         ((J, peak, delay), raw gradients)."""
         which = self._raw_which(which)
-        *out, grads = self._take_stats(self.engine.signal_xcorr_value_and_grad(spec.signal_spec.terms, spec.signal_spec.n_signals, spec.pairs,
+        *out, grads = self._take_stats(self.engine.signal_xcorr_value_and_grad(*self._terms(spec.signal_spec), spec.pairs,
                                                                                spec.max_lag, which=which, device=device, **self._xcorr_kwargs(spec)))
         return tuple(out), grads
 

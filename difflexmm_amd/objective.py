@@ -362,6 +362,32 @@ def host_peak_strain_value(spec, fields, centroid_node_vectors, bond_connectivit
 
 # ---- signal misfit on the device-resident history -------------------------------------------------------------------------------------
 DISPLACEMENT, VELOCITY, FORCE = 0, 3, 6          # first component of each kind: + 0, 1, 2 for x, y, theta
+HINGE = 9                                        # first hinge component: + 3 * node + (0, 1, 2 for x, y, theta)
+MAX_NODES_PER_BLOCK = 4
+
+
+def hinge_component(node, dof):
+    """The component of the force that ONE hinge carries: 9 + 3 node + dof, the part dE_h/d(x, y, theta) that the ligament on ``node``
+    of a block (with its two void-angle penalties on a lattice with the angle contact) contributes to the block's components 6..8."""
+    if int(node) != node or int(dof) != dof or not 0 <= node < MAX_NODES_PER_BLOCK or not 0 <= dof <= 2:
+        raise ValueError(f"hinge_component: node must be in 0..{MAX_NODES_PER_BLOCK - 1} and dof in 0..2, got ({node!r}, {dof!r})")
+    return HINGE + 3 * int(node) + int(dof)
+
+
+def bonds_across(bond_connectivity, n_nodes_per_block, blocks_inside):
+    """The hinges that cross the boundary of a region, seen from inside: the (block, node) pairs, in ascending order, of the bond ends that
+    sit on a block of ``blocks_inside`` while the bond's other end sits on a block outside it.  ``bond_connectivity`` (n_bonds, 2) node
+    ids, node n on block n // n_nodes_per_block -- the arguments of ``bond_weights_from_blocks``.  The sum of these hinges' force
+    components is the force the region's surroundings transmit into it through the ligaments (``SignalSpec.cut_force``)."""
+    npb = int(n_nodes_per_block)
+    bonds = np.asarray(bond_connectivity, dtype=np.int64).reshape(-1, 2)
+    inside = np.unique(np.asarray(blocks_inside, dtype=np.int64).reshape(-1))
+    if inside.size == 0 or inside.min() < 0:
+        raise ValueError("blocks_inside must be a non-empty sequence of block numbers >= 0")
+    blocks = bonds // npb
+    isin = np.isin(blocks, inside)
+    out = [(int(blocks[i, e]), int(bonds[i, e] % npb)) for i in range(len(bonds)) for e in (0, 1) if isin[i, e] and not isin[i, 1 - e]]
+    return sorted(out)
 
 
 class SignalSpec:
@@ -372,19 +398,25 @@ class SignalSpec:
         J_m   = 1/2 sum_k tau_k sum_s omega_s (S_mks - Starget_mks)^2
 
     ``terms``: a sequence of (signal, block, component, coef); component 0..2 displacement x, y, theta, 3..5 velocity, 6..8 the elastic force
-    dE/d(x, y, theta) on the block; a signal adds its terms in list order.  ``targets`` (T, n_signals) shared or (batch, T, n_signals), or
+    dE/d(x, y, theta) on the block, 9 + 3 node + dof (``hinge_component``) the part of that force that the ligament on one node of the block
+    carries -- same sign and units, so the force the hinge exerts on the block is minus the channel, and a block's hinge channels add up to its
+    components 6..8 -- accepted with ``hinge_channels=True`` only (the constructors ``hinge_force`` and ``cut_force`` set it; without it
+    component 9 and above are out of range, as before these channels existed, and the engine refuses them likewise); a signal adds its
+    terms in list order.  ``targets`` (T, n_signals) shared or (batch, T, n_signals), or
     None for a spec that only evaluates signals; ``omega`` (n_signals,) or None = ones; ``tau`` (T,) or None = ones.  Shapes are checked here
     (``ValueError``); block numbers and lengths against a solve are checked where the spec is used."""
-    __slots__ = ("terms", "n_signals", "targets", "omega", "tau")
+    __slots__ = ("terms", "n_signals", "targets", "omega", "tau", "hinge_channels")
 
-    def __init__(self, terms, n_signals=None, targets=None, omega=None, tau=None):
+    def __init__(self, terms, n_signals=None, targets=None, omega=None, tau=None, hinge_channels=False):
         t = np.array(terms, dtype=float)
         if t.ndim != 2 or t.shape[1] != 4 or len(t) == 0:
             raise ValueError(f"terms must be a non-empty sequence of (signal, block, component, coef), got shape {t.shape}")
         if not np.isfinite(t).all() or (t[:, :3] != np.round(t[:, :3])).any():
             raise ValueError("terms: signal, block and component must be integers and every coefficient finite")
-        if (t[:, :3] < 0).any() or (t[:, 2] > 8).any():
-            raise ValueError("terms: signal and block must be >= 0 and component in 0..8 (0..2 displacement, 3..5 velocity, 6..8 force)")
+        top = HINGE + 3 * MAX_NODES_PER_BLOCK - 1 if hinge_channels else HINGE - 1
+        if (t[:, :3] < 0).any() or (t[:, 2] > top).any():
+            raise ValueError(f"terms: signal and block must be >= 0 and component in 0..{top} (0..2 displacement, 3..5 velocity, 6..8 force" +
+                             (", 9 + 3 node + dof hinge force)" if hinge_channels else "; 9 + 3 node + dof hinge force with hinge_channels=True)"))
         ns = int(t[:, 0].max()) + 1 if n_signals is None else int(n_signals)
         if ns <= 0 or t[:, 0].max() >= ns:
             raise ValueError(f"terms name signal {int(t[:, 0].max())} but n_signals = {ns}")
@@ -407,7 +439,7 @@ class SignalSpec:
             if ta.ndim != 1 or (tg is not None and ta.shape[0] != tg.shape[-2]):
                 raise ValueError(f"tau must be (T,){'' if tg is None else f' with T = {tg.shape[-2]}'}, got {ta.shape}")
         self.terms = [(int(a), int(b), int(c), float(d)) for a, b, c, d in t]
-        self.n_signals, self.targets, self.omega, self.tau = ns, tg, om, ta
+        self.n_signals, self.targets, self.omega, self.tau, self.hinge_channels = ns, tg, om, ta, bool(hinge_channels)
 
     def __repr__(self):
         return (f"SignalSpec({len(self.terms)} terms, n_signals={self.n_signals}, targets={None if self.targets is None else self.targets.shape}, "
@@ -415,6 +447,7 @@ class SignalSpec:
 
     @property
     def has_force(self):
+        """a block-force or hinge-force term: evaluated on the device only"""
         return any(c >= FORCE for _, _, c, _ in self.terms)
 
     @classmethod
@@ -438,20 +471,39 @@ class SignalSpec:
             raise ValueError("block_dofs must be a non-empty sequence of (block, dof) with dof in 0..2")
         return cls([(0, int(b), FORCE + int(d), float(scale)) for b, d in bd], 1, targets, omega, tau)
 
+    @classmethod
+    def hinge_force(cls, block_node_dofs, targets=None, omega=None, tau=None):
+        """One signal per (block, node, dof): the force component dof (0, 1, 2 = x, y, moment) that the hinge on ``node`` of ``block``
+        carries -- a ligament against a load cell or a strain gauge."""
+        bnd = np.array(block_node_dofs, dtype=np.int64).reshape(-1, 3)
+        if len(bnd) == 0 or (bnd[:, 0] < 0).any():
+            raise ValueError("block_node_dofs must be a non-empty sequence of (block, node, dof) with block >= 0")
+        return cls([(s, int(b), hinge_component(n, d), 1.0) for s, (b, n, d) in enumerate(bnd)], len(bnd), targets, omega, tau, True)
+
+    @classmethod
+    def cut_force(cls, hinges, dofs=(0, 1), scale=1.0, targets=None, omega=None, tau=None):
+        """One signal per dof of ``dofs``: ``scale`` times the sum of that force component over ``hinges``, a sequence of (block, node) --
+        the resultant through a line of hinges (``bonds_across``: the force transmitted into a region)."""
+        hg = np.array(hinges, dtype=np.int64).reshape(-1, 2)
+        dofs = [int(d) for d in np.atleast_1d(dofs)]
+        if len(hg) == 0 or (hg[:, 0] < 0).any() or not dofs or len(set(dofs)) != len(dofs):
+            raise ValueError("hinges must be a non-empty sequence of (block, node) with block >= 0 and dofs a non-empty sequence of distinct dofs")
+        return cls([(s, int(b), hinge_component(n, d), float(scale)) for s, d in enumerate(dofs) for b, n in hg], len(dofs), targets, omega, tau, True)
+
     def with_targets(self, targets, omega=None, tau=None):
         """The same terms against other targets and weights."""
-        return SignalSpec(self.terms, self.n_signals, targets, omega, tau)
+        return SignalSpec(self.terms, self.n_signals, targets, omega, tau, self.hinge_channels)
 
 
 def host_signal_values(spec, fields):
     """NumPy restatement of the signals of a ``SignalSpec`` whose terms are field components (displacement, velocity): ``fields``
-    (batch, T, 2, n_blocks, 3) -> (batch, T, n_signals), or (T, 2, n_blocks, 3) -> (T, n_signals).  Force components have no host path
-    (``ValueError``): they are evaluated on the device, that is the point of ``DynamicSolver.signal_values``."""
+    (batch, T, 2, n_blocks, 3) -> (batch, T, n_signals), or (T, 2, n_blocks, 3) -> (T, n_signals).  Force and hinge-force components have
+    no host path (``ValueError``): they are evaluated on the device, that is the point of ``DynamicSolver.signal_values``."""
     f = np.asarray(fields, dtype=float)
     if f.ndim not in (4, 5) or f.shape[-3] != 2 or f.shape[-1] != 3:
         raise ValueError(f"fields must be (batch, T, 2, n_blocks, 3) or (T, 2, n_blocks, 3), got {f.shape}")
     if spec.has_force:
-        raise ValueError("host_signal_values: force components are evaluated on the device only (DynamicSolver.signal_values)")
+        raise ValueError("host_signal_values: force and hinge-force components are evaluated on the device only (DynamicSolver.signal_values)")
     out = np.zeros(f.shape[:-3] + (spec.n_signals,))
     for s, b, c, coef in spec.terms:
         if b >= f.shape[-2]:

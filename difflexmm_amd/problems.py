@@ -1406,6 +1406,67 @@ def TargetWaveDelay(forward, source_block_dofs, target_block_dofs, kind, max_lag
     return TargetCrossCorrelation(forward, spec)
 
 
+def _cut_hinges(forward, blocks_inside, who):
+    """The forward problem set up, and the hinges through which ``blocks_inside`` hangs on the rest of the lattice."""
+    from .objective import bonds_across
+    if not getattr(forward, "is_setup", False):
+        forward.setup()
+    geo = forward.geometry
+    inside = np.asarray(blocks_inside, dtype=np.int64).reshape(-1)
+    if inside.size == 0 or inside.min() < 0 or inside.max() >= geo.n_blocks:
+        raise ValueError(f"{who}: blocks_inside must be a non-empty sequence of blocks in [0, {geo.n_blocks})")
+    hinges = bonds_across(geo.bond_connectivity(), geo.n_npb, inside)
+    if not hinges:
+        raise ValueError(f"{who}: no ligament joins blocks_inside to the rest of the lattice")
+    return hinges
+
+
+def TargetTransmittedForce(forward, blocks_inside, dofs=(0, 1), tau=None):
+    """A ``TargetSignalMisfit`` on zero targets whose value is 1/2 sum_k tau_k |resultant_k|^2: the resultant, per dof of ``dofs``, of the
+    force that the hinges between ``blocks_inside`` and the rest of the lattice carry (``objective.bonds_across``,
+    ``SignalSpec.cut_force``) -- the force transmitted into a protected region, to be minimised.  ``tau`` (T,) or None = ones over the
+    forward problem's own output times.  Hinge forces are evaluated on the device: one design needs ``on_device=True``."""
+    from .objective import SignalSpec
+    hinges = _cut_hinges(forward, blocks_inside, "TargetTransmittedForce")
+    tp = getattr(forward, "timepoints", None)
+    if tp is None:
+        raise ValueError("TargetTransmittedForce: the forward problem has no output times of its own")
+    sig = SignalSpec.cut_force(hinges, dofs)
+    return TargetSignalMisfit(forward, sig.with_targets(np.zeros((np.shape(tp)[-1], sig.n_signals)), None, tau))
+
+
+def TargetCutEnergy(forward, blocks_inside, sign=+1):
+    """A ``TargetCrossCorrelation`` whose value is ``sign`` times the work done on ``blocks_inside`` through its boundary hinges,
+
+        W = -dt * sum_k sum_h sum_d f_hd(t_k) v_{b(h) d}(t_k)
+
+    with h the hinges between the region and the rest of the lattice (``objective.bonds_across``), f_hd their force channels (dE_h/du of
+    the hinge's own block b(h): the hinge pulls on the block with minus that), v the velocity of that block and d = x, y, theta.  This
+    is a RECTANGLE RULE on the forward problem's output times t_k with their spacing dt: as accurate as the outputs are dense.  Built as
+    the lag-0 value of the un-normalised correlation (``CorrelationSpec(normalisation="none", reduce="at", lag=0, w_peak=-sign * dt)``)
+    of one pair per boundary hinge and dof -- that hinge-force signal against the velocity signal of the hinge's block -- so it comes
+    with gradients on the kept solve.  ``sign=-1`` turns a minimiser into a maximiser of the delivered energy.  Lags are output indices:
+    per-member or non-uniform output times are refused, as in ``TargetWaveDelay``.  ``hinges``: the boundary hinges (block, node)."""
+    from .objective import VELOCITY, CorrelationSpec, SignalSpec, hinge_component
+    hinges = _cut_hinges(forward, blocks_inside, "TargetCutEnergy")
+    tp = getattr(forward, "timepoints", None)
+    if tp is None or np.ndim(tp) != 1:
+        raise ValueError("TargetCutEnergy: the forward problem has no output times of its own shared by all members (per-member timepoints)")
+    dt = np.diff(np.asarray(tp, dtype=float))
+    if len(dt) < 1 or not np.isfinite(dt).all() or (dt <= 0).any() or np.abs(dt - dt.mean()).max() > 1e-9 * abs(dt.mean()):
+        raise ValueError("TargetCutEnergy: the output times are not uniformly spaced (relative 1e-9): W is a rectangle rule with one dt")
+    if sign not in (1, -1):
+        raise ValueError(f"TargetCutEnergy: sign must be +1 or -1, got {sign!r}")
+    hd = [(b, n, d) for b, n in hinges for d in range(3)]
+    terms = [(i, b, hinge_component(n, d), 1.0) for i, (b, n, d) in enumerate(hd)]
+    terms += [(len(hd) + i, b, VELOCITY + d, 1.0) for i, (b, n, d) in enumerate(hd)]
+    spec = CorrelationSpec(SignalSpec(terms, 2 * len(hd), hinge_channels=True), [(i, len(hd) + i) for i in range(len(hd))], 0, None, "none", "at", 0, None,
+                           -sign * float(dt.mean()))
+    out = TargetCrossCorrelation(forward, spec)
+    out.hinges = hinges
+    return out
+
+
 class MultiInputTargetKineticEnergy:
     """weights @ [target kinetic energy of every forward problem], all sharing one design
     (problems/quads_focusing_multi_input.py:43-86).  The forward problems differ in their boundary conditions

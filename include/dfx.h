@@ -288,7 +288,7 @@ int dfx_forward_tangent_dense_multi(dfx_handle* h, const double* state0, const d
 
 /* Forward-mode SIGNALS: the two _multi solves above with the history kept on the device.  Instead of fields / fields_dots the call
  * returns the signals of a term list (dfx_signal_values: terms (signal, block, component, coef), components 0..2 displacement, 3..5
- * velocity, 6..8 elastic force dE/d(x, y, theta) on the block) and their tangents: signals (batch, T, n_signals), from the first pass, and
+ * velocity, 6..8 elastic force dE/d(x, y, theta) on the block, 9 + 3 node + dof the part of it one hinge carries) and their tangents: signals (batch, T, n_signals), from the first pass, and
  * signals_dots (batch, n_dirs, T, n_signals) -- the columns of the Jacobian of a least-squares fit of those signals.  At the end of every
  * pass the force channels and their tangents K(u) du + (d grad_u E / dp) dp are evaluated on the pass's own buffers (one dual-number
  * evaluation of the ligament gradient per listed slot and output time, with the pass's parameter tangents), the terms are added in list
@@ -456,6 +456,15 @@ int dfx_strain_peak_value_and_grad(dfx_handle* h, const double* bond_coef, int32
  * ligament plus angle-contact energy the handle was created with, at output configuration k with member m's parameters, prescribed DOFs at
  * the values the fields hold (no damping, no loading, no velocity: what dfx_rhs gives for a state at rest, times the inertia, with the sign
  * of an energy gradient).
+ * component 9 + 3 n + d (n = 0 .. nodes per block - 1, d = 0, 1, 2): the HINGE force dE_h/d(x, y, theta)_block, E_h the energy of the one
+ * ligament on node n of the block -- its bond energy and, with the angle contact, the penalty of its two void angles: the summand of
+ * components 6..8, with their sign and units (the hinge pulls on the block with minus it; the hinge channels of a block add up to its
+ * components 6..8; on the two ends of a ligament the x and y channels are opposite).  What one ligament carries, and -- summed over a line
+ * of hinges -- what crosses a cut; paired with a velocity in dfx_signal_xcorr_value (DFX_XCORR_NORM_NONE, lag 0) the energy that crosses it.
+ * Its cotangent is Hess(E_h) w_h on both end blocks, its explicit terms reach the parameters of that ligament alone.
+ * The hinge components are OFF on a new handle -- component 9 and above are then out of range, as they were before these channels
+ * existed -- and dfx_signal_hinge_channels(h, 1) switches them on for every entry that takes signal terms (these, the projections, the
+ * cross-correlation, dfx_forward_tangent_signals_*), until dfx_signal_hinge_channels(h, 0).  Returns 0.
  * Terms are parallel arrays of n_terms entries (term_signal in 0..n_signals-1, term_block, term_component, term_coef); a signal adds its
  * terms in list order.  targets: (batch, T, n_signals) when targets_per_member != 0, else (T, n_signals); signal_weights omega: (n_signals,)
  * or NULL = ones; time_weights tau: EXACTLY T doubles or NULL = ones.
@@ -471,8 +480,10 @@ int dfx_strain_peak_value_and_grad(dfx_handle* h, const double* bond_coef, int32
  * shared checkpoint are those of dfx_strain_objective_value_and_grad; without reference_vector / k_bond / contact in `want` the reverse
  * sweep runs the same builds as for the kinetic kinds.  Signals of field components alone work for every physics the sweep serves.
  * Return 1 (dfx_last_error says why): no forward pass (no kept trajectory for the gradient call), a signal, block or component out of
- * range, a signal without terms, a NULL or non-finite argument, force components on a problem with the distance-based contact or with
- * nodes that carry more than one ligament. */
+ * range, a signal without terms, a NULL or non-finite argument, force or hinge components on a problem with the distance-based contact or
+ * with nodes that carry more than one ligament, a hinge component while they are off, on a node the lattice's blocks do not have or on one
+ * that carries no ligament. */
+int dfx_signal_hinge_channels(dfx_handle* h, int32_t enable);
 int dfx_signal_values(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block, const int32_t* term_component,
                       const double* term_coef, int32_t n_signals, double* values);
 int dfx_signal_misfit_value(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block,
@@ -484,7 +495,7 @@ int dfx_signal_misfit_value_and_grad(dfx_handle* h, int32_t n_terms, const int32
                                      double* objective, const dfx_grads* want, dfx_grads* views, int32_t device_views, dfx_stats* stats);
 
 /* Signal projections on the device-resident history (HIP library only): the signals S_mks of dfx_signal_values (the same term arrays, the
- * same components 0..8) projected on n_rows rows of a time basis, and a weighted quadratic form of the coefficients -- band power (a cos
+ * same components 0..20) projected on n_rows rows of a time basis, and a weighted quadratic form of the coefficients -- band power (a cos
  * and a sin row per frequency with equal weights), transmission at the drive frequency, harmonic generation, a matched filter (one row
  * holding the shifted template).  For member m, signal s and row j
  *   P_msj = sum_k B_jk S_mks                              k = 0 .. T-1
