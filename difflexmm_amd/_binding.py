@@ -75,7 +75,8 @@ COMM_EXPORTS = ["dfx_comm_unique_id", "dfx_comm_init", "dfx_comm_destroy", "dfx_
                 "dfx_signal_misfit_value_and_grad", "dfx_signal_projections", "dfx_signal_projection_value",
                 "dfx_signal_projection_value_and_grad", "dfx_forward_tangent_signals_multi", "dfx_forward_tangent_signals_dense_multi",
                 "dfx_signal_xcorr", "dfx_signal_xcorr_value", "dfx_signal_xcorr_value_and_grad", "dfx_strain_peak_value",
-                "dfx_strain_peak_value_and_grad"]
+                "dfx_strain_peak_value_and_grad", "dfx_fn_table_values", "dfx_fn_table_grads", "dfx_fn_table_grad", "dfx_drive_cotangent",
+                "dfx_fn_table_tangents"]
 EXPORTS = EXPORTS + COMM_EXPORTS
 
 
@@ -193,6 +194,12 @@ def declare(lib):
         peak = [_dp, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, C.c_double, _dp, _dp, _ip]      # coef, weights, tau, aggregate, sharpness, outputs
         lib.dfx_strain_peak_value.argtypes = [H] + peak
         lib.dfx_strain_peak_value_and_grad.argtypes = [H] + peak + [C.POINTER(dfx_grads), C.POINTER(dfx_grads), C.c_int32, C.POINTER(dfx_stats)]
+    if hasattr(lib, "dfx_fn_table_grads"):
+        lib.dfx_fn_table_values.argtypes = [H, C.c_int32, _dp, C.c_int32]
+        lib.dfx_fn_table_grads.argtypes = [H, C.c_int32]
+        lib.dfx_fn_table_grad.argtypes = [H, C.c_int32, _dp]
+        lib.dfx_drive_cotangent.argtypes = [H, C.c_int32, _dp, _dp, C.c_int64, C.POINTER(C.c_int64)]
+        lib.dfx_fn_table_tangents.argtypes = [H, C.c_int32, _dp, C.c_int32]
     if hasattr(lib, "dfx_comm_init"):
         lib.dfx_comm_unique_id.argtypes = [C.c_char_p]
         lib.dfx_comm_init.argtypes = [C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(H)]
@@ -362,6 +369,7 @@ class Engine:
                 prob.fn_table_n[f], prob.fn_table[f] = len(tv) // 2, tv.ctypes.data_as(_dp)
             else:
                 prob.fn_table_n[f], prob.fn_table[f] = 0, None
+        self.fn_table_n = [int(prob.fn_table_n[f]) for f in range(DFX_MAX_FNS)]
         self._h = C.c_void_p()
         rc = self.lib.dfx_create(C.byref(prob), C.byref(self._h))
         if rc != 0:
@@ -1094,6 +1102,60 @@ class Engine:
                                                              C.byref(views), int(bool(device)), C.byref(st)),
                     "dfx_signal_xcorr_value_and_grad")
         return obj, peak, delay, self._grad_views(views, names, device), _stats(st)
+
+    # -- the samples of a table drive as a differentiable leaf ------------------------------------------------
+    @property
+    def has_fn_table_grads(self):
+        return hasattr(self.lib, "dfx_fn_table_grads")
+
+    def _need_table(self, entry):
+        self._need(entry, "table-sample gradients", self._STALE)
+
+    def fn_table_values(self, fn, values):
+        """New values of the table of time function ``fn`` (``dfx_fn_table_values``): (n_tab,) for all members or (batch, n_tab).  They
+        hold for every later solve; the kept trajectory is dropped, as by :meth:`set_params`."""
+        self._need_table("dfx_fn_table_values")
+        n = self.fn_table_n[int(fn)] if 0 <= int(fn) < DFX_MAX_FNS else 0
+        v = _f64(values)
+        if v.shape not in ((n,), (self.batch, n)):
+            raise ValueError(f"fn_table_values: values must be ({n},) or ({self.batch}, {n}), got {v.shape}")
+        self._check(self.lib.dfx_fn_table_values(self._h, int(fn), _ptr(v), int(v.ndim == 2)), "dfx_fn_table_values")
+
+    def fn_table_grads(self, enable=True):
+        """Opt in (or out): every later reverse sweep keeps the cotangent of the drive per stage and reduces it onto the samples of the
+        table functions (``dfx_fn_table_grads``)."""
+        self._need_table("dfx_fn_table_grads")
+        self._check(self.lib.dfx_fn_table_grads(self._h, int(bool(enable))), "dfx_fn_table_grads")
+
+    def fn_table_grad(self, fn):
+        """(batch, n_tab) gradient of the samples of table function ``fn`` from the last reverse sweep (``dfx_fn_table_grad``)."""
+        self._need_table("dfx_fn_table_grad")
+        out = np.zeros((self.batch, max(self.fn_table_n[int(fn)] if 0 <= int(fn) < DFX_MAX_FNS else 0, 1)))
+        self._check(self.lib.dfx_fn_table_grad(self._h, int(fn), _ptr(out)), "dfx_fn_table_grad")
+        return out
+
+    def drive_cotangent(self, member=0):
+        """(times (n,), gbar (n_fns, n)) of one member from the last reverse sweep (``dfx_drive_cotangent``): the stage times in order
+        and the cotangent of every drive value g_f there."""
+        self._need_table("dfx_drive_cotangent")
+        n = C.c_int64(0)
+        self._check(self.lib.dfx_drive_cotangent(self._h, int(member), None, None, 0, C.byref(n)), "dfx_drive_cotangent")
+        times, gbar = np.zeros(n.value), np.zeros((max(self.n_fns, 1), n.value))
+        self._check(self.lib.dfx_drive_cotangent(self._h, int(member), _ptr(times), _ptr(gbar), n.value, C.byref(n)), "dfx_drive_cotangent")
+        return times, gbar[:self.n_fns]
+
+    def fn_table_tangents(self, fn, values_dots):
+        """Per-direction sample tangents (n_dirs, batch, n_tab) of table function ``fn`` for the forward-mode entries
+        (``dfx_fn_table_tangents``); None clears them."""
+        self._need_table("dfx_fn_table_tangents")
+        if values_dots is None:
+            self._check(self.lib.dfx_fn_table_tangents(self._h, int(fn), None, 0), "dfx_fn_table_tangents")
+            return
+        v = _f64(values_dots)
+        n = self.fn_table_n[int(fn)] if 0 <= int(fn) < DFX_MAX_FNS else 0
+        if v.ndim != 3 or v.shape[1:] != (self.batch, n):
+            raise ValueError(f"fn_table_tangents: values_dots must be (n_dirs, {self.batch}, {n}), got {v.shape}")
+        self._check(self.lib.dfx_fn_table_tangents(self._h, int(fn), _ptr(v), v.shape[0]), "dfx_fn_table_tangents")
 
     def response_data(self, strains=True, kinetic=True):
         """Per-ligament strain energies (batch, T, n_bonds) x 3 and per-block kinetic energy (batch, T, n_blocks) of the last

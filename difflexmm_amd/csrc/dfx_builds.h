@@ -16,6 +16,7 @@ struct BuildQuery {
   bool k_uniform, l_dict_on, l_dict_lds, damping_uniform, t_steps, AD, clock;
   bool records;                 // the stage records live in the trajectory checkpoint (DevCtx::rps > 1)
   bool fn_tab, g_b;             // the segment's time-function table is there; per-ligament gradients are wanted
+  bool trace = false;           // the drive cotangent is kept per stage (dfx_fn_table_grads)
 };
 constexpr int kStageBuilds = 6;       // per-stage builds exist for the stages 0 .. 5
 
@@ -25,9 +26,10 @@ struct FwdBuild {
   int istage, recs;             // ISTAGE (-1: the generic build) and, for a per-stage build, RECS
   bool packed_grid;             // the grid of the packed mapping (DevCtx::n_wg3), else the slot grid
 };
-enum AdjKind { kAdjGeneric, kAdjBondGrads, kAdjRebuild, kAdjOvf };
+enum AdjKind { kAdjGeneric, kAdjBondGrads, kAdjRebuild, kAdjOvf, kAdjTrace };
 struct AdjBuild {
-  AdjKind kind;       // generic: k_adj_stage<M, C, 0, 0, NPB, TAB, 0, WT, ISTAGE>; bond_grads: <M, C, 1, 1>; rebuild: k_adj_stage_rb; ovf: <M, C, 1, 1, 4, 0, 1>
+  AdjKind kind;       // generic: k_adj_stage<M, C, 0, 0, NPB, TAB, 0, WT, ISTAGE>; bond_grads: <M, C, 1, 1>; rebuild: k_adj_stage_rb; ovf: <M, C, 1, 1, 4, 0, 1>;
+                      // trace: k_adj_stage_trace<M, C> (the bond_grads build + the drive-cotangent trace)
   int npb, tab, wt, istage;
   bool packed_grid;
 };
@@ -56,6 +58,9 @@ inline FwdBuild select_fwd_build(const BuildQuery& q, int i, int in_buf, int out
 
 inline AdjBuild select_adj_build(const BuildQuery& q, int i, int local_only) {
   if (q.n_ovf) return {kAdjOvf, q.contact != 2 ? 4 : 0, 0, 0, -1, false};      // general bond lists: one build for every checkpoint level
+  // sample gradients of a table drive: like per-ligament gradients, one build for every checkpoint level, off the per-stage builds (the
+  // engine refuses the request on general bond lists before it launches; the single-stage hook keeps its build)
+  if (q.trace && !local_only) return {kAdjTrace, 4, 0, 0, -1, false};
   if (q.g_b) return {kAdjBondGrads, 4, 0, 0, -1, false};
   if (q.AD) return {kAdjRebuild, 4, 0, 0, -1, false};
   const bool tab = q.fn_tab && !local_only;

@@ -60,4 +60,11 @@ __global__ __launch_bounds__(kThreads) void k_adj_stage_dense(DevCtx c, AdjCoef 
   adj_stage_body<MODEL, CONTACT, BOND_GRADS, BOND_GRADS, 4, 1, 0, 0, -1, 1>(c, ac, i, j, -1 - i, -1, 0, rc, 0, dn);
 }
 
+// ... and the build with per-ligament gradients that also keeps the drive cotangent per stage (TraceCtx, dfx_fn_table_grads)
+template <int MODEL, int CONTACT>
+__global__ __launch_bounds__(kThreads) void k_adj_stage_dense_trace(DevCtx c, AdjCoef ac, DenseCtx dn, int i, int j, TraceCtx tr) {
+  StageCoef rc;
+  adj_stage_body<MODEL, CONTACT, 1, 1, 4, 1, 0, 0, -1, 1, 1>(c, ac, i, j, -1 - i, -1, 0, rc, 0, dn, tr);
+}
+
 }  // namespace

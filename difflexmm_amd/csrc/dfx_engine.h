@@ -7,6 +7,7 @@
 //   engine_objective.hip objectives on the device-resident history (kernels: dfx_objective.h): a prepare_* and a launch_* per family, one
 //                        sweep driver (objective_sweep) behind every gradient entry
 //   engine_abi.hip       create / destroy / set_params / reserve, test hooks, post-processing, downloads
+//   engine_drive.hip     the samples of a table drive as a leaf: per-member values, the drive-cotangent trace and its reduction (dfx_drive.h)
 // The kernels live in dfx_kernels.h (stage kernels: instantiated by engine_launch.hip, the reverse per-stage builds by stage_builds_adj.hip)
 // and dfx_persist.hip.
 #pragma once
@@ -125,6 +126,19 @@ struct dfx_handle {
   DevBuf<uint8_t> d_l_idx;
   DevBuf<TimeFn> d_fns;
   DevBuf<double> d_fn_table[DFX_MAX_FNS];
+  // table drives whose samples are a differentiable leaf (engine_drive.hip): per-member copies of a table (times then values, set by
+  // dfx_fn_table_values; TimeFn::tab of every member then points at its own), the opt-in of dfx_fn_table_grads, the drive-cotangent trace of
+  // the last reverse sweep with its stage times ([member][row][stage]; gbar: [member][function][row][stage]) and the sample gradients
+  // reduced from it, and the per-direction sample tangents of dfx_fn_table_tangents ([direction][member][sample]; tab_dots_n: how many)
+  DevBuf<double> d_fn_table_m[DFX_MAX_FNS];
+  bool fn_table_member[DFX_MAX_FNS] = {false, false};
+  bool table_grads = false, have_trace = false;
+  long long trace_rows = 0;
+  DevBuf<double> d_gbar, d_gtimes, d_tab_grad[DFX_MAX_FNS];
+  int tab_dots_n[DFX_MAX_FNS] = {0, 0};
+  DevBuf<double> d_tab_dots[DFX_MAX_FNS];
+  hipEvent_t ev_red0 = nullptr, ev_red1 = nullptr;      // DFX_TIMING: around the reduction (trace_report)
+  bool trace_timed = false;
   DevBuf<Seg> d_segs, d_cur;
   DevBuf<Clock> d_clock;
   DevBuf<double> d_err_partial, d_ts;
@@ -199,7 +213,10 @@ struct dfx_handle {
   std::map<std::pair<int, int>, hipGraphExec_t> graphs;
   // what the cached graphs have baked in: every kernel argument (the DevCtx passed by value) and the addresses the tick node
   // reads and writes (segment table, cursors) -- any of them changing (a buffer re-allocated by a larger solve) drops the graphs
-  struct GraphKey { DevCtx ctx; const void* segs; const void* seg_idx; const void* cur; int pair_fwd, pair_adj, pair_rows, pad; } graph_key;
+  // ... and what the TRACE builds of the reverse stage take besides (TraceCtx, by value in the kernel nodes: dfx_fn_table_grads switched on or
+  // off, the trace buffer re-allocated, another number of rows)
+  struct GraphKey { DevCtx ctx; const void* segs; const void* seg_idx; const void* cur; int pair_fwd, pair_adj, pair_rows, trace;
+                    const void* gbar; long long trace_rows; } graph_key;
   bool graph_ctx_valid = false;
   // the adaptive controller's graph of 32 attempts (small lattices only), valid for the arguments it was captured with
   hipGraphExec_t adaptive_exec = nullptr;
@@ -311,6 +328,15 @@ int collect_grads(dfx_handle* h, const dfx_grads* want, dfx_grads* grads, dfx_gr
 void set_grad_wishes(dfx_handle* h, const dfx_grads* g);
 int run_adjoint(dfx_handle* h, const dfx_grads* want, dfx_grads* grads, dfx_grads* views, dfx_stats* stats, bool kinetic, int n_target,
     bool accumulators_cleared = false);
+// engine_drive.hip: the drive-cotangent trace around a reverse sweep (no-ops unless dfx_fn_table_grads switched it on): refusals, the
+// zeroed trace of `rows` step ordinals (before the sweep's first launch), and behind the sweep the stage times and the reduction onto
+// the samples of every table function (n_acc: the members' accepted steps, kept adaptive solve; null otherwise); what a stage launch takes
+int trace_begin(dfx_handle* h, long long rows);
+int trace_finish(dfx_handle* h, const DevCtx& c, const int* n_acc);
+TraceCtx trace_ctx(const dfx_handle* h);
+void trace_report(dfx_handle* h);              // DFX_TIMING: the reduction's device time, after the sweep has been waited for
+void patch_member_tables(dfx_handle* h);
+void release_drive_buffers(dfx_handle* h);
 // engine_objective.hip: the explicit terms of the objective call in flight (h->obj_job), queued behind the sweep
 void launch_objective_explicit(dfx_handle* h, const DevCtx& c);
 // engine_objective.hip: the term list of a signal call (dfx_signal_*, dfx_forward_tangent_signals_*), checked (return 1 with h->err: a

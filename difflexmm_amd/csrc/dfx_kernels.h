@@ -110,6 +110,14 @@ struct DenseCtx {
   int n_out, pad;
 };
 
+// The drive-cotangent trace (dfx_fn_table_grads): the TRACE builds of the reverse stage keep the cotangent of the drive value g_f at
+// every stage time instead of only folding it with the five parameter partials -- gbar[m][f][n][i], member m, time function f, step
+// ordinal n (rows of them per function: one more than the sweep has steps), stage i.  dfx_drive.h reduces it onto the samples of a table.
+struct TraceCtx {
+  double* gbar;          // batch * n_fns * rows * s, zeroed before the sweep
+  long long rows;
+};
+
 // arguments of the adaptive controller inside the persistent stage loop (dfx_persist_dense.h)
 struct AdaptLoopCoef {          // Dormand-Prince with embedded error and dense output (dfx_physics.h: Dopri), acceleration form
   double a[7][7], aa[7][7], e[7], ee[7], cm[7], cma[7], c[7];
@@ -1128,7 +1136,9 @@ __global__ __launch_bounds__(kThreads) void k_rebuild_first(DevCtx c, StageCoef 
 //   wbuf_static: >= 0 selects the (w, kbar_q) input buffer (test hook); -1: parity of the stage ordinal
 //   BOND_GRADS: also accumulate d/d(reference vector, stiffnesses, contact constants) (only when the caller asks for them:
 //   a compile-time switch, the dual parts of those derivatives are dead code otherwise)
-template <int MODEL, int CONTACT, int BOND_GRADS, int REBUILD, int NPB = 4, int TAB = 0, int OVF = 0, int WT = 0, int ISTAGE = -1, int DENSE = 0>
+template <int MODEL, int CONTACT, int BOND_GRADS, int REBUILD, int NPB = 4, int TAB = 0, int OVF = 0, int WT = 0, int ISTAGE = -1, int DENSE = 0,
+          int TRACE = 0>
+//   TRACE: also keep the cotangent of every drive value per stage (TraceCtx; builds of their own: k_adj_stage_trace, k_adj_stage_dense_trace)
 //   REBUILD (compile-time: the rebuild code and its registers exist only in the stage-checkpoint build), rb > 0: after its own work the launch rebuilds stage record rb -- of the same step when i >= 2
 //   (rb = i - 1, read by the next reverse launch), of the previous step when i == 0 (rb = s - 1); rc = stage_coef(rb - 1)
 //   NPB: lanes per block (lane_pos); the packed mapping exists for the records build only
@@ -1137,7 +1147,8 @@ template <int MODEL, int CONTACT, int BOND_GRADS, int REBUILD, int NPB = 4, int 
 //   (N_m, 0) is the extra evaluation at the final state: a step of size zero), and the cotangents of the outputs enter through the dense
 //   output -- an output inside step n adds g to lambda_n and h_n B_j g to Kbar_j, the FSAL slope's share (j = 6) joins Kbar_0 of step n + 1
 __device__ __forceinline__ void adj_stage_body(const DevCtx& c_arg, const AdjCoef& ac, int i_arg, int j, int in_buf, int wbuf_static,
-                                               int local_only, const StageCoef& rc, int rb, const DenseCtx& dn = DenseCtx{}) {
+                                               int local_only, const StageCoef& rc, int rb, const DenseCtx& dn = DenseCtx{},
+                                               const TraceCtx& tr = TraceCtx{}) {
   // ISTAGE: see k_fwd_stage.  The per-stage builds take the stage index and the PARAMETER shape (uniform stiffnesses / damping, LDS
   // dictionary, equal steps) as constants -- launch 29.7 -> 29.1 us, 112 VGPRs -- but not the buffer / mode arguments: with those
   // folded as well (in_buf, local_only, wbuf, rb, AD, clock) three variants measured 0.6 - 1.5 us SLOWER although they shed more
@@ -1415,6 +1426,9 @@ __device__ __forceinline__ void adj_stage_body(const DevCtx& c_arg, const AdjCoe
       for (int f = 0; f < c.n_fns; ++f) {
         const double coef = constrained ? -hw * sp.con_coef[k][f] : w_d * sp.load_coef[k][f];
         const bool loaded = !constrained && sp.load_coef[k][f] != 0.0;
+        if constexpr (TRACE) {      // up to 3 DOF lanes of every special block share an entry
+          if (coef != 0.0) acc_add(tr.gbar + ((((size_t)m * (u32)c.n_fns + f) * (size_t)tr.rows + (size_t)n) * (u32)c.s + (u32)i), coef);
+        }
         if ((coef != 0.0 && c.fn_g) || loaded) {
           double g, gt;
           if (TAB) {
@@ -1486,6 +1500,14 @@ template <int MODEL, int CONTACT>
 __global__ __launch_bounds__(kThreads) DFX_ADJ_RB_OCC void k_adj_stage_rb(DevCtx c, AdjCoef ac, int i, int j, int in_buf, int wbuf_static,
                                                            int local_only, StageCoef rc, int rb) {
   adj_stage_body<MODEL, CONTACT, 0, 1>(c, ac, i, j, in_buf, wbuf_static, local_only, rc, rb);
+}
+
+// The TRACE build: the build with per-ligament gradients (it serves every checkpoint level: records, stages, state, segments) that also
+// keeps the drive cotangent per stage.  One per (model, contact): a request for sample gradients routes the sweep here (select_adj_build).
+template <int MODEL, int CONTACT>
+__global__ __launch_bounds__(kThreads) DFX_ADJ_OCC void k_adj_stage_trace(DevCtx c, AdjCoef ac, int i, int j, int in_buf, int wbuf_static,
+                                                              int local_only, StageCoef rc, int rb, TraceCtx tr) {
+  adj_stage_body<MODEL, CONTACT, 1, 1, 4, 0, 0, 0, -1, 0, 1>(c, ac, i, j, in_buf, wbuf_static, local_only, rc, rb, DenseCtx{}, tr);
 }
 
 // start of the reverse sweep: lambda_N = G_last; kbar_{s-1} of the last step into buffer `buf`

@@ -92,6 +92,10 @@ struct TanCtx {
   int t0_stride;                 // 1: one t0 per member, 0: shared
   int a_rows;                    // places per member in A / DA: n_stages, or 7 in the dense pass (A_6 = the FSAL acceleration)
   const long long* n_steps;      // B: the step count N_m of every member (dense pass), or null: every member takes every step
+  // sample tangents of table drives (dfx_fn_table_tangents): per function (tab_dirs, B, n_tab) or null; tab_k0: the call's direction that
+  // is direction 0 of this pass (a spare direction of the last chunk, tab_k0 + k >= tab_dirs, has no tangent)
+  const double* tabdot[DFX_MAX_FNS];
+  int tab_k0, tab_dirs;
 };
 
 struct TanStage {
@@ -164,9 +168,11 @@ DFX_HD DualN<K> tan_scalar_n(const double* p, int vi, int ti, int stride) {
 
 // sum over f of coef_f * g_f(t), its time derivative, and per direction the tangent sum coef_f * dg_f/dp . dp_f; the time functions are
 // evaluated once
+// (dir0: direction 0 of this slice within the pass.  A table whose samples carry tangents adds A interp(tau; T, dY_k) per direction: the
+// bin and the weight are found once per evaluation, by eval_time_fn's own branches, and serve all K directions)
 template <int K>
 DFX_HD void tan_drive_n(const TanCtx& c, int m, const double* mem /* the member's image of this slice */, const double* coef /* DFX_MAX_FNS */,
-                        double t, double& g_sum, double& gt_sum, double (&dg_sum)[K]) {
+                        double t, double& g_sum, double& gt_sum, double (&dg_sum)[K], int dir0) {
   g_sum = 0.0; gt_sum = 0.0;
   DFX_DN_EACH dg_sum[k] = 0.0;
   const double* dfn = mem + 3 + 3;
@@ -180,6 +186,27 @@ DFX_HD void tan_drive_n(const TanCtx& c, int m, const double* mem /* the member'
       double dg = 0.0;
       for (int j = 0; j < kMaxFnParams; ++j) dg += gp[j] * dfn[kTanMemDir * k + f * DFX_FN_PARAMS + j];
       dg_sum[k] += coef[f] * dg;
+    }
+    const TimeFn& tf = c.fns[(size_t)m * DFX_MAX_FNS + f];
+    if (c.tabdot[f] && tf.type == kFnTable) {
+      const int n = tf.n_tab;
+      const double* T = tf.tab;
+      const double tau = t - tf.p[1];
+      int lo = 0;
+      double w = 0.0;
+      if (tau >= T[n - 1]) { lo = n - 2; w = 1.0; }
+      else if (tau > T[0]) {
+        int hi = n - 1;
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (T[mid] <= tau) lo = mid; else hi = mid; }
+        w = (tau - T[lo]) / (T[hi] - T[lo]);
+      }
+      DFX_DN_EACH {
+        const int dir = c.tab_k0 + dir0 + k;
+        if (dir < c.tab_dirs) {
+          const double* dY = c.tabdot[f] + ((size_t)dir * c.B + m) * n;
+          dg_sum[k] += coef[f] * tf.p[0] * (dY[lo] + w * (dY[lo + 1] - dY[lo]));
+        }
+      }
     }
   }
 }
@@ -210,7 +237,7 @@ __global__ void k_tan_init_multi(TanCtx c, const double* state0, const double* s
       dv[k] = state0_dot ? state0_dot[k * s0_plane + (size_t)m * 2 * nd + nd + b * 3 + j] : 0.0;
     }
     if (sidx >= 0 && ((c.special[sidx].con_mask >> j) & 1)) {
-      tan_drive_n<K>(c, m, mem, c.special[sidx].con_coef[j], t0, q, v, dq);
+      tan_drive_n<K>(c, m, mem, c.special[sidx].con_coef[j], t0, q, v, dq, slice * K);
       DFX_DN_EACH dv[k] = 0.0;
     }
     r[j] = q; r[5 + j] = v;
@@ -332,8 +359,8 @@ __global__ void __launch_bounds__(256) k_tan_stage_multi(TanCtx c, Tableau T, Ta
       const dfx_special& sp = c.special[sidx];
       constrained = (sp.con_mask >> d) & 1;
       double unused;
-      if (constrained) tan_drive_n<K>(c, m, mem, sp.con_coef[d], t_next, cnext, cdnext, dcnext);
-      else tan_drive_n<K>(c, m, mem, sp.load_coef[d], t_i, fload, unused, dfload);
+      if (constrained) tan_drive_n<K>(c, m, mem, sp.con_coef[d], t_next, cnext, cdnext, dcnext, slice * K);
+      else tan_drive_n<K>(c, m, mem, sp.load_coef[d], t_i, fload, unused, dfload, slice * K);
     }
     const double v_i = rin[5 + d];
     const double inv_m = bk[d], damp = bk[3 + d];
@@ -498,7 +525,7 @@ __global__ void __launch_bounds__(256) k_tan_dense_multi(TanCtx c, TanDenseM dm)
         dov[k] = dopri_dense(dvn[k], dv1[k], dvmid[k], da0[k], da6[k], h, r);
       }
       if (constrained) {
-        tan_drive_n<K>(c, m, mem, c.special[sidx].con_coef[d], dn.ts[kk], oq, ov, doq);
+        tan_drive_n<K>(c, m, mem, c.special[sidx].con_coef[d], dn.ts[kk], oq, ov, doq, slice * K);
         DFX_DN_EACH dov[k] = 0.0;
       }
       const size_t row = ((size_t)m * dn.Tn + kk) * 2 * nd;

@@ -160,6 +160,7 @@ int dfx_destroy(dfx_handle* h) {
   h->d_p_r.release(); h->d_p_l.release(); h->d_p_k.release(); h->d_p_phi.release(); h->d_cst.release(); h->d_l_dict.release(); h->d_l_idx.release();
   h->d_inv_m.release(); h->d_damping.release(); h->d_fns.release(); h->d_p_c.release(); h->d_g_c.release();
   for (int f = 0; f < DFX_MAX_FNS; ++f) h->d_fn_table[f].release();
+  release_drive_buffers(h);
   h->d_segs.release(); h->d_cur.release(); h->d_seg_idx.release(); h->d_clock.release(); h->d_err_partial.release(); h->d_ts.release();
       h->d_step_counts.release(); h->d_acc_times.release(); h->d_tsteps.release();
   if (--h->ck->users == 0) { h->ck->traj.release(); h->ck->AD.release(); delete h->ck; }
@@ -196,6 +197,7 @@ int dfx_set_params(dfx_handle* h, const dfx_params* params) {
   const bool timing = getenv("DFX_TIMING") != nullptr;
   auto t0 = std::chrono::steady_clock::now();
   if (pack_params(h->pl, params, h->pp, h->err)) return 1;
+  patch_member_tables(h);          // (tables whose values were set per member: dfx_fn_table_values)
   auto t1 = std::chrono::steady_clock::now();
   const PackedParams& pp = h->pp;
   {

@@ -10,7 +10,8 @@ using namespace dfx_persist;
 static void launch_adj_dense(dfx_handle* h, const DevCtx& c, hipStream_t st, dim3 grid, const DenseCtx& dn, int i, int j) {
   const AdjCoef ac = adj_coef(h->pl.tab, i);
   with_physics<loop_physics>(h->pl.model, h->pl.contact, [&](auto M, auto C) {
-    if (c.g_b) hipLaunchKernelGGL((k_adj_stage_dense<M(), C(), 1>), grid, dim3(kThreads), 0, st, c, ac, dn, i, j);
+    if (h->table_grads) hipLaunchKernelGGL((k_adj_stage_dense_trace<M(), C()>), grid, dim3(kThreads), 0, st, c, ac, dn, i, j, trace_ctx(h));
+    else if (c.g_b) hipLaunchKernelGGL((k_adj_stage_dense<M(), C(), 1>), grid, dim3(kThreads), 0, st, c, ac, dn, i, j);
     else hipLaunchKernelGGL((k_adj_stage_dense<M(), C(), 0>), grid, dim3(kThreads), 0, st, c, ac, dn, i, j);
   });
   h->launches++;
@@ -42,6 +43,7 @@ int run_adjoint_dense(dfx_handle* h, const dfx_grads* want, dfx_grads* grads, df
   HIP_OK(hipMemsetAsync(h->d_LAM.p, 0, sizeof(double) * B * nb * 6, h->stream));
   HIP_OK(h->d_dw.ensure(B * (size_t)Tn * 8));
   HIP_OK(hipEventRecord(h->ev2, h->stream));
+  if (int rc = trace_begin(h, n_total + 1)) return rc;
   DenseCtx dn;
   dn.out_ptr = h->d_out_ptr.p; dn.dw = h->d_dw.p; dn.n_acc = h->d_nacc.p; dn.stride = h->a_stride; dn.n_out = Tn; dn.pad = 0;
   const int total_w = (int)(B * (size_t)Tn);
@@ -70,8 +72,10 @@ int run_adjoint_dense(dfx_handle* h, const dfx_grads* want, dfx_grads* grads, df
     hipLaunchKernelGGL(k_kinetic_mass_grad, g, dim3(64), 0, h->stream, c, (const double*)h->d_fields.p, (const int32_t*)h->d_target.p, n_target);
   }
   if (h->obj_job) launch_objective_explicit(h, c);
+  if (int rc = trace_finish(h, c, h->d_nacc.p)) return rc;
   HIP_OK(hipEventRecord(h->ev3, h->stream));
   if (int rc = collect_grads(h, want, grads, views, true)) return rc;
+  trace_report(h);
   if (*persist_give_up_word(h)) {
     // a workgroup of a persistent launch was not resident: one launch per stage from now on, and the sweep once more -- same process, same records
     persist_fell_back(h);

@@ -50,7 +50,7 @@ DevCtx make_ctx(dfx_handle* h) {
   c.POS = h->d_POS.p; c.VEL = h->d_VEL.p; c.A = h->d_A.p;
   c.YB = h->d_YB.p; c.LAM = h->d_LAM.p; c.W = h->d_W.p; c.KQ = h->d_KQ.p; c.G = h->d_G.p;
   // (general bond lists run the one reverse build that has them)
-  c.g_r = h->d_g_r.p; c.g_phi = h->d_g_phi.p; c.g_b = (h->want_bond_grads || pl.n_ovf) ? h->d_g_b.p : nullptr;
+  c.g_r = h->d_g_r.p; c.g_phi = h->d_g_phi.p; c.g_b = (h->want_bond_grads || pl.n_ovf || h->table_grads) ? h->d_g_b.p : nullptr;     // (the TRACE builds: the per-ligament ones)
   c.touch = h->d_touch.p;
   c.lam_pairs = (c.g_b || c.AD) ? 0 : 1;      // the REBUILD builds of the reverse stage (launch_adj) keep the scalar layout
   c.blk_m = h->d_blk_m.p; c.blk_c = h->want_damping_grads ? h->d_blk_c.p : nullptr;
@@ -126,6 +126,7 @@ static BuildQuery build_query(const dfx_handle* h, const DevCtx& c) {
   q.k_uniform = c.k_uniform; q.l_dict_on = c.l_dict_on; q.l_dict_lds = c.l_dict_lds; q.damping_uniform = c.damping_uniform;
   q.t_steps = c.t_steps != nullptr; q.AD = c.AD != nullptr; q.clock = c.clock != nullptr;
   q.records = c.rps > 1; q.fn_tab = c.fn_tab != nullptr; q.g_b = c.g_b != nullptr;
+  q.trace = h->table_grads;
   return q;
 }
 // what dfx_stats.tile_kernels reports: 1 tile kernels, 2 the per-stage / common-shape builds of the slot kernels, 0 their generic builds
@@ -197,6 +198,10 @@ void launch_adj(dfx_handle* h, const DevCtx& c, hipStream_t st, dim3 grid, int i
 #endif
     if (b.istage >= 0) return dfx_hot::launch_adj_stage_build(MODEL, CONTACT, b.npb, st, g, c, acf, i, j, in_buf, wbuf, local_only, rc, rb);
     if constexpr (CONTACT != 2) if (b.kind == kAdjOvf) return go(k_adj_stage<MODEL, CONTACT, 1, 1, 4, 0, 1>);
+    if (b.kind == kAdjTrace) {
+      hipLaunchKernelGGL((k_adj_stage_trace<MODEL, CONTACT>), g, dim3(kThreads), 0, st, c, acf, i, j, in_buf, wbuf, local_only, rc, rb, trace_ctx(h));
+      return;
+    }
     if (b.kind == kAdjBondGrads) return go(k_adj_stage<MODEL, CONTACT, 1, 1>);
     if (b.kind == kAdjRebuild) return go(k_adj_stage_rb<MODEL, CONTACT>);
     if constexpr (CONTACT != 2) {
@@ -833,6 +838,7 @@ int run_segment(dfx_handle* h, const DevCtx& c, int gi, int n_steps, int kind) {
   gk.ctx.n_timepoints = 0;  // not read by the stage kernels
   gk.segs = h->d_segs.p; gk.seg_idx = h->d_seg_idx.p; gk.cur = h->d_cur.p;
   gk.pair_fwd = h->pair_fwd; gk.pair_adj = h->pair_adj; gk.pair_rows = h->pair_rows;
+  gk.trace = h->table_grads ? 1 : 0; gk.gbar = h->table_grads ? h->d_gbar.p : nullptr; gk.trace_rows = h->table_grads ? h->trace_rows : 0;
   if (!h->graph_ctx_valid || memcmp(&h->graph_key, &gk, sizeof(gk)) != 0) {
     drop_graphs(h);
     memcpy(&h->graph_key, &gk, sizeof(gk));

@@ -43,7 +43,7 @@ int zero_grad_accumulators(dfx_handle* h, double* extra, size_t n_extra, int cur
   if (h->lig_ok && h->lig.g) { zero(h->d_lig_g.p, B * nb * 8); zero(h->d_lig_gphi.p, B * nb * 4); }
 #endif
   if (pl.n_ovf) zero(h->d_ovf_g.p, B * pl.n_ovf * kOvfG);
-  if (h->want_bond_grads || pl.n_ovf) zero(h->d_g_b.p, B * pl.n_slots * 8);
+  if (h->want_bond_grads || pl.n_ovf || h->table_grads) zero(h->d_g_b.p, B * pl.n_slots * 8);
   zero(h->d_blk_m.p, B * nb * 3);
   if (pl.contact == DFX_CONTACT_DISTANCE || h->obj_centroids) zero(h->d_g_c.p, B * nb * 2);
   if (h->want_damping_grads) zero(h->d_blk_c.p, B * nb * 3);
@@ -285,6 +285,7 @@ int run_adjoint(dfx_handle* h, const dfx_grads* want, dfx_grads* grads, dfx_grad
   const double h_last = Tn > 1 ? (h->t_steps.empty() ? (h->ts[Tn - 1] - h->ts[Tn - 2]) / h->spis[Tn - 2]
                                                      : h->t_steps[h->n_total] - h->t_steps[h->n_total - 1]) : 0.0;
   HIP_OK(hipEventRecord(h->ev2, h->stream));
+  if (int rc = trace_begin(h, h->n_total + 1)) return rc;
   pair_plan(h, c);
   if (use_fn_table(h)) c.fn_tab = h->d_fn_tab.p;
   // tile kernels: their accumulators are ligament-major (decided here, not in the launch functions: a graph replay does not call them)
@@ -389,9 +390,11 @@ int run_adjoint(dfx_handle* h, const dfx_grads* want, dfx_grads* grads, dfx_grad
     hipLaunchKernelGGL(k_kinetic_mass_grad, g, dim3(64), 0, h->stream, c, (const double*)h->d_fields.p, (const int32_t*)h->d_target.p, n_target);
   }
   if (h->obj_job) launch_objective_explicit(h, c);
+  if (int rc = trace_finish(h, c, nullptr)) return rc;
   HIP_OK(hipEventRecord(h->ev3, h->stream));
   if (timing) fprintf(stderr, "[dfx] adjoint: sweep enqueued %.0f us after entry\n", since(ta0));
   if (int rc = collect_grads(h, want, grads, views, true)) return rc;
+  trace_report(h);
 #ifdef DFX_PERSIST_TIMING
   if (getenv("DFX_TIMING_REVERSE") && getenv("DFX_TIMING_WAVES")) {
     extern unsigned* persist_dbg_buffer();

@@ -216,6 +216,8 @@ void multi_image(const dfx_handle* h, const dfx_params* params_dots, const Pass&
   }
 }
 
+int fail(dfx_handle* h, const char* who, const std::string& what, int rc = 1);
+
 // What a call needs on the device, sized for its widest pass: the image, the time grid, the initial state, the work buffers.  Everything is
 // allocated here, before any pass is paid for; a failure releases all of it (MultiBufs) and is an ordinary error return.
 int multi_alloc(dfx_handle* h, const Pass& widest, const std::vector<double>& tgrid, const std::vector<double>& t0, const double* state0, bool have_s0d,
@@ -248,6 +250,21 @@ int multi_alloc(dfx_handle* h, const Pass& widest, const std::vector<double>& tg
   c.tgrid = d.tgrid.p; c.t0 = d.t0.p;
   c.grid_stride = 0; c.t0_stride = 0;
   c.a_rows = a_rows; c.n_steps = nullptr;
+  for (int f = 0; f < DFX_MAX_FNS; ++f) c.tabdot[f] = nullptr;
+  c.tab_k0 = 0; c.tab_dirs = 0;
+  return 0;
+}
+
+// the sample tangents of table drives the handle holds (dfx_fn_table_tangents) for a call of n_dirs directions
+int table_tangents(dfx_handle* h, const char* who, int n_dirs, TanCtx& c) {
+  for (int f = 0; f < h->pl.n_fns; ++f) {
+    if (!h->tab_dots_n[f]) continue;
+    if (h->tab_dots_n[f] != n_dirs)
+      return fail(h, who, "the sample tangents of table function " + std::to_string(f) + " were set for " + std::to_string(h->tab_dots_n[f]) +
+                              " directions, this call has " + std::to_string(n_dirs) + " (dfx_fn_table_tangents)");
+    c.tabdot[f] = h->d_tab_dots[f].p;
+    c.tab_dirs = n_dirs;
+  }
   return 0;
 }
 
@@ -432,7 +449,7 @@ TanStageM stage_args(const MultiBufs& d, int y, int i, int S, long long n, int a
   return tm;
 }
 
-int fail(dfx_handle* h, const char* who, const std::string& what, int rc = 1) {
+int fail(dfx_handle* h, const char* who, const std::string& what, int rc) {
   h->err = std::string(who) + ": " + what;
   return rc;
 }
@@ -564,6 +581,7 @@ int forward_tangent(dfx_handle* h, const char* who, const double* state0, const 
   MultiBufs d;
   TanCtx c;
   if (int rc = multi_alloc(h, passes[0], tgrid, t0, state0, state0_dots != nullptr, S, Tn, d, c)) return rc;
+  if (int rc = table_tangents(h, who, n_dirs, c)) return rc;
   if (sink) if (int rc = sink_alloc(h, *sink, passes[0], Tn)) return rc;
   hipStream_t st = h->stream;
   c.grid_stride = per_member_times ? 2 * N : 0;
@@ -573,6 +591,7 @@ int forward_tangent(dfx_handle* h, const char* who, const double* state0, const 
   double ms_all = 0.0;
   for (const Pass& p : passes) {
     if (int rc = multi_upload_pass(h, params_dots, state0_dots, n_dirs, p, d)) return rc;
+    c.tab_k0 = p.k0;
     const MultiKernels kn = pick_kernels(pl.model, pl.contact, pl.n_npb, p.kc);
     const dim3 grid((unsigned)(((size_t)B * nb + 255) / 256), (unsigned)p.slices);
     const TanSlices sl = pass_slices(h, p, S);
@@ -623,6 +642,7 @@ int forward_tangent_dense(dfx_handle* h, const char* who, const double* state0, 
   MultiBufs d;
   TanCtx c;
   if (int rc = multi_alloc(h, passes[0], g.tgrid, t0, state0, state0_dots != nullptr, 7, Tn, d, c)) return rc;
+  if (int rc = table_tangents(h, who, n_dirs, c)) return rc;
   if (sink) if (int rc = sink_alloc(h, *sink, passes[0], Tn)) return rc;
   hipStream_t st = h->stream;
   c.grid_stride = g.gs; c.t0_stride = 0;
@@ -640,6 +660,7 @@ int forward_tangent_dense(dfx_handle* h, const char* who, const double* state0, 
   double ms_all = 0.0;
   for (const Pass& p : passes) {
     if (int rc = multi_upload_pass(h, params_dots, state0_dots, n_dirs, p, d)) return rc;
+    c.tab_k0 = p.k0;
     const MultiKernels kn = pick_kernels(pl.model, pl.contact, pl.n_npb, p.kc);
     const dim3 grid((unsigned)(((size_t)B * nb + 255) / 256), (unsigned)p.slices);
     const TanSlices sl = pass_slices(h, p, 7);
@@ -781,9 +802,11 @@ extern "C" int dfx_rhs_jvp(dfx_handle* h, const double* y, double t, const doubl
   MultiBufs d;
   TanCtx c;
   if (int rc = multi_alloc(h, passes[0], tgrid, t0, y, y_dots != nullptr, 1, 1, d, c)) return rc;
+  if (int rc = table_tangents(h, "rhs_jvp", n_dirs, c)) return rc;
   hipStream_t st = h->stream;
   for (const Pass& p : passes) {
     if (int rc = multi_upload_pass(h, params_dots, y_dots, n_dirs, p, d)) return rc;
+    c.tab_k0 = p.k0;
     const MultiKernels kn = pick_kernels(pl.model, pl.contact, pl.n_npb, p.kc);
     const dim3 grid((unsigned)(((size_t)B * nb + 255) / 256), (unsigned)p.slices);
     const TanSlices sl = pass_slices(h, p, 1);

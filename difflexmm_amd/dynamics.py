@@ -86,6 +86,27 @@ def _bcast(x, n):
 JACFWD_LEAVES = ("k_stretch", "k_shear", "k_rot", "density", "damping", "min_angle", "cutoff_angle", "k_contact")
 
 
+def _sample_leaf(who, control_params, name):
+    """``(name, j)``: sample j of the 1-D array ``name`` of ``constraint_params`` / ``loading_params`` (the values of a named
+    ``loading.Table``).  Returns (field of ControlParams, key, j, length); ``ValueError`` on anything else."""
+    if len(name) != 2 or not isinstance(name[0], str):
+        raise ValueError(f"{who}: a sample of an array leaf is addressed as (name, j), got {name!r}")
+    key, j = name
+    in_con = key in (control_params.constraint_params or {})
+    in_load = key in (control_params.loading_params or {})
+    if in_con and in_load:
+        raise ValueError(f"{who}: {key!r} is a key of both constraint_params and loading_params: seed it with jvp_multi")
+    if not (in_con or in_load):
+        raise ValueError(f"{who}: {key!r} is not a key of constraint_params / loading_params")
+    field = "constraint_params" if in_con else "loading_params"
+    arr = np.asarray(getattr(control_params, field)[key])
+    if arr.ndim != 1:
+        raise ValueError(f"{who}: {key!r} is not a 1-D array leaf (shape {arr.shape})")
+    if not isinstance(j, (int, np.integer)) or not 0 <= int(j) < len(arr):
+        raise ValueError(f"{who}: sample {j!r} of {key!r} is out of range (it has {len(arr)} samples)")
+    return field, key, int(j), len(arr)
+
+
 def unit_tangent(control_params: ControlParams, name):
     """The ``ControlParams``-shaped tangent tree that is 1 on the scalar leaf ``name`` and zero (None) elsewhere -- one column of
     :meth:`DynamicSolver.jacfwd`.  ``name``: one of ``JACFWD_LEAVES`` (stiffnesses of ``bond_params``, ``density`` / ``damping`` of
@@ -93,6 +114,11 @@ def unit_tangent(control_params: ControlParams, name):
     Python / 0-d scalar, or an array that holds one value broadcast over bonds or blocks -- that one gets an all-ones tangent of its
     shape.  ``ValueError``: an unknown name, a name both dicts hold, a leaf that is missing or holds different values."""
     mp = control_params.mechanical_params
+    if isinstance(name, tuple):
+        field, key, j, n = _sample_leaf("unit_tangent", control_params, name)
+        e = np.zeros(n)
+        e[j] = 1.0
+        return ControlParams(GeometricalParams(None, None), MechanicalParams(None, None), **{field: {key: e}})
 
     def ones(leaf, where):
         if leaf is None:
@@ -125,13 +151,19 @@ def unit_tangent(control_params: ControlParams, name):
         if np.ndim(src[name]) != 0:
             raise ValueError(f"unit_tangent: {name!r} is not a scalar leaf (shape {np.shape(src[name])})")
         return ControlParams(geo0, MechanicalParams(None, None), **{"constraint_params" if in_con else "loading_params": {name: 1.0}})
-    raise ValueError(f"unit_tangent: unknown leaf {name!r} (one of {', '.join(JACFWD_LEAVES)}, or a key of constraint_params / loading_params)")
+    raise ValueError(f"unit_tangent: unknown leaf {name!r} (one of {', '.join(JACFWD_LEAVES)}, a key of constraint_params / loading_params, "
+                     "or (key, j): sample j of an array held there)")
 
 
 def with_leaf(control_params: ControlParams, name, value):
     """The setter beside :func:`unit_tangent`: a copy of ``control_params`` with the scalar leaf ``name`` set to ``value`` -- the same
     names (``JACFWD_LEAVES``, keys of ``constraint_params`` / ``loading_params``) and the same "scalar leaf" rule: a Python / 0-d scalar
     is replaced, an array that holds one value is filled with ``value`` in its shape.  ``ValueError``: what :func:`unit_tangent` raises."""
+    if isinstance(name, tuple):
+        field, key, j, _ = _sample_leaf("with_leaf", control_params, name)
+        arr = np.array(getattr(control_params, field)[key], dtype=float)
+        arr[j] = float(value)
+        return control_params._replace(**{field: dict(getattr(control_params, field), **{key: arr})})
     shape = unit_tangent(control_params, name)          # (the checks; the tree itself tells where the leaf sits and its shape)
     value = float(value)
     mp = control_params.mechanical_params
@@ -208,6 +240,17 @@ class DynamicSolver:
                                 int(self.spec.contact or 0), self._special, fn_types,
                                 batch=self.batch, tableau=integrator, device=device, lib=lib,
                                 fn_tables=[getattr(f, "table", None) for f in self.con_terms + self.load_terms], streams=streams)
+        # table drives whose samples are a leaf of the params dict (loading.Table with named values): (function slot, term, field of
+        # ControlParams).  Their values go to the device with every prepare, and every reverse sweep of this solver keeps the
+        # drive-cotangent trace that gives their gradient (dfx_fn_table_grads: stage launches, never the persistent loops)
+        nc = len(self.con_terms)
+        self._table_leaves = [(f, t, "constraint_params") for f, t in enumerate(self.con_terms) if getattr(t, "values_name", None)] + \
+                             [(nc + f, t, "loading_params") for f, t in enumerate(self.load_terms) if getattr(t, "values_name", None)]
+        if self._table_leaves:
+            if not self.engine.has_fn_table_grads:
+                raise NotImplementedError(f"loading.Table with named values: the library {getattr(self.engine.lib, '_name', self.engine.lib)!r} has no "
+                                          "dfx_fn_table_grads (a stale libdfx.so, or the CPU port of the oracle; build the HIP engine)")
+            self.engine.fn_table_grads(True)
         self._last = None
         self._memo_pass = None
         self.solve_count = 0          # forward solves run so far (what the engine's resident history belongs to)
@@ -422,6 +465,8 @@ class DynamicSolver:
         finally:
             self._memo_pass = None
         self.engine.set_params(**self._stack(flats))
+        for f, term, field in self._table_leaves:
+            self.engine.fn_table_values(f, np.stack([term.resolve_values(getattr(cp, field)) for cp in cps]))
         self._prepared = (cps, flats)
         return cps, flats
 
@@ -521,7 +566,9 @@ class DynamicSolver:
           and differentiates the same solve.  Step sizes and accept / reject decisions are not differentiated.  ``self.stats`` reports
           ``step_control="adaptive-dense"`` and ``steps_per_member``.
         * rows of PRESCRIBED DOFs in ``fields_dot`` are  sum_f coef (dg_f/dp . dp, dg_f'/dp . dp)  from each term's ``param_partials``,
-          as :meth:`vjp` computes their cotangents -- a central difference, accurate to ~1e-9 relative, not to rounding.
+          as :meth:`vjp` computes their cotangents -- a central difference, accurate to ~1e-9 relative, not to rounding.  The samples
+          of a ``loading.Table`` with named values are the exception: value and rate are linear in them, and their share of these rows
+          (an array tangent under the table's key) is the analytic hat weights ``Table.hat_weights`` / ``rate_weights``, to rounding.
         * not supported (``RuntimeError`` from the engine): lattices whose nodes carry more than one ligament.  The CPU port of the
           oracle has no forward mode (``NotImplementedError``).
 
@@ -542,13 +589,46 @@ class DynamicSolver:
         fdm[:, :, dofs] = 0.0
         for term in self.con_terms:
             dp = term.resolve_jvp(cp.constraint_params, getattr(cd, "constraint_params", None))
-            if not np.any(dp):
+            dy = self._table_tangent(term, getattr(cd, "constraint_params", None))
+            if not np.any(dp) and dy is None:
                 continue
             p = term.resolve(cp.constraint_params)
+            bound = term.bind(cp.constraint_params)
             vec = _bcast(term.vector, n_con)
             for k, t in enumerate(ts_m):
-                fdm[k, 0, dofs] += vec * float(term.param_partials(float(t), p, "value") @ dp)
-                fdm[k, 1, dofs] += vec * float(term.param_partials(float(t), p, "rate") @ dp)
+                if np.any(dp):
+                    fdm[k, 0, dofs] += vec * float(bound.param_partials(float(t), p, "value") @ dp)
+                    fdm[k, 1, dofs] += vec * float(bound.param_partials(float(t), p, "rate") @ dp)
+                if dy is not None:          # the samples of a named table: analytic hat weights
+                    fdm[k, 0, dofs] += vec * p[0] * float(term.hat_weights(float(t) - p[1]) @ dy)
+                    fdm[k, 1, dofs] += vec * p[0] * float(term.rate_weights(float(t) - p[1]) @ dy)
+
+    @staticmethod
+    def _table_tangent(term, params_dot):
+        """The (n_tab,) tangent of a named table's values in a tangent dict, or None (no such leaf, no entry, an all-zero entry)."""
+        name = getattr(term, "values_name", None)
+        v = None if (name is None or params_dot is None) else params_dot.get(name)
+        if v is None:
+            return None
+        v = np.asarray(v, dtype=float)
+        if v.shape != term.times.shape:
+            raise ValueError(f"tangent of '{name}' must have shape {term.times.shape}, got {v.shape}")
+        return v if np.any(v) else None
+
+    def _set_table_tangents(self, dots, K):
+        """The sample tangents of every named table, [direction][member], on the device for the next forward-mode call of K directions."""
+        for f, term, field in self._table_leaves:
+            arr = np.zeros((K, self.batch, len(term.times)))
+            for k in range(K):
+                for m in range(self.batch):
+                    v = self._table_tangent(term, getattr(dots[k][m], field, None))
+                    if v is not None:
+                        arr[k, m] = v
+            self.engine.fn_table_tangents(f, arr)
+
+    def _clear_table_tangents(self):
+        for f, _, _ in self._table_leaves:
+            self.engine.fn_table_tangents(f, None)
 
     def _member_tangents(self, control_params_dot):
         """``control_params_dot`` of one direction as a list of one tangent tree per member (:meth:`jvp`'s rules)."""
@@ -639,7 +719,11 @@ class DynamicSolver:
                 primal, astats = engine.forward_adaptive(s0, ts, self.rtol, self.atol, max_attempts=self.max_attempts)
             self.adaptive_stats = astats
             grid, n_steps = _b.padded_step_times([engine.adaptive_step_times(m) for m in range(B)], ts[0])
-            fields, fields_dot, stats = dense(s0, s0ds, params_dots, K, ts, grid, n_steps)
+            self._set_table_tangents(dots, K)
+            try:
+                fields, fields_dot, stats = dense(s0, s0ds, params_dots, K, ts, grid, n_steps)
+            finally:
+                self._clear_table_tangents()
             if kept:        # as a differentiable solve leaves it: vjp reverses the adaptive pass above
                 self._last = (cps, flats, ts)
                 self._last_fields = primal
@@ -653,7 +737,11 @@ class DynamicSolver:
                 fixed(s0, None, None, 1, ts[:1], 1)
                 spi, step_times = self.adaptive_grid(np.zeros((B, 2, nb, 3)) if s0 is None else s0, ts, flats)
                 control = "adaptive-grid"
-            fields, fields_dot, stats = fixed(s0, s0ds, params_dots, K, ts, spi, step_times=step_times)
+            self._set_table_tangents(dots, K)
+            try:
+                fields, fields_dot, stats = fixed(s0, s0ds, params_dots, K, ts, spi, step_times=step_times)
+            finally:
+                self._clear_table_tangents()
             self.stats = dict(stats, steps_per_interval=spi, step_times=step_times, step_control=control)
         return fields, fields_dot, cps, dots, ts
 
@@ -701,11 +789,17 @@ class DynamicSolver:
                 for k in range(len(dots)):
                     for term in self.con_terms:
                         dp = term.resolve_jvp(cp.constraint_params, getattr(dots[k][m], "constraint_params", None))
-                        if not np.any(dp):
+                        dy = self._table_tangent(term, getattr(dots[k][m], "constraint_params", None))
+                        if not np.any(dp) and dy is None:
                             continue
                         p = term.resolve(cp.constraint_params)
+                        bound = term.bind(cp.constraint_params)
                         vec = _bcast(term.vector, n_con)
-                        rate = np.array([float(term.param_partials(float(t), p, "rate") @ dp) for t in ts_m])
+                        rate = np.zeros(len(ts_m))
+                        if np.any(dp):
+                            rate += np.array([float(bound.param_partials(float(t), p, "rate") @ dp) for t in ts_m])
+                        if dy is not None:
+                            rate += np.array([p[0] * float(term.rate_weights(float(t) - p[1]) @ dy) for t in ts_m])
                         for s_, i, coef in driven:
                             Sd[m, k, :, s_] += coef * vec[i] * rate
         if self.batch == 1 and not isinstance(control_params, list):
@@ -768,12 +862,17 @@ class DynamicSolver:
                     if not (np.any(wq) or np.any(wv)):
                         continue
                     p = term.resolve(cp.constraint_params)
+                    bound = term.bind(cp.constraint_params)
+                    leaf = getattr(term, "values_name", None)
                     g5 = np.zeros(_b.DFX_FN_PARAMS)
                     for k, t in enumerate(ts[m] if ts.ndim == 2 else ts):
                         if wq[k]:
-                            g5 += wq[k] * term.param_partials(float(t), p, "value")
+                            g5 += wq[k] * bound.param_partials(float(t), p, "value")
                         if wv[k]:
-                            g5 += wv[k] * term.param_partials(float(t), p, "rate")
+                            g5 += wv[k] * bound.param_partials(float(t), p, "rate")
+                        if leaf and (wq[k] or wv[k]):      # the samples: value and rate are linear in them, analytic hat weights
+                            tree.constraint_params[leaf] = tree.constraint_params[leaf] + p[0] * (
+                                wq[k] * term.hat_weights(float(t) - p[1]) + wv[k] * term.rate_weights(float(t) - p[1]))
                     term.scatter_grad(g5, tree.constraint_params, cp.constraint_params)
         return trees, s0
 
@@ -815,7 +914,8 @@ class DynamicSolver:
                         for term in self.con_terms:
                             p = term.resolve(cps[m].constraint_params)
                             h = 1e-4 * max(float(np.ptp(tsm[m])), 1e-300)      # (central difference of the rate, in the scale of the horizon)
-                            acc += _bcast(term.vector, n_con) * (term.rate(float(t) + h, p) - term.rate(float(t) - h, p)) / (2 * h)
+                            bt = term.bind(cps[m].constraint_params)
+                            acc += _bcast(term.vector, n_con) * (bt.rate(float(t) + h, p) - bt.rate(float(t) - h, p)) / (2 * h)
                         rate[1, con] = acc                        # c''(t)
                     g = fb[m, i]
                     if i == 0:
@@ -839,7 +939,22 @@ class DynamicSolver:
     def _take_stats(self, result):
         """An engine result that ends with the stats of its reverse sweep: those kept as ``adjoint_stats``, the rest returned."""
         self.adjoint_stats = result[-1]
+        if self._table_leaves:      # the sample gradients of named tables, by function slot: {slot: (batch, n_tab)}
+            for r in result[:-1]:
+                if isinstance(r, dict):
+                    r["fn_table_values"] = self._fn_table_grads()
         return result[:-1]
+
+    def _fn_table_grads(self):
+        """{function slot: (batch, n_tab)} sample gradients of the named tables from the last reverse sweep."""
+        return {f: self.engine.fn_table_grad(f) for f, _, _ in self._table_leaves}
+
+    def drive_cotangent(self, member=0):
+        """``(times (n,), gbar (n_fns, n))`` of one member from the last reverse sweep of a solver with a named ``loading.Table``: the
+        stage times in order and the cotangent dL/dg_f of every drive value there (function slots: constraint terms first, then loading
+        terms).  For any parameter p of function f the sweep's part of dL/dp is ``sum(gbar[f] * dg_f/dp(times))`` -- the adjoint
+        sensitivity of the objective to the drive itself."""
+        return self.engine.drive_cotangent(member)
 
     def vjp_raw(self, fields_bar, which=("centroid_node_vectors", "void_angle0", "inertia")):
         """Reverse sweep for a cotangent of the fields, returning the engine's raw gradient arrays (batch-leading) of the requested
@@ -1001,6 +1116,7 @@ class DynamicSolver:
     def _unflatten_grads(self, g, fields_bar):
         cps, flats, ts = self._last
         trees = []
+        tab = (g.get("fn_table_values") or self._fn_table_grads()) if self._table_leaves else {}
         for m, (cp, flat) in enumerate(zip(cps, flats)):
             gp, mp = cp.geometrical_params, cp.mechanical_params
             cnv = flat["centroid_node_vectors"]
@@ -1031,6 +1147,9 @@ class DynamicSolver:
                 term.scatter_grad(g["fn_params"][m][f], con_bar, cp.constraint_params)
             for f, term in enumerate(self.load_terms):
                 term.scatter_grad(g["fn_params"][m][len(self.con_terms) + f], load_bar, cp.loading_params)
+            for f, term, field in self._table_leaves:
+                bar = con_bar if field == "constraint_params" else load_bar
+                bar[term.values_name] = bar.get(term.values_name, 0.0) + tab[f][m]
             trees.append(ControlParams(
                 geometrical_params=GeometricalParams(
                     block_centroids=(np.array(g["block_centroids"][m]).reshape(np.shape(gp.block_centroids)) if "block_centroids" in g

@@ -66,6 +66,10 @@ class TimeFunction:
     def value(self, t, p):
         return 0.0
 
+    def bind(self, params_dict):
+        """The function with everything it reads from the params dict besides its 5 numbers in place (``Table``: its named values)."""
+        return self
+
     def rate(self, t, p, eps=1e-7):
         """d value / dt (central difference in the scale of t; the kernels use the analytic form)."""
         h = eps * max(1.0, abs(t))
@@ -229,19 +233,76 @@ def static_tuning_drive(static_vector, dynamic_vector, length):
 class Table(TimeFunction):
     """amplitude * interp(t - delay; times, values): a recorded input signal, piecewise linear, end values held
     (``jnp.interp`` semantics; the reference resamples its experimental signals with it, problems/hinge_characterization.py:546-551).
-    The table is static data of the solver; ``amplitude`` and ``delay`` are parameters."""
+    ``amplitude`` and ``delay`` are parameters.  ``values`` is an array -- then the table is static data of the solver -- or a string:
+    the key of a ``(n_tab,)`` array in ``constraint_params`` / ``loading_params``, a differentiable leaf like any other (``vjp`` returns
+    its gradient under that key, ``jvp`` takes an array tangent there; HIP engine only).  The times are fixed at setup either way."""
     type_id = FN_TABLE
     param_names = ("amplitude", "delay")
 
     def __init__(self, times, values, vector=1.0, amplitude=1.0, delay=0.0):
         super().__init__(vector, amplitude=amplitude, delay=delay)
-        self.times, self.values = np.asarray(times, dtype=float), np.asarray(values, dtype=float)
-        if self.times.ndim != 1 or self.times.shape != self.values.shape or len(self.times) < 2 or np.any(np.diff(self.times) <= 0):
+        self.times = np.asarray(times, dtype=float)
+        self.values_name = values if isinstance(values, str) else None
+        self.values = None if self.values_name is not None else np.asarray(values, dtype=float)
+        if self.times.ndim != 1 or len(self.times) < 2 or np.any(np.diff(self.times) <= 0) or \
+                (self.values is not None and self.times.shape != self.values.shape):
             raise ValueError("Table: times must be 1-D, strictly increasing, as long as values, with >= 2 entries")
-        self.table = (self.times, self.values)
+        # what dfx_create copies: a named table starts at zero and takes its values with every solve
+        self.table = (self.times, np.zeros_like(self.times) if self.values is None else self.values)
+
+    def resolve_values(self, params_dict):
+        """The (n_tab,) values of a solve: the array given at setup, or the entry of the params dict a named table reads."""
+        if self.values_name is None:
+            return self.values
+        if params_dict is None or self.values_name not in params_dict:
+            raise KeyError(f"Table: values '{self.values_name}' missing from the params dict")
+        v = np.asarray(params_dict[self.values_name], dtype=float)
+        if v.shape != self.times.shape:
+            raise ValueError(f"Table: '{self.values_name}' must have shape {self.times.shape} (one value per breakpoint), got {v.shape}")
+        if not np.all(np.isfinite(v)):
+            raise ValueError(f"Table: '{self.values_name}' holds a value that is not finite")
+        return v
+
+    def bind(self, params_dict):
+        """This table with the values of one solve as its array (``value`` / ``rate`` / ``param_partials`` of a named table need them)."""
+        if self.values_name is None:
+            return self
+        return Table(self.times, self.resolve_values(params_dict), self.vector, **self.params)
 
     def value(self, t, p):
+        if self.values is None:
+            raise ValueError(f"Table: the values are the entry '{self.values_name}' of the params dict: bind(params) first")
         return p[0] * float(np.interp(t - p[1], self.times, self.values))
+
+    def _eval(self, t, kwargs):
+        return self.bind(kwargs)._eval(t, kwargs) if self.values is None else super()._eval(t, kwargs)
+
+    def _bin(self, tau):
+        """(lo, w, inside): interp(tau) = Y[lo] + w (Y[lo + 1] - Y[lo]); the branches of the kernels -- tau <= T[0] and tau >= T[-1] hold
+        the end values, a breakpoint belongs to the piece that starts there."""
+        T = self.times
+        if tau <= T[0]:
+            return 0, 0.0, False
+        if tau >= T[-1]:
+            return len(T) - 2, 1.0, False
+        lo = int(np.searchsorted(T, tau, side="right")) - 1
+        return lo, (tau - T[lo]) / (T[lo + 1] - T[lo]), True
+
+    def hat_weights(self, tau):
+        """d interp(tau; times, Y) / dY, (n_tab,): the hat functions of the breakpoints at tau = t - delay."""
+        lo, w, _ = self._bin(float(tau))
+        out = np.zeros(len(self.times))
+        out[lo], out[lo + 1] = 1.0 - w, w
+        return out
+
+    def rate_weights(self, tau):
+        """d/dY of d interp(tau; times, Y) / d tau, (n_tab,): -+ 1 / (T[lo + 1] - T[lo]) inside a piece, zero where the end values are held."""
+        lo, _, inside = self._bin(float(tau))
+        out = np.zeros(len(self.times))
+        if inside:
+            out[lo + 1] = 1.0 / (self.times[lo + 1] - self.times[lo])
+            out[lo] = -out[lo + 1]
+        return out
 
 
 zero = Zero()

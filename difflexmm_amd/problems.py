@@ -187,7 +187,8 @@ def _make_drive(self, vec, excited_blocks_fn):
         return self._drive_cls(vec)
     if not isinstance(excited_blocks_fn, L.Table):
         raise TypeError("excited_blocks_fn must be a difflexmm_amd.loading.Table (a recorded signal the device can interpolate)")
-    return L.Table(excited_blocks_fn.times, excited_blocks_fn.values, vector=vec)
+    # (a table with named values stays one: its samples are then an entry of constraint_params, see DriveWaveformDesign)
+    return L.Table(excited_blocks_fn.times, excited_blocks_fn.values_name or excited_blocks_fn.values, vector=vec)
 
 
 def _drive_params(self):
@@ -1282,6 +1283,87 @@ class SignalCalibration:
                 print(f"Iteration: {len(self.objective_values)}\nObjective = {v}")
             return r, J
         return levenberg_marquardt(fun, np.asarray(x0, dtype=float), lower=lower_bound, upper=upper_bound, max_evaluations=n_iterations)
+
+
+class DriveWaveformDesign:
+    """The drive itself as the design: the unknowns ``y`` are the samples of a ``loading.Table`` with named values -- the (n_tab,) array
+    ``leaf`` of ``constraint_params`` / ``loading_params`` of ``control_params`` -- and the objective is any of the device objective specs
+    (``objective.ObjectiveSpec``, ``StrainObjectiveSpec``, ``PeakStrainSpec``, ``SignalSpec`` with targets, ``ProjectionSpec``,
+    ``CorrelationSpec``), dispatched to the solver's ``*_value_and_raw``: one kept forward solve and one reverse sweep per evaluation, the
+    history never leaves the device, and the sample gradient comes from the sweep's drive-cotangent trace (``fn_table_values`` of the raw
+    gradients).  Shape the pulse that focuses the most energy at a target under an amplitude bound, find the excitation that reproduces a
+    measured reaction force, ...  ``fixed``: samples held at their initial values (default: the two ends, so that the drive starts and
+    ends where it was); ``maximize=True`` turns the objective's sign for :meth:`run_mma`; ``grid_kwargs``: ``steps_per_interval``,
+    ``step_times``.  A solver of batch 1.  As with every device objective, the direct dependence of a prescribed OUTPUT row on its drive
+    is not in the gradient: measure free DOFs (or forces)."""
+
+    def __init__(self, solve_dynamics, state0, timepoints, control_params, leaf, spec, fixed=(0, -1), maximize=False, **grid_kwargs):
+        from . import objective as O
+        if solve_dynamics.batch != 1 or isinstance(control_params, (list, tuple)) and not isinstance(control_params, ControlParams):
+            raise ValueError("DriveWaveformDesign: one design on a solver of batch 1")
+        slots = [(f, field) for f, term, field in getattr(solve_dynamics, "_table_leaves", ()) if term.values_name == leaf]
+        if not slots:
+            raise ValueError(f"DriveWaveformDesign: the solver has no loading.Table whose values are the entry {leaf!r} of its params dict")
+        self.slot, self.field = slots[0]
+        if leaf not in (getattr(control_params, self.field) or {}):
+            raise ValueError(f"DriveWaveformDesign: {leaf!r} is missing from {self.field}")
+        methods = ((O.ObjectiveSpec, "objective_value_and_raw"), (O.StrainObjectiveSpec, "strain_objective_value_and_raw"),
+                   (O.PeakStrainSpec, "peak_strain_value_and_raw"), (O.SignalSpec, "signal_misfit_value_and_raw"),
+                   (O.ProjectionSpec, "signal_projection_value_and_raw"), (O.CorrelationSpec, "signal_xcorr_value_and_raw"))
+        self.method = next((name for cls, name in methods if isinstance(spec, cls)), None)
+        if self.method is None:
+            raise TypeError("DriveWaveformDesign: spec must be one of the device objective specs of difflexmm_amd.objective")
+        if isinstance(spec, O.SignalSpec) and spec.targets is None:
+            raise ValueError("DriveWaveformDesign: the SignalSpec has no targets")
+        self.solve_dynamics, self.state0, self.timepoints, self.control_params = solve_dynamics, state0, timepoints, control_params
+        self.leaf, self.spec, self.maximize, self.grid_kwargs = leaf, spec, bool(maximize), grid_kwargs
+        self.n = len(np.asarray(getattr(control_params, self.field)[leaf]))
+        self.fixed = sorted({int(i) % self.n for i in fixed})
+        self.free = np.array([i for i in range(self.n) if i not in self.fixed], dtype=np.int64)
+        self.objective_values, self.design_values = [], []
+
+    def params_at(self, y):
+        y = np.asarray(y, dtype=float).reshape(-1)
+        if y.size != self.n:
+            raise ValueError(f"DriveWaveformDesign: {y.size} values for the {self.n} samples of {self.leaf!r}")
+        return self.control_params._replace(**{self.field: dict(getattr(self.control_params, self.field), **{self.leaf: y.copy()})})
+
+    def value_and_grad(self, y):
+        """(value, d value / d y (n_tab,)) of the objective at the samples ``y``."""
+        s = self.solve_dynamics
+        s(self.state0, self.timepoints, self.params_at(y), keep_trajectory=True, want_fields=False, **self.grid_kwargs)
+        value, raw = getattr(s, self.method)(self.spec, which=("fn_params",))
+        value = value[0] if isinstance(value, tuple) else value            # (peak strain, correlation: (J, ...))
+        return float(np.asarray(value).reshape(-1)[0]), np.array(raw["fn_table_values"][self.slot][0])
+
+    def run_mma(self, y0, n_iterations, lower_bound=None, upper_bound=None, verbose=False):
+        """The MMA of ``difflexmm_amd.optimize`` on the free samples between the bounds (scalars or (n_tab,) arrays), at most
+        ``n_iterations`` evaluations; the samples of ``fixed`` keep their values of ``y0``.  Every evaluation is recorded in
+        ``objective_values`` and ``design_values``; returns the best samples (n_tab,)."""
+        from .optimize import mma_minimize
+        y0 = np.array(y0, dtype=float).reshape(-1)
+        if y0.size != self.n:
+            raise ValueError(f"DriveWaveformDesign: {y0.size} values for the {self.n} samples of {self.leaf!r}")
+        sign = -1.0 if self.maximize else 1.0
+
+        def bound(b):
+            return None if b is None else np.broadcast_to(np.asarray(b, dtype=float), (self.n,))[self.free]
+
+        def full(x):
+            y = y0.copy()
+            y[self.free] = x
+            return y
+
+        def fun(x):
+            y = full(x)
+            v, g = self.value_and_grad(y)
+            self.objective_values.append(v)
+            self.design_values.append(y)
+            if verbose:
+                print(f"Iteration: {len(self.objective_values)}\nObjective = {v}")
+            return sign * v, sign * g[self.free]
+        res = mma_minimize(fun, y0[self.free], lower=bound(lower_bound), upper=bound(upper_bound), maxeval=int(n_iterations))
+        return full(res.x)
 
 
 class TargetSignalProjection(_SignalTarget):

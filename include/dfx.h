@@ -55,7 +55,8 @@ enum {
   DFX_FN_RAMP_CAP = 6,     /* (L, r, cap): L min(t r, cap)  static compression, problems/quads_kinetic_energy_static_tuning.py:176-182;
                               the delayed pulse of :184-186 is DFX_FN_PULSE with t_d = cap / r + input_delay (host-side chain rule) */
   DFX_FN_TABLE = 7         /* (A, t_d): A * interp(t - t_d; table), piecewise linear, end values held (jnp.interp semantics):
-                              a recorded input signal; the table itself is static data of dfx_problem             */
+                              a recorded input signal; the times are static data of dfx_problem, the values can be
+                              set per member and differentiated (dfx_fn_table_values, dfx_fn_table_grads)          */
 };
 
 /* A block that has constrained and/or force-loaded DOFs.  u[dof] = sum_m con_coef[d][m] * g_m(t)
@@ -225,6 +226,34 @@ int dfx_adaptive_step_times(dfx_handle* h, int32_t member, double* times, int64_
 /* Reverse sweep over the checkpointed trajectory of the last dfx_forward(keep_trajectory=1).
  * fields_bar: (batch, T, 2, n_blocks, 3) cotangent of `fields`. */
 int dfx_adjoint(dfx_handle* h, const double* fields_bar, dfx_grads* grads, dfx_stats* stats);
+
+/* ---- the samples of a DFX_FN_TABLE drive as a differentiable leaf (HIP library only) ----------------------------------------------------
+ * g_f(t) = A interp(t - t_d; T, Y): the times T stay those of dfx_create (they are not differentiated), the values Y are a leaf like any
+ * other.  `fn` names a time function of type DFX_FN_TABLE (anything else: return 1); n_tab = fn_table_n[fn].
+ *
+ * dfx_fn_table_values: new values for every member -- values (n_tab), or (batch, n_tab) with per_member != 0 -- without rebuilding the
+ *   handle; they hold for every later call (dfx_set_params keeps them).  Like dfx_set_params it drops the kept trajectory.
+ * dfx_fn_table_grads(h, 1): from now on every reverse sweep of the handle -- dfx_adjoint and every *_value_and_grad entry, on every
+ *   checkpoint level and on the kept adaptive solve -- also keeps the cotangent gbar of the drive value g_f at every stage time (the
+ *   "trace"; the sum over the member's DOFs of -(H w) con_coef on prescribed DOFs, w load_coef on loaded ones) and reduces it onto the
+ *   samples: dL/dY[j] = A sum gbar hat_j(t - t_d), the end samples collecting everything at or beyond T[0] / T[n_tab - 1].  Such a sweep
+ *   runs on stage launches in the build that also accumulates per-ligament gradients (dfx_stats.tile_kernels = 0), never on the
+ *   persistent loops; it is refused (return 1) on lattices whose nodes carry more than one ligament.  Without the request every call
+ *   launches what it launched before.  dfx_fn_table_grads(h, 0) switches it off.
+ * dfx_fn_table_grad: the sample gradient (batch, n_tab) of the last such sweep.  The direct dependence of a prescribed OUTPUT row on its
+ *   drive is not in it (as with fn_params): the caller adds fields_bar . hat weights for those rows.
+ * dfx_drive_cotangent: the trace of one member, in the style of dfx_adaptive_step_times: *n = its number of stage evaluations (steps x
+ *   stages in sweep order of time; the kept adaptive solve: the member's accepted steps and the evaluation at its final state),
+ *   min(*n, capacity) stage times into `times` and, for function f, as many cotangents into gbar + f * capacity (either may be NULL).
+ *   For any parameter p of function f the sweep's part of dL/dp is sum gbar[f] * dg_f/dp(times).
+ * dfx_fn_table_tangents: per-direction sample tangents (n_dirs, batch, n_tab) for the forward-mode entries (dfx_forward_tangent*,
+ *   dfx_rhs_jvp): direction k of a later call with the same n_dirs adds A interp(t - t_d; T, values_dots[k]) to the tangent of g_f.
+ *   They stay until cleared (values_dots = NULL); a call with another number of directions is refused while they are set. */
+int dfx_fn_table_values(dfx_handle* h, int32_t fn, const double* values, int32_t per_member);
+int dfx_fn_table_grads(dfx_handle* h, int32_t enable);
+int dfx_fn_table_grad(dfx_handle* h, int32_t fn, double* grad);
+int dfx_drive_cotangent(dfx_handle* h, int32_t member, double* times, double* gbar, int64_t capacity, int64_t* n);
+int dfx_fn_table_tangents(dfx_handle* h, int32_t fn, const double* values_dots, int32_t n_dirs);
 
 /* Forward mode: the directional derivative of the fixed-grid solve (dfx_forward_grid, or dfx_forward_grid_members when
  * per_member_times != 0: timepoints (batch, n_timepoints), step_times (batch, sum(steps_per_interval) + 1) required) along
