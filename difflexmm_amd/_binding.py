@@ -22,6 +22,7 @@ FN_ZERO, FN_PULSE, FN_HARMONIC, FN_RAMP, FN_SECH2TANH, FN_CONSTANT, FN_RAMP_CAP,
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
+_lp = C.POINTER(C.c_int64)
 
 
 class dfx_special(C.Structure):
@@ -101,122 +102,115 @@ def check_abi_layout(lib):
                            "include/dfx.h and difflexmm_amd/_binding.py are out of step")
 
 
+def _argtypes():
+    """Entry name -> argument types for every entry point of include/dfx.h, from argument groups that are each written once."""
+    P, H, i32, i64, f64 = C.POINTER, C.c_void_p, C.c_int32, C.c_int64, C.c_double
+    lp, stats, grads, params, dmap = P(i64), P(dfx_stats), P(dfx_grads), P(dfx_params), P(dfx_design_map)
+    terms = [i32, _ip, _ip, _ip, _dp, i32]                       # n_terms, signal, block, component, coef, n_signals
+    tail = [grads, grads, i32, stats]                            # want, views, device_views, stats of every *_value_and_grad
+    corr = [i32, _ip, _ip, _dp, i32, i32, i32, i32]              # pairs, templates, max_lag, normalisation
+    xval = [i32, i32, f64, f64, f64, f64, _dp, _dp, _dp]         # reduce, lag, beta, w_peak, w_delay, delay_target, J, peak, delay
+    peak = [_dp, i32, _dp, i32, _dp, i32, f64, _dp, _dp, _ip]    # coef, weights, tau, aggregate, sharpness, J, peak, peak_at
+    grid = [H, _dp, _dp, i32, _ip, _dp, i32, _dp, stats]         # a fixed-grid forward pass
+    kinetic = [H, _ip, i32, _dp, grads, grads, stats]
+    adaptive = [H, _dp, _dp, i32, f64, f64, i64]                 # state0, timepoints, T, rtol, atol, max_attempts
+    design = [dmap, _dp, i32, f64, _dp, _dp, _dp, _dp]           # the native design map: designs, count, density, four arrays
+    fixed, dense = [_dp, i32, _ip, _dp, i32], [_dp, i32, _dp, lp, i64]      # timepoints and steps of the two kinds of tangent solve
+    one, multi = [H, _dp, _dp, params], [H, _dp, _dp, params, i32]          # state0, its tangent(s), the parameter tangent(s)[, n_dirs]
+    out = [_dp, _dp, stats]
+    objective, strain = [H, i32, _dp, i32, _dp, _dp, i32, _dp], [H, _dp, i32, _dp, _dp, _dp]
+    misfit, projection = [H] + terms + [_dp, i32, _dp, _dp, _dp], [H] + terms + [_dp, i32, _dp, _dp, i32, _dp]
+    return {
+        "dfx_create": [P(dfx_problem), P(H)],
+        "dfx_destroy": [H],
+        "dfx_share_checkpoint": [H, H],
+        "dfx_last_error": [H],
+        "dfx_set_params": [H, params],
+        "dfx_reserve": [H, i64, i32, i32],
+        "dfx_abi_layout": [_ip, i32],
+        "dfx_forward": [H, _dp, _dp, i32, i32, i32, _dp, stats],
+        "dfx_forward_grid": grid,
+        "dfx_forward_grid_members": grid,
+        "dfx_adaptive_step_counts": [H, _ip],
+        "dfx_adaptive_step_times": [H, i32, _dp, i64, lp],
+        "dfx_forward_adaptive": adaptive + [_dp, stats],
+        "dfx_forward_adaptive_keep": adaptive + [i32, _dp, stats],
+        "dfx_design_forward": design,
+        "dfx_design_vjp": design + [_dp],
+        "dfx_member_status": [H, _ip],
+        "dfx_set_failure_policy": [H, i32],
+        "dfx_test_set_spin_limit": [H, i32],
+        "dfx_adjoint": [H, _dp, grads, stats],
+        "dfx_objective_kinetic": [H, _ip, i32, _dp],
+        "dfx_adjoint_kinetic": [H, _ip, i32, grads, stats],
+        "dfx_kinetic_value_and_grad": kinetic,
+        "dfx_kinetic_value_and_grad_device": kinetic,
+        "dfx_forward_kinetic_value_and_grad": [H, _dp, _dp, i32, _ip, _ip, i32, _dp] + tail + [stats],
+        "dfx_response_data": [H, _dp, _dp, _dp, _dp],
+        "dfx_rhs": [H, _dp, f64, _dp],
+        "dfx_rhs_vjp": [H, _dp, f64, _dp, _dp, grads],
+        "dfx_rhs_jvp": [H, _dp, f64, _dp, params, i32, _dp, _dp],
+        "dfx_energy": [H, _dp, _dp],
+        "dfx_device_count": [],
+        "dfx_version": [],
+        "dfx_forward_tangent": one + fixed + out,
+        "dfx_forward_tangent_dense": one + dense + out,
+        "dfx_forward_tangent_multi": multi + fixed + out,
+        "dfx_forward_tangent_dense_multi": multi + dense + out,
+        "dfx_forward_tangent_signals_multi": multi + fixed + terms + out,
+        "dfx_forward_tangent_signals_dense_multi": multi + dense + terms + out,
+        "dfx_dense_output_map": [_dp, lp, i64, i32, _dp, i32, _ip, _dp],
+        "dfx_objective_value": objective,
+        "dfx_objective_value_and_grad": objective + tail,
+        "dfx_strain_objective_value": strain,
+        "dfx_strain_objective_value_and_grad": strain + tail,
+        "dfx_strain_peak_value": [H] + peak,
+        "dfx_strain_peak_value_and_grad": [H] + peak + tail,
+        "dfx_signal_values": [H] + terms + [_dp],
+        "dfx_signal_hinge_channels": [H, i32],
+        "dfx_signal_misfit_value": misfit,
+        "dfx_signal_misfit_value_and_grad": misfit + tail,
+        "dfx_signal_projections": [H] + terms + [_dp, i32, _dp],
+        "dfx_signal_projection_value": projection,
+        "dfx_signal_projection_value_and_grad": projection + tail,
+        "dfx_signal_xcorr": [H] + terms + corr + [_dp],
+        "dfx_signal_xcorr_value": [H] + terms + corr + xval,
+        "dfx_signal_xcorr_value_and_grad": [H] + terms + corr + xval + tail,
+        "dfx_fn_table_values": [H, i32, _dp, i32],
+        "dfx_fn_table_grads": [H, i32],
+        "dfx_fn_table_grad": [H, i32, _dp],
+        "dfx_drive_cotangent": [H, i32, _dp, _dp, i64, lp],
+        "dfx_fn_table_tangents": [H, i32, _dp, i32],
+        "dfx_comm_unique_id": [C.c_char_p],
+        "dfx_comm_init": [i32, i32, C.c_char_p, i32, P(H)],
+        "dfx_comm_destroy": [H],
+        "dfx_comm_rank": [H],
+        "dfx_comm_size": [H],
+        "dfx_comm_barrier": [H],
+        "dfx_comm_rccl_version": [_ip, _ip],
+        "dfx_gather_objectives": [H, _dp, i32, _dp],
+        "dfx_reduce_grads": [H, _dp, i64],
+        "dfx_comm_allreduce": [H, _dp, i64, i32],
+        "dfx_comm_last_error": [],
+        "dfx_mem_info": [i32, lp, lp],
+        "dfx_device_synchronize": [i32],
+        "dfx_download": [H, _dp, H, i64],
+    }
+
+
+_ARGTYPES = _argtypes()
+_STRING_RETURNS = ("dfx_last_error", "dfx_version", "dfx_comm_last_error")
+
+
 def declare(lib):
-    """Attach argument / result types to every entry point of include/dfx.h."""
-    H = C.c_void_p
+    """Attach argument / result types to every entry point of include/dfx.h that the library has (the CPU port of the oracle and a stale
+    libdfx.so lack the later ones): no entry's types depend on another entry's presence."""
     check_abi_layout(lib)
-    lib.dfx_create.argtypes = [C.POINTER(dfx_problem), C.POINTER(H)]
-    lib.dfx_destroy.argtypes = [H]
-    if hasattr(lib, "dfx_share_checkpoint"):
-        lib.dfx_share_checkpoint.argtypes = [H, H]
-    lib.dfx_last_error.argtypes = [H]
-    lib.dfx_last_error.restype = C.c_char_p
-    lib.dfx_set_params.argtypes = [H, C.POINTER(dfx_params)]
-    lib.dfx_reserve.argtypes = [H, C.c_int64, C.c_int32, C.c_int32]
-    lib.dfx_forward.argtypes = [H, _dp, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, C.POINTER(dfx_stats)]
-    lib.dfx_forward_grid.argtypes = [H, _dp, _dp, C.c_int32, _ip, _dp, C.c_int32, _dp, C.POINTER(dfx_stats)]
-    lib.dfx_forward_grid_members.argtypes = [H, _dp, _dp, C.c_int32, _ip, _dp, C.c_int32, _dp, C.POINTER(dfx_stats)]
-    lib.dfx_adaptive_step_counts.argtypes = [H, _ip]
-    lib.dfx_adaptive_step_times.argtypes = [H, C.c_int32, _dp, C.c_int64, C.POINTER(C.c_int64)]
-    lib.dfx_forward_adaptive.argtypes = [H, _dp, _dp, C.c_int32, C.c_double, C.c_double, C.c_int64, _dp, C.POINTER(dfx_stats)]
-    lib.dfx_forward_adaptive_keep.argtypes = [H, _dp, _dp, C.c_int32, C.c_double, C.c_double, C.c_int64, C.c_int32, _dp, C.POINTER(dfx_stats)]
-    lib.dfx_design_forward.argtypes = [C.POINTER(dfx_design_map), _dp, C.c_int32, C.c_double, _dp, _dp, _dp, _dp]
-    lib.dfx_design_vjp.argtypes = [C.POINTER(dfx_design_map), _dp, C.c_int32, C.c_double, _dp, _dp, _dp, _dp, _dp]
-    lib.dfx_member_status.argtypes = [H, _ip]
-    lib.dfx_set_failure_policy.argtypes = [H, C.c_int32]
-    lib.dfx_test_set_spin_limit.argtypes = [H, C.c_int32]
-    lib.dfx_adjoint.argtypes = [H, _dp, C.POINTER(dfx_grads), C.POINTER(dfx_stats)]
-    lib.dfx_objective_kinetic.argtypes = [H, _ip, C.c_int32, _dp]
-    lib.dfx_adjoint_kinetic.argtypes = [H, _ip, C.c_int32, C.POINTER(dfx_grads), C.POINTER(dfx_stats)]
-    lib.dfx_kinetic_value_and_grad.argtypes = [H, _ip, C.c_int32, _dp, C.POINTER(dfx_grads), C.POINTER(dfx_grads), C.POINTER(dfx_stats)]
-    lib.dfx_response_data.argtypes = [H, _dp, _dp, _dp, _dp]
-    lib.dfx_rhs.argtypes = [H, _dp, C.c_double, _dp]
-    lib.dfx_rhs_vjp.argtypes = [H, _dp, C.c_double, _dp, _dp, C.POINTER(dfx_grads)]
-    lib.dfx_energy.argtypes = [H, _dp, _dp]
-    lib.dfx_device_count.restype = C.c_int
-    lib.dfx_version.restype = C.c_char_p
-    for name in EXPORTS:
-        if name not in ("dfx_last_error", "dfx_version", "dfx_comm_last_error") and (name not in COMM_EXPORTS or hasattr(lib, name)):
-            getattr(lib, name).restype = C.c_int
-    if hasattr(lib, "dfx_forward_tangent"):      # (the CPU port of the oracle has no forward mode)
-        lib.dfx_forward_tangent.argtypes = [H, _dp, _dp, C.POINTER(dfx_params), _dp, C.c_int32, _ip, _dp, C.c_int32, _dp, _dp,
-                                            C.POINTER(dfx_stats)]
-    if hasattr(lib, "dfx_forward_tangent_dense"):
-        _lp = C.POINTER(C.c_int64)
-        lib.dfx_forward_tangent_dense.argtypes = [H, _dp, _dp, C.POINTER(dfx_params), _dp, C.c_int32, _dp, _lp, C.c_int64, _dp, _dp,
-                                                  C.POINTER(dfx_stats)]
-        lib.dfx_dense_output_map.argtypes = [_dp, _lp, C.c_int64, C.c_int32, _dp, C.c_int32, _ip, _dp]
-    if hasattr(lib, "dfx_forward_tangent_multi"):
-        lib.dfx_forward_tangent_multi.argtypes = [H, _dp, _dp, C.POINTER(dfx_params), C.c_int32, _dp, C.c_int32, _ip, _dp, C.c_int32, _dp, _dp,
-                                                  C.POINTER(dfx_stats)]
-    if hasattr(lib, "dfx_forward_tangent_dense_multi"):
-        lib.dfx_forward_tangent_dense_multi.argtypes = [H, _dp, _dp, C.POINTER(dfx_params), C.c_int32, _dp, C.c_int32, _dp, C.POINTER(C.c_int64),
-                                                        C.c_int64, _dp, _dp, C.POINTER(dfx_stats)]
-    if hasattr(lib, "dfx_forward_tangent_signals_multi"):
-        _terms = [C.c_int32, _ip, _ip, _ip, _dp, C.c_int32]
-        lib.dfx_forward_tangent_signals_multi.argtypes = [H, _dp, _dp, C.POINTER(dfx_params), C.c_int32, _dp, C.c_int32, _ip, _dp, C.c_int32] + _terms + [
-            _dp, _dp, C.POINTER(dfx_stats)]
-        lib.dfx_forward_tangent_signals_dense_multi.argtypes = [H, _dp, _dp, C.POINTER(dfx_params), C.c_int32, _dp, C.c_int32, _dp,
-                                                                C.POINTER(C.c_int64), C.c_int64] + _terms + [_dp, _dp, C.POINTER(dfx_stats)]
-    if hasattr(lib, "dfx_rhs_jvp"):
-        lib.dfx_rhs_jvp.argtypes = [H, _dp, C.c_double, _dp, C.POINTER(dfx_params), C.c_int32, _dp, _dp]
-    if hasattr(lib, "dfx_objective_value_and_grad"):
-        lib.dfx_objective_value.argtypes = [H, C.c_int32, _dp, C.c_int32, _dp, _dp, C.c_int32, _dp]
-        lib.dfx_objective_value_and_grad.argtypes = [H, C.c_int32, _dp, C.c_int32, _dp, _dp, C.c_int32, _dp, C.POINTER(dfx_grads),
-                                                     C.POINTER(dfx_grads), C.c_int32, C.POINTER(dfx_stats)]
-    if hasattr(lib, "dfx_strain_objective_value_and_grad"):
-        lib.dfx_strain_objective_value.argtypes = [H, _dp, C.c_int32, _dp, _dp, _dp]
-        lib.dfx_strain_objective_value_and_grad.argtypes = [H, _dp, C.c_int32, _dp, _dp, _dp, C.POINTER(dfx_grads), C.POINTER(dfx_grads),
-                                                            C.c_int32, C.POINTER(dfx_stats)]
-    if hasattr(lib, "dfx_signal_misfit_value_and_grad"):
-        terms = [C.c_int32, _ip, _ip, _ip, _dp, C.c_int32]
-        lib.dfx_signal_values.argtypes = [H] + terms + [_dp]
-    if hasattr(lib, "dfx_signal_hinge_channels"):
-        lib.dfx_signal_hinge_channels.argtypes = [H, C.c_int32]
-        lib.dfx_signal_misfit_value.argtypes = [H] + terms + [_dp, C.c_int32, _dp, _dp, _dp]
-        lib.dfx_signal_misfit_value_and_grad.argtypes = [H] + terms + [_dp, C.c_int32, _dp, _dp, _dp, C.POINTER(dfx_grads), C.POINTER(dfx_grads),
-                                                                        C.c_int32, C.POINTER(dfx_stats)]
-    if hasattr(lib, "dfx_signal_projection_value_and_grad"):
-        terms = [C.c_int32, _ip, _ip, _ip, _dp, C.c_int32]
-        lib.dfx_signal_projections.argtypes = [H] + terms + [_dp, C.c_int32, _dp]
-        lib.dfx_signal_projection_value.argtypes = [H] + terms + [_dp, C.c_int32, _dp, _dp, C.c_int32, _dp]
-        lib.dfx_signal_projection_value_and_grad.argtypes = [H] + terms + [_dp, C.c_int32, _dp, _dp, C.c_int32, _dp, C.POINTER(dfx_grads),
-                                                                            C.POINTER(dfx_grads), C.c_int32, C.POINTER(dfx_stats)]
-    if hasattr(lib, "dfx_signal_xcorr_value_and_grad"):
-        terms = [C.c_int32, _ip, _ip, _ip, _dp, C.c_int32]
-        corr = [C.c_int32, _ip, _ip, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32]      # pairs, templates, max_lag, normalisation
-        value = [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, _dp, _dp, _dp]
-        lib.dfx_signal_xcorr.argtypes = [H] + terms + corr + [_dp]
-        lib.dfx_signal_xcorr_value.argtypes = [H] + terms + corr + value
-        lib.dfx_signal_xcorr_value_and_grad.argtypes = [H] + terms + corr + value + [C.POINTER(dfx_grads), C.POINTER(dfx_grads), C.c_int32,
-                                                                                      C.POINTER(dfx_stats)]
-    if hasattr(lib, "dfx_strain_peak_value_and_grad"):
-        peak = [_dp, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, C.c_double, _dp, _dp, _ip]      # coef, weights, tau, aggregate, sharpness, outputs
-        lib.dfx_strain_peak_value.argtypes = [H] + peak
-        lib.dfx_strain_peak_value_and_grad.argtypes = [H] + peak + [C.POINTER(dfx_grads), C.POINTER(dfx_grads), C.c_int32, C.POINTER(dfx_stats)]
-    if hasattr(lib, "dfx_fn_table_grads"):
-        lib.dfx_fn_table_values.argtypes = [H, C.c_int32, _dp, C.c_int32]
-        lib.dfx_fn_table_grads.argtypes = [H, C.c_int32]
-        lib.dfx_fn_table_grad.argtypes = [H, C.c_int32, _dp]
-        lib.dfx_drive_cotangent.argtypes = [H, C.c_int32, _dp, _dp, C.c_int64, C.POINTER(C.c_int64)]
-        lib.dfx_fn_table_tangents.argtypes = [H, C.c_int32, _dp, C.c_int32]
-    if hasattr(lib, "dfx_comm_init"):
-        lib.dfx_comm_unique_id.argtypes = [C.c_char_p]
-        lib.dfx_comm_init.argtypes = [C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(H)]
-        for n in ("dfx_comm_destroy", "dfx_comm_rank", "dfx_comm_size", "dfx_comm_barrier"):
-            getattr(lib, n).argtypes = [H]
-        lib.dfx_comm_rccl_version.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        lib.dfx_gather_objectives.argtypes = [H, _dp, C.c_int32, _dp]
-        lib.dfx_reduce_grads.argtypes = [H, _dp, C.c_int64]
-        lib.dfx_comm_allreduce.argtypes = [H, _dp, C.c_int64, C.c_int32]
-        lib.dfx_comm_last_error.argtypes = []
-        lib.dfx_comm_last_error.restype = C.c_char_p
-        lib.dfx_mem_info.argtypes = [C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        lib.dfx_device_synchronize.argtypes = [C.c_int32]
-        lib.dfx_kinetic_value_and_grad_device.argtypes = lib.dfx_kinetic_value_and_grad.argtypes
-        lib.dfx_download.argtypes = [H, _dp, C.c_void_p, C.c_int64]
-        lib.dfx_forward_kinetic_value_and_grad.argtypes = [H, _dp, _dp, C.c_int32, _ip, _ip, C.c_int32, _dp, C.POINTER(dfx_grads), C.POINTER(dfx_grads),
-                                                           C.c_int32, C.POINTER(dfx_stats), C.POINTER(dfx_stats)]
+    for name, argtypes in _ARGTYPES.items():
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = C.c_char_p if name in _STRING_RETURNS else C.c_int
     return lib
 
 
@@ -328,6 +322,18 @@ def _ptr(a):
     return a.ctypes.data_as(_dp) if a is not None else None
 
 
+_POINTER_OF = {np.dtype(np.float64): _dp, np.dtype(np.int32): _ip, np.dtype(np.int64): _lp}
+
+
+def _c(a):
+    """An array as the pointer of its element type (float64, int32 or int64); anything else -- a number, None, a pointer -- as it is."""
+    if not isinstance(a, np.ndarray):
+        return a
+    if a.dtype not in _POINTER_OF or not a.flags.c_contiguous:
+        raise TypeError(f"an array argument must be C-contiguous float64, int32 or int64, got {a.dtype}, C-contiguous: {a.flags.c_contiguous}")
+    return a.ctypes.data_as(_POINTER_OF[a.dtype])
+
+
 _WANTED = np.zeros(1)        # what a non-null field of a ``want`` points at (the library tests the pointer only)
 
 
@@ -421,32 +427,18 @@ class Engine:
 
     # -- solves -------------------------------------------------------------------------------
     def forward(self, state0, timepoints, steps_per_interval, keep_trajectory=False, want_fields=True, step_times=None):
-        B, nb = self.batch, self.n_blocks
-        state0 = _f64(state0, (B, 2, nb, 3)) if state0 is not None else None      # None: at rest (no upload)
-        ts = _f64(timepoints)
-        T = ts.shape[-1]
-        fields = np.empty((B, T, 2, nb, 3)) if want_fields else None
+        # state0 None: at rest (no upload); timepoints (batch, T): every member its own output times and step boundaries, shared
+        # step counts; step_times: caller-chosen step boundaries (every timepoint must be one of them)
+        scalar = np.ndim(steps_per_interval) == 0 and step_times is None
+        state0, ts, T, spis, step_times, per_member = self._fixed_grid_args(state0, timepoints, steps_per_interval, step_times)
+        fields = np.empty((self.batch, T, 2, self.n_blocks, 3)) if want_fields else None
         st = dfx_stats()
-        if ts.ndim == 2:        # (batch, T): every member its own output times and step boundaries, shared step counts
-            if ts.shape[0] != B:
-                raise ValueError(f"per-member timepoints must be (batch={B}, T)")
-            spis = np.ascontiguousarray(np.broadcast_to(steps_per_interval, (max(T - 1, 0),)), dtype=np.int32)
-            n = int(spis.sum())
-            if step_times is None:      # equal steps inside every member's own intervals
-                step_times = np.stack([np.concatenate([a + (b - a) * np.arange(k) / k for a, b, k in zip(row[:-1], row[1:], spis)] + [row[-1:]])
-                                       for row in ts])
-            step_times = _f64(step_times, (B, n + 1))
-            self._check(self.lib.dfx_forward_grid_members(self._h, _ptr(state0), _ptr(ts), T, spis.ctypes.data_as(_ip), _ptr(step_times),
-                                                          int(bool(keep_trajectory)), _ptr(fields), C.byref(st)), "dfx_forward_grid_members")
-        elif np.ndim(steps_per_interval) == 0 and step_times is None:
-            self._check(self.lib.dfx_forward(self._h, _ptr(state0), _ptr(ts), T, int(steps_per_interval),
-                                             int(bool(keep_trajectory)), _ptr(fields), C.byref(st)), "dfx_forward")
+        if scalar and not per_member:
+            entry, steps = "dfx_forward", (int(steps_per_interval),)
         else:   # its own number of equal steps in every output interval
-            spis = np.ascontiguousarray(np.broadcast_to(steps_per_interval, (max(T - 1, 0),)), dtype=np.int32)
-            if step_times is not None:      # caller-chosen step boundaries (every timepoint must be one of them)
-                step_times = _f64(step_times, (int(spis.sum()) + 1,))
-            self._check(self.lib.dfx_forward_grid(self._h, _ptr(state0), _ptr(ts), T, spis.ctypes.data_as(_ip), _ptr(step_times),
-                                                  int(bool(keep_trajectory)), _ptr(fields), C.byref(st)), "dfx_forward_grid")
+            entry, steps = "dfx_forward_grid_members" if per_member else "dfx_forward_grid", (_c(spis), _ptr(step_times))
+        self._check(getattr(self.lib, entry)(self._h, _ptr(state0), _ptr(ts), T, *steps, int(bool(keep_trajectory)), _ptr(fields), C.byref(st)),
+                    entry)
         self.n_timepoints = T
         return fields, _stats(st)
 
@@ -515,6 +507,42 @@ class Engine:
             raise ValueError(f"{who}: step_times (batch={B}, stride) and n_steps (batch,)")
         return state0, ts, len(ts), st_times, ns
 
+    def _forward_tangent(self, entry, state0, state0_dots, params_dots, n_dirs, timepoints, fixed=None, dense=None, signals=None):
+        """The six forward-tangent entries: ``fixed = (steps_per_interval, step_times)`` or ``dense = (step_times, n_steps)``;
+        ``n_dirs = None`` for the single-direction entries, which take one state0_dot / params_dot and no count; ``signals =
+        (terms, n_signals)`` keeps the history on the device and returns the signals instead of the fields."""
+        who = entry[len("dfx_"):]
+        self._need(entry)
+        K = 1 if n_dirs is None else int(n_dirs)
+        if K < 1 or (n_dirs is not None and params_dots is not None and len(params_dots) != K):
+            raise ValueError(f"{who}: need n_dirs >= 1 and one params_dot per direction (n_dirs={K})")
+        B, nb = self.batch, self.n_blocks
+        if dense is None:
+            state0, ts, T, spis, step_times, per_member = self._fixed_grid_args(state0, timepoints, *fixed)
+            grid = (_c(spis), _ptr(step_times), int(per_member))
+        else:
+            state0, ts, T, st_times, ns = self._dense_grid_args(who, state0, timepoints, *dense)
+            grid = (_ptr(st_times), _c(ns), st_times.shape[1])
+        if n_dirs is None:
+            state0_dots = _f64(state0_dots, (B, 2, nb, 3)) if state0_dots is not None else None
+            p, keep = self._params_dots([params_dots], 1)
+            dirs = ()
+        else:
+            state0_dots = self._state0_dots(state0_dots, K)
+            p, keep = self._params_dots(params_dots, K)
+            dirs = (K,)
+        if signals is None:
+            targs = ()
+            out, out_dots = np.empty((B, T, 2, nb, 3)), np.empty((B,) + dirs + (T, 2, nb, 3))
+        else:
+            targs, tkeep = self._signal_terms(*signals)
+            n_sig = max(int(signals[1]), 1)
+            out, out_dots = np.zeros((B, T, n_sig)), np.zeros((B, K, T, n_sig))      # (a refusal comes before the library writes)
+        st = dfx_stats()
+        self._check(getattr(self.lib, entry)(self._h, _ptr(state0), _ptr(state0_dots), p, *dirs, _ptr(ts), T, *grid, *targs, _ptr(out),
+                                             _ptr(out_dots), C.byref(st)), entry)
+        return out, out_dots, _stats(st)
+
     @property
     def has_forward_tangent(self):
         return hasattr(self.lib, "dfx_forward_tangent")
@@ -523,17 +551,8 @@ class Engine:
         """Primal fields and their directional derivative along (state0_dot, params_dot) of the fixed-grid solve (``dfx_forward_tangent``)
         on the parameters of the last :meth:`set_params`.  ``params_dot``: arrays by ``dfx_params`` field name (a missing one: zero
         tangent); ``timepoints`` (T,) or (batch, T) (then every member its own grid, as :meth:`forward`).  Returns (fields, fields_dot, stats)."""
-        self._need("dfx_forward_tangent")
-        B, nb = self.batch, self.n_blocks
-        state0, ts, T, spis, step_times, per_member = self._fixed_grid_args(state0, timepoints, steps_per_interval, step_times)
-        state0_dot = _f64(state0_dot, (B, 2, nb, 3)) if state0_dot is not None else None
-        p, keep = self._params_dots([params_dot], 1)
-        fields, fields_dot = np.empty((B, T, 2, nb, 3)), np.empty((B, T, 2, nb, 3))
-        st = dfx_stats()
-        self._check(self.lib.dfx_forward_tangent(self._h, _ptr(state0), _ptr(state0_dot), p, _ptr(ts), T, spis.ctypes.data_as(_ip),
-                                                 _ptr(step_times), int(per_member), _ptr(fields), _ptr(fields_dot), C.byref(st)),
-                    "dfx_forward_tangent")
-        return fields, fields_dot, _stats(st)
+        return self._forward_tangent("dfx_forward_tangent", state0, state0_dot, params_dot, None, timepoints,
+                                     fixed=(steps_per_interval, step_times))
 
     @property
     def has_forward_tangent_dense(self):
@@ -543,17 +562,7 @@ class Engine:
         """Primal fields and their directional derivative of the ADAPTIVE solve's dense output on every member's own frozen accepted steps
         (``dfx_forward_tangent_dense``): ``step_times`` (batch, stride) rows ``t_0 .. t_{N_m}``, ``n_steps`` (batch,)
         (:func:`padded_step_times`), ``timepoints`` (T,).  Otherwise as :meth:`forward_tangent`.  Returns (fields, fields_dot, stats)."""
-        self._need("dfx_forward_tangent_dense")
-        B, nb = self.batch, self.n_blocks
-        state0, ts, T, st_times, ns = self._dense_grid_args("forward_tangent_dense", state0, timepoints, step_times, n_steps)
-        state0_dot = _f64(state0_dot, (B, 2, nb, 3)) if state0_dot is not None else None
-        p, keep = self._params_dots([params_dot], 1)
-        fields, fields_dot = np.empty((B, T, 2, nb, 3)), np.empty((B, T, 2, nb, 3))
-        st = dfx_stats()
-        self._check(self.lib.dfx_forward_tangent_dense(self._h, _ptr(state0), _ptr(state0_dot), p, _ptr(ts), T, _ptr(st_times),
-                                                       ns.ctypes.data_as(C.POINTER(C.c_int64)), st_times.shape[1], _ptr(fields),
-                                                       _ptr(fields_dot), C.byref(st)), "dfx_forward_tangent_dense")
-        return fields, fields_dot, _stats(st)
+        return self._forward_tangent("dfx_forward_tangent_dense", state0, state0_dot, params_dot, None, timepoints, dense=(step_times, n_steps))
 
     @property
     def has_forward_tangent_multi(self):
@@ -563,20 +572,8 @@ class Engine:
         """:meth:`forward_tangent` for ``n_dirs`` directions per member with the primal evaluated once per stage
         (``dfx_forward_tangent_multi``): ``state0_dots`` (batch, n_dirs, 2, nb, 3) or None, ``params_dots`` a list of ``n_dirs`` dicts of
         arrays by ``dfx_params`` field name (or None).  Returns (fields (batch, T, ...), fields_dots (batch, n_dirs, T, ...), stats)."""
-        self._need("dfx_forward_tangent_multi")
-        K = int(n_dirs)
-        if K < 1 or (params_dots is not None and len(params_dots) != K):
-            raise ValueError(f"forward_tangent_multi: need n_dirs >= 1 and one params_dot per direction (n_dirs={K})")
-        B, nb = self.batch, self.n_blocks
-        state0, ts, T, spis, step_times, per_member = self._fixed_grid_args(state0, timepoints, steps_per_interval, step_times)
-        state0_dots = self._state0_dots(state0_dots, K)
-        p, keep = self._params_dots(params_dots, K)
-        fields, fields_dots = np.empty((B, T, 2, nb, 3)), np.empty((B, K, T, 2, nb, 3))
-        st = dfx_stats()
-        self._check(self.lib.dfx_forward_tangent_multi(self._h, _ptr(state0), _ptr(state0_dots), p, K, _ptr(ts), T, spis.ctypes.data_as(_ip),
-                                                       _ptr(step_times), int(per_member), _ptr(fields), _ptr(fields_dots), C.byref(st)),
-                    "dfx_forward_tangent_multi")
-        return fields, fields_dots, _stats(st)
+        return self._forward_tangent("dfx_forward_tangent_multi", state0, state0_dots, params_dots, n_dirs, timepoints,
+                                     fixed=(steps_per_interval, step_times))
 
     @property
     def has_forward_tangent_dense_multi(self):
@@ -585,20 +582,8 @@ class Engine:
     def forward_tangent_dense_multi(self, state0, state0_dots, params_dots, n_dirs, timepoints, step_times, n_steps):
         """:meth:`forward_tangent_dense` for ``n_dirs`` directions per member (``dfx_forward_tangent_dense_multi``); arguments as
         :meth:`forward_tangent_multi` and :meth:`forward_tangent_dense`.  Returns (fields, fields_dots (batch, n_dirs, T, ...), stats)."""
-        self._need("dfx_forward_tangent_dense_multi")
-        K = int(n_dirs)
-        if K < 1 or (params_dots is not None and len(params_dots) != K):
-            raise ValueError(f"forward_tangent_dense_multi: need n_dirs >= 1 and one params_dot per direction (n_dirs={K})")
-        B, nb = self.batch, self.n_blocks
-        state0, ts, T, st_times, ns = self._dense_grid_args("forward_tangent_dense_multi", state0, timepoints, step_times, n_steps)
-        state0_dots = self._state0_dots(state0_dots, K)
-        p, keep = self._params_dots(params_dots, K)
-        fields, fields_dots = np.empty((B, T, 2, nb, 3)), np.empty((B, K, T, 2, nb, 3))
-        st = dfx_stats()
-        self._check(self.lib.dfx_forward_tangent_dense_multi(self._h, _ptr(state0), _ptr(state0_dots), p, K, _ptr(ts), T, _ptr(st_times),
-                                                             ns.ctypes.data_as(C.POINTER(C.c_int64)), st_times.shape[1], _ptr(fields),
-                                                             _ptr(fields_dots), C.byref(st)), "dfx_forward_tangent_dense_multi")
-        return fields, fields_dots, _stats(st)
+        return self._forward_tangent("dfx_forward_tangent_dense_multi", state0, state0_dots, params_dots, n_dirs, timepoints,
+                                     dense=(step_times, n_steps))
 
     @property
     def has_forward_tangent_signals(self):
@@ -609,42 +594,14 @@ class Engine:
         """:meth:`forward_tangent_multi` with the history kept on the device (``dfx_forward_tangent_signals_multi``): the signals of
         ``terms`` (sequence of (signal, block, component, coef), as :meth:`signal_values`) and their tangents along the ``n_dirs``
         directions.  Returns (signals (batch, T, n_signals), signals_dots (batch, n_dirs, T, n_signals), stats)."""
-        self._need("dfx_forward_tangent_signals_multi")
-        K = int(n_dirs)
-        if K < 1 or (params_dots is not None and len(params_dots) != K):
-            raise ValueError(f"forward_tangent_signals_multi: need n_dirs >= 1 and one params_dot per direction (n_dirs={K})")
-        B, ns = self.batch, max(int(n_signals), 1)
-        state0, ts, T, spis, step_times, per_member = self._fixed_grid_args(state0, timepoints, steps_per_interval, step_times)
-        state0_dots = self._state0_dots(state0_dots, K)
-        p, keep = self._params_dots(params_dots, K)
-        targs, tkeep = self._signal_terms(terms, n_signals)
-        signals, signals_dots = np.zeros((B, T, ns)), np.zeros((B, K, T, ns))      # (a refusal comes before the library writes)
-        st = dfx_stats()
-        self._check(self.lib.dfx_forward_tangent_signals_multi(self._h, _ptr(state0), _ptr(state0_dots), p, K, _ptr(ts), T,
-                                                               spis.ctypes.data_as(_ip), _ptr(step_times), int(per_member), *targs,
-                                                               _ptr(signals), _ptr(signals_dots), C.byref(st)),
-                    "dfx_forward_tangent_signals_multi")
-        return signals, signals_dots, _stats(st)
+        return self._forward_tangent("dfx_forward_tangent_signals_multi", state0, state0_dots, params_dots, n_dirs, timepoints,
+                                     fixed=(steps_per_interval, step_times), signals=(terms, n_signals))
 
     def forward_tangent_signals_dense_multi(self, state0, state0_dots, params_dots, n_dirs, timepoints, step_times, n_steps, terms, n_signals):
         """:meth:`forward_tangent_dense_multi` with the history kept on the device (``dfx_forward_tangent_signals_dense_multi``);
         ``terms`` and the results as :meth:`forward_tangent_signals_multi`."""
-        self._need("dfx_forward_tangent_signals_dense_multi")
-        K = int(n_dirs)
-        if K < 1 or (params_dots is not None and len(params_dots) != K):
-            raise ValueError(f"forward_tangent_signals_dense_multi: need n_dirs >= 1 and one params_dot per direction (n_dirs={K})")
-        B, ns = self.batch, max(int(n_signals), 1)
-        state0, ts, T, st_times, nst = self._dense_grid_args("forward_tangent_signals_dense_multi", state0, timepoints, step_times, n_steps)
-        state0_dots = self._state0_dots(state0_dots, K)
-        p, keep = self._params_dots(params_dots, K)
-        targs, tkeep = self._signal_terms(terms, n_signals)
-        signals, signals_dots = np.zeros((B, T, ns)), np.zeros((B, K, T, ns))
-        st = dfx_stats()
-        self._check(self.lib.dfx_forward_tangent_signals_dense_multi(self._h, _ptr(state0), _ptr(state0_dots), p, K, _ptr(ts), T, _ptr(st_times),
-                                                                     nst.ctypes.data_as(C.POINTER(C.c_int64)), st_times.shape[1], *targs,
-                                                                     _ptr(signals), _ptr(signals_dots), C.byref(st)),
-                    "dfx_forward_tangent_signals_dense_multi")
-        return signals, signals_dots, _stats(st)
+        return self._forward_tangent("dfx_forward_tangent_signals_dense_multi", state0, state0_dots, params_dots, n_dirs, timepoints,
+                                     dense=(step_times, n_steps), signals=(terms, n_signals))
 
     def adaptive_step_counts(self):
         """(batch, T-1) accepted steps of the last forward_adaptive per member and output interval."""
@@ -730,6 +687,21 @@ class Engine:
             out[n] = a
         return out
 
+    def _value(self, entry, lead, outs):
+        """Run a value entry: ``lead`` its arguments behind the handle (arrays go as pointers), ``outs`` the arrays it fills."""
+        self._check(getattr(self.lib, entry)(self._h, *map(_c, lead), *map(_c, outs)), entry)
+        return outs
+
+    def _value_and_grad(self, entry, lead, outs, which, device, centroids=False, device_flag=True, more_stats=()):
+        """Run a ``*_value_and_grad`` entry: as :meth:`_value`, then the tail ``want, views[, device_views], stats`` (``device_flag=False``:
+        the kinetic entries, whose name says where the gradients stay; ``more_stats``: structs that go before the sweep's).  Returns
+        (gradients, stats of the reverse sweep)."""
+        want, views, names, st = self._grad_request(which, centroids)
+        tail = (int(bool(device)),) if device_flag else ()
+        self._check(getattr(self.lib, entry)(self._h, *map(_c, lead), *map(_c, outs), C.byref(want), C.byref(views), *tail,
+                                             *map(C.byref, more_stats), C.byref(st)), entry)
+        return self._grad_views(views, names, device), _stats(st)
+
     def _time_weights(self, time_weights):
         if time_weights is None:
             return None
@@ -770,13 +742,11 @@ class Engine:
         memory (valid until the next call on this engine: copy what must outlive it).  ``device=True`` leaves the gradients in HBM
         (HIP library only): the values are ``DeviceArray`` handles, ``.to_host()`` downloads one."""
         tb = np.ascontiguousarray(target_blocks, dtype=np.int32)
-        want, views, names, st = self._grad_request(which)
         obj = np.zeros(self.batch)
         entry = "dfx_kinetic_value_and_grad_device" if device else "dfx_kinetic_value_and_grad"
         if device and not hasattr(self.lib, entry):
             raise RuntimeError("device-resident gradients need the HIP library")
-        self._check(getattr(self.lib, entry)(self._h, tb.ctypes.data_as(_ip), len(tb), _ptr(obj), C.byref(want), C.byref(views), C.byref(st)), entry)
-        return obj, self._grad_views(views, names, device), _stats(st)
+        return (obj,) + self._value_and_grad(entry, (tb, len(tb)), (obj,), which, device, device_flag=False)
 
     def forward_kinetic_value_and_grad(self, state0, timepoints, steps_per_interval, target_blocks, which=ALL_GRADS, device=False):
         """``forward(keep_trajectory=True, want_fields=False)`` + ``kinetic_value_and_grad`` as ONE library call (HIP library only): the host
@@ -791,14 +761,12 @@ class Engine:
         T = len(ts)
         spis = np.ascontiguousarray(np.broadcast_to(steps_per_interval, (max(T - 1, 0),)), dtype=np.int32)
         tb = np.ascontiguousarray(target_blocks, dtype=np.int32)
-        want, views, names, st_a = self._grad_request(which)
         obj = np.zeros(B)
         st_f = dfx_stats()
-        self._check(self.lib.dfx_forward_kinetic_value_and_grad(self._h, _ptr(state0), _ptr(ts), T, spis.ctypes.data_as(_ip), tb.ctypes.data_as(_ip),
-                                                                len(tb), _ptr(obj), C.byref(want), C.byref(views), int(bool(device)),
-                                                                C.byref(st_f), C.byref(st_a)), "dfx_forward_kinetic_value_and_grad")
+        grads, st_a = self._value_and_grad("dfx_forward_kinetic_value_and_grad", (state0, ts, T, spis, tb, len(tb)), (obj,), which, device,
+                                           more_stats=(st_f,))
         self.n_timepoints = T
-        return obj, self._grad_views(views, names, device), _stats(st_f), _stats(st_a)
+        return obj, grads, _stats(st_f), st_a
 
     # -- weighted objectives on the device-resident history ----------------------------------------------
     @property
@@ -819,27 +787,20 @@ class Engine:
             lev = _f64(lever0)
             if lev.shape not in ((nb, 2), (B, nb, 2)):
                 raise ValueError(f"lever0 must be ({nb}, 2) or ({B}, {nb}, 2), got {lev.shape}")
-        return w, int(w.ndim == 2), tau, lev, int(lev is not None and lev.ndim == 3)
+        return int(kind), w, int(w.ndim == 2), tau, lev, int(lev is not None and lev.ndim == 3)
 
     def objective_value(self, kind, block_weights, time_weights=None, lever0=None):
         """(batch,) value of a weighted objective (``OBJ_KINETIC`` / ``OBJ_ANGULAR_MOMENTUM``, ``dfx_objective_value``) on the resident
         history of the last forward pass."""
-        w, wpm, tau, lev, lpm = self._objective_args(kind, block_weights, time_weights, lever0)
-        obj = np.zeros(self.batch)
-        self._check(self.lib.dfx_objective_value(self._h, int(kind), _ptr(w), wpm, _ptr(tau), _ptr(lev), lpm, _ptr(obj)), "dfx_objective_value")
-        return obj
+        return self._value("dfx_objective_value", self._objective_args(kind, block_weights, time_weights, lever0), [np.zeros(self.batch)])[0]
 
     def objective_value_and_grad(self, kind, block_weights, time_weights=None, lever0=None, which=ALL_GRADS, device=False):
         """Value (batch,) and the requested gradients of a weighted objective in ONE call (``dfx_objective_value_and_grad``): the cotangent
         is formed on the device, the objective rides along with the reverse sweep, the explicit inertia / block-centroid terms are added
         behind it.  Results as :meth:`kinetic_value_and_grad`: read-only views of pinned memory, or ``DeviceArray`` handles with
         ``device=True``; ``block_centroids`` is available on every lattice for the angular kind."""
-        w, wpm, tau, lev, lpm = self._objective_args(kind, block_weights, time_weights, lever0)
-        want, views, names, st = self._grad_request(which, int(kind) == OBJ_ANGULAR_MOMENTUM)
-        obj = np.zeros(self.batch)
-        self._check(self.lib.dfx_objective_value_and_grad(self._h, int(kind), _ptr(w), wpm, _ptr(tau), _ptr(lev), lpm, _ptr(obj), C.byref(want),
-                                                          C.byref(views), int(bool(device)), C.byref(st)), "dfx_objective_value_and_grad")
-        return obj, self._grad_views(views, names, device), _stats(st)
+        lead, obj = self._objective_args(kind, block_weights, time_weights, lever0), np.zeros(self.batch)
+        return (obj,) + self._value_and_grad("dfx_objective_value_and_grad", lead, (obj,), which, device, centroids=lead[0] == OBJ_ANGULAR_MOMENTUM)
 
     # -- ligament strain-energy objective on the device-resident history ----------------------------------
     @property
@@ -862,22 +823,14 @@ class Engine:
 
     def strain_objective_value(self, bond_weights, time_weights=None, parts=(1.0, 1.0, 1.0, 0.0)):
         """(batch,) weighted ligament strain energy (``dfx_strain_objective_value``) on the resident history of the last forward pass."""
-        w, wpm, tau, c = self._strain_objective_args(bond_weights, time_weights, parts)
-        obj = np.zeros(self.batch)
-        self._check(self.lib.dfx_strain_objective_value(self._h, _ptr(w), wpm, _ptr(tau), _ptr(c), _ptr(obj)), "dfx_strain_objective_value")
-        return obj
+        return self._value("dfx_strain_objective_value", self._strain_objective_args(bond_weights, time_weights, parts), [np.zeros(self.batch)])[0]
 
     def strain_objective_value_and_grad(self, bond_weights, time_weights=None, parts=(1.0, 1.0, 1.0, 0.0), which=ALL_GRADS, device=False):
         """Value (batch,) and the requested gradients of the weighted ligament strain energy in ONE call
         (``dfx_strain_objective_value_and_grad``): the ligament forces are formed on the device as the cotangent of the reverse sweep, the
         explicit node-vector / void-angle / per-ligament terms are added behind it.  Results as :meth:`objective_value_and_grad`."""
-        w, wpm, tau, c = self._strain_objective_args(bond_weights, time_weights, parts)
-        want, views, names, st = self._grad_request(which)
-        obj = np.zeros(self.batch)
-        self._check(self.lib.dfx_strain_objective_value_and_grad(self._h, _ptr(w), wpm, _ptr(tau), _ptr(c), _ptr(obj), C.byref(want),
-                                                                 C.byref(views), int(bool(device)), C.byref(st)),
-                    "dfx_strain_objective_value_and_grad")
-        return obj, self._grad_views(views, names, device), _stats(st)
+        lead, obj = self._strain_objective_args(bond_weights, time_weights, parts), np.zeros(self.batch)
+        return (obj,) + self._value_and_grad("dfx_strain_objective_value_and_grad", lead, (obj,), which, device)
 
     # -- peak ligament strain on the device-resident history --------------------------------------------------
     @property
@@ -901,27 +854,22 @@ class Engine:
         agg = {"ks": PEAK_KS, "pnorm": PEAK_PNORM}.get(aggregate, aggregate)
         return c, int(c.ndim == 3), w, int(w is not None and w.ndim == 2), tau, int(agg), float(sharpness)
 
+    def _peak_outs(self):
+        return np.zeros(self.batch), np.zeros(self.batch), np.zeros((self.batch, 2), dtype=np.int32)          # J, peak, peak_at
+
     def strain_peak_value(self, bond_coef, bond_weights=None, time_weights=None, aggregate="ks", sharpness=1.0):
         """(J, peak, peak_at): the smooth maximum (batch,), the hard maximum (batch,) and its (output, bond) (batch, 2) of the ligament strain
         measure (``dfx_strain_peak_value``) on the resident history of the last forward pass."""
-        c, cpm, w, wpm, tau, agg, sharp = self._strain_peak_args(bond_coef, bond_weights, time_weights, aggregate, sharpness)
-        obj, peak, at = np.zeros(self.batch), np.zeros(self.batch), np.zeros((self.batch, 2), dtype=np.int32)
-        self._check(self.lib.dfx_strain_peak_value(self._h, _ptr(c), cpm, _ptr(w), wpm, _ptr(tau), agg, sharp, _ptr(obj), _ptr(peak),
-                                                   at.ctypes.data_as(_ip)), "dfx_strain_peak_value")
-        return obj, peak, at
+        lead = self._strain_peak_args(bond_coef, bond_weights, time_weights, aggregate, sharpness)
+        return self._value("dfx_strain_peak_value", lead, self._peak_outs())
 
     def strain_peak_value_and_grad(self, bond_coef, bond_weights=None, time_weights=None, aggregate="ks", sharpness=1.0, which=ALL_GRADS,
                                    device=False):
         """(J, peak, peak_at) and the requested gradients of J in ONE call (``dfx_strain_peak_value_and_grad``): maximum, softmax sum and
         the softmax-weighted ligament forces are formed on the device as the cotangent of the reverse sweep, the explicit node-vector /
         reference-vector terms are added behind it.  Results as :meth:`objective_value_and_grad`."""
-        c, cpm, w, wpm, tau, agg, sharp = self._strain_peak_args(bond_coef, bond_weights, time_weights, aggregate, sharpness)
-        want, views, names, st = self._grad_request(which)
-        obj, peak, at = np.zeros(self.batch), np.zeros(self.batch), np.zeros((self.batch, 2), dtype=np.int32)
-        self._check(self.lib.dfx_strain_peak_value_and_grad(self._h, _ptr(c), cpm, _ptr(w), wpm, _ptr(tau), agg, sharp, _ptr(obj), _ptr(peak),
-                                                            at.ctypes.data_as(_ip), C.byref(want), C.byref(views), int(bool(device)),
-                                                            C.byref(st)), "dfx_strain_peak_value_and_grad")
-        return (obj, peak, at), self._grad_views(views, names, device), _stats(st)
+        lead, outs = self._strain_peak_args(bond_coef, bond_weights, time_weights, aggregate, sharpness), self._peak_outs()
+        return (outs,) + self._value_and_grad("dfx_strain_peak_value_and_grad", lead, outs, which, device)
 
     # -- signal misfit on the device-resident history ---------------------------------------------------------
     @property
@@ -961,29 +909,21 @@ class Engine:
         displacement (components 0..2), velocity (3..5), elastic-force (6..8) and, with ``hinge_channels`` set, hinge-force (9 + 3 node + dof) components of blocks."""
         args, keep = self._signal_terms(terms, n_signals)
         out = np.zeros((self.batch, self.n_timepoints or 1, max(int(n_signals), 1)))       # (no forward pass yet: the library refuses before it writes)
-        self._check(self.lib.dfx_signal_values(self._h, *args, _ptr(out)), "dfx_signal_values")
-        return out
+        return self._value("dfx_signal_values", args, [out])[0]
 
     def signal_misfit_value(self, terms, n_signals, targets, signal_weights=None, time_weights=None):
         """(batch,) least-squares misfit of the signals against ``targets`` (``dfx_signal_misfit_value``)."""
         args, keep = self._signal_terms(terms, n_signals)
-        tg, tpm, om, tau = self._signal_targets(n_signals, targets, signal_weights, time_weights)
-        obj = np.zeros(self.batch)
-        self._check(self.lib.dfx_signal_misfit_value(self._h, *args, _ptr(tg), tpm, _ptr(om), _ptr(tau), _ptr(obj)), "dfx_signal_misfit_value")
-        return obj
+        lead = args + self._signal_targets(n_signals, targets, signal_weights, time_weights)
+        return self._value("dfx_signal_misfit_value", lead, [np.zeros(self.batch)])[0]
 
     def signal_misfit_value_and_grad(self, terms, n_signals, targets, signal_weights=None, time_weights=None, which=ALL_GRADS, device=False):
         """Value (batch,) and the requested gradients of the signal misfit in ONE call (``dfx_signal_misfit_value_and_grad``): channels,
         signals and residual cotangents are formed on the device, force terms add the Hessian-vector product K w to the cotangent of the
         reverse sweep and their mixed second derivatives behind it.  Results as :meth:`objective_value_and_grad`."""
         args, keep = self._signal_terms(terms, n_signals)
-        tg, tpm, om, tau = self._signal_targets(n_signals, targets, signal_weights, time_weights)
-        want, views, names, st = self._grad_request(which)
-        obj = np.zeros(self.batch)
-        self._check(self.lib.dfx_signal_misfit_value_and_grad(self._h, *args, _ptr(tg), tpm, _ptr(om), _ptr(tau), _ptr(obj), C.byref(want),
-                                                              C.byref(views), int(bool(device)), C.byref(st)),
-                    "dfx_signal_misfit_value_and_grad")
-        return obj, self._grad_views(views, names, device), _stats(st)
+        lead, obj = args + self._signal_targets(n_signals, targets, signal_weights, time_weights), np.zeros(self.batch)
+        return (obj,) + self._value_and_grad("dfx_signal_misfit_value_and_grad", lead, (obj,), which, device)
 
     # -- signal projections on the device-resident history -----------------------------------------------------
     @property
@@ -1017,29 +957,21 @@ class Engine:
         args, keep = self._signal_terms(terms, n_signals)
         b, nr, _, _, _ = self._projection_args(n_signals, basis, weights=False)
         out = np.zeros((self.batch, max(int(n_signals), 1), max(nr, 1)))       # (a refused call: the library refuses before it writes)
-        self._check(self.lib.dfx_signal_projections(self._h, *args, _ptr(b), nr, _ptr(out)), "dfx_signal_projections")
-        return out
+        return self._value("dfx_signal_projections", args + (b, nr), [out])[0]
 
     def signal_projection_value(self, terms, n_signals, basis, row_weights, targets=None):
         """(batch,) weighted quadratic form 1/2 sum W (P - Ptarget)^2 of the projections (``dfx_signal_projection_value``)."""
         args, keep = self._signal_terms(terms, n_signals)
-        b, nr, w, tg, tpm = self._projection_args(n_signals, basis, row_weights, targets)
-        obj = np.zeros(self.batch)
-        self._check(self.lib.dfx_signal_projection_value(self._h, *args, _ptr(b), nr, _ptr(w), _ptr(tg), tpm, _ptr(obj)), "dfx_signal_projection_value")
-        return obj
+        lead = args + self._projection_args(n_signals, basis, row_weights, targets)
+        return self._value("dfx_signal_projection_value", lead, [np.zeros(self.batch)])[0]
 
     def signal_projection_value_and_grad(self, terms, n_signals, basis, row_weights, targets=None, which=ALL_GRADS, device=False):
         """Value (batch,) and the requested gradients of the projection objective in ONE call (``dfx_signal_projection_value_and_grad``):
         the time reduction and the cotangent on the signals are formed on the device, everything behind them is the signal misfit's.
         Results as :meth:`signal_misfit_value_and_grad`."""
         args, keep = self._signal_terms(terms, n_signals)
-        b, nr, w, tg, tpm = self._projection_args(n_signals, basis, row_weights, targets)
-        want, views, names, st = self._grad_request(which)
-        obj = np.zeros(self.batch)
-        self._check(self.lib.dfx_signal_projection_value_and_grad(self._h, *args, _ptr(b), nr, _ptr(w), _ptr(tg), tpm, _ptr(obj), C.byref(want),
-                                                                  C.byref(views), int(bool(device)), C.byref(st)),
-                    "dfx_signal_projection_value_and_grad")
-        return obj, self._grad_views(views, names, device), _stats(st)
+        lead, obj = args + self._projection_args(n_signals, basis, row_weights, targets), np.zeros(self.batch)
+        return (obj,) + self._value_and_grad("dfx_signal_projection_value_and_grad", lead, (obj,), which, device)
 
     # -- signal cross-correlation on the device-resident history ------------------------------------------------
     @property
@@ -1049,7 +981,7 @@ class Engine:
     def _xcorr_args(self, n_signals, pairs, max_lag, templates, normalisation):
         """The pair, template, lag and normalisation arguments of ``dfx_signal_xcorr*``: ``pairs`` a sequence of (a, b), b < 0 naming
         column -1 - b of ``templates`` (T, n_templates) or (batch, T, n_templates); ``normalisation`` a name of ``XCORR_NORMS`` (or its
-        number).  Returns (the C arguments, the arrays they point into)."""
+        number)."""
         self._need("dfx_signal_xcorr_value_and_grad", "signal cross-correlation", self._STALE)
         B, T = self.batch, self.n_timepoints
         p = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
@@ -1061,7 +993,7 @@ class Engine:
                 raise ValueError(f"templates must be ({T}, n_templates) or ({B}, {T}, n_templates), got {tp.shape}")
             nt = tp.shape[-1]
         norm = XCORR_NORMS[normalisation] if isinstance(normalisation, str) else int(normalisation)
-        return (len(p), pa.ctypes.data_as(_ip), pb.ctypes.data_as(_ip), _ptr(tp), nt, int(tp is not None and tp.ndim == 3), int(max_lag), norm), (pa, pb, tp)
+        return len(p), pa, pb, tp, nt, int(tp is not None and tp.ndim == 3), int(max_lag), norm
 
     @staticmethod
     def _xcorr_value_args(reduce, lag, beta, w_peak, w_delay, delay_target):
@@ -1071,37 +1003,29 @@ class Engine:
     def signal_xcorr(self, terms, n_signals, pairs, max_lag, templates=None, normalisation="reference"):
         """(batch, 2 max_lag + 1) normalised cross-correlation rho of the signal pairs over the lags -max_lag .. max_lag in output indices
         (``dfx_signal_xcorr``; lag d at index d + max_lag, d > 0: side B lags side A) on the resident history of the last forward pass."""
-        xa, keep2 = self._xcorr_args(n_signals, pairs, max_lag, templates, normalisation)
+        xa = self._xcorr_args(n_signals, pairs, max_lag, templates, normalisation)
         args, keep = self._signal_terms(terms, n_signals)
-        out = np.zeros((self.batch, 2 * max(int(max_lag), 0) + 1))
-        self._check(self.lib.dfx_signal_xcorr(self._h, *args, *xa, _ptr(out)), "dfx_signal_xcorr")
-        return out
+        return self._value("dfx_signal_xcorr", args + xa, [np.zeros((self.batch, 2 * max(int(max_lag), 0) + 1))])[0]
 
     def signal_xcorr_value(self, terms, n_signals, pairs, max_lag, templates=None, normalisation="reference", reduce="max", lag=None, beta=None,
                            w_peak=1.0, w_delay=0.0, delay_target=0.0):
         """(J, peak, delay), (batch,) each: J = w_peak M + 1/2 w_delay (delta - delay_target)^2 of the reduction ``reduce`` ("at" the lag
         ``lag``, "max", "softmax" with ``beta``) of the cross-correlation over the lags (``dfx_signal_xcorr_value``)."""
-        xa, keep2 = self._xcorr_args(n_signals, pairs, max_lag, templates, normalisation)
+        xa = self._xcorr_args(n_signals, pairs, max_lag, templates, normalisation)
         args, keep = self._signal_terms(terms, n_signals)
-        va = self._xcorr_value_args(reduce, lag, beta, w_peak, w_delay, delay_target)
-        obj, peak, delay = np.zeros(self.batch), np.zeros(self.batch), np.zeros(self.batch)
-        self._check(self.lib.dfx_signal_xcorr_value(self._h, *args, *xa, *va, _ptr(obj), _ptr(peak), _ptr(delay)), "dfx_signal_xcorr_value")
-        return obj, peak, delay
+        lead = args + xa + self._xcorr_value_args(reduce, lag, beta, w_peak, w_delay, delay_target)
+        return self._value("dfx_signal_xcorr_value", lead, (np.zeros(self.batch), np.zeros(self.batch), np.zeros(self.batch)))
 
     def signal_xcorr_value_and_grad(self, terms, n_signals, pairs, max_lag, templates=None, normalisation="reference", reduce="max", lag=None,
                                     beta=None, w_peak=1.0, w_delay=0.0, delay_target=0.0, which=ALL_GRADS, device=False):
         """(J, peak, delay) and the requested gradients of J in ONE call (``dfx_signal_xcorr_value_and_grad``): the correlation over the lags,
         its reduction and the cotangent on the signals are formed on the device, everything behind them is the signal misfit's.  Returns
         (J, peak, delay, gradients, stats), the gradients as :meth:`signal_misfit_value_and_grad`."""
-        xa, keep2 = self._xcorr_args(n_signals, pairs, max_lag, templates, normalisation)
+        xa = self._xcorr_args(n_signals, pairs, max_lag, templates, normalisation)
         args, keep = self._signal_terms(terms, n_signals)
-        va = self._xcorr_value_args(reduce, lag, beta, w_peak, w_delay, delay_target)
-        want, views, names, st = self._grad_request(which)
-        obj, peak, delay = np.zeros(self.batch), np.zeros(self.batch), np.zeros(self.batch)
-        self._check(self.lib.dfx_signal_xcorr_value_and_grad(self._h, *args, *xa, *va, _ptr(obj), _ptr(peak), _ptr(delay), C.byref(want),
-                                                             C.byref(views), int(bool(device)), C.byref(st)),
-                    "dfx_signal_xcorr_value_and_grad")
-        return obj, peak, delay, self._grad_views(views, names, device), _stats(st)
+        lead = args + xa + self._xcorr_value_args(reduce, lag, beta, w_peak, w_delay, delay_target)
+        outs = np.zeros(self.batch), np.zeros(self.batch), np.zeros(self.batch)          # J, peak, delay
+        return outs + self._value_and_grad("dfx_signal_xcorr_value_and_grad", lead, outs, which, device)
 
     # -- the samples of a table drive as a differentiable leaf ------------------------------------------------
     @property

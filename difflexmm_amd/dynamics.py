@@ -984,24 +984,39 @@ class DynamicSolver:
         which = self._raw_which(which)
         return self._take_stats(self.engine.kinetic_value_and_grad(target_blocks, which=which))
 
+    def _engine_call(self, spec, suffix, **kwargs):
+        """``Engine.<family><suffix>`` on the arguments ``spec.engine_call()`` states; the terms of its ``SignalSpec``, if any, lead them."""
+        family, signal_spec, args, spec_kwargs = spec.engine_call()
+        terms = () if signal_spec is None else self._terms(signal_spec)
+        return getattr(self.engine, family + suffix)(*terms, *args, **spec_kwargs, **kwargs)
+
+    def value(self, spec):
+        """The value of any spec of ``objective`` on the device-resident history of the last solve (any forward pass): (batch,), or
+        (J, peak, peak_at) / (J, peak, delay) for the peak-strain and cross-correlation specs."""
+        return self._engine_call(spec, "_value")
+
+    def value_and_raw(self, spec, which=("centroid_node_vectors", "void_angle0", "inertia"), device=False):
+        """``(value, raw)`` of any spec of ``objective`` on the last kept solve: ``value`` as :meth:`value` returns it, ``raw`` the raw
+        gradients of the parameter groups ``which`` as :meth:`kinetic_energy_value_and_raw` (``device=True``: ``DeviceArray`` handles)."""
+        which = self._raw_which(which, centroids=getattr(spec, "needs_centroids", False))
+        *out, raw = self._take_stats(self._engine_call(spec, "_value_and_grad", which=which, device=device))
+        return (out[0] if len(out) == 1 else tuple(out)), raw
+
     def objective_value(self, spec):
         """(batch,) value of a weighted objective (``objective.ObjectiveSpec``) on the device-resident history of the last solve."""
-        return self.engine.objective_value(spec.kind, spec.block_weights, spec.time_weights, spec.lever0)
+        return self.value(spec)
 
     def objective_value_and_raw(self, spec, which=("centroid_node_vectors", "void_angle0", "inertia"), device=False):
         """A weighted kinetic-energy / angular-momentum objective (``objective.ObjectiveSpec``) of the last kept solve, evaluated and
         differentiated on the device like :meth:`kinetic_energy_value_and_raw`: the history stays in HBM, the cotangent is formed there,
         and the explicit inertia / block-centroid terms are already in the raw gradients returned (``block_centroids`` is added to
         ``which`` for the angular kind: its levers contain the centroids)."""
-        from .objective import ANGULAR_MOMENTUM
-        which = self._raw_which(which, centroids=spec.kind == ANGULAR_MOMENTUM)
-        return self._take_stats(self.engine.objective_value_and_grad(spec.kind, spec.block_weights, spec.time_weights, spec.lever0, which=which,
-                                                                     device=device))
+        return self.value_and_raw(spec, which, device)
 
     def strain_objective_value(self, spec):
         """(batch,) value of a weighted ligament strain-energy objective (``objective.StrainObjectiveSpec``) on the device-resident history
         of the last solve (any forward pass: no kept trajectory needed)."""
-        return self.engine.strain_objective_value(spec.bond_weights, spec.time_weights, spec.parts)
+        return self.value(spec)
 
     def strain_objective_value_and_raw(self, spec, which=("centroid_node_vectors", "void_angle0", "inertia"), device=False):
         """The weighted ligament strain energy (``objective.StrainObjectiveSpec``) of the last kept solve, evaluated and differentiated on
@@ -1009,15 +1024,13 @@ class DynamicSolver:
         of the reverse sweep, and the explicit node-vector, void-angle and (when ``which`` names ``reference_vector`` / ``k_bond`` /
         ``contact``) per-ligament terms are already in the raw gradients returned.  As with :meth:`vjp_raw`, ``fn_params`` holds what the
         sweep accumulates: the direct dependence of a prescribed output DOF on its drive is not in it."""
-        which = self._raw_which(which)
-        return self._take_stats(self.engine.strain_objective_value_and_grad(spec.bond_weights, spec.time_weights, spec.parts, which=which,
-                                                                            device=device))
+        return self.value_and_raw(spec, which, device)
 
     def peak_strain_value(self, spec):
         """(J, peak, peak_at) of a peak ligament-strain measure (``objective.PeakStrainSpec``) on the device-resident history of the last
         solve (any forward pass: no kept trajectory needed): the smooth maximum (batch,), the hard maximum (batch,) and its (output, bond)
         (batch, 2)."""
-        return self.engine.strain_peak_value(spec.bond_coef, spec.bond_weights, spec.time_weights, spec.aggregate, spec.sharpness)
+        return self.value(spec)
 
     def peak_strain_value_and_raw(self, spec, which=("centroid_node_vectors", "void_angle0", "inertia"), device=False):
         """The peak ligament strain (``objective.PeakStrainSpec``) of the last kept solve, evaluated and differentiated on the device beside
@@ -1026,9 +1039,7 @@ class DynamicSolver:
         vector terms are already in the raw gradients returned.  The coefficients of the spec are constants: the ``reference_vector``
         gradient does not see how ``objective.strain_limit_coefficients`` derived them from l0.  As with :meth:`vjp_raw`, ``fn_params``
         holds what the sweep accumulates: the direct dependence of a prescribed output DOF on its drive is not in it."""
-        which = self._raw_which(which)
-        return self._take_stats(self.engine.strain_peak_value_and_grad(spec.bond_coef, spec.bond_weights, spec.time_weights, spec.aggregate,
-                                                                       spec.sharpness, which=which, device=device))
+        return self.value_and_raw(spec, which, device)
 
     def _terms(self, spec):
         """(terms, n_signals) of an ``objective.SignalSpec`` for the engine, whose hinge components are switched on or off as the spec says
@@ -1044,7 +1055,7 @@ class DynamicSolver:
 
     def signal_misfit_value(self, spec):
         """(batch,) least-squares misfit of an ``objective.SignalSpec`` against its targets on the device-resident history."""
-        return self.engine.signal_misfit_value(*self._terms(spec), spec.targets, spec.omega, spec.tau)
+        return self.value(spec)
 
     def signal_misfit_value_and_raw(self, spec, which=("centroid_node_vectors", "void_angle0", "inertia"), device=False):
         """The signal misfit (``objective.SignalSpec``) of the last kept solve, evaluated and differentiated on the device beside
@@ -1052,9 +1063,7 @@ class DynamicSolver:
         onto the fields are formed in HBM; the mixed second derivatives of the force terms (node vectors, void angles and, when ``which``
         names them, ``reference_vector`` / ``k_bond`` / ``contact``) are already in the raw gradients returned.  As with :meth:`vjp_raw`,
         ``fn_params`` holds what the sweep accumulates: the direct dependence of a prescribed output DOF on its drive is not in it."""
-        which = self._raw_which(which)
-        return self._take_stats(self.engine.signal_misfit_value_and_grad(*self._terms(spec), spec.targets, spec.omega, spec.tau,
-                                                                         which=which, device=device))
+        return self.value_and_raw(spec, which, device)
 
     def signal_projections(self, spec):
         """(batch, n_signals, n_rows) projections of the signals of an ``objective.ProjectionSpec`` on the rows of its time basis, on the
@@ -1063,20 +1072,13 @@ class DynamicSolver:
 
     def signal_projection_value(self, spec):
         """(batch,) weighted quadratic form of the projections of an ``objective.ProjectionSpec`` on the device-resident history."""
-        return self.engine.signal_projection_value(*self._terms(spec.signal_spec), spec.basis, spec.row_weights, spec.targets)
+        return self.value(spec)
 
     def signal_projection_value_and_raw(self, spec, which=("centroid_node_vectors", "void_angle0", "inertia"), device=False):
         """The projection objective (``objective.ProjectionSpec``) of the last kept solve, evaluated and differentiated on the device
         beside :meth:`signal_misfit_value_and_raw`: the time reduction and the cotangent on the signals are formed in HBM; what follows
         (the Hessian-vector product of force terms, their mixed second derivatives, what ``fn_params`` holds) is that method's."""
-        which = self._raw_which(which)
-        return self._take_stats(self.engine.signal_projection_value_and_grad(*self._terms(spec.signal_spec), spec.basis,
-                                                                             spec.row_weights, spec.targets, which=which, device=device))
-
-    @staticmethod
-    def _xcorr_kwargs(spec):
-        return dict(templates=spec.templates, normalisation=spec.normalisation, reduce=spec.reduce, lag=spec.lag, beta=spec.beta,
-                    w_peak=spec.w_peak, w_delay=spec.w_delay, delay_target=spec.delay_target)
+        return self.value_and_raw(spec, which, device)
 
     def signal_xcorr(self, spec):
         """(batch, 2 max_lag + 1) normalised cross-correlation of the signal pairs of an ``objective.CorrelationSpec`` over its lags (lag d
@@ -1086,17 +1088,14 @@ class DynamicSolver:
 
     def signal_xcorr_value(self, spec):
         """(J, peak, delay), (batch,) each, of an ``objective.CorrelationSpec`` on the device-resident history."""
-        return self.engine.signal_xcorr_value(*self._terms(spec.signal_spec), spec.pairs, spec.max_lag, **self._xcorr_kwargs(spec))
+        return self.value(spec)
 
     def signal_xcorr_value_and_raw(self, spec, which=("centroid_node_vectors", "void_angle0", "inertia"), device=False):
         """The cross-correlation objective (``objective.CorrelationSpec``) of the last kept solve, evaluated and differentiated on the
         device beside :meth:`signal_projection_value_and_raw`: the correlation over the lags, its reduction to a peak and a delay and the
         cotangent on the signals are formed in HBM; what follows is :meth:`signal_misfit_value_and_raw`'s.  Returns
         ((J, peak, delay), raw gradients)."""
-        which = self._raw_which(which)
-        *out, grads = self._take_stats(self.engine.signal_xcorr_value_and_grad(*self._terms(spec.signal_spec), spec.pairs,
-                                                                               spec.max_lag, which=which, device=device, **self._xcorr_kwargs(spec)))
-        return tuple(out), grads
+        return self.value_and_raw(spec, which, device)
 
     @staticmethod
     def _bond_params_bar(bp, kb, refv_bar, like):

@@ -62,6 +62,17 @@ class ObjectiveSpec(NamedTuple):
     time_weights: Any = None
     lever0: Any = None
 
+    def engine_call(self):
+        """How ``DynamicSolver.value`` / ``value_and_raw`` reach the engine with a spec, stated once per spec class: (family -- the
+        methods are ``Engine.<family>_value`` and ``<family>_value_and_grad`` --, the ``SignalSpec`` whose terms lead the arguments or
+        None, the positional arguments, the keyword arguments)."""
+        return "objective", None, (self.kind, self.block_weights, self.time_weights, self.lever0), {}
+
+    @property
+    def needs_centroids(self):
+        """the levers of the angular kind contain the block centroids: their gradient exists on every lattice (no other spec has this)"""
+        return self.kind == ANGULAR_MOMENTUM
+
 
 def block_weights_from_targets(n_blocks, target_blocks_list, weights):
     """Weights of target regions -> weights of blocks.  ``target_blocks_list``: one array of block ids per target; ``weights``: one row
@@ -149,6 +160,9 @@ class StrainObjectiveSpec:
 
     def __repr__(self):
         return f"StrainObjectiveSpec(bond_weights={self.bond_weights.shape}, time_weights={self.time_weights!r}, parts={self.parts})"
+
+    def engine_call(self):
+        return "strain_objective", None, (self.bond_weights, self.time_weights, self.parts), {}
 
 
 def bond_weights_from_blocks(bond_connectivity, n_nodes_per_block, target_blocks_list, weights, ends="both"):
@@ -266,6 +280,9 @@ class PeakStrainSpec:
     def __repr__(self):
         return (f"PeakStrainSpec(bond_coef={self.bond_coef.shape}, bond_weights={None if self.bond_weights is None else self.bond_weights.shape}, "
                 f"time_weights={self.time_weights!r}, aggregate={self.aggregate!r}, sharpness={self.sharpness})")
+
+    def engine_call(self):
+        return "strain_peak", None, (self.bond_coef, self.bond_weights, self.time_weights, self.aggregate, self.sharpness), {}
 
 
 def strain_limit_coefficients(reference_bond_vectors, eps_lim=None, gamma_lim=None, kappa_lim=None):
@@ -445,6 +462,9 @@ class SignalSpec:
         return (f"SignalSpec({len(self.terms)} terms, n_signals={self.n_signals}, targets={None if self.targets is None else self.targets.shape}, "
                 f"omega={self.omega!r}, tau={self.tau!r})")
 
+    def engine_call(self):
+        return "signal_misfit", self, (self.targets, self.omega, self.tau), {}
+
     @property
     def has_force(self):
         """a block-force or hinge-force term: evaluated on the device only"""
@@ -552,6 +572,9 @@ class ProjectionSpec:
     def __repr__(self):
         return (f"ProjectionSpec({self.signal_spec!r}, basis={self.basis.shape}, row_weights={self.row_weights.shape}, "
                 f"targets={None if self.targets is None else self.targets.shape})")
+
+    def engine_call(self):
+        return "signal_projection", self.signal_spec, (self.basis, self.row_weights, self.targets), {}
 
     @property
     def n_rows(self):
@@ -712,6 +735,11 @@ class CorrelationSpec:
                 f"templates={None if self.templates is None else self.templates.shape}, normalisation={self.normalisation!r}, "
                 f"reduce={self.reduce!r}, lag={self.lag!r}, beta={self.beta!r}, w_peak={self.w_peak}, w_delay={self.w_delay}, "
                 f"delay_target={self.delay_target})")
+
+    def engine_call(self):
+        return "signal_xcorr", self.signal_spec, (self.pairs, self.max_lag), dict(
+            templates=self.templates, normalisation=self.normalisation, reduce=self.reduce, lag=self.lag, beta=self.beta, w_peak=self.w_peak,
+            w_delay=self.w_delay, delay_target=self.delay_target)
 
     @property
     def n_lags(self):

@@ -753,17 +753,6 @@ class StaticTuningKineticEnergy:
         return float(self.weights @ vals), grads
 
 
-def _in_batches(fw, design, evaluate):
-    """A list of designs longer than the engine integrates side by side (``fw.batch``) is evaluated one engine call after the other:
-    ``evaluate(chunk)`` for consecutive chunks of ``fw.batch`` designs, results in order -- or None when ``design`` fits one call.  A
-    list whose length is no multiple of ``fw.batch`` is refused here."""
-    if not isinstance(design, list) or len(design) == fw.batch:
-        return None
-    if len(design) == 0 or len(design) % fw.batch:
-        raise ValueError(f"{len(design)} designs for a forward problem built with batch={fw.batch}: pass batch designs, or a multiple of it")
-    return [evaluate(design[i:i + fw.batch]) for i in range(0, len(design), fw.batch)]
-
-
 def design_gradients(fw, designs, raw):
     """The engine's raw gradients (batch-leading arrays for centroid_node_vectors, void_angle0, inertia[, block_centroids]) mapped
     back to the designs: void-angle and inertia chain rules, then the lattice map (all linear in the cotangent) -- one native pass over the
@@ -792,17 +781,76 @@ def design_gradients(fw, designs, raw):
     return grads
 
 
-class TargetKineticEnergy:
+def _target_regions(forward, target_sizes, target_shifts, weights=None):
+    """(target_sizes, target_shifts) as tuples of tuples and the blocks of every region, on a quad or kagome lattice."""
+    pick = kagome_target_blocks if isinstance(forward.geometry, KagomeGeometry) else quads_target_blocks
+    sizes, shifts = tuple(map(tuple, target_sizes)), tuple(map(tuple, target_shifts))
+    if weights is not None and (len(sizes) != len(shifts) or len(weights) != len(sizes)):
+        raise ValueError("target_sizes, target_shifts and weights must have the same length")
+    if len(sizes) != len(shifts):
+        raise ValueError("target_sizes and target_shifts must have the same length")
+    return sizes, shifts, [pick(forward.geometry, ts, sh) for ts, sh in zip(sizes, shifts)]
+
+
+class _DeviceTarget:
+    """An objective of a design that is evaluated and differentiated on the device: one design, a list of ``forward.batch`` designs as
+    one ensemble, or a longer list (a multiple of it) one engine call after the other -- an ensemble whose checkpoint does not fit the
+    device at once (config 4 as written, 64 designs x 75 000 steps on ONE GPU) runs as two calls of 32.  Per call: the solve with the
+    history left on the device, ``_device_value`` (by default ``DynamicSolver.value`` / ``value_and_raw`` of ``_spec_for`` the
+    designs), the design maps.  What ``_device_value`` returns behind the objective (``((obj, extra, ...), raw)``) is kept per design
+    under the names ``_extras``: arrays for a list of designs, a float or a row for one."""
+    spec = None                 # an ``objective`` spec, where one serves every call (``_spec_for``)
+    _extras = ()
+    _per_member = None          # the array of the spec that may carry one entry per design
+
+    def __init__(self, forward):
+        self.forward = forward
+        if not getattr(forward, "is_setup", False):
+            forward.setup()
+
+    def _spec_for(self, designs, many, start=None):
+        """The spec of one engine call on ``designs`` (``start``: they are entries start .. of a list longer than the batch)."""
+        return self.spec
+
+    def _device_value(self, spec, many, grad):
+        sd = self.forward.solve_dynamics
+        return sd.value_and_raw(spec) if grad else (sd.value(spec), None)
+
+    def _evaluate(self, design, grad):
+        """``value`` (``grad=False``: no trajectory kept) or ``value_and_grad`` of a design or a list of designs."""
+        fw, many = self.forward, isinstance(design, list)
+        per = getattr(self.spec, self._per_member) if self._per_member else None
+        if many and per is not None and per.ndim == 3 and len(per) != len(design):
+            raise ValueError(f"{len(design)} designs against {self._per_member} for {len(per)} members")
+        calls = [(design if many else [design], None)]
+        if many and len(design) != fw.batch:
+            if len(design) == 0 or len(design) % fw.batch:
+                raise ValueError(f"{len(design)} designs for a forward problem built with batch={fw.batch}: pass batch designs, or a multiple of it")
+            calls = [(design[i:i + fw.batch], i) for i in range(0, len(design), fw.batch)]
+        outs, grads = [], []
+        for designs, start in calls:
+            spec = self._spec_for(designs, many, start)
+            fw.solve(designs if many else design, keep_trajectory=grad, want_fields=False)
+            out, raw = self._device_value(spec, many, grad)
+            outs.append([np.array(a) for a in (out if isinstance(out, tuple) else (out,))])
+            if grad:
+                grads += design_gradients(fw, designs, raw)
+        obj, *extras = (np.concatenate(col) for col in zip(*outs))
+        for name, e in zip(self._extras, extras):
+            setattr(self, name, e if many else e[0] if e.ndim > 1 else float(e[0]))
+        obj = np.asarray(obj, dtype=float)
+        if not grad:
+            return obj if many else float(obj[0])
+        return (obj, grads) if many else (float(obj[0]), grads[0])
+
+
+class TargetKineticEnergy(_DeviceTarget):
     """objective(design) = sum_t sum_{b in target} m v^2/2 and its gradient w.r.t. the design
     (problems/quads_focusing.py:432-471 + jit(value_and_grad(.)) at :565; kagome_focusing.py:388-424)."""
 
     def __init__(self, forward, target_size, target_shift):
-        self.forward = forward
-        if not getattr(forward, "is_setup", False):
-            forward.setup()
-        pick = kagome_target_blocks if isinstance(forward.geometry, KagomeGeometry) else quads_target_blocks
-        self.target_size, self.target_shift = tuple(target_size), tuple(target_shift)
-        self.target_blocks = pick(forward.geometry, target_size, target_shift)
+        super().__init__(forward)
+        (self.target_size,), (self.target_shift,), (self.target_blocks,) = _target_regions(forward, [target_size], [target_shift])
 
     def value(self, design):
         sol = self.forward.solve(design)
@@ -816,42 +864,31 @@ class TargetKineticEnergy:
         inertia, block centroids for the distance-based contact): asking the engine for every ControlParams leaf switches the
         reverse stage to its variant that also accumulates per-ligament stiffness / reference-vector / contact-constant / damping
         gradients -- twice the time per launch on the 64x64 kagome of config 4 (profiles/r02_c4_design_gradient_subset.txt)."""
-        fw = self.forward
-        # more designs than the engine integrates side by side: one call after the other (an ensemble whose checkpoint does not fit
-        # the device at once -- config 4 as written, 64 designs x 75 000 steps on ONE GPU -- runs as two calls of 32)
-        parts = _in_batches(fw, design, self.value_and_grad)
-        if parts is not None:
-            return np.concatenate([p[0] for p in parts]), [g for p in parts for g in p[1]]
-        fw.solve(design, keep_trajectory=True, want_fields=False)
-        obj, raw = fw.solve_dynamics.kinetic_energy_value_and_raw(self.target_blocks)
+        return self._evaluate(design, True)
+
+    def _device_value(self, spec, many, grad):
+        sd = self.forward.solve_dynamics
+        out = sd.kinetic_energy_value_and_raw(self.target_blocks)
         # device time of this evaluation (forward + reverse sweep), for throughput reports
-        self.device_ms_forward = getattr(self, "device_ms_forward", 0.0) + fw.solve_dynamics.stats["kernel_ms"]
-        self.device_ms_adjoint = getattr(self, "device_ms_adjoint", 0.0) + fw.solve_dynamics.adjoint_stats["kernel_ms"]
-        self.device_ms = getattr(self, "device_ms", 0.0) + fw.solve_dynamics.stats["kernel_ms"] + fw.solve_dynamics.adjoint_stats["kernel_ms"]
-        many = isinstance(design, list)
-        designs = design if many else [design]
-        grads = design_gradients(fw, designs, raw)
-        obj = np.asarray(obj, dtype=float)
-        return (obj, grads) if many else (float(obj[0]), grads[0])
+        self.device_ms_forward = getattr(self, "device_ms_forward", 0.0) + sd.stats["kernel_ms"]
+        self.device_ms_adjoint = getattr(self, "device_ms_adjoint", 0.0) + sd.adjoint_stats["kernel_ms"]
+        self.device_ms = getattr(self, "device_ms", 0.0) + sd.stats["kernel_ms"] + sd.adjoint_stats["kernel_ms"]
+        return out
 
 
-class SplitTargetKineticEnergy:
+class SplitTargetKineticEnergy(_DeviceTarget):
     """objective(design) = weights @ [kinetic energy of every target region] for ONE forward problem -- the energy of a single input
     split between several targets (problems/quads_energy_splitting.py:14-88).  One forward solve and ONE reverse sweep: the cotangent
     of the weighted sum goes through ``solve_dynamics.vjp`` (w_k m v on the velocities of target k), the explicit dependence on the
     inertia of the target blocks (w_k sum_t v^2 / 2) is added here.  A list of designs (an ensemble, ``run_ensemble_optimization``) or
     ``on_device=True`` evaluates and differentiates the objective on the device instead (``objective.ObjectiveSpec``)."""
 
+    _extras = ("last_individual",)
+
     def __init__(self, forward, target_sizes, target_shifts, weights):
-        self.forward = forward
-        if not getattr(forward, "is_setup", False):
-            forward.setup()
-        pick = kagome_target_blocks if isinstance(forward.geometry, KagomeGeometry) else quads_target_blocks
-        self.target_sizes, self.target_shifts = tuple(map(tuple, target_sizes)), tuple(map(tuple, target_shifts))
-        if len(self.target_sizes) != len(self.target_shifts) or len(weights) != len(self.target_sizes):
-            raise ValueError("target_sizes, target_shifts and weights must have the same length")
+        super().__init__(forward)
+        self.target_sizes, self.target_shifts, self.target_blocks_list = _target_regions(forward, target_sizes, target_shifts, weights)
         self.weights = np.asarray(weights, dtype=float)
-        self.target_blocks_list = [pick(forward.geometry, ts, sh) for ts, sh in zip(self.target_sizes, self.target_shifts)]
 
     def _individual(self, sol):
         inertia = compute_inertia(sol.centroid_node_vectors, self.forward.density)
@@ -864,32 +901,21 @@ class SplitTargetKineticEnergy:
     def value(self, design):
         return float(self.weights @ self.individual(design))
 
-    def _value_and_grad_device(self, design):
+    def _device_value(self, spec, many, grad):
         """The objective on the device (``dfx_objective_value_and_grad``, kinetic kind with the targets' weights on their blocks): the
         histories stay in HBM, the cotangent is formed there, one design or a list of ``forward.batch`` designs as one ensemble."""
         from .objective import KINETIC, ObjectiveSpec, block_weights_from_targets
-        fw = self.forward
-        many = isinstance(design, list)
-        parts = _in_batches(fw, design, lambda chunk: self._value_and_grad_device(chunk) + (self.last_individual,))
-        if parts is not None:
-            self.last_individual = np.concatenate([p[2] for p in parts])
-            return np.concatenate([p[0] for p in parts]), [g for p in parts for g in p[1]]
-        fw.solve(design, keep_trajectory=True, want_fields=False)
-        sd, nb = fw.solve_dynamics, fw.geometry.n_blocks
+        sd, nb = self.forward.solve_dynamics, self.forward.geometry.n_blocks
         # every target's own kinetic energy: one reduction over the resident history per target
-        ind = np.stack([sd.objective_value(ObjectiveSpec(KINETIC, block_weights_from_targets(nb, [tb], [1.0])))
-                        for tb in self.target_blocks_list], axis=-1)
-        obj, raw = sd.objective_value_and_raw(ObjectiveSpec(KINETIC, block_weights_from_targets(nb, self.target_blocks_list, self.weights)))
-        grads = design_gradients(fw, design if many else [design], raw)
-        self.last_individual = ind if many else ind[0]
-        obj = np.asarray(obj, dtype=float)
-        return (obj, grads) if many else (float(obj[0]), grads[0])
+        ind = np.stack([sd.value(ObjectiveSpec(KINETIC, block_weights_from_targets(nb, [tb], [1.0]))) for tb in self.target_blocks_list], axis=-1)
+        obj, raw = sd.value_and_raw(ObjectiveSpec(KINETIC, block_weights_from_targets(nb, self.target_blocks_list, self.weights)))
+        return (obj, ind), raw
 
     def value_and_grad(self, design, on_device=False):
         """A single design takes the host path (the history is downloaded, the cotangent built in NumPy) unless ``on_device``; a list of
         designs is an ensemble and always runs on the device.  Return shapes as ``TargetKineticEnergy.value_and_grad``."""
         if on_device or isinstance(design, list):
-            return self._value_and_grad_device(design)
+            return self._evaluate(design, True)
         fw = self.forward
         sol = fw.solve(design, keep_trajectory=True)
         vals, inertia = self._individual(sol)
@@ -905,7 +931,7 @@ class SplitTargetKineticEnergy:
         return float(self.weights @ vals), design_gradients(fw, [design], raw)[0]
 
 
-class TargetAngularMomentum:
+class TargetAngularMomentum(_DeviceTarget):
     """objective(design) = sum_t sum_{b in target} [ (c_b + u_b - p) x (m v_b) + J omega_b ]: angular momentum of the
     target blocks about ``spin_center`` summed over the output times (problems/quads_spin.py:380-430 with
     energy.py:502-519).  Evaluated on the host from the fields; its cotangent goes through ``solve_dynamics.vjp`` (any
@@ -914,11 +940,8 @@ class TargetAngularMomentum:
     blocks in the design the objective was set up with (quads_spin.py:400-402)."""
 
     def __init__(self, forward, target_size, target_shift, spin_center="center", reference_design=None):
-        self.forward = forward
-        if not getattr(forward, "is_setup", False):
-            forward.setup()
-        pick = kagome_target_blocks if isinstance(forward.geometry, KagomeGeometry) else quads_target_blocks
-        self.target_blocks = pick(forward.geometry, target_size, target_shift)
+        super().__init__(forward)
+        self.target_blocks = _target_regions(forward, [target_size], [target_shift])[2][0]
         if isinstance(spin_center, str):
             if reference_design is None:
                 raise ValueError("spin_center='center' needs the reference design")
@@ -937,31 +960,20 @@ class TargetAngularMomentum:
     def value(self, design):
         return self._value(self.forward.solve(design))[0]
 
-    def _value_and_grad_device(self, design):
+    def _spec_for(self, designs, many, start=None):
         """The objective on the device (``dfx_objective_value_and_grad``, angular kind, levers = block centroids of every design - spin
         centre): one design or a list of ``forward.batch`` designs as one ensemble; the explicit centroid and inertia terms come back
         inside the raw gradients."""
         from .objective import ANGULAR_MOMENTUM, ObjectiveSpec, block_weights_from_targets
-        fw = self.forward
-        many = isinstance(design, list)
-        parts = _in_batches(fw, design, self._value_and_grad_device)
-        if parts is not None:
-            return np.concatenate([p[0] for p in parts]), [g for p in parts for g in p[1]]
-        designs = design if many else [design]
-        fw.solve(design, keep_trajectory=True, want_fields=False)
-        nb = fw.geometry.n_blocks
-        lever0 = np.stack([np.asarray(geometry_from_design_cached(fw.geometry, d)[0], dtype=float) - self.spin_center for d in designs])
-        spec = ObjectiveSpec(ANGULAR_MOMENTUM, block_weights_from_targets(nb, [self.target_blocks], [1.0]), None, lever0)
-        obj, raw = fw.solve_dynamics.objective_value_and_raw(spec)
-        grads = design_gradients(fw, designs, raw)
-        obj = np.asarray(obj, dtype=float)
-        return (obj, grads) if many else (float(obj[0]), grads[0])
+        geo = self.forward.geometry
+        lever0 = np.stack([np.asarray(geometry_from_design_cached(geo, d)[0], dtype=float) - self.spin_center for d in designs])
+        return ObjectiveSpec(ANGULAR_MOMENTUM, block_weights_from_targets(geo.n_blocks, [self.target_blocks], [1.0]), None, lever0)
 
     def value_and_grad(self, design, on_device=False):
         """A single design takes the host path unless ``on_device``; a list of designs always runs on the device (see
         ``SplitTargetKineticEnergy.value_and_grad``)."""
         if on_device or isinstance(design, list):
-            return self._value_and_grad_device(design)
+            return self._evaluate(design, True)
         from .geometry import compute_inertia_vjp
         fw, tb = self.forward, self.target_blocks
         sol = fw.solve(design, keep_trajectory=True)
@@ -985,7 +997,7 @@ class TargetAngularMomentum:
         return val, design_gradients(fw, [design], raw)[0]
 
 
-class TargetStrainEnergy:
+class TargetStrainEnergy(_DeviceTarget):
     """objective(design) = weights @ [elastic energy stored in the ligaments of every target region, summed over the output times]: the
     quantity ``compute_response_data`` reports as strain_energy_{stretch,shear,bending} (plus, with ``parts[3] != 0``, the angle-contact
     penalty), as an objective -- minimised to protect a region, maximised to concentrate deformation in it.  A ligament belongs to a region
@@ -997,15 +1009,9 @@ class TargetStrainEnergy:
 
     def __init__(self, forward, target_sizes, target_shifts, weights, parts=(1.0, 1.0, 1.0, 0.0), ends="both"):
         from .objective import StrainObjectiveSpec, bond_weights_from_blocks
-        self.forward = forward
-        if not getattr(forward, "is_setup", False):
-            forward.setup()
-        pick = kagome_target_blocks if isinstance(forward.geometry, KagomeGeometry) else quads_target_blocks
-        self.target_sizes, self.target_shifts = tuple(map(tuple, target_sizes)), tuple(map(tuple, target_shifts))
-        if len(self.target_sizes) != len(self.target_shifts) or len(weights) != len(self.target_sizes):
-            raise ValueError("target_sizes, target_shifts and weights must have the same length")
+        super().__init__(forward)
+        self.target_sizes, self.target_shifts, self.target_blocks_list = _target_regions(forward, target_sizes, target_shifts, weights)
         self.weights, self.ends = np.asarray(weights, dtype=float), ends
-        self.target_blocks_list = [pick(forward.geometry, ts, sh) for ts, sh in zip(self.target_sizes, self.target_shifts)]
         self.bond_weights = bond_weights_from_blocks(forward.bond_connectivity, forward.geometry.n_npb, self.target_blocks_list, self.weights,
                                                      ends=ends)
         self.spec = StrainObjectiveSpec(self.bond_weights, None, parts)
@@ -1013,29 +1019,14 @@ class TargetStrainEnergy:
 
     def value(self, design):
         """One design -> float, a list of ``forward.batch`` designs (or a multiple of it) -> (n,) array; no trajectory is kept."""
-        fw = self.forward
-        parts = _in_batches(fw, design, self.value)
-        if parts is not None:
-            return np.concatenate(parts)
-        fw.solve(design, keep_trajectory=False, want_fields=False)
-        obj = np.asarray(fw.solve_dynamics.strain_objective_value(self.spec), dtype=float)
-        return obj if isinstance(design, list) else float(obj[0])
+        return self._evaluate(design, False)
 
     def value_and_grad(self, design):
         """Return shapes as ``TargetKineticEnergy.value_and_grad``; only the parameter groups a design reaches are differentiated."""
-        fw = self.forward
-        parts = _in_batches(fw, design, self.value_and_grad)
-        if parts is not None:
-            return np.concatenate([p[0] for p in parts]), [g for p in parts for g in p[1]]
-        many = isinstance(design, list)
-        fw.solve(design, keep_trajectory=True, want_fields=False)
-        obj, raw = fw.solve_dynamics.strain_objective_value_and_raw(self.spec)
-        grads = design_gradients(fw, design if many else [design], raw)
-        obj = np.asarray(obj, dtype=float)
-        return (obj, grads) if many else (float(obj[0]), grads[0])
+        return self._evaluate(design, True)
 
 
-class PeakLigamentStrain:
+class PeakLigamentStrain(_DeviceTarget):
     """constraint(design) = J - 1 with J a smooth maximum, over all output times and the watched ligaments, of the squared strain
     utilisation  q = (eps / eps_lim)^2 + (gamma / gamma_lim)^2 + (kappa / kappa_lim)^2  (``objective.PeakStrainSpec`` with the coefficients
     of ``objective.strain_limit_coefficients``): feasible when <= 0 -- "no ligament exceeds its allowable strain at any instant" with a
@@ -1047,11 +1038,11 @@ class PeakLigamentStrain:
     ensemble (``run_ensemble_optimization`` accepts the class).  ``last_peak`` / ``last_peak_at`` keep the hard maximum of q and its
     (output, bond) of the last evaluation (per design)."""
 
+    _extras = ("last_peak", "last_peak_at")
+
     def __init__(self, forward, limits, beta=20.0, aggregate="ks", target_sizes=None, target_shifts=None, ends="any"):
         from .objective import PeakStrainSpec, bond_weights_from_blocks, strain_limit_coefficients
-        self.forward = forward
-        if not getattr(forward, "is_setup", False):
-            forward.setup()
+        super().__init__(forward)
         if len(limits) != 3:
             raise ValueError("limits must be (eps_lim, gamma_lim, kappa_lim)")
         self.limits = tuple(limits)
@@ -1062,11 +1053,7 @@ class PeakLigamentStrain:
             raise ValueError("target_sizes and target_shifts go together")
         self.bond_weights, self.target_blocks_list = None, None
         if target_sizes is not None:
-            pick = kagome_target_blocks if isinstance(forward.geometry, KagomeGeometry) else quads_target_blocks
-            self.target_sizes, self.target_shifts = tuple(map(tuple, target_sizes)), tuple(map(tuple, target_shifts))
-            if len(self.target_sizes) != len(self.target_shifts):
-                raise ValueError("target_sizes and target_shifts must have the same length")
-            self.target_blocks_list = [pick(forward.geometry, ts, sh) for ts, sh in zip(self.target_sizes, self.target_shifts)]
+            self.target_sizes, self.target_shifts, self.target_blocks_list = _target_regions(forward, target_sizes, target_shifts)
             w = bond_weights_from_blocks(forward.bond_connectivity, forward.geometry.n_npb, self.target_blocks_list,
                                          np.ones(len(self.target_blocks_list)), ends=ends)
             self.bond_weights = (w > 0).astype(float)           # watched or not: overlapping regions do not weigh a ligament twice
@@ -1074,49 +1061,29 @@ class PeakLigamentStrain:
         self.spec = PeakStrainSpec(coef, self.bond_weights, None, aggregate, beta)
         self.last_peak = self.last_peak_at = None
 
-    def _keep(self, out, many):
-        obj, peak, at = (np.array(a) for a in out)
-        self.last_peak, self.last_peak_at = (peak, at) if many else (float(peak[0]), at[0])
-        return obj - 1.0
+    def _device_value(self, spec, many, grad):
+        (obj, peak, at), raw = super()._device_value(spec, many, grad)
+        return (np.array(obj) - 1.0, peak, at), raw
 
     def value(self, design):
         """One design -> float, a list of ``forward.batch`` designs (or a multiple of it) -> (n,) array; no trajectory is kept."""
-        fw = self.forward
-        parts = _in_batches(fw, design, lambda d: (self.value(d), self.last_peak, self.last_peak_at))
-        if parts is not None:
-            self.last_peak, self.last_peak_at = np.concatenate([p[1] for p in parts]), np.concatenate([p[2] for p in parts])
-            return np.concatenate([p[0] for p in parts])
-        many = isinstance(design, list)
-        fw.solve(design, keep_trajectory=False, want_fields=False)
-        c = self._keep(fw.solve_dynamics.peak_strain_value(self.spec), many)
-        return c if many else float(c[0])
+        return self._evaluate(design, False)
 
     def value_and_grad(self, design):
         """Return shapes as ``TargetStrainEnergy.value_and_grad``; only the parameter groups a design reaches are differentiated."""
-        fw = self.forward
-        parts = _in_batches(fw, design, lambda d: self.value_and_grad(d) + (self.last_peak, self.last_peak_at))
-        if parts is not None:
-            self.last_peak, self.last_peak_at = np.concatenate([p[2] for p in parts]), np.concatenate([p[3] for p in parts])
-            return np.concatenate([p[0] for p in parts]), [g for p in parts for g in p[1]]
-        many = isinstance(design, list)
-        fw.solve(design, keep_trajectory=True, want_fields=False)
-        out, raw = fw.solve_dynamics.peak_strain_value_and_raw(self.spec)
-        grads = design_gradients(fw, design if many else [design], raw)
-        c = self._keep(out, many)
-        return (c, grads) if many else (float(c[0]), grads[0])
+        return self._evaluate(design, True)
 
 
-class _SignalTarget:
+class _SignalTarget(_DeviceTarget):
     """What ``TargetSignalMisfit``, ``TargetSignalProjection`` and ``TargetCrossCorrelation`` share: the range check of the terms, a list
     of designs as ensembles of ``forward.batch`` on the device, one design on the host, the return shapes.  Per class: ``_per_member``
     (the spec's array that may carry one entry per design), ``_chunk_spec``, ``_first`` (the spec cut to the first member's entry, for one
-    design), ``_device_value`` -> (values, raw gradients or None) and ``_host_value`` -> (value, cotangent of the fields)."""
+    design) and ``_host_value`` -> (value, cotangent of the fields)."""
     _cut_on_device = False
 
     def __init__(self, forward, spec):
-        self.forward, self.spec = forward, spec
-        if not getattr(forward, "is_setup", False):
-            forward.setup()
+        super().__init__(forward)
+        self.spec = spec
         nb = forward.geometry.n_blocks
         if max(b for _, b, _, _ in getattr(spec, "signal_spec", spec).terms) >= nb:
             raise ValueError(f"{type(self).__name__}: a term names a block out of range [0, {nb})")
@@ -1124,33 +1091,10 @@ class _SignalTarget:
     def _first(self, sp):
         return sp
 
-    def _gather(self, chunks):
-        pass
-
-    def _device(self, design, grad):
-        fw, sp = self.forward, self.spec
-        many = isinstance(design, list)
-        per = getattr(sp, self._per_member)
-        if many and per is not None and per.ndim == 3 and len(per) != len(design):
-            raise ValueError(f"{len(design)} designs against {self._per_member} for {len(per)} members")
-        if many and len(design) != fw.batch:
-            if len(design) == 0 or len(design) % fw.batch:
-                raise ValueError(f"{len(design)} designs for a forward problem built with batch={fw.batch}: pass batch designs, or a multiple of it")
-            chunks = [type(self)(fw, self._chunk_spec(i, fw.batch)) for i in range(0, len(design), fw.batch)]
-            parts = [c._device(design[i * fw.batch:(i + 1) * fw.batch], grad) for i, c in enumerate(chunks)]
-            self._gather(chunks)
-            if not grad:
-                return np.concatenate(parts)
-            return np.concatenate([p[0] for p in parts]), [g for p in parts for g in p[1]]
-        if not many and self._cut_on_device:
-            sp = self._first(sp)
-        fw.solve(design, keep_trajectory=grad, want_fields=False)
-        obj, raw = self._device_value(sp, many, grad)
-        obj = np.asarray(obj, dtype=float)
-        if not grad:
-            return obj if many else float(obj[0])
-        grads = design_gradients(fw, design if many else [design], raw)
-        return (obj, grads) if many else (float(obj[0]), grads[0])
+    def _spec_for(self, designs, many, start=None):
+        if start is not None:
+            return self._chunk_spec(start, len(designs))
+        return self.spec if many or not self._cut_on_device else self._first(self.spec)
 
     def _host(self, design, grad):
         fw = self.forward
@@ -1166,11 +1110,11 @@ class _SignalTarget:
 
     def value(self, design, on_device=False):
         """One design -> float, a list of designs -> (n,) array."""
-        return self._device(design, False) if on_device or isinstance(design, list) else self._host(design, False)
+        return self._evaluate(design, False) if on_device or isinstance(design, list) else self._host(design, False)
 
     def value_and_grad(self, design, on_device=False):
         """Return shapes as ``TargetKineticEnergy.value_and_grad``; only the parameter groups a design reaches are differentiated."""
-        return self._device(design, True) if on_device or isinstance(design, list) else self._host(design, True)
+        return self._evaluate(design, True) if on_device or isinstance(design, list) else self._host(design, True)
 
 
 class TargetSignalMisfit(_SignalTarget):
@@ -1192,10 +1136,6 @@ class TargetSignalMisfit(_SignalTarget):
         """the spec of designs i .. i + n of a longer list (per-member targets are cut alike)"""
         sp = self.spec
         return sp if sp.targets.ndim == 2 else sp.with_targets(sp.targets[i:i + n], sp.omega, sp.tau)
-
-    def _device_value(self, sp, many, grad):
-        sd = self.forward.solve_dynamics
-        return sd.signal_misfit_value_and_raw(sp) if grad else (sd.signal_misfit_value(sp), None)
 
     def _host_value(self, sp, fields, grad):
         from .objective import host_signal_values
@@ -1384,10 +1324,6 @@ class TargetSignalProjection(_SignalTarget):
     def _first(self, sp):
         return sp.with_targets(sp.targets[0]) if sp.targets is not None and sp.targets.ndim == 3 else sp
 
-    def _device_value(self, sp, many, grad):
-        sd = self.forward.solve_dynamics
-        return sd.signal_projection_value_and_raw(sp) if grad else (sd.signal_projection_value(sp), None)
-
     def _host_value(self, sp, fields, grad):
         from .objective import host_projection_value_and_cotangent
         return host_projection_value_and_cotangent(sp, fields)
@@ -1424,7 +1360,7 @@ class TargetCrossCorrelation(_SignalTarget):
     the host path -- field components only -- unless ``on_device``.  Force components have no host path.  ``last_peak`` / ``last_delay``:
     M and delta of the last evaluation (floats for one design, (n,) arrays for a list)."""
 
-    _per_member = "templates"
+    _per_member, _extras = "templates", ("last_peak", "last_delay")
     _cut_on_device = True
 
     def __init__(self, forward, spec):
@@ -1438,16 +1374,6 @@ class TargetCrossCorrelation(_SignalTarget):
 
     def _first(self, sp):
         return sp.with_templates(sp.templates[0]) if sp.templates is not None and sp.templates.ndim == 3 else sp
-
-    def _gather(self, chunks):
-        self.last_peak, self.last_delay = np.concatenate([c.last_peak for c in chunks]), np.concatenate([c.last_delay for c in chunks])
-
-    def _device_value(self, sp, many, grad):
-        sd = self.forward.solve_dynamics
-        (obj, peak, delay), raw = sd.signal_xcorr_value_and_raw(sp) if grad else (sd.signal_xcorr_value(sp), None)
-        peak, delay = np.array(peak, dtype=float), np.array(delay, dtype=float)
-        self.last_peak, self.last_delay = (peak, delay) if many else (float(peak[0]), float(delay[0]))
-        return obj, raw
 
     def _host_value(self, sp, fields, grad):
         from .objective import host_xcorr_value_and_cotangent

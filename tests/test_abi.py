@@ -12,9 +12,43 @@ def declared_symbols():
     return sorted(set(re.findall(r"\b(dfx_[a-z_0-9]+)\s*\(", text)))
 
 
+def declared_parameters():
+    """{function: [parameter declaration, ...]} of include/dfx.h, comments stripped; ``(void)`` and ``()`` are no parameters."""
+    text = open(os.path.join(ROOT, "include", "dfx.h")).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    out = {}
+    for name, params in re.findall(r"\b(dfx_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", text):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        out[name] = [] if params in ([""], ["void"]) else params
+    return out
+
+
 def test_header_and_binding_agree():
     from difflexmm_amd._binding import EXPORTS
     assert sorted(EXPORTS) == declared_symbols()
+
+
+def test_argtypes_agree_with_the_header(hip_lib):
+    """Every function include/dfx.h declares is typed on the loaded library, with one ctypes type per parameter of the header and each
+    of the header's kind: double <-> c_double, int32_t / int <-> c_int32, int64_t <-> c_int64, any pointer <-> a ctypes pointer type,
+    c_char_p or c_void_p.  An entry left untyped (ctypes then passes whatever it is given) or typed with another entry's list fails here."""
+    import ctypes as C
+    declared = declared_parameters()
+    assert sorted(declared) == declared_symbols()
+    scalars = {"double": C.c_double, "int32_t": C.c_int32, "int": C.c_int32, "int64_t": C.c_int64}
+    for name, params in declared.items():
+        argtypes = getattr(hip_lib, name).argtypes
+        assert argtypes is not None, f"{name}: no argtypes"
+        assert len(argtypes) == len(params), f"{name}: {len(argtypes)} argtypes for {len(params)} parameters"
+        for i, (param, got) in enumerate(zip(params, argtypes)):
+            if "*" in param:
+                ok = got in (C.c_char_p, C.c_void_p) or issubclass(got, C._Pointer)
+            else:
+                words = [w for w in re.findall(r"\w+", param) if w != "const"]
+                assert words[0] in scalars, f"{name}: parameter {i} ({param!r}) has a type this test does not know"
+                ok = got is scalars[words[0]]
+            assert ok, f"{name}: parameter {i} is {param!r} in the header and {got.__name__} in the binding"
 
 
 def test_libdfx_exports_every_declared_symbol(hip_lib):
