@@ -18,6 +18,8 @@ OBJ_KINETIC, OBJ_ANGULAR_MOMENTUM = 0, 1
 XCORR_NORMS = {"reference": 0, "coefficient": 1, "none": 2}          # DFX_XCORR_NORM_*
 XCORR_REDUCES = {"at": 0, "max": 1, "softmax": 2}                    # DFX_XCORR_AT / _MAX / _SOFTMAX
 PEAK_KS, PEAK_PNORM = 0, 1                                           # DFX_PEAK_*
+SPECTRUM_MEASURES = {"ratio": 0, "log": 1}                           # DFX_SPECTRUM_RATIO / _LOG
+SPECTRUM_AGGREGATES = {"sum": 0, "ks": 1}                            # DFX_SPECTRUM_SUM / _KS
 FN_ZERO, FN_PULSE, FN_HARMONIC, FN_RAMP, FN_SECH2TANH, FN_CONSTANT, FN_RAMP_CAP, FN_TABLE = range(8)
 
 _dp = C.POINTER(C.c_double)
@@ -75,7 +77,8 @@ COMM_EXPORTS = ["dfx_comm_unique_id", "dfx_comm_init", "dfx_comm_destroy", "dfx_
                 "dfx_strain_objective_value", "dfx_strain_objective_value_and_grad", "dfx_signal_values", "dfx_signal_hinge_channels", "dfx_signal_misfit_value",
                 "dfx_signal_misfit_value_and_grad", "dfx_signal_projections", "dfx_signal_projection_value",
                 "dfx_signal_projection_value_and_grad", "dfx_forward_tangent_signals_multi", "dfx_forward_tangent_signals_dense_multi",
-                "dfx_signal_xcorr", "dfx_signal_xcorr_value", "dfx_signal_xcorr_value_and_grad", "dfx_strain_peak_value",
+                "dfx_signal_xcorr", "dfx_signal_xcorr_value", "dfx_signal_xcorr_value_and_grad", "dfx_signal_spectrum",
+                "dfx_signal_spectrum_value", "dfx_signal_spectrum_value_and_grad", "dfx_strain_peak_value",
                 "dfx_strain_peak_value_and_grad", "dfx_fn_table_values", "dfx_fn_table_grads", "dfx_fn_table_grad", "dfx_drive_cotangent",
                 "dfx_fn_table_tangents"]
 EXPORTS = EXPORTS + COMM_EXPORTS
@@ -111,6 +114,8 @@ def _argtypes():
     corr = [i32, _ip, _ip, _dp, i32, i32, i32, i32]              # pairs, templates, max_lag, normalisation
     xval = [i32, i32, f64, f64, f64, f64, _dp, _dp, _dp]         # reduce, lag, beta, w_peak, w_delay, delay_target, J, peak, delay
     peak = [_dp, i32, _dp, i32, _dp, i32, f64, _dp, _dp, _ip]    # coef, weights, tau, aggregate, sharpness, J, peak, peak_at
+    spec = [_dp, i32, i32, _dp, _dp, _dp, _dp, i32]              # basis, n_rows, n_groups, Wn, Wd, n0, d0, offsets_per_member
+    sval = [i32, i32, f64, _dp, _dp, _dp]                        # measure, aggregate, beta, group_coef, J, measures
     grid = [H, _dp, _dp, i32, _ip, _dp, i32, _dp, stats]         # a fixed-grid forward pass
     kinetic = [H, _ip, i32, _dp, grads, grads, stats]
     adaptive = [H, _dp, _dp, i32, f64, f64, i64]                 # state0, timepoints, T, rtol, atol, max_attempts
@@ -176,6 +181,9 @@ def _argtypes():
         "dfx_signal_xcorr": [H] + terms + corr + [_dp],
         "dfx_signal_xcorr_value": [H] + terms + corr + xval,
         "dfx_signal_xcorr_value_and_grad": [H] + terms + corr + xval + tail,
+        "dfx_signal_spectrum": [H] + terms + spec + [i32, _dp],
+        "dfx_signal_spectrum_value": [H] + terms + spec + sval,
+        "dfx_signal_spectrum_value_and_grad": [H] + terms + spec + sval + tail,
         "dfx_fn_table_values": [H, i32, _dp, i32],
         "dfx_fn_table_grads": [H, i32],
         "dfx_fn_table_grad": [H, i32, _dp],
@@ -1026,6 +1034,69 @@ class Engine:
         lead = args + xa + self._xcorr_value_args(reduce, lag, beta, w_peak, w_delay, delay_target)
         outs = np.zeros(self.batch), np.zeros(self.batch), np.zeros(self.batch)          # J, peak, delay
         return outs + self._value_and_grad("dfx_signal_xcorr_value_and_grad", lead, outs, which, device)
+
+    # -- signal spectral ratios on the device-resident history --------------------------------------------------
+    @property
+    def has_signal_spectrum(self):
+        return hasattr(self.lib, "dfx_signal_spectrum_value_and_grad")
+
+    def _spectrum_args(self, n_signals, basis, num_weights, den_weights, num_offset, den_offset):
+        """The array arguments of ``dfx_signal_spectrum*``: basis (n_rows, T), group weights (G, n_signals, n_rows) each, offsets (G,) or
+        (batch, G) or None = zeros (one per member as soon as either is)."""
+        self._need("dfx_signal_spectrum_value_and_grad", "signal spectral ratios", self._STALE)
+        B, T, ns = self.batch, self.n_timepoints, int(n_signals)
+        b = _f64(basis)
+        if b.ndim != 2 or (T is not None and b.shape[1] != T):
+            raise ValueError(f"basis must be (n_rows, {T}), got {b.shape}")
+        nr = b.shape[0]
+        wn, wd = _f64(num_weights), _f64(den_weights)
+        if wn.ndim != 3 or wn.shape[1:] != (ns, nr) or wd.shape != wn.shape:
+            raise ValueError(f"num_weights and den_weights must be (G, {ns}, {nr}), got {wn.shape} and {wd.shape}")
+        G = wn.shape[0]
+        offs = [None if o is None else _f64(o) for o in (num_offset, den_offset)]
+        for name, o in zip(("num_offset", "den_offset"), offs):
+            if o is not None and o.shape not in ((G,), (B, G)):
+                raise ValueError(f"{name} must be ({G},) or ({B}, {G}), got {o.shape}")
+        per = any(o is not None and o.ndim == 2 for o in offs)
+        if per:
+            offs = [None if o is None else _f64(o, (B, G)) for o in offs]
+        return b, nr, G, wn, wd, offs[0], offs[1], int(per)
+
+    def _spectrum_value_args(self, G, measure, aggregate, beta, group_coef):
+        a = _f64(np.ones(G) if group_coef is None else group_coef)
+        if a.shape != (G,):
+            raise ValueError(f"group_coef must be ({G},), got {a.shape}")
+        mea = SPECTRUM_MEASURES[measure] if isinstance(measure, str) else int(measure)
+        agg = SPECTRUM_AGGREGATES[aggregate] if isinstance(aggregate, str) else int(aggregate)
+        return mea, agg, float(1.0 if beta is None else beta), a
+
+    def signal_spectrum(self, terms, n_signals, basis, num_weights, den_weights, num_offset=None, den_offset=None, measure="log"):
+        """(batch, G, 3) = N | D | l of the groups of a spectral-ratio objective (``dfx_signal_spectrum``), l the ``measure`` ("ratio" N / D
+        or "log" ln N - ln D; NaN where it does not exist), on the resident history of the last forward pass."""
+        sa = self._spectrum_args(n_signals, basis, num_weights, den_weights, num_offset, den_offset)
+        args, keep = self._signal_terms(terms, n_signals)
+        mea = SPECTRUM_MEASURES[measure] if isinstance(measure, str) else int(measure)
+        return self._value("dfx_signal_spectrum", args + sa + (mea,), [np.zeros((self.batch, sa[2], 3))])[0]
+
+    def signal_spectrum_value(self, terms, n_signals, basis, num_weights, den_weights, num_offset=None, den_offset=None, group_coef=None,
+                              measure="log", aggregate="sum", beta=None):
+        """(J, l): the aggregate (batch,) over the groups ("sum", or "ks" with ``beta``) of the measures l (batch, G) ("ratio" N / D or
+        "log" ln N - ln D) of the band-power forms of the projections (``dfx_signal_spectrum_value``)."""
+        sa = self._spectrum_args(n_signals, basis, num_weights, den_weights, num_offset, den_offset)
+        args, keep = self._signal_terms(terms, n_signals)
+        lead = args + sa + self._spectrum_value_args(sa[2], measure, aggregate, beta, group_coef)
+        return self._value("dfx_signal_spectrum_value", lead, (np.zeros(self.batch), np.zeros((self.batch, sa[2]))))
+
+    def signal_spectrum_value_and_grad(self, terms, n_signals, basis, num_weights, den_weights, num_offset=None, den_offset=None,
+                                       group_coef=None, measure="log", aggregate="sum", beta=None, which=ALL_GRADS, device=False):
+        """(J, l) and the requested gradients of J in ONE call (``dfx_signal_spectrum_value_and_grad``): the forms, their reduction and
+        the cotangent on the signals are formed on the device, everything behind them is the signal misfit's.  Returns
+        (J, l, gradients, stats), the gradients as :meth:`signal_misfit_value_and_grad`."""
+        sa = self._spectrum_args(n_signals, basis, num_weights, den_weights, num_offset, den_offset)
+        args, keep = self._signal_terms(terms, n_signals)
+        lead = args + sa + self._spectrum_value_args(sa[2], measure, aggregate, beta, group_coef)
+        outs = np.zeros(self.batch), np.zeros((self.batch, sa[2]))          # J, l
+        return outs + self._value_and_grad("dfx_signal_spectrum_value_and_grad", lead, outs, which, device)
 
     # -- the samples of a table drive as a differentiable leaf ------------------------------------------------
     @property

@@ -176,6 +176,10 @@ struct dfx_handle {
   DevBuf<double> d_xc_coef, d_xc_R, d_xc_s;
   struct XcorrJob { int n_pairs = 0, n_templ = 0, D = 0, norm = 0, reduce = 0, lag0 = 0; bool has_templ = false; long long templ_stride = 0;
                     double beta = 1.0, w_peak = 1.0, w_delay = 0.0, delay_target = 0.0; } xc;
+  // dfx_signal_spectrum* (engine_objective.hip): basis | Wn | Wd | n0 | d0 | a of the call in one buffer; per member the forms (G, 2) = N | D,
+  // the measures l (G), lam dl/dN | lam dl/dD (G, 2) and the effective row weights Weff (n_signals, n_rows); sp: the layout and the scalars
+  DevBuf<double> d_sp_coef, d_sp_forms, d_sp_l, d_sp_lam, d_sp_weff;
+  struct SpecJob { int n_rows = 0, G = 0, measure = 0, aggregate = 0; double beta = 1.0; long long off_stride = 0; } sp;
   // dfx_strain_peak_* (engine_objective.hip): slot coefficients, the q image, per-workgroup maxima and keys, per member q_hat | S | J and
   // (k_hat, b_hat); pk: the scalars of the call (the explicit terms behind the sweep read them)
   DevBuf<double> d_pk_coef, d_pk_q, d_pk_max, d_pk_res;

@@ -75,6 +75,17 @@
 //   k_signal_xcorr_residual  one lane per (member, output, signal): c from Rbar, eA, eB, the signals and the templates, pairs and lags
 //                            ascending, into the residual-cotangent buffer; lags whose Rbar is exactly 0 are skipped
 //
+// The signal spectral ratios (dfx_signal_spectrum, dfx_signal_spectrum_value[_and_grad]): a third occupant of that slot.  G groups of two
+// non-negative forms of the projections, N_mg = n0_g + sum W^n_gsj P_msj^2 and D_mg likewise, a measure l = N / D or ln N - ln D per group,
+// J = sum_g a_g l_g or its KS smooth maximum.  S and P as for the projections (k_signal_project with W == nullptr); from c on as above.
+//   k_signal_spectrum_forms     one wave per (member, group, side): lane l adds W P^2 over the (signal, row) pairs l, l + 64, ... ascending,
+//                               obj_wave_sum, lane 0 adds the offset
+//   k_signal_spectrum_reduce    one wave per member, lane l holds groups l, l + 64, ...: the measures, the maximum (lowest group on a tie),
+//                               the exponent sums with the maximum subtracted; J, l, lam dl/dN, lam dl/dD.  A member with some D <= 0 (LOG:
+//                               or N <= 0; KS: or a non-finite l) gets J = NaN, NaN in the offending l and an all-zero cotangent
+//   k_signal_spectrum_weights   one lane per (member, signal, row): Weff = 2 sum_g (lam dl/dN Wn + lam dl/dD Wd), g ascending
+//   k_signal_spectrum_residual  k_signal_project_residual with per-member weights and no targets: c_mks = sum_j Weff_msj P_msj B_jk
+//
 // The peak ligament strain (dfx_strain_peak_value[_and_grad]): NOT a sum but a smooth maximum over (output time, ligament) pairs of
 //   q_mkb = a_mb (l0 eps)^2 + s_mb (l0 gamma)^2 + r_mb kappa^2 = 2 E_bond with the coefficient triple in place of the stiffnesses,
 // weighted W = tau_k omega_mb >= 0: KS  J = q_hat + log(sum W exp(beta (q - q_hat))) / beta, or PNORM  J = q_hat (sum W (q / q_hat)^p)^(1/p).
@@ -805,6 +816,140 @@ __global__ __launch_bounds__(kObjThreads) void k_signal_xcorr_residual(DevCtx c,
     }
     cr += acc + 2.0 * eB * S[(size_t)k * a.n_sig + s];
   }
+  a.cres[(size_t)m * total + (size_t)item] = cr;
+}
+
+// ---- signal spectral ratios -----------------------------------------------------------------------------------------------------------
+constexpr int kObjSpectrum = 7;            // ObjJob::kind of a spectral-ratio call: a signal job behind the sweep (k_signal_explicit)
+
+struct SpecArgs {
+  const double *Wn, *Wd;            // (G, n_sig * n_rows) each, shared by the members, entries >= 0
+  const double *n0, *d0;            // (G,), members off_stride apart (0: shared)
+  const double* a;                  // (G,) group coefficients
+  double* forms;                    // batch * G * 2: N | D per group
+  double* l;                        // batch * G: the measures
+  double* lam;                      // batch * G * 2: lam_g dl_g/dN | lam_g dl_g/dD
+  double* Weff;                     // batch * n_sig * n_rows
+  long long off_stride;
+  int G, measure, aggregate;
+  double beta;
+};
+
+// grid (chunks of kObjWaves (group, side) rows, members), behind k_signal_project on the same stream: wave `row` of a member holds group
+// row / 2, side row % 2 (0: numerator, 1: denominator).  Lane l adds W P^2 over the flattened (signal, row) pairs l, l + 64, ... ascending
+// (a weight that is exactly 0 adds nothing, whatever P holds), obj_wave_sum adds the lanes, lane 0 adds the offset and stores.  A wave past
+// the last row stores nothing (no barrier in this kernel: a whole wave leaves).
+__global__ __launch_bounds__(kObjThreads) void k_signal_spectrum_forms(SigArgs a, ProjArgs p, SpecArgs x) {
+  const int m = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int row = blockIdx.x * kObjWaves + wv;
+  if (row >= 2 * x.G) return;
+  const int g = row >> 1, side = row & 1;
+  const int np = a.n_sig * p.n_rows;
+  const double* W = (side ? x.Wd : x.Wn) + (size_t)g * np;
+  const double* P = p.P + (size_t)m * np;
+  double v = 0.0;
+  for (int i = lane; i < np; i += 64) {
+    const double w = W[i];
+    if (w != 0.0) v += w * P[i] * P[i];
+  }
+  v = obj_wave_sum(v);
+  if (lane == 0) x.forms[((size_t)m * x.G + g) * 2 + side] = (side ? x.d0 : x.n0)[(size_t)m * x.off_stride + g] + v;
+}
+
+// grid (members), one wave each, behind k_signal_spectrum_forms: lane l holds groups l, l + 64, ... ascending.  The measures first
+// (l = N / D or ln N - ln D), then -- DFX_SPECTRUM_KS -- the maximum of z = a l (lowest group on a tie), then the exponent sums with the
+// maximum subtracted; obj_wave_sum over the lanes.  J into objective[m] and, when given, J | l into pinned host memory (J at host[m], l at
+// host[batch + m * G + g]); lam_g dl_g/dN and lam_g dl_g/dD per group.  A member with some D <= 0 (DFX_SPECTRUM_LOG: or some N <= 0;
+// DFX_SPECTRUM_KS: or some non-finite l) gets J = NaN, NaN in the offending l and zeros in lam: no division by zero reaches the sweep.
+__global__ __launch_bounds__(64) void k_signal_spectrum_reduce(SpecArgs x, double* objective, double* host, int batch) {
+  const int m = blockIdx.x, lane = threadIdx.x;
+  const int G = x.G;
+  const double* F = x.forms + (size_t)m * G * 2;
+  double* L = x.l + (size_t)m * G;
+  double* lam = x.lam + (size_t)m * G * 2;
+  double* hl = host ? host + batch + (size_t)m * G : nullptr;
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  const bool log_m = x.measure == DFX_SPECTRUM_LOG, ks = x.aggregate == DFX_SPECTRUM_KS;
+  // the measures
+  int bad = 0;
+  for (int g = lane; g < G; g += 64) {
+    const double N = F[g * 2], D = F[g * 2 + 1];
+    double l = nan;
+    if (D > 0.0 && (!log_m || N > 0.0)) {
+      l = log_m ? log(N) - log(D) : N / D;
+      if (ks && !isfinite(l)) l = nan;
+    }
+    if (l != l) bad = 1;
+    L[g] = l;
+    if (hl) hl[g] = l;
+  }
+  for (int off = 32; off > 0; off >>= 1) bad |= __shfl_xor(bad, off, 64);
+  if (bad) {
+    for (int g = lane; g < G; g += 64) lam[g * 2] = lam[g * 2 + 1] = 0.0;
+    if (lane == 0) {
+      if (objective) objective[m] = nan;
+      if (host) host[m] = nan;
+    }
+    return;
+  }
+  double J, M = 0.0, Z = 1.0;
+  if (ks) {
+    double best = 0.0;
+    int at = -1;
+    for (int g = lane; g < G; g += 64) {
+      const double z = x.a[g] * L[g];
+      if (at < 0 || z > best) { best = z; at = g; }
+    }
+    xcorr_wave_argmax(best, at);
+    M = best;
+    double e = 0.0;
+    for (int g = lane; g < G; g += 64) e += exp(x.beta * (x.a[g] * L[g] - M));
+    e = obj_wave_sum(e);
+    Z = __shfl(e, 0, 64);
+    J = M + log(Z) / x.beta;
+  } else {
+    double s = 0.0;
+    for (int g = lane; g < G; g += 64) s += x.a[g] * L[g];
+    J = obj_wave_sum(s);
+  }
+  for (int g = lane; g < G; g += 64) {
+    const double N = F[g * 2], D = F[g * 2 + 1];
+    const double lg = ks ? x.a[g] * (exp(x.beta * (x.a[g] * L[g] - M)) / Z) : x.a[g];
+    lam[g * 2] = lg * (log_m ? 1.0 / N : 1.0 / D);
+    lam[g * 2 + 1] = lg * (log_m ? -1.0 / D : -N / (D * D));
+  }
+  if (lane == 0) {
+    if (objective) objective[m] = J;
+    if (host) host[m] = J;                              // pinned host memory, as k_objective_finish
+  }
+}
+
+// grid (chunks of kObjThreads (signal, row) pairs, members), behind k_signal_spectrum_reduce: the effective row weights of the member,
+// Weff_msj = 2 sum_g (lam_g dl_g/dN Wn_gsj + lam_g dl_g/dD Wd_gsj) with g ascending
+__global__ __launch_bounds__(kObjThreads) void k_signal_spectrum_weights(SigArgs a, ProjArgs p, SpecArgs x) {
+  const int m = blockIdx.y;
+  const int np = a.n_sig * p.n_rows;
+  const int i = blockIdx.x * kObjThreads + threadIdx.x;
+  if (i >= np) return;
+  const double* lam = x.lam + (size_t)m * x.G * 2;
+  double acc = 0.0;
+  for (int g = 0; g < x.G; ++g) acc += lam[g * 2] * x.Wn[(size_t)g * np + i] + lam[g * 2 + 1] * x.Wd[(size_t)g * np + i];
+  x.Weff[(size_t)m * np + i] = 2.0 * acc;
+}
+
+// grid (chunks of kObjThreads (output, signal) pairs, members), behind k_signal_spectrum_weights: the twin of k_signal_project_residual
+// with per-member row weights and no targets, c_mks = sum_j Weff_msj P_msj B_jk with j ascending, into cres
+__global__ __launch_bounds__(kObjThreads) void k_signal_spectrum_residual(DevCtx c, SigArgs a, ProjArgs p, SpecArgs x) {
+  const int m = blockIdx.y;
+  const int T = c.n_timepoints;
+  const long long total = (long long)T * a.n_sig;
+  const long long item = (long long)blockIdx.x * kObjThreads + threadIdx.x;
+  if (item >= total) return;
+  const int k = (int)(item / a.n_sig), s = (int)(item % a.n_sig);
+  const double* P = p.P + ((size_t)m * a.n_sig + s) * p.n_rows;
+  const double* W = x.Weff + ((size_t)m * a.n_sig + s) * p.n_rows;
+  double cr = 0.0;
+  for (int j = 0; j < p.n_rows; ++j) cr += W[j] * P[j] * p.basis[(size_t)j * T + k];
   a.cres[(size_t)m * total + (size_t)item] = cr;
 }
 

@@ -642,6 +642,112 @@ int launch_xcorr(dfx_handle* h, double* G, double* host3) {
   return 0;
 }
 
+// ---- signal spectral ratios: the checks of the basis, the group weights, the offsets and the reduction (return 1 with h->err),
+// prepare_signal without targets for the terms, then basis | Wn | Wd | n0 | d0 | a into one buffer.  value: the call forms J (aggregate,
+// beta and the group coefficients are checked); without, only the measures are asked for and a is zeros
+struct SpectrumCall {
+  const double* basis; int32_t n_rows, G; const double *Wn, *Wd, *n0, *d0; int32_t off_per_member;
+  bool value; int32_t measure, aggregate; double beta; const double* a;
+};
+
+int prepare_spectrum(dfx_handle* h, const char* who, const SigTerms& t, const SpectrumCall& q) {
+  const size_t B = h->pl.batch;
+  const size_t Tn = h->ts.size();
+  const std::string w(who);
+  if (q.n_rows < 1) { h->err = w + ": n_rows must be at least 1, got " + std::to_string(q.n_rows); return 1; }
+  if (!q.basis) { h->err = w + ": basis is NULL"; return 1; }
+  if (q.G < 1) { h->err = w + ": n_groups must be at least 1, got " + std::to_string(q.G); return 1; }
+  if (!q.Wn || !q.Wd) { h->err = w + ": num_weights or den_weights is NULL"; return 1; }
+  if (q.measure != DFX_SPECTRUM_RATIO && q.measure != DFX_SPECTRUM_LOG) {
+    h->err = w + ": unknown measure " + std::to_string(q.measure) + " (DFX_SPECTRUM_RATIO = 0, DFX_SPECTRUM_LOG = 1)";
+    return 1;
+  }
+  if (q.value) {
+    if (q.aggregate != DFX_SPECTRUM_SUM && q.aggregate != DFX_SPECTRUM_KS) {
+      h->err = w + ": unknown aggregate " + std::to_string(q.aggregate) + " (DFX_SPECTRUM_SUM = 0, DFX_SPECTRUM_KS = 1)";
+      return 1;
+    }
+    if (q.aggregate == DFX_SPECTRUM_KS && !(std::isfinite(q.beta) && q.beta > 0.0)) { h->err = w + ": beta must be positive and finite with the KS aggregate"; return 1; }
+    if (!q.a) { h->err = w + ": group_coef is NULL"; return 1; }
+  }
+  const size_t G = (size_t)q.G, ns = t.n_signals > 0 ? (size_t)t.n_signals : 0, np = ns * q.n_rows, om = q.off_per_member ? B : 1;
+  if (!all_finite(h, who, "basis entry", q.basis, (size_t)q.n_rows * Tn) || !all_finite(h, who, "group weight", q.Wn, G * np, true) ||
+      !all_finite(h, who, "group weight", q.Wd, G * np, true) || !all_finite(h, who, "offset", q.n0, om * G, true) ||
+      !all_finite(h, who, "offset", q.d0, om * G, true) || !all_finite(h, who, "group coefficient", q.value ? q.a : nullptr, G))
+    return 1;
+  for (size_t g = 0; g < G && ns; ++g) {
+    if (std::any_of(q.Wn + g * np, q.Wn + (g + 1) * np, [](double v) { return v > 0.0; })) continue;
+    for (size_t m = 0; m < om; ++m)
+      if (!q.n0 || q.n0[m * G + g] == 0.0) {
+        h->err = w + ": the numerator of group " + std::to_string(g) + " is empty (no weight and a zero offset)";
+        return 1;
+      }
+  }
+  if (int rc = prepare_signal(h, who, t, nullptr, 0, nullptr, nullptr, false)) return rc;
+  dfx_handle::SpecJob& J = h->sp;
+  J.n_rows = q.n_rows; J.G = q.G; J.off_stride = q.off_per_member ? (long long)G : 0;
+  J.measure = q.measure; J.aggregate = q.value ? q.aggregate : DFX_SPECTRUM_SUM; J.beta = q.value ? q.beta : 1.0;
+  std::vector<double> dbl(q.basis, q.basis + (size_t)q.n_rows * Tn);
+  dbl.insert(dbl.end(), q.Wn, q.Wn + G * np);
+  dbl.insert(dbl.end(), q.Wd, q.Wd + G * np);
+  for (const double* off : {q.n0, q.d0}) {
+    if (off) dbl.insert(dbl.end(), off, off + om * G);
+    else dbl.insert(dbl.end(), om * G, 0.0);
+  }
+  if (q.value) dbl.insert(dbl.end(), q.a, q.a + G);
+  else dbl.insert(dbl.end(), G, 0.0);
+  HIP_OK(h->d_sp_coef.ensure(dbl.size()));
+  HIP_OK(h->d_proj_P.ensure(B * np));
+  HIP_OK(h->d_sp_forms.ensure(B * G * 2));
+  HIP_OK(h->d_sp_l.ensure(B * G));
+  HIP_OK(h->d_sp_lam.ensure(B * G * 2));
+  HIP_OK(h->d_sp_weff.ensure(B * np));
+  HIP_OK(hipMemcpyAsync(h->d_sp_coef.p, dbl.data(), sizeof(double) * dbl.size(), hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));       // the table is a local of this function
+  return 0;
+}
+
+// the projections of a spectrum call (basis in its own buffer, no row weights, no targets) and the spectrum arguments
+void spectrum_args(const dfx_handle* h, ProjArgs& p, SpecArgs& x) {
+  const dfx_handle::SpecJob& J = h->sp;
+  const size_t B = h->pl.batch, G = (size_t)J.G, np = (size_t)h->sig.n_sig * J.n_rows, om = J.off_stride ? B : 1;
+  const double* dp = h->d_sp_coef.p;
+  p.basis = dp; dp += (size_t)J.n_rows * h->ts.size();
+  p.W = nullptr; p.target = nullptr; p.P = h->d_proj_P.p; p.target_stride = 0; p.n_rows = J.n_rows;
+  x.Wn = dp; dp += G * np;
+  x.Wd = dp; dp += G * np;
+  x.n0 = dp; dp += om * G;
+  x.d0 = dp; dp += om * G;
+  x.a = dp;
+  x.forms = h->d_sp_forms.p; x.l = h->d_sp_l.p; x.lam = h->d_sp_lam.p; x.Weff = h->d_sp_weff.p;
+  x.off_stride = J.off_stride;
+  x.G = J.G; x.measure = J.measure; x.aggregate = J.aggregate; x.beta = J.beta;
+}
+
+// channels and signals (launch_signal without targets), the projections, the forms N, D of every group, the reduction (J into d_obj and, when
+// given, J | l into pinned host memory); with G the effective row weights, the cotangent c on the signals and from it the cotangent of the sweep
+int launch_spectrum(dfx_handle* h, double* G, double* host) {
+  const dfx_handle::SpecJob& J = h->sp;
+  const size_t B = h->pl.batch;
+  if (int rc = launch_signal(h, nullptr, nullptr)) return rc;
+  DevCtx c = make_ctx(h);
+  const SigArgs a = sig_args(h);
+  ProjArgs p;
+  SpecArgs x;
+  spectrum_args(h, p, x);
+  const long long np = (long long)h->sig.n_sig * J.n_rows;
+  hipLaunchKernelGGL(k_signal_project, dim3(chunks_of(np, kObjWaves), (unsigned)B), dim3(kObjThreads), 0, h->stream, c, a, p, (double*)nullptr);
+  hipLaunchKernelGGL(k_signal_spectrum_forms, dim3(chunks_of(2LL * J.G, kObjWaves), (unsigned)B), dim3(kObjThreads), 0, h->stream, a, p, x);
+  hipLaunchKernelGGL(k_signal_spectrum_reduce, dim3((unsigned)B), dim3(64), 0, h->stream, x, h->d_obj.p, host, (int)B);
+  if (G) {
+    hipLaunchKernelGGL(k_signal_spectrum_weights, dim3(chunks_of(np, kObjThreads), (unsigned)B), dim3(kObjThreads), 0, h->stream, a, p, x);
+    hipLaunchKernelGGL(k_signal_spectrum_residual, dim3(chunks_of((long long)h->ts.size() * h->sig.n_sig, kObjThreads), (unsigned)B), dim3(kObjThreads), 0,
+                       h->stream, c, a, p, x);
+    launch_signal_reverse(h, c, a, G);
+  }
+  return 0;
+}
+
 // ---- what the entries share
 // A value entry needs the fields of a forward pass (and, all but dfx_objective_value, its parameters) and somewhere to put its result
 int need_fields(dfx_handle* h, const char* who, const void* out, const char* out_name, bool params = true) {
@@ -706,7 +812,7 @@ ObjJob signal_job(const dfx_handle* h, int kind, bool has_tau) { return ObjJob{k
 void launch_objective_explicit(dfx_handle* h, const DevCtx& c) {
   const ObjJob& j = *h->obj_job;
   if (j.n_act == 0) return;
-  if (j.kind == kObjSignal || j.kind == kObjProject || j.kind == kObjXcorr) {       // the same direction w, whichever residual it came from
+  if (j.kind == kObjSignal || j.kind == kObjProject || j.kind == kObjXcorr || j.kind == kObjSpectrum) {       // the same direction w, whichever residual it came from
     const SigArgs a = sig_args(h);
     const dim3 grid((unsigned)((a.n_set * 4 + 63) / 64), (unsigned)h->pl.batch);
     with_strain_physics(h, [&](auto M, auto C) { hipLaunchKernelGGL((k_signal_explicit<M(), C()>), grid, dim3(64), 0, h->stream, c, a); });
@@ -965,5 +1071,64 @@ int dfx_signal_xcorr_value_and_grad(dfx_handle* h, int32_t n_terms, const int32_
   if (objective) memcpy(objective, st, sizeof(double) * B);
   if (peak) memcpy(peak, st + B, sizeof(double) * B);
   if (delay) memcpy(delay, st + 2 * B, sizeof(double) * B);
+  return 0;
+}
+
+int dfx_signal_spectrum(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block, const int32_t* term_component,
+                        const double* term_coef, int32_t n_signals, const double* basis, int32_t n_rows, int32_t n_groups,
+                        const double* num_weights, const double* den_weights, const double* num_offset, const double* den_offset,
+                        int32_t offsets_per_member, int32_t measure, double* values) {
+  const char* who = "signal_spectrum";
+  HIP_OK(hipSetDevice(h->device));
+  if (int rc = need_fields(h, who, values, "values")) return rc;
+  const SigTerms t{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
+  const SpectrumCall q{basis, n_rows, n_groups, num_weights, den_weights, num_offset, den_offset, offsets_per_member, false, measure, DFX_SPECTRUM_SUM, 1.0, nullptr};
+  if (int rc = prepare_spectrum(h, who, t, q)) return rc;
+  if (int rc = launch_spectrum(h, nullptr, nullptr)) return rc;
+  const size_t n = h->pl.batch * (size_t)n_groups;
+  std::vector<double> forms(n * 2), l(n);
+  if (int rc = download(h, {{forms.data(), h->d_sp_forms.p, sizeof(double) * n * 2}, {l.data(), h->d_sp_l.p, sizeof(double) * n}})) return rc;
+  for (size_t i = 0; i < n; ++i) { values[i * 3] = forms[i * 2]; values[i * 3 + 1] = forms[i * 2 + 1]; values[i * 3 + 2] = l[i]; }
+  return 0;
+}
+
+int dfx_signal_spectrum_value(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block,
+                              const int32_t* term_component, const double* term_coef, int32_t n_signals, const double* basis, int32_t n_rows,
+                              int32_t n_groups, const double* num_weights, const double* den_weights, const double* num_offset,
+                              const double* den_offset, int32_t offsets_per_member, int32_t measure, int32_t aggregate, double beta,
+                              const double* group_coef, double* objective, double* measures) {
+  const char* who = "signal_spectrum_value";
+  HIP_OK(hipSetDevice(h->device));
+  if (int rc = need_fields(h, who, objective, "objective")) return rc;
+  const SigTerms t{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
+  const SpectrumCall q{basis, n_rows, n_groups, num_weights, den_weights, num_offset, den_offset, offsets_per_member, true, measure, aggregate, beta,
+                       group_coef};
+  if (int rc = prepare_spectrum(h, who, t, q)) return rc;
+  if (int rc = launch_spectrum(h, nullptr, nullptr)) return rc;
+  const size_t B = h->pl.batch;
+  return download(h, {{objective, h->d_obj.p, sizeof(double) * B}, {measures, h->d_sp_l.p, sizeof(double) * B * (size_t)n_groups}});
+}
+
+int dfx_signal_spectrum_value_and_grad(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block,
+                                       const int32_t* term_component, const double* term_coef, int32_t n_signals, const double* basis,
+                                       int32_t n_rows, int32_t n_groups, const double* num_weights, const double* den_weights,
+                                       const double* num_offset, const double* den_offset, int32_t offsets_per_member, int32_t measure,
+                                       int32_t aggregate, double beta, const double* group_coef, double* objective, double* measures,
+                                       const dfx_grads* want, dfx_grads* views, int32_t device_views, dfx_stats* stats) {
+  const char* who = "signal_spectrum_value_and_grad";
+  HIP_OK(hipSetDevice(h->device));
+  if (int rc = need_trajectory(h, who)) return rc;
+  const size_t B = h->pl.batch;
+  const SigTerms t{n_terms, term_signal, term_block, term_component, term_coef, n_signals};
+  const SpectrumCall q{basis, n_rows, n_groups, num_weights, den_weights, num_offset, den_offset, offsets_per_member, true, measure, aggregate, beta,
+                       group_coef};
+  if (int rc = prepare_spectrum(h, who, t, q)) return rc;
+  const bool any = objective || measures;
+  if (int rc = objective_sweep(h, signal_job(h, kObjSpectrum, false), false, any ? sizeof(double) * B * (1 + (size_t)n_groups) : 0,
+                               [&](double* G, double* host) { return launch_spectrum(h, G, host); }, want, views, device_views, stats))
+    return rc;
+  const double* st = reinterpret_cast<const double*>(h->obj_stage.p);      // J | l
+  if (objective) memcpy(objective, st, sizeof(double) * B);
+  if (measures) memcpy(measures, st + B, sizeof(double) * B * (size_t)n_groups);
   return 0;
 }

@@ -1097,6 +1097,24 @@ class DynamicSolver:
         ((J, peak, delay), raw gradients)."""
         return self.value_and_raw(spec, which, device)
 
+    def signal_spectrum(self, spec):
+        """(N, D, l), (batch, G) each: the numerator and denominator forms of the groups of an ``objective.SpectrumSpec`` and their measures
+        (N / D or ln N - ln D as the spec says; NaN where the measure does not exist), on the device-resident history of the last solve
+        (any forward pass)."""
+        out = self.engine.signal_spectrum(*self._terms(spec.signal_spec), spec.basis, spec.num_weights, spec.den_weights, spec.num_offset,
+                                          spec.den_offset, spec.measure)
+        return out[..., 0], out[..., 1], out[..., 2]
+
+    def signal_spectrum_value(self, spec):
+        """(J, l): the value (batch,) and the measures (batch, G) of an ``objective.SpectrumSpec`` on the device-resident history."""
+        return self.value(spec)
+
+    def signal_spectrum_value_and_raw(self, spec, which=("centroid_node_vectors", "void_angle0", "inertia"), device=False):
+        """The spectral-ratio objective (``objective.SpectrumSpec``) of the last kept solve, evaluated and differentiated on the device
+        beside :meth:`signal_projection_value_and_raw`: the band-power forms, their ratios, the aggregate over the groups and the cotangent
+        on the signals are formed in HBM; what follows is :meth:`signal_misfit_value_and_raw`'s.  Returns ((J, l), raw gradients)."""
+        return self.value_and_raw(spec, which, device)
+
     @staticmethod
     def _bond_params_bar(bp, kb, refv_bar, like):
         """Gradient tree with the structure of the bond parameters that were passed in (LigamentParams /

@@ -858,3 +858,184 @@ def host_xcorr_value_and_cotangent(spec, fields):
     if f.ndim == 4:
         return float(J), float(M), float(delta), fb
     return J, M, delta, fb
+
+
+# ---- signal spectral ratios on the device-resident history ------------------------------------------------------------------------------
+MEASURES = ("ratio", "log")
+AGGREGATES = ("sum", "ks")
+
+
+class SpectrumSpec:
+    """Ratios of band powers of the projections of a ``ProjectionSpec``-like basis (``include/dfx.h``: ``dfx_signal_spectrum``,
+    ``dfx_signal_spectrum_value[_and_grad]``) -- transmissibility, a band gap, harmonic generation.  G groups, per member:
+
+        N_g = n0_g + sum_s sum_j Wn_gsj P_sj^2        D_g = d0_g + sum_s sum_j Wd_gsj P_sj^2        P_sj = sum_k B_jk S_ks
+        l_g = N_g / D_g ("ratio")  or  ln N_g - ln D_g ("log"; dB = 10 / ln 10 * l)
+        J   = sum_g a_g l_g ("sum")  or  M + ln(sum_g exp(beta (a_g l_g - M))) / beta with M = max_g a_g l_g ("ks", ``beta`` > 0)
+
+    ``signal_spec``: the terms (its own targets, omega and tau play no part; targets, when present, fix T); ``basis`` (n_rows, T), shared
+    by the members; ``num_weights``, ``den_weights`` (G, n_signals, n_rows), entries >= 0; ``num_offset``, ``den_offset`` (G,) shared or
+    (batch, G), entries >= 0, None = zeros -- ``den_offset`` > 0 with zero ``den_weights`` normalises by a known constant; ``group_coef``
+    (G,) of any sign, None = ones.  A group whose numerator is empty (no weight, zero offset) is refused.  A member with some D_g <= 0
+    ("log": or N_g <= 0; "ks": or a non-finite l_g) gets J = NaN and a zero gradient.  Shapes, signs and finiteness are checked here
+    (``ValueError``); T against a solve where the spec is used."""
+    __slots__ = ("signal_spec", "basis", "num_weights", "den_weights", "num_offset", "den_offset", "group_coef", "measure", "aggregate", "beta")
+
+    def __init__(self, signal_spec, basis, num_weights, den_weights, num_offset=None, den_offset=None, group_coef=None, measure="log",
+                 aggregate="sum", beta=None):
+        ns = signal_spec.n_signals
+        b = np.array(basis, dtype=float)
+        if b.ndim != 2 or b.shape[0] < 1 or b.shape[1] < 1:
+            raise ValueError(f"basis must be (n_rows, T) with n_rows >= 1, got {b.shape}")
+        if signal_spec.targets is not None and signal_spec.targets.shape[-2] != b.shape[1]:
+            raise ValueError(f"basis has T = {b.shape[1]} but the targets of the signal spec have T = {signal_spec.targets.shape[-2]}")
+        if signal_spec.tau is not None and signal_spec.tau.shape[0] != b.shape[1]:
+            raise ValueError(f"basis has T = {b.shape[1]} but tau of the signal spec has T = {signal_spec.tau.shape[0]}")
+        wn, wd = np.array(num_weights, dtype=float), np.array(den_weights, dtype=float)
+        if wn.ndim != 3 or wn.shape[0] < 1 or wn.shape[1:] != (ns, b.shape[0]) or wd.shape != wn.shape:
+            raise ValueError(f"num_weights and den_weights must be (G, {ns}, {b.shape[0]}) with G >= 1, got {wn.shape} and {wd.shape}")
+        G = wn.shape[0]
+        offs = []
+        for name, o in (("num_offset", num_offset), ("den_offset", den_offset)):
+            o = None if o is None else np.array(o, dtype=float)
+            if o is not None and (o.ndim not in (1, 2) or o.shape[-1] != G):
+                raise ValueError(f"{name} must be ({G},) or (batch, {G}), got {o.shape}")
+            offs.append(o)
+        if offs[0] is not None and offs[1] is not None and offs[0].ndim == 2 and offs[1].ndim == 2 and len(offs[0]) != len(offs[1]):
+            raise ValueError(f"num_offset is for {len(offs[0])} members and den_offset for {len(offs[1])}")
+        a = np.ones(G) if group_coef is None else np.array(group_coef, dtype=float)
+        if a.shape != (G,):
+            raise ValueError(f"group_coef must be ({G},), got {a.shape}")
+        for name, v, nonneg in (("basis", b, False), ("num_weights", wn, True), ("den_weights", wd, True), ("num_offset", offs[0], True),
+                                ("den_offset", offs[1], True), ("group_coef", a, False)):
+            if v is not None and not np.isfinite(v).all():
+                raise ValueError(f"{name}: non-finite entry")
+            if v is not None and nonneg and (v < 0).any():
+                raise ValueError(f"{name}: negative entry")
+        n0 = np.zeros(G) if offs[0] is None else offs[0]
+        empty = [g for g in range(G) if not (wn[g] > 0).any() and (np.atleast_2d(n0)[:, g] == 0).any()]
+        if empty:
+            raise ValueError(f"groups with an empty numerator (no weight and a zero offset): {empty}")
+        if measure not in MEASURES:
+            raise ValueError(f"measure must be one of {MEASURES}, got {measure!r}")
+        if aggregate not in AGGREGATES:
+            raise ValueError(f"aggregate must be one of {AGGREGATES}, got {aggregate!r}")
+        if aggregate == "ks" and (beta is None or not np.isfinite(beta) or beta <= 0):
+            raise ValueError(f"the ks aggregate needs a finite beta > 0, got {beta!r}")
+        self.signal_spec, self.basis, self.num_weights, self.den_weights = signal_spec, b, wn, wd
+        self.num_offset, self.den_offset, self.group_coef = offs[0], offs[1], a
+        self.measure, self.aggregate, self.beta = measure, aggregate, None if beta is None else float(beta)
+
+    def __repr__(self):
+        return (f"SpectrumSpec({self.signal_spec!r}, basis={self.basis.shape}, groups={self.n_groups}, measure={self.measure!r}, "
+                f"aggregate={self.aggregate!r}, beta={self.beta!r})")
+
+    def engine_call(self):
+        return "signal_spectrum", self.signal_spec, (self.basis, self.num_weights, self.den_weights), dict(
+            num_offset=self.num_offset, den_offset=self.den_offset, group_coef=self.group_coef, measure=self.measure,
+            aggregate=self.aggregate, beta=self.beta)
+
+    @property
+    def n_rows(self):
+        return self.basis.shape[0]
+
+    @property
+    def n_groups(self):
+        return self.num_weights.shape[0]
+
+    def with_offsets(self, num_offset, den_offset):
+        """The same signals, basis, weights and reduction with other offsets."""
+        return SpectrumSpec(self.signal_spec, self.basis, self.num_weights, self.den_weights, num_offset, den_offset, self.group_coef,
+                            self.measure, self.aggregate, self.beta)
+
+
+def band_groups(n_signals, n_frequencies, numerator, denominator):
+    """(Wn, Wd), each (G, n_signals, 2 n_frequencies), of a ``SpectrumSpec`` on a ``fourier_basis``: group g has unit weight on the cos and
+    the sin row (they weigh alike, as in ``TargetBandPower``) of every (signal, frequency index) of ``numerator[g]`` in Wn and of
+    ``denominator[g]`` in Wd.  A pair listed twice in one list counts once; an empty denominator list leaves the row of Wd zero (normalise
+    by ``den_offset``)."""
+    ns, nf = int(n_signals), int(n_frequencies)
+    if ns < 1 or nf < 1:
+        raise ValueError(f"n_signals and n_frequencies must be positive, got {n_signals!r} and {n_frequencies!r}")
+    if len(numerator) != len(denominator) or len(numerator) == 0:
+        raise ValueError(f"numerator and denominator must list the same number (>= 1) of groups, got {len(numerator)} and {len(denominator)}")
+    out = np.zeros((2, len(numerator), ns, 2 * nf))
+    for side, groups in enumerate((numerator, denominator)):
+        for g, pairs in enumerate(groups):
+            for s, f in np.array(pairs, dtype=np.int64).reshape(-1, 2):
+                if not (0 <= s < ns and 0 <= f < nf):
+                    raise ValueError(f"group {g}: (signal, frequency) = ({s}, {f}) out of range ({ns} signals, {nf} frequencies)")
+                out[side, g, s, 2 * f] = out[side, g, s, 2 * f + 1] = 1.0
+    return out[0], out[1]
+
+
+def _spectrum_offsets(spec, lead):
+    """n0, d0 of a ``SpectrumSpec`` broadcast against projections whose leading axes are ``lead``"""
+    G, out = spec.n_groups, []
+    for o in (spec.num_offset, spec.den_offset):
+        o = np.zeros(G) if o is None else o
+        if o.ndim == 2 and (len(lead) == 0 or lead[-1] != len(o)):
+            raise ValueError(f"per-member offsets for {len(o)} members against projections with leading axes {lead}")
+        out.append(np.broadcast_to(o, lead + (G,)))
+    return out
+
+
+def spectrum_of_projections(spec, P):
+    """(N, D, l) of a ``SpectrumSpec`` from projections ``P`` (..., n_signals, n_rows): the forms and the measures (..., G), the formulas
+    of the class in NumPy.  A group with D <= 0 ("log": or N <= 0) gets l = NaN."""
+    P = np.asarray(P, dtype=float)
+    if P.shape[-2:] != spec.num_weights.shape[1:]:
+        raise ValueError(f"the projections must be (..., {spec.num_weights.shape[1]}, {spec.num_weights.shape[2]}), got {P.shape}")
+    n0, d0 = _spectrum_offsets(spec, P.shape[:-2])
+    N = n0 + np.einsum("gsj,...sj->...g", spec.num_weights, P * P)
+    D = d0 + np.einsum("gsj,...sj->...g", spec.den_weights, P * P)
+    ok = (D > 0) & ((N > 0) | (spec.measure != "log"))
+    Ns, Ds = np.where(ok, N, 1.0), np.where(ok, D, 1.0)
+    l = np.where(ok, np.log(Ns) - np.log(Ds) if spec.measure == "log" else Ns / Ds, np.nan)
+    return N, D, l
+
+
+def spectrum_value_and_projection_cotangent(spec, P):
+    """(J, l, Pbar) of a ``SpectrumSpec`` on projections ``P`` (..., n_signals, n_rows): the value (...), the measures (..., G) and
+    dJ/dP = Weff P.  A member with a NaN measure ("ks": or a non-finite one) gets J = NaN and Pbar = 0."""
+    P = np.asarray(P, dtype=float)
+    N, D, l = spectrum_of_projections(spec, P)
+    if spec.aggregate == "ks":
+        l = np.where(np.isfinite(l), l, np.nan)
+    dead = np.isnan(l).any(-1)
+    ls = np.where(dead[..., None], 0.0, l)
+    Ns, Ds = np.where(dead[..., None], 1.0, N), np.where(dead[..., None], 1.0, D)
+    a = spec.group_coef
+    if spec.aggregate == "ks":
+        z = a * ls
+        M = z.max(-1, keepdims=True)
+        e = np.exp(spec.beta * (z - M))
+        Z = e.sum(-1, keepdims=True)
+        J = (M + np.log(Z) / spec.beta)[..., 0]
+        lam = a * e / Z
+    else:
+        J = (a * ls).sum(-1)
+        lam = np.broadcast_to(a, ls.shape)
+    dN, dD = (1.0 / Ns, -1.0 / Ds) if spec.measure == "log" else (1.0 / Ds, -Ns / Ds ** 2)
+    Weff = 2.0 * (np.einsum("...g,gsj->...sj", lam * dN, spec.num_weights) + np.einsum("...g,gsj->...sj", lam * dD, spec.den_weights))
+    Weff = np.where(dead[..., None, None], 0.0, Weff)
+    return np.where(dead, np.nan, J), l, Weff * P
+
+
+def host_spectrum_value_and_cotangent(spec, fields):
+    """(J, l, fields_bar) of a ``SpectrumSpec`` whose terms are field components: the value and the measures per member and the cotangent
+    of J on the fields (what ``vjp`` / ``dfx_adjoint`` take), coef * c_ks on the row of every term with c_ks = sum_j Weff_sj P_sj B_jk.
+    ``fields`` with or without the member axis; the value is (batch,) or a float.  Force components raise, as in ``host_signal_values``."""
+    f = np.asarray(fields, dtype=float)
+    S = host_signal_values(spec.signal_spec, f)
+    if S.shape[-2] != spec.basis.shape[1]:
+        raise ValueError(f"basis has T = {spec.basis.shape[1]} but the fields have T = {S.shape[-2]}")
+    if f.ndim == 4 and any(o is not None and o.ndim == 2 for o in (spec.num_offset, spec.den_offset)):
+        raise ValueError("per-member offsets against the fields of one member")
+    P = np.einsum("jk,...ks->...sj", spec.basis, S)
+    J, l, Pbar = spectrum_value_and_projection_cotangent(spec, P)
+    c = np.einsum("...sj,jk->...ks", Pbar, spec.basis)
+    fb = np.zeros_like(f)
+    for s, b, comp, coef in spec.signal_spec.terms:
+        fb[..., comp // 3, b, comp % 3] += coef * c[..., s]
+    return (float(J) if f.ndim == 4 else J), l, fb

@@ -1229,7 +1229,7 @@ class DriveWaveformDesign:
     """The drive itself as the design: the unknowns ``y`` are the samples of a ``loading.Table`` with named values -- the (n_tab,) array
     ``leaf`` of ``constraint_params`` / ``loading_params`` of ``control_params`` -- and the objective is any of the device objective specs
     (``objective.ObjectiveSpec``, ``StrainObjectiveSpec``, ``PeakStrainSpec``, ``SignalSpec`` with targets, ``ProjectionSpec``,
-    ``CorrelationSpec``), dispatched to the solver's ``*_value_and_raw``: one kept forward solve and one reverse sweep per evaluation, the
+    ``CorrelationSpec``, ``SpectrumSpec``), dispatched to the solver's ``*_value_and_raw``: one kept forward solve and one reverse sweep per evaluation, the
     history never leaves the device, and the sample gradient comes from the sweep's drive-cotangent trace (``fn_table_values`` of the raw
     gradients).  Shape the pulse that focuses the most energy at a target under an amplitude bound, find the excitation that reproduces a
     measured reaction force, ...  ``fixed``: samples held at their initial values (default: the two ends, so that the drive starts and
@@ -1249,7 +1249,8 @@ class DriveWaveformDesign:
             raise ValueError(f"DriveWaveformDesign: {leaf!r} is missing from {self.field}")
         methods = ((O.ObjectiveSpec, "objective_value_and_raw"), (O.StrainObjectiveSpec, "strain_objective_value_and_raw"),
                    (O.PeakStrainSpec, "peak_strain_value_and_raw"), (O.SignalSpec, "signal_misfit_value_and_raw"),
-                   (O.ProjectionSpec, "signal_projection_value_and_raw"), (O.CorrelationSpec, "signal_xcorr_value_and_raw"))
+                   (O.ProjectionSpec, "signal_projection_value_and_raw"), (O.CorrelationSpec, "signal_xcorr_value_and_raw"),
+                   (O.SpectrumSpec, "signal_spectrum_value_and_raw"))
         self.method = next((name for cls, name in methods if isinstance(spec, cls)), None)
         if self.method is None:
             raise TypeError("DriveWaveformDesign: spec must be one of the device objective specs of difflexmm_amd.objective")
@@ -1412,6 +1413,112 @@ def TargetWaveDelay(forward, source_block_dofs, target_block_dofs, kind, max_lag
     if spec.max_lag > len(tp) - 1:
         raise ValueError(f"TargetWaveDelay: max_lag = {max_lag} outside [0, T - 1] with T = {len(tp)}")
     return TargetCrossCorrelation(forward, spec)
+
+
+class TargetSpectrum(_SignalTarget):
+    """objective(design) = the aggregate J over groups of ratios (or log ratios) of band powers for an ``objective.SpectrumSpec``:
+    transmissibility, the worst transmission over a band, harmonic generation -- scale-free measures, which a weighted sum of band powers
+    (``TargetSignalProjection``) is not.  Shaped as ``TargetCrossCorrelation``: a list of designs runs as one ensemble (offsets (G,) shared
+    or (len(designs), G); ``run_ensemble_optimization`` accepts the class) on the device (``dfx_signal_spectrum_value_and_grad``); one
+    design takes the host path -- field components only -- unless ``on_device``.  Force and hinge components have no host path.
+    ``last_measures``: the measures l of the last evaluation ((G,) for one design, (n, G) for a list)."""
+
+    _extras = ("last_measures",)
+    _cut_on_device = True
+
+    def __init__(self, forward, spec):
+        self.last_measures = None
+        super().__init__(forward, spec)
+
+    def _offsets(self, cut):
+        sp = self.spec
+        return [o if o is None or o.ndim == 1 else cut(o) for o in (sp.num_offset, sp.den_offset)]
+
+    def _evaluate(self, design, grad):
+        for o in (self.spec.num_offset, self.spec.den_offset):
+            if isinstance(design, list) and o is not None and o.ndim == 2 and len(o) != len(design):
+                raise ValueError(f"{len(design)} designs against offsets for {len(o)} members")
+        return super()._evaluate(design, grad)
+
+    def _chunk_spec(self, i, n):
+        """the spec of designs i .. i + n of a longer list (per-member offsets are cut alike)"""
+        return self.spec.with_offsets(*self._offsets(lambda o: o[i:i + n]))
+
+    def _first(self, sp):
+        return sp.with_offsets(*self._offsets(lambda o: o[0]))
+
+    def _host_value(self, sp, fields, grad):
+        from .objective import host_spectrum_value_and_cotangent
+        val, self.last_measures, fb = host_spectrum_value_and_cotangent(sp, fields)
+        return val, fb
+
+
+def _shared_timepoints(forward, who):
+    if not getattr(forward, "is_setup", False):
+        forward.setup()
+    tp = getattr(forward, "timepoints", None)
+    if tp is None or np.ndim(tp) != 1:
+        raise ValueError(f"{who}: the forward problem has no output times of its own shared by all members (per-member timepoints): "
+                         "build an objective.SpectrumSpec for one time grid")
+    return tp
+
+
+def TargetTransmission(forward, in_block_dofs, out_block_dofs, kind, frequencies, window=None, worst_case=False, beta=None):
+    """A ``TargetSpectrum`` with one group per frequency f: l_f = ln(power of the ``out_block_dofs`` signals at f) - ln(power of the
+    ``in_block_dofs`` signals at f), displacement or velocity (``kind``, as ``SignalSpec.fields_of``), the powers from the windowed Fourier
+    integrals over the forward problem's own output times (``objective.fourier_basis``).  The value is the mean of l over the frequencies
+    (times 10 / ln 10: the mean transmission in dB), or with ``worst_case`` their KS smooth maximum of sharpness ``beta`` -- the worst
+    transmission over the band, to be minimised for a band gap.  ``last_measures`` holds l per frequency."""
+    from .objective import SignalSpec, SpectrumSpec, band_groups, fourier_basis
+    tp = _shared_timepoints(forward, "TargetTransmission")
+    src, out = np.array(in_block_dofs, dtype=np.int64).reshape(-1, 2), np.array(out_block_dofs, dtype=np.int64).reshape(-1, 2)
+    if len(src) == 0 or len(out) == 0:
+        raise ValueError("TargetTransmission: in_block_dofs and out_block_dofs must be non-empty sequences of (block, dof)")
+    f = np.atleast_1d(np.asarray(frequencies, dtype=float))
+    sig = SignalSpec.fields_of(np.concatenate([src, out]), kind)
+    wn, wd = band_groups(sig.n_signals, len(f), [[(len(src) + s, i) for s in range(len(out))] for i in range(len(f))],
+                         [[(s, i) for s in range(len(src))] for i in range(len(f))])
+    coef = np.ones(len(f)) if worst_case else np.full(len(f), 1.0 / len(f))
+    return TargetSpectrum(forward, SpectrumSpec(sig, fourier_basis(tp, f, window), wn, wd, None, None, coef, "log",
+                                                "ks" if worst_case else "sum", beta if worst_case else None))
+
+
+def TargetHarmonicRatio(forward, block_dofs, kind, fundamental, harmonic=2, window=None, measure="log"):
+    """A ``TargetSpectrum`` with one group: the power of the listed (block, dof) signals at ``harmonic * fundamental`` over their power at
+    ``fundamental`` -- harmonic generation, the signature of the nonlinearity; ``measure`` "log" or "ratio"."""
+    from .objective import SignalSpec, SpectrumSpec, band_groups, fourier_basis
+    tp = _shared_timepoints(forward, "TargetHarmonicRatio")
+    if not np.isfinite(fundamental) or fundamental <= 0 or not np.isfinite(harmonic) or harmonic <= 0 or harmonic == 1:
+        raise ValueError(f"TargetHarmonicRatio: fundamental must be positive and harmonic positive and not 1, got {fundamental!r}, {harmonic!r}")
+    sig = SignalSpec.fields_of(block_dofs, kind)
+    ns = sig.n_signals
+    wn, wd = band_groups(ns, 2, [[(s, 1) for s in range(ns)]], [[(s, 0) for s in range(ns)]])
+    basis = fourier_basis(tp, [float(fundamental), float(harmonic) * float(fundamental)], window)
+    return TargetSpectrum(forward, SpectrumSpec(sig, basis, wn, wd, measure=measure))
+
+
+class TransmissionLimit:
+    """constraint(design) = (10 / ln 10) J - limit_db with J the ``TargetTransmission`` of the same arguments (by default its worst case
+    over the band): feasible when <= 0, "the transmission stays below ``limit_db`` dB over the band" -- the sign convention of the
+    ``state_constraints`` of ``OptimizationProblem.run_optimization_nlopt``, as ``PeakLigamentStrain``."""
+    DB = 10.0 / np.log(10.0)
+
+    def __init__(self, forward, in_block_dofs, out_block_dofs, kind, frequencies, limit_db, window=None, worst_case=True, beta=None,
+                 on_device=False):
+        if not np.isfinite(limit_db):
+            raise ValueError(f"TransmissionLimit: limit_db must be finite, got {limit_db!r}")
+        self.target = TargetTransmission(forward, in_block_dofs, out_block_dofs, kind, frequencies, window, worst_case, beta)
+        self.forward, self.limit_db, self.on_device = forward, float(limit_db), bool(on_device)
+
+    def value(self, design):
+        return self.DB * self.target.value(design, self.on_device) - self.limit_db
+
+    def value_and_grad(self, design):
+        """(c, grad) for one design, ((n,), list of grads) for a list"""
+        val, grad = self.target.value_and_grad(design, self.on_device)
+        if isinstance(design, list):
+            return self.DB * val - self.limit_db, [tuple(self.DB * np.asarray(a) for a in g) for g in grad]
+        return self.DB * val - self.limit_db, tuple(self.DB * np.asarray(a) for a in grad)
 
 
 def _cut_hinges(forward, blocks_inside, who):

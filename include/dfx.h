@@ -615,6 +615,56 @@ int dfx_signal_xcorr_value_and_grad(dfx_handle* h, int32_t n_terms, const int32_
                                     double beta, double w_peak, double w_delay, double delay_target, double* objective, double* peak,
                                     double* delay, const dfx_grads* want, dfx_grads* views, int32_t device_views, dfx_stats* stats);
 
+/* Signal spectral ratios on the device-resident history (HIP library only): ratios of band powers of the projections P_msj = sum_k B_jk S_mks
+ * of dfx_signal_projections (the same term arrays, components 0..20, basis and hinge opt-in) -- transmissibility (the band power that
+ * arrives over the band power that went in, in dB), a band gap (the worst transmission over a band of frequencies), harmonic generation
+ * (the power at 2 f over the power at f).  n_groups = G >= 1 groups of a numerator and a denominator form, per member m:
+ *   N_mg = n0_g + sum_s sum_j Wn_gsj P_msj^2          D_mg = d0_g + sum_s sum_j Wd_gsj P_msj^2
+ * num_weights Wn, den_weights Wd: (G, n_signals, n_rows), entries >= 0, shared by the members.  num_offset n0, den_offset d0: (G,) shared,
+ * or (batch, G) when offsets_per_member != 0, entries >= 0; NULL = zeros.  d0_g > 0 with Wd_g all zero normalises by a known constant (the
+ * band power of a prescribed drive).  The measure of a group and the aggregate over the groups (group_coef a_g of any sign):
+ *   DFX_SPECTRUM_RATIO  l_mg = N_mg / D_mg
+ *   DFX_SPECTRUM_LOG    l_mg = ln N_mg - ln D_mg                (dB = 10 / ln 10 * l)
+ *   DFX_SPECTRUM_SUM    J_m = sum_g a_g l_mg
+ *   DFX_SPECTRUM_KS     z_g = a_g l_mg, M = max_g z_g (lowest g on a tie), J_m = M + ln( sum_g exp(beta (z_g - M)) ) / beta,  beta > 0
+ * (a = +1 with KS: the worst-case transmission of a stop band, to be minimised; a = -1: minus the weakest transmission of a pass band.)
+ * The cotangent: lam_g = dJ/dl_g = a_g (SUM) or a_g softmax(beta z)_g (KS); (dl/dN, dl/dD) = (1/D, -N/D^2) (RATIO) or (1/N, -1/D) (LOG);
+ *   Weff_msj = 2 sum_g lam_g (dl_g/dN Wn_gsj + dl_g/dD Wd_gsj)     g ascending
+ *   c_mks    = sum_j Weff_msj P_msj B_jk                           j ascending, the cotangent of J on the signals
+ * A member for which some D_mg <= 0 (DFX_SPECTRUM_LOG: or some N_mg <= 0; DFX_SPECTRUM_KS: or some l_mg is not finite) gets J = NaN, NaN in
+ * the offending l_mg and an all-zero cotangent: no division by zero reaches the sweep, the other members are unaffected.
+ * dfx_signal_spectrum takes `measure` alone and writes (batch, G, 3) = N | D | l (NaN in l where the rule above says so), and dfx_signal_spectrum_value J (batch,) and
+ * the measures l (batch, G) into `measures` (may be NULL), after any forward pass.  dfx_signal_spectrum_value_and_grad needs the kept
+ * trajectory and equals dfx_adjoint on the fields_bar of these formulas -- c takes the place of tau omega (S - Starget) in
+ * dfx_signal_misfit_value_and_grad, all that follows is that entry's, as for dfx_signal_projection_value_and_grad: want / views /
+ * device_views / stats, the sweep forms, the checkpoint levels, the kept steps of an adaptive solve, what fn_params holds and the refusals
+ * of a missing trajectory or a stale shared checkpoint.  Every sum has a fixed order and no atomics -- N, D: lane l of a wave adds the
+ * flattened (signal, row) pairs l, l + 64, ... ascending (zero weights add nothing), the shuffle tree, then the offset; the reduction: lane
+ * l holds groups l, l + 64, ..., the measures first, then the maximum, then the exponent sums -- so the same history gives the same bits.
+ * The arrays must hold EXACTLY the sizes stated: the library cannot check a length.
+ * Return 1 (dfx_last_error says why): n_groups < 1, a NULL num_weights or den_weights, a negative or non-finite weight or offset, a group
+ * whose numerator has no positive weight and a zero offset, an unknown measure or aggregate, beta <= 0 or non-finite (DFX_SPECTRUM_KS), a
+ * NULL or non-finite group_coef, and everything the projection entries refuse. */
+#define DFX_SPECTRUM_RATIO 0
+#define DFX_SPECTRUM_LOG 1
+#define DFX_SPECTRUM_SUM 0
+#define DFX_SPECTRUM_KS 1
+int dfx_signal_spectrum(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block, const int32_t* term_component,
+                        const double* term_coef, int32_t n_signals, const double* basis, int32_t n_rows, int32_t n_groups,
+                        const double* num_weights, const double* den_weights, const double* num_offset, const double* den_offset,
+                        int32_t offsets_per_member, int32_t measure, double* values);
+int dfx_signal_spectrum_value(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block,
+                              const int32_t* term_component, const double* term_coef, int32_t n_signals, const double* basis, int32_t n_rows,
+                              int32_t n_groups, const double* num_weights, const double* den_weights, const double* num_offset,
+                              const double* den_offset, int32_t offsets_per_member, int32_t measure, int32_t aggregate, double beta,
+                              const double* group_coef, double* objective, double* measures);
+int dfx_signal_spectrum_value_and_grad(dfx_handle* h, int32_t n_terms, const int32_t* term_signal, const int32_t* term_block,
+                                       const int32_t* term_component, const double* term_coef, int32_t n_signals, const double* basis,
+                                       int32_t n_rows, int32_t n_groups, const double* num_weights, const double* den_weights,
+                                       const double* num_offset, const double* den_offset, int32_t offsets_per_member, int32_t measure,
+                                       int32_t aggregate, double beta, const double* group_coef, double* objective, double* measures,
+                                       const dfx_grads* want, dfx_grads* views, int32_t device_views, dfx_stats* stats);
+
 /* Post-processing of the last forward solve on its device-resident history (problems/quads_focusing.py:319-372 with
  * energy.py:522-534): strain energies of every ligament 1/2 k (strain |l0|)^2 for the axial, shear and bending strain of
  * the NONLINEAR kinematics, (batch, T, n_bonds) each, and the kinetic energy of every block sum_d m_d v_d^2 / 2,
